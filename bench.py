@@ -4,14 +4,19 @@ decode -> per-class NMS -> packed detections [-> all-gather when N>1]) on synthe
 are already resident in HBM.  Workload at N=1 = BASELINE.json configs[1]:
 MobileNetV2-0.75x @416, batch 64, fp32, random weights.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement): value = whole-job img/s,
-`roofline` for the dominant kernel symbol (measured live with hipEvents), `roofline_step` for the
-whole step against the conv-granular algorithmic bytes of SURVEY.md 8(d), and `cpu_baseline` =
-the oracle's torch-CPU port timed on this box's host cores (N=1, rank 0 only).
+Prints ONE JSON line on rank 0: value = whole-job img/s over the K timed steps, ms_per_step = the
+milliseconds one timed step took.  A plain run does only that: set-up, warm-up, the timed steps.
+--dump-outputs DIR writes the detections of the last timed step (what a caller of the step receives)
+as DIR/*.npy, so that two builds can be compared output for output on identical seeded inputs.
+--full adds everything else: `roofline` for the dominant kernel symbol (measured live with
+hipEvents), `roofline_step` for the whole step against the conv-granular algorithmic bytes of
+SURVEY.md 8(d), the serial / batch-1 / incl-H2D figures, the other BASELINE configurations, the
+all-float32-MFMA sub-run and `cpu_baseline` = the oracle's torch-CPU port timed on the host cores
+(N=1, rank 0 only).
 """
 import argparse
 import json
@@ -48,10 +53,17 @@ def parse():
     ap.add_argument('--dtype', default='f32', choices=['f32', 'bf16', 'f16'],
                     help='element type of the activations between fused ops and of the 1x1-conv weights (BASELINE configs 3 / 5 '
                          'run bf16 / f16; the headline config 2 is f32)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the last timed step\'s detections (det_boxes, det_scores, det_classes, det_count) '
+                         'as DIR/<name>.npy in float32 / float64')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every measurement beyond the headline: per-kernel and whole-step roofline, serial steps, batch-1 '
+                         'latency, incl-H2D feeds, other BASELINE configurations, the all-float32-MFMA sub-run, the CPU baseline '
+                         '(the --no-* / --per-op / --profile-iters / --cpu-seconds options below trim or extend this part)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-seconds', type=float, default=15.0, help='budget of the CPU baseline sample')
     ap.add_argument('--profile-iters', type=int, default=3)
-    ap.add_argument('--per-op', action='store_true', help='also print the per-op table to stderr')
+    ap.add_argument('--per-op', action='store_true', help='also print the per-op table to stderr (with --full)')
     ap.add_argument('--force-dist', action='store_true',
                     help='initialise RCCL and issue the detection all-gather even with one rank (single-GPU check of the N>1 path)')
     ap.add_argument('--depth', type=int, default=0,
@@ -62,8 +74,26 @@ def parse():
                     help='skip the batch-1 p50 loop (use under rocprofv3 so that every launch is a batch-%d launch)' % 64)
     ap.add_argument('--no-fp32-forms', action='store_true', help='skip the sub-run with every float32 GEMM on the float32 MFMA')
     ap.add_argument('--no-other-configs', action='store_true',
-                    help='skip the short runs of BASELINE.json configs 3, 4, 5 (and the SE EfficientNets) that the default 1-GPU run attaches as `other_configs`')
-    return ap.parse_args()
+                    help='skip the short runs of BASELINE.json configs 3, 4, 5 (and the SE EfficientNets) that the 1-GPU --full run attaches as `other_configs`')
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
+    if a.warmup < 0:
+        ap.error('--warmup must not be negative')
+    if a.per_op and not a.full:
+        ap.error('--per-op is part of the --full measurements')
+    return a
+
+
+def dump_outputs(path, det, det_count):
+    """The step's packed detections (yoloret_hip.h: det [B, C*max_boxes, 6] int32 words = ymin, xmin, ymax, xmax (truncated
+    to int32), score (float32 bits), class (-1 in padding slots); det_count [B]) as .npy files a NumPy reader can compare."""
+    os.makedirs(path, exist_ok=True)
+    d = np.ascontiguousarray(det.cpu().numpy())
+    arrays = {'det_boxes': d[..., :4].astype(np.float64), 'det_scores': np.ascontiguousarray(d[..., 4]).view(np.float32),
+              'det_classes': d[..., 5].astype(np.float64), 'det_count': det_count.cpu().numpy().astype(np.float64)}
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), arr)
 
 
 # BASELINE.json's other single-GPU workloads (SURVEY.md 8(d) rows c3, c4, c5: the share of one GPU) and the reference's own
@@ -215,7 +245,7 @@ def fp32_mfma_forms(a):
     import subprocess
     env = dict(os.environ, YOLORET_MBR_SPLIT='0', YOLORET_PW_SPLIT='0', YOLORET_FUSE_HEAD='0', YOLORET_TUNE_CACHE='')
     cmd = [sys.executable, os.path.abspath(__file__), '--steps', '20', '--warmup', str(a.warmup), '--batch', str(a.batch), '--model', a.model, '--size', str(a.size),
-           '--classes', str(a.classes), '--no-cpu-baseline', '--no-latency', '--no-other-configs', '--no-fp32-forms', '--depth', str(a.depth)]
+           '--classes', str(a.classes), '--full', '--no-cpu-baseline', '--no-latency', '--no-other-configs', '--no-fp32-forms', '--depth', str(a.depth)]
     try:
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)
         d = json.loads(r.stdout.strip().splitlines()[-1])
@@ -442,9 +472,15 @@ def main():
         elapsed = float(t.item())
     ms_per_step = elapsed / a.steps * 1e3
     value = world * b * a.steps / elapsed
+    if rank == 0 and a.dump_outputs:
+        # the last timed step's detections as its consumer receives them (with N > 1: gathered over all ranks)
+        last_det, last_cnt = pending[0].wait()
+        torch.cuda.synchronize(dev)
+        dump_outputs(a.dump_outputs, last_det, last_cnt)
 
     out = None
-    if rank == 0:
+    full = {}     # --full: every figure beyond the headline
+    if rank == 0 and a.full:
         plan = model.plan
         n_boxes = pipe1.n
         alg_fwd = plan.algorithmic_bytes_per_image()
@@ -818,6 +854,23 @@ def main():
                                                    'the network-entry kernel reads the bytes (x/255 inside), no conversion launch'}
             except Exception as e:   # a model whose entry op has no uint8 form
                 incl_h2d['uint8_entry'] = {'error': str(e)[:200]}
+        full.update({'serial_steps': serial_steps, 'p50_ms_b1': p50, 'roofline': roofline, 'roofline_family': roofline_family,
+                     'roofline_step': roofline_step, 'incl_h2d': incl_h2d})
+        if p50 is not None:
+            full['p50_ms_b1_detail'] = {'eager_launches': p50_eager, 'hip_graph_replay': p50_graph}
+        if (world == 1 and not a.no_other_configs and not a.force_dist
+                and (a.model, a.size, a.batch, a.dtype) == ('mobilenetv2x75', 416, 64, 'f32')):
+            full['other_configs'] = other_configs(dev, anchors, a.classes, max(a.steps, 20), a.depth)
+        if world == 1 and a.dtype == 'f32' and not a.no_fp32_forms and not a.force_dist:
+            full['fp32_mfma_forms'] = fp32_mfma_forms(a)
+            # for a strict reader of `dtype: f32`: the headline's 1x1 convolutions run as three float16-plane products (22 bits per factor,
+            # float32-grade: DESIGN.md 4-5); with every GEMM on v_mfma_f32_16x16x4_f32 instead the same step gives
+            full['value_strict_fp32'] = full['fp32_mfma_forms'].get('img_s')
+            full['serial_strict_fp32'] = full['fp32_mfma_forms'].get('serial_img_s')
+        if world == 1 and not a.no_cpu_baseline:
+            full['cpu_baseline'] = cpu_baseline(a.model, a.size, a.classes, anchors, a.cpu_seconds,
+                                                gpu_logits=(lambda xs: [y.cpu().numpy() for y in model(torch.from_numpy(np.ascontiguousarray(xs)).to(dev))]) if a.dtype == 'f32' else None)
+    if rank == 0:
         out = {'metric': 'images/sec (+ p50 per-image ms) MobileNetV2-0.75x @416, 1/2/4/8 MI355X',
                'value': round(value, 1), 'unit': 'img/s', 'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup,
                'ms_per_step': round(ms_per_step, 4), 'higher_is_better': True, 'scaling': 'weak',
@@ -831,9 +884,7 @@ def main():
                                       + ('; %d steps in flight (each step = one whole batch on its own HIP stream and workspace)' % a.depth if a.depth > 1 else '')
                                       + ('; the -lite form = no squeeze-excite, ReLU6, and it KEEPS the width-scaled stem' if a.model.endswith('-lite') else ''),
                           'global_batch': b * world, 'parallelism': 'dp%d (image-sharded)' % world},
-               'steps_in_flight': a.depth, 'serial_steps': serial_steps, 'p50_ms_b1': p50, 'roofline': roofline, 'roofline_family': roofline_family, 'roofline_step': roofline_step, 'incl_h2d': incl_h2d}
-        if p50 is not None:
-            out['p50_ms_b1_detail'] = {'eager_launches': p50_eager, 'hip_graph_replay': p50_graph}
+               'steps_in_flight': a.depth}
         if use_dist:
             out['rccl_ranks'] = world
             out['per_rank_img_s'] = [round(b * a.steps / v, 1) for v in per_rank]
@@ -845,18 +896,7 @@ def main():
                                                  'bytes_per_rank': int(pipe.record.numel() * 4)}
         from yoloret_amd.pipeline import hw_queue_check
         out['hw_queues'] = hw_queue_check(dev)
-        if (world == 1 and not a.no_other_configs and not a.force_dist
-                and (a.model, a.size, a.batch, a.dtype) == ('mobilenetv2x75', 416, 64, 'f32')):
-            out['other_configs'] = other_configs(dev, anchors, a.classes, max(a.steps, 20), a.depth)
-        if world == 1 and a.dtype == 'f32' and not a.no_fp32_forms and not a.force_dist:
-            out['fp32_mfma_forms'] = fp32_mfma_forms(a)
-            # for a strict reader of `dtype: f32`: the headline's 1x1 convolutions run as three float16-plane products (22 bits per factor,
-            # float32-grade: DESIGN.md 4-5); with every GEMM on v_mfma_f32_16x16x4_f32 instead the same step gives
-            out['value_strict_fp32'] = out['fp32_mfma_forms'].get('img_s')
-            out['serial_strict_fp32'] = out['fp32_mfma_forms'].get('serial_img_s')
-        if world == 1 and not a.no_cpu_baseline:
-            out['cpu_baseline'] = cpu_baseline(a.model, a.size, a.classes, anchors, a.cpu_seconds,
-                                               gpu_logits=(lambda xs: [y.cpu().numpy() for y in model(torch.from_numpy(np.ascontiguousarray(xs)).to(dev))]) if a.dtype == 'f32' else None)
+        out.update(full)
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()

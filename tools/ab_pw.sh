@@ -1,13 +1,13 @@
 #!/bin/bash
 # c2 / c4 with the float32 pointwise convs in the split form (default) and on the float32 MFMA (YOLORET_PW_SPLIT=0).
-mkdir -p gpurun_out/ab
+mkdir -p "${AB_OUT:-ab_out}"; O=$(cd "${AB_OUT:-ab_out}" && pwd)   # output folder (AB_OUT, default ./ab_out)
 run() {
   local tag=$1; shift
   for sp in 1 0; do
     export YOLORET_PW_SPLIT=$sp
-    export YOLORET_TUNE_CACHE=$PWD/gpurun_out/ab/tuned_${tag}_pw$sp.json
-    python bench.py "$@" --no-cpu-baseline --no-latency --no-other-configs > gpurun_out/ab/${tag}_pw$sp.json 2> gpurun_out/ab/${tag}_pw$sp.err
-    python - gpurun_out/ab/${tag}_pw$sp.json $tag $sp <<'PY'
+    export YOLORET_TUNE_CACHE=$O/tuned_${tag}_pw$sp.json
+    python bench.py --full "$@" --no-cpu-baseline --no-latency --no-other-configs > $O/${tag}_pw$sp.json 2> $O/${tag}_pw$sp.err
+    python - $O/${tag}_pw$sp.json $tag $sp <<'PY'
 import json, sys
 try:
     d = json.load(open(sys.argv[1]))

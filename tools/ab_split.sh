@@ -1,13 +1,13 @@
 #!/bin/bash
 # c2 / c4 with YR_OP_MBR in its split form (default) and in the float32-MFMA form (YOLORET_MBR_SPLIT=0): img/s in flight and serial.
-mkdir -p gpurun_out/ab
+mkdir -p "${AB_OUT:-ab_out}"; O=$(cd "${AB_OUT:-ab_out}" && pwd)   # output folder (AB_OUT, default ./ab_out)
 run() {
   local tag=$1; shift
   for sp in 1 0; do
     export YOLORET_MBR_SPLIT=$sp
-    export YOLORET_TUNE_CACHE=$PWD/gpurun_out/ab/tuned_${tag}_sp$sp.json
-    python bench.py "$@" --no-cpu-baseline --no-latency --no-other-configs > gpurun_out/ab/${tag}_sp$sp.json 2> gpurun_out/ab/${tag}_sp$sp.err
-    python - gpurun_out/ab/${tag}_sp$sp.json $tag $sp <<'PY'
+    export YOLORET_TUNE_CACHE=$O/tuned_${tag}_sp$sp.json
+    python bench.py --full "$@" --no-cpu-baseline --no-latency --no-other-configs > $O/${tag}_sp$sp.json 2> $O/${tag}_sp$sp.err
+    python - $O/${tag}_sp$sp.json $tag $sp <<'PY'
 import json, sys
 try:
     d = json.load(open(sys.argv[1]))

@@ -1,13 +1,13 @@
 #!/bin/bash
 # c3 / c5 and the SE EfficientNets with the walking depthwise form (default) and with the tile walk (YOLORET_DW_WALK=0): img/s in flight and serial.
-mkdir -p gpurun_out/ab
+mkdir -p "${AB_OUT:-ab_out}"; O=$(cd "${AB_OUT:-ab_out}" && pwd)   # output folder (AB_OUT, default ./ab_out)
 run() {  # run <tag> <bench args...>
   local tag=$1; shift
   for walk in 1 0; do
     export YOLORET_DW_WALK=$walk
-    export YOLORET_TUNE_CACHE=$PWD/gpurun_out/ab/tuned_${tag}_$walk.json
-    python bench.py "$@" --no-cpu-baseline --no-latency --no-other-configs > gpurun_out/ab/${tag}_walk$walk.json 2> gpurun_out/ab/${tag}_walk$walk.err
-    python - gpurun_out/ab/${tag}_walk$walk.json $tag $walk <<'PY'
+    export YOLORET_TUNE_CACHE=$O/tuned_${tag}_$walk.json
+    python bench.py --full "$@" --no-cpu-baseline --no-latency --no-other-configs > $O/${tag}_walk$walk.json 2> $O/${tag}_walk$walk.err
+    python - $O/${tag}_walk$walk.json $tag $walk <<'PY'
 import json, sys
 try:
     d = json.load(open(sys.argv[1]))
