@@ -578,3 +578,61 @@ def test_nosplit_names_hold_in_every_plan_variant():
         assert not ({o.name: o for o in plan.ops}['block_12_mbe'].k & 0x80)
     finally:
         C.FUSE_MBK = saved
+
+
+@pytest.mark.parametrize('hoist', [True, False])
+def test_head_stream_form_takes_only_identity_or_pooled_sources(monkeypatch, hoist):
+    """The weight-streaming head form (headstream.hip, YR_OP_HEAD with k bits 5 and 6) gathers identity and max-pooled sources, plus
+    at most a trailing up-sampled addend; yr_launch_head_stream refuses anything else.  The compiler's guard must hold on every head it
+    streams - with the up-sampling hoisted into the previous op (the default) and without (where td3 sees two up2 sources) - over the
+    models and sizes the product compiles."""
+    from yoloret_amd import compiler
+    from yoloret_amd import layers as L
+    from yoloret_amd import runtime as rt
+    monkeypatch.setattr(compiler, 'HOIST_UPSAMPLE', hoist)
+    streamed = 0
+    for name in ('mobilenetv2x75', 'mobilenetv2x14', 'efficientnetb0-lite'):
+        for size in range(96, 609, 32):
+            for policy in ('float32', 'mixed_bfloat16'):
+                L.set_global_policy(policy)
+                try:
+                    plan = _model(name, size).plan
+                finally:
+                    L.set_global_policy('float32')
+                for o in plan.ops:
+                    if o.kind == rt.OP_HEAD and (o.k & 0x60) == 0x60:
+                        streamed += 1
+                        xs = [s.xform for s in o.srcs]
+                        body = xs[:-1] if xs[-1] == 'up2_add' else xs
+                        assert all(x in ('identity', 'maxpool2') for x in body), (name, size, policy, o.name, xs)
+    assert streamed > 0
+
+
+def test_autotune_candidate_mirror_matches_the_library():
+    """tests/util.py restates yr_autotune's candidate lists (what the tuning-table tests of tests/test_gpu_invariance.py try per op);
+    they must be the lists runtime.hip holds, and the pointwise config counts those of pointwise.hip / pointwise_h.hip."""
+    from tests import util as U
+    csrc = os.path.join(ROOT, 'yoloret_amd', 'csrc')
+    src = open(os.path.join(csrc, 'runtime.hip')).read()
+
+    def pairs(name):
+        body = re.search(r'static const int %s\[\]\[2\] = \{(.*?)\};' % name, src, re.S).group(1)
+        return [(int(a), int(b)) for a, b in re.findall(r'\{\s*(\d+)\s*,\s*(\d+)\s*\}', body)]
+
+    assert pairs('tiles') == U.AUTOTUNE_MBH_TILES
+    assert pairs('chained') == U.AUTOTUNE_MBH_CHAINED
+    segs = re.search(r'static const int segs_list\[\] = \{(.*?)\};', src, re.S).group(1)
+    assert [int(v) for v in segs.split(',')] == U.AUTOTUNE_MBR_SEGS
+    pw = open(os.path.join(csrc, 'pointwise.hip')).read()
+    assert int(re.search(r'int yr_pointwise_num_cfgs\(int dtype\) \{ return dtype == YR_F32 \? (\d+) : yr_pwh_num_cfgs\(\); \}', pw).group(1)) == U.PW_NUM_CFGS[0]
+    ph = open(os.path.join(csrc, 'pointwise_h.hip')).read()
+    assert re.search(r'int yr_pwh_num_cfgs\(\) \{ return PWH_NCFG \+ PWH_NWALK \+ PWH_NSQ; \}', ph)
+    ncfg = len(re.findall(r'\{\s*\d+\s*,\s*\d+\s*\}', re.search(r'static const PwhCfg pwh_cfgs\[\] = \{(.*?)\};', ph, re.S).group(1)))
+    nwalk = int(re.search(r'constexpr int PWH_NWALK = (\d+);', ph).group(1))
+    nsq = int(re.search(r'constexpr int PWH_NSQ = (\d+);', ph).group(1))
+    assert ncfg + nwalk + nsq == U.PW_NUM_CFGS[1] == U.PW_NUM_CFGS[2]
+    # ... and the tuner skips exactly the forms the mirror skips
+    assert 'if (h->ops[i].dtype == YR_F32 && (h->ops[i].se_reduced & 0x40000)) continue;' in src
+    assert 'if (h->ops[i].kind == YR_OP_MBR && (h->ops[i].k & 0x40)) continue;' in src
+    assert 'if (segs_list[c] > h->ops[i].h) continue;' in src and 'best_cfg = (base & 0xff00) | (segs_list[c] << 16)' in src
+    assert 'const int cfg = c < 0 ? 0 : (cand[c][0] << 8) | (cand[c][1] << 16);' in src

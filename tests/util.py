@@ -96,3 +96,59 @@ def entry_on_matrix_pipe(model):
     rt = _rt()
     op = model.plan.ops[0]
     return model.plan.dtype != 0 and op.kind == rt.OP_STEMBLOCK and ('scale' in op.params or ((op.k >> 8) & 0xff) == 1)
+
+
+# ---- whole-plan invariance helpers (tests/test_gpu_invariance.py)
+# Byte patterns a workspace is poisoned with: 0xFF is a NaN in float32, float16 and bfloat16; 0x7B a large finite value in all three
+# (float16 61280, float32 / bfloat16 about 1.3e36); 'random' seeded random bytes (any mixture of the above, subnormals, infinities).
+POISON_PATTERNS = (0xFF, 0x7B, 'random')
+
+
+def poison_workspace(model, device_index, ctx=0, pattern=0xFF, seed=0):
+    """Fills the WHOLE workspace tensor of execution context `ctx` (Model.__call__: `_workspace[idx]`, or `[(idx, ctx)]` for ctx > 0)
+    with one byte pattern - the arena, its unwritten padding lanes and the squeeze-excite arrival counters behind it (which the runtime
+    clears at the start of every pass).  Enqueued on the current stream."""
+    ws = model._workspace[device_index if ctx == 0 else (device_index, ctx)]
+    if pattern == 'random':
+        g = torch.Generator(device=ws.device)
+        g.manual_seed(seed)
+        ws.random_(0, 256, generator=g)
+    else:
+        ws.fill_(int(pattern))
+    return ws
+
+
+def nan_outputs(model, b):
+    """float32 output tensors for a batch of `b` images filled with NaN, for Model.__call__(x, out=...): an output element a plan
+    does not write stays NaN."""
+    dev = torch.device('cuda', torch.cuda.current_device())
+    return [torch.full((b, ob.h, ob.w, ob.c), float('nan'), dtype=torch.float32, device=dev) for ob in model.plan.output_bufs]
+
+
+# ---- yr_autotune's candidate lists (yoloret_amd/csrc/runtime.hip), restated: tests/test_host_logic.py checks them against the source.
+# Only these entries are dispatched by the tuner, so only these are what a tuning table can hold in practice.
+AUTOTUNE_MBH_TILES = [(4, 8), (8, 4), (7, 4), (7, 8), (8, 8), (13, 4), (4, 16), (8, 16), (7, 16), (13, 8),
+                      (16, 8), (13, 16), (8, 12), (7, 12), (13, 12), (16, 12), (16, 16), (4, 12), (6, 8)]     # (th, tw)
+AUTOTUNE_MBH_CHAINED = [(255, 1), (255, 2), (255, 3), (255, 4), (255, 6)]       # the register-chained form: (255, row segments)
+AUTOTUNE_MBR_SEGS = [0, 1, 2, 3, 4, 6, 8, 13, 18, 26]                           # row segments per strip of YR_OP_MBR / YR_OP_MBE
+PW_NUM_CFGS = {0: 29, 1: 26, 2: 26}        # == yr_pointwise_num_cfgs(dtype): entries 0 .. n are valid for a pointwise op
+
+
+def autotune_candidates(op):
+    """The non-default tuning entries yr_autotune times for plan op `op` ([] for an op it does not tune).  For YR_OP_MBH / YR_OP_MBX
+    both lists are returned as ('chained', [...]) / ('tiles', [...]): which one applies (yr_mbh_prefers_chained) is the library's
+    choice by shape, which the caller finds by whether the op takes a chained entry."""
+    rt = _rt()
+    if op.kind == rt.OP_POINTWISE:
+        if op.dtype == 0 and op.se_reduced & 0x40000:       # the pixel-stationary form: nothing to tune
+            return []
+        return list(range(1, PW_NUM_CFGS[op.dtype] + 1))
+    if op.kind == rt.OP_MBR and op.k & 0x40:                # the weight-streaming block form: nothing to tune
+        return []
+    if op.kind in (rt.OP_MBR, rt.OP_MBE):
+        base = op.k & 0xffff
+        return [(base & 0xff00) | (s << 16) for s in AUTOTUNE_MBR_SEGS if 0 < s <= op.h]
+    if op.kind in (rt.OP_MBH, rt.OP_MBX):
+        return [('chained', [th << 8 | tw << 16 for th, tw in AUTOTUNE_MBH_CHAINED]),
+                ('tiles', [th << 8 | tw << 16 for th, tw in AUTOTUNE_MBH_TILES])]
+    return []

@@ -1109,7 +1109,9 @@ def fuse_head_blocks(ops, bufs, output_buf_ids, nosplit=frozenset(), stream_ok=T
         # (... and, with up to four workgroups sharing an (image, strip, segment) by runs of tile pairs, td1 - 7 chunks, a pooled source: 52 -> 37 us; bu1 -
         #  11 chunks - stays: 42 | 40)
         hs_shape = HEAD_STREAM_ONLY or (20 <= d.h <= 30 and d.w <= 28 and nk >= 5) or (d.h < 20 and d.w <= 14 and 5 <= nk <= 8)
-        stream = (HEAD_STREAM and stream_ok and hs_shape and not SE_TAIL and (not HEAD_STREAM_ONLY or bname_h in HEAD_STREAM_ONLY)      # (the opt-in SE tail lives in the older forms) and all(s_.xform in ('identity', 'maxpool2', 'up2_add') for s_ in c.srcs)
+        # (not SE_TAIL: the opt-in SE tail lives in the older forms)
+        stream = (HEAD_STREAM and stream_ok and hs_shape and not SE_TAIL and (not HEAD_STREAM_ONLY or bname_h in HEAD_STREAM_ONLY)
+                  and all(s_.xform in ('identity', 'maxpool2', 'up2_add') for s_ in c.srcs)
                   and all(s_.xform != 'up2_add' for s_ in c.srcs[:-1]) and 1 <= len(ksrc) <= 3 and F % 32 == 0 and c.act in ('relu6', 'none')
                   and nk <= (7 if head_stream_geometry(d.h, d.w)[0] == 2 else 11) and not (c.gate is not None and (len(ksrc) != 1 or ksrc[0].xform != 'identity'))
                   and all(s_.buf.ld % 4 == 0 for s_ in ksrc)
