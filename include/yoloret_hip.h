@@ -69,7 +69,7 @@ typedef enum {
      * the loads of its projection (MobileNetV2 block_* [3P] depthwise + project; efficientnet.py:501-533).  The
      * depthwise result (the block's widest tensor besides the expand output) never reaches HBM; values are
      * bit-identical to a DEPTHWISE op followed by the same POINTWISE op.  Op fields: src[0] = the depthwise INPUT
-     * (its h, w), op.h/op.w = the depthwise OUTPUT dims, se_reduced = stride | (yr_act of the depthwise stage << 8),
+     * (its h, w), op.h/op.w = the depthwise OUTPUT dims, se_reduced = stride | (yr_act of the depthwise stage << YR_PWDW_ACT_SHIFT),
      * wgt2 = depthwise weights [9][ld], b1 / b2 = its folded BN scale / shift [ld], ld = round_up(src.c, 4). */
     YR_X_DW3 = 5
 } yr_xform;
@@ -93,20 +93,20 @@ typedef enum {
                             wgt2 = the same parameters packed per channel PAIR, [round_up(cout,4)/2][27 taps x 2, times the BN
                             scale | 1 1 | BN shift 2] (STEMBLOCK's stem layout): selects the scalar-operand kernel */
     YR_OP_POINTWISE = 2, /* Conv2D 1x1 (+bias)(+BN)(+act)(+residual)  (model.py:25-30,98-114,152-155,243-251; efficientnet.py:485-496,517-533)
-                            se_reduced flag bits (no depthwise-folded source): float32 ops, bit 16 = keep the float32 MFMA (not the
-                            float16-plane split form); bit 17 (round 5, no layout change) = the k-split form of the split kernel - a
+                            se_reduced flags YR_PWF_* (no depthwise-folded source): float32 ops, YR_PWF_F32_MFMA = keep the float32 MFMA (not the
+                            float16-plane split form); YR_PWF_KSPLIT (round 5, no layout change) = the k-split form of the split kernel - a
                             workgroup is one 16 x 16 output tile, its four waves split the k range (pointwise_split.hip: pwk_kernel; 16-bit ops:
                             one 16 x 32 tile, pointwise_h.hip: pwkh_kernel);
                             what the compiler's plan for one or two images asks of maps up to 32 x 32.  The form groups the sums by wave: it
                             belongs to the plan, not to the tuner (yr_op.k is not looked at); ignored below 64 input channels.
-                            bit 18 (ABI 9, float32 ops without bit 16 / 17; identity | up2 sources, no residual / up2_add, act none | ReLU6,
+                            YR_PWF_STATIONARY (ABI 9, float32 ops without YR_PWF_F32_MFMA / YR_PWF_KSPLIT; identity | up2 sources, no residual / up2_add, act none | ReLU6,
                             k space <= 384 channels): the PIXEL-STATIONARY form (pointwise_stream.hip) - `wgt` is NOT Wt[cout][kp] but its float16
                             planes in MFMA fragment order, [ceil(cout / 16)][NK][2 planes h | m][64 lanes][8 halves] as float32 words with
                             NK = yr_pwt_chunks(kp) chunks of 32 channels (lane (m, g) of tile t, chunk c: W[16 t + m][32 c + 8 g + i], zero
                             beyond cout / kp; h = f16(w), m = f16((w - h) 2^11): compiler.head_pack).  Results are bit-identical to the tiled
-                            split kernel's.  bit 19 (with bit 18): TWO outputs - a second 1x1 conv of the same (gated) single identity source in
+                            split kernel's.  YR_PWF_TWO_OUT (with YR_PWF_STATIONARY): TWO outputs - a second 1x1 conv of the same (gated) single identity source in
                             the same launch: gate_out / gate_out_buf / gate_out_ld = its output (float32), se_hidden = its couts,
-                            reserved0 = its yr_act | pooled << 8 (MaxPooling2D(2) of its result, like stride = 2 for the first); its cout tiles
+                            reserved0 = its yr_act | YR_PW2_POOLED (MaxPooling2D(2) of its result, like stride = 2 for the first); its cout tiles
                             follow the first output's in `wgt`, and scale / shift are [16 (tiles of the first + tiles of the second)]
                             floats, each output's values padded to a multiple of 16. */
     YR_OP_DEPTHWISE = 3, /* DepthwiseConv2D k3/k5 s1/s2 SAME + BN + act (model.py:20-24; efficientnet.py:501-510).  With `gate` set (SE
@@ -138,7 +138,7 @@ typedef enum {
                             taps times the BN scale | BN shift;  b1 = project Wt[COP][C1P] as dtype;  b2 = project BN [2][COP] */
     YR_OP_MBH = 11,      /* the MBCONV block on 16-bit activations, both 1x1 convs on bf16 / f16 MFMA, depthwise K = 3 | 5 from an
                             LDS tile (dtype must be YR_BF16 / YR_F16; cin, cout <= 128).  se_reduced = Cexp; k = K, optionally
-                            | th << 8 | tw << 16 to force the output tile.  CexpP = round_up(Cexp,32), KP = round_up(cin,32),
+                            | th << YR_MBH_TH_SHIFT | tw << YR_MBH_TW_SHIFT to force the output tile.  CexpP = round_up(Cexp,32), KP = round_up(cin,32),
                             zero padded: wgt = expand Wt[CexpP][KP] (16-bit); wgt2 = [K*K + 4][CexpP] float32: depthwise taps |
                             depthwise BN scale | shift | expand BN scale | shift;
                             b1 = project Wt[cout][CexpP] (16-bit); b2 = project BN scale ++ shift, [round_up(cout,8)] each;
@@ -163,7 +163,7 @@ typedef enum {
                             in registers) -> the depthwise result registers ARE the projection MFMAs' B operand.  The expanded tensor
                             never leaves the register file; the waves of a workgroup split the expanded channels and add their partial
                             projections through LDS.  dtype = YR_F32; act = YR_ACT_RELU6; cin % 16 in {0, 8}; se_reduced = Cexp, a
-                            multiple of 16; cout % 4 == 0; k = 3 | nw << 8 | segs << 16 (nw: waves per workgroup, segs: row segments
+                            multiple of 16; cout % 4 == 0; k = 3 | nw << YR_MBR_NW_SHIFT | segs << YR_MBR_SEGS_SHIFT (nw: waves per workgroup, segs: row segments
                             per strip; 0 = the library's choice); res (optional) = the block input.  T = Cexp / 16 expanded tiles,
                             TO = ceil(cout / 16), KE = cin / 4 expand steps; scale / shift / b1 unused:
                             wgt  = MFMA A fragments [T][KE + 4 TO][64 lanes]; register rho of lane l (m = l % 16, g = l / 16) of tile j:
@@ -172,19 +172,19 @@ typedef enum {
                                    rho = KE + 4 t + s: Wp[16 t + m][16 j + 4 g + s] x project BN scale (0 for 16 t + m >= cout);
                             wgt2 = [T][11][16]: the nine depthwise taps (ky, kx) x depthwise BN scale | depthwise BN shift | expand BN shift;
                             b2   = project BN shift [16 TO].
-                            k bit 7 (0x80) = the SPLIT form (ABI 6): both 1x1 convolutions on the 16-bit matrix pipe with float32-grade operands -
+                            k & YR_MBR_SPLIT = the SPLIT form (ABI 6): both 1x1 convolutions on the 16-bit matrix pipe with float32-grade operands -
                             every float32 value as two float16 planes, x = h + 2^-11 m, three MFMAs per product (mbr.hip "SPLIT form") -; then
                             wgt  = the float32 words holding [T][ceil(cin / 32)][2 planes][64 lanes][8 halves] (lane (m, g), step c:
                                    We[16 j + m][32 c + 8 g + i] x BN scale, zero beyond cin) followed by, per expanded-tile pair (tA, tB) of the nw
                                    waves in order (a wave pairs ITS tiles, an odd last one with nothing), [TO][2 planes][64][8]:
                                    Wp[16 t + m][16 tA + 4 g + i] (i < 4) | Wp[16 t + m][16 tB + 4 g + i - 4]; nw must be what the fragments were
                                    packed for (yoloret_amd.compiler.mbs_pack).  Precondition: |block input| < 65504 (undefined beyond: NaN or a ReLU6-clamped value).
-                            k bits 6 AND 7 (0xc0) = the WEIGHT-STREAMING form (ABI 8; mbk.hip): the same block in ONE launch where the fragments of both
+                            k & (YR_MBR_STREAM | YR_MBR_SPLIT), both = the WEIGHT-STREAMING form (ABI 8; mbk.hip): the same block in ONE launch where the fragments of both
                             convolutions do not fit a CU's register file (MobileNetV2 x0.75 block_7..15, reference [3P] via code/yolo3/override.py:290-341).
                             The pixels are stationary - a wave owns `rows` (1 | 2) input rows of a 16-column strip and the projection accumulators of
                             its output rows for the whole kernel - and the weights stream through LDS one pair of expanded tiles at a time (LDS-direct
                             buffer loads, three chunk buffers); the neighbour rows of the vertical taps are exchanged between waves through LDS, one
-                            barrier per pair.  k = 3 | 0xc0 | nw << 8 | rows << 16 (both fixed by the plan: nothing is tuned, the sums are grouped by
+                            barrier per pair.  k = 3 | YR_MBR_STREAM | YR_MBR_SPLIT | nw << YR_MBR_NW_SHIFT | rows << YR_MBR_SEGS_SHIFT (both fixed by the plan: nothing is tuned, the sums are grouped by
                             the shape alone); wgt2 unused;
                             wgt  = ceil(T / 2) chunks of (4 ceil(cin / 32) + 2 TO) KB + 2 KB: chunk q = pair (2 q, 2 q + 1) =
                                    [2 tiles][ceil(cin / 32)][2 planes][64 lanes][8 halves] expand fragments (as above) |
@@ -198,9 +198,9 @@ typedef enum {
                             BN + ReLU6 - in YR_OP_MBR's register-chained form (mbr.hip: mbe_kernel), for blocks whose weights do not fit
                             one CU's register file (MobileNetV2 x0.75 block_11 on): every wave walks a strip segment for a few expanded
                             tiles and stores the depthwise map; the expand output never exists, the projection stays a POINTWISE op.
-                            src[0] = block input (cin % 16 in {0, 8}); cout = Cexp (multiple of 16); k = 3 | segs << 16; act = RELU6;
+                            src[0] = block input (cin % 16 in {0, 8}); cout = Cexp (multiple of 16); k = 3 | segs << YR_MBR_SEGS_SHIFT; act = RELU6;
                             wgt = expand A fragments [T][KE][64] (YR_OP_MBR's register order, rho < KE); wgt2 = [T][11][16] as YR_OP_MBR.
-                            k bit 7 = the split form (see YR_OP_MBR): wgt = the float32 words holding [T][ceil(cin / 32)][2 planes][64][8 halves].
+                            k & YR_MBR_SPLIT = the split form (see YR_OP_MBR): wgt = the float32 words holding [T][ceil(cin / 32)][2 planes][64][8 halves].
                             Built for cin in {48, 72, 88, 120, 136, 224} (the split form: all but 224) */
     YR_OP_HEAD = 15,     /* ABI 7: the first two thirds of a detection-head block (model.py:91-115: Conv2D 1x1 + BN + ReLU6 -> MBConvBlock's
                             depthwise 3x3 + BN + Swish [-> SE]) in one launch, float32 (headblock.hip): the 1x1 convolution as YR_OP_POINTWISE's
@@ -209,25 +209,25 @@ typedef enum {
                             one-pixel halo, the F-wide conv output kept in LDS, the depthwise conv (stride 1, TF SAME) computed from there,
                             stored, and - with the SE-tail fields below - summed per channel.  The F-wide conv output never reaches HBM.
                             h, w = the map (conv and depthwise output alike); cin = sum of src[].c; cout = F; act = the depthwise activation;
-                            k = 3 | conv activation << 8; stride = 1; wgt = Wt[F][kp], scale / shift [F] (conv BN) as POINTWISE;
-                            k bit 7 (0x80): wgt = the float32 words holding float16 planes in fragment order instead,
+                            k = 3 | conv activation << YR_HEAD_ACT_SHIFT; stride = 1; wgt = Wt[F][kp], scale / shift [F] (conv BN) as POINTWISE;
+                            k & YR_HEAD_PLANES: wgt = the float32 words holding float16 planes in fragment order instead,
                             [ceil(F / 16)][NK][2 planes][64 lanes][8 halves] with the k space cut into chunks of 32 channels PER SOURCE (NK =
                             sum of ceil(src.c / 32); lane (m = l % 16, g = l / 16) of cout tile t, chunk j of source s: W[16 t + m][channel
                             32 j + 8 g + i of s], zero beyond the source / beyond F; h plane, then m = f16((w - h) 2^11)) - the LDS-direct
                             kernel (identity / up-sampled sources only; yoloret_amd.compiler.head_pack);
                             wgt2 = float32 [10][round_up(F, 4)]: the nine depthwise taps (ky, kx) x depthwise BN scale | depthwise BN shift.
-                            k bit 6 (0x40): the WALKING form (headwalk.hip: a wave walks a strip of 16 columns with the weights of its cout tiles
+                            k & YR_HEAD_WALK: the WALKING form (headwalk.hip: a wave walks a strip of 16 columns with the weights of its cout tiles
                             in registers - YR_OP_MBE's scheme; identity sources only, at most 7 chunks of 32 channels, F % 16 == 0, conv
-                            activation ReLU6 / none): wgt = the planes of bit 7 WITH the conv's BN scale folded in, scale = that BN scale [F],
+                            activation ReLU6 / none): wgt = the planes of YR_HEAD_PLANES WITH the conv's BN scale folded in, scale = that BN scale [F],
                             shift unused, wgt2 = [F / 16][11][16]: depthwise taps x BN scale | depthwise BN shift | conv BN shift (YR_OP_MBR's
                             table); se_reduced = yr_head_walk_rows(h, w).
-                            k bits 5 AND 6 (0x60; ABI 8): the WEIGHT-STREAMING form (headstream.hip; float32 plans): the pixels of a wave's one or two
+                            (k & YR_HEAD_STREAM) == YR_HEAD_STREAM (ABI 8): the WEIGHT-STREAMING form (headstream.hip; float32 plans): the pixels of a wave's one or two
                             rows of a 16-column strip stay in registers over the whole k space (gathered once: identity or 2 x 2 max-pooled
                             sources, the single source's SE gate), the conv's output channels stream past them in pairs of tiles through LDS.
-                            Parameters exactly as bit 6 alone; one to three k-space sources (YR_X_IDENTITY | YR_X_MAXPOOL2) + an optional
+                            Parameters exactly as YR_HEAD_WALK alone; one to three k-space sources (YR_X_IDENTITY | YR_X_MAXPOOL2) + an optional
                             YR_X_UP2_ADD last; at most 11 chunks of 32 channels on maps below 20 rows, 7 otherwise; F % 32 == 0; no SE tail;
                             se_reduced = yr_head_stream_rows(h, w) (one row of sums per strip, row segment and wave).
-                            16-BIT PLANS (dtype = out_dtype = bf16 | f16; headwalk_h.hip): the walking form only (k bit 6) - identity sources
+                            16-BIT PLANS (dtype = out_dtype = bf16 | f16; headwalk_h.hip): the walking form only (YR_HEAD_WALK) - identity sources
                             of the op's type (ld % 8 == 0), optionally a float32 YR_X_UP2_ADD last source, at most 8 chunks of 32 channels,
                             F % 128 == 0; wgt = the conv's 16-bit weights in fragment order [F / 16][NK][64 lanes][8] WITHOUT the BN scale
                             (yoloret_amd.compiler.head_pack16), scale = conv BN scale [F] float32, wgt2 as above; float32 from the
@@ -235,7 +235,7 @@ typedef enum {
                             those of the stored values; an SE gate (res) is folded into the stationary weights (w * g rounded once);
                             no SE tail (gate_out must be null).
                             res / res_ld (optional) = the float32 SE gate vector [B][res_ld] multiplied onto the single identity source on load
-                            (`gate` is taken by the sums this op writes); k bits 16-23 (optional) = cout tiles of 16 per workgroup.
+                            (`gate` is taken by the sums this op writes); k & YR_HEAD_TILES_MASK (optional) = cout tiles of 16 per workgroup.
                             SE tail: gate = OUTPUT float32 [B][se_reduced][gate_ld] channel sums, one row per region (se_reduced = regions per
                             image: yr_head_regions()) */
     YR_OP_MBX = 12       /* the first two thirds of an MBConv block WITH squeeze-excite (efficientnet.py:406-536), 16-bit
@@ -247,6 +247,58 @@ typedef enum {
                             per output tile, unused rows zeroed (se_reduced = rows >= tiles per image: the buffer is sized
                             for the smallest tile the host may pick, 4 x 8, or 4 x 4 on maps under 1000 pixels); SE_FC (k = H*W) adds the rows up; the projection stays a POINTWISE op */
 } yr_op_kind;
+
+/* ---- LAUNCH-FORM BITS: every sub-field and flag that is packed into yr_op.k, yr_op.se_reduced and yr_op.reserved0, per op kind.
+ * (yoloret_amd/runtime.py mirrors this block name by name, without the YR_ prefix; tests/test_host_logic.py compares the two.)
+ * A name of one op kind means nothing on another: the same bit of `k` is a different form there.  A *_MASK selects its field in
+ * place, the field's value is (x & *_MASK) >> *_SHIFT. */
+/* YR_OP_POINTWISE, se_reduced of an op WITHOUT a depthwise-folded source (float32 ops unless stated): */
+#define YR_PWF_F32_MFMA     0x10000    /* bit 16: keep the float32 MFMA (not the float16-plane split form) */
+#define YR_PWF_KSPLIT       0x20000    /* bit 17: the k-split form of the split kernel (float32 and 16-bit ops) */
+#define YR_PWF_STATIONARY   0x40000    /* bit 18: the pixel-stationary form - `wgt` holds float16 planes in fragment order */
+#define YR_PWF_TWO_OUT      0x80000    /* bit 19 (with bit 18): two outputs */
+/* YR_OP_POINTWISE, se_reduced of an op WITH a YR_X_DW3 source = the depthwise stage's stride | its yr_act << 8: */
+#define YR_PWDW_STRIDE_MASK 0xff
+#define YR_PWDW_ACT_SHIFT   8
+#define YR_PWDW_ACT_MASK    0xff00
+/* YR_OP_POINTWISE, reserved0 of a two-output op = the second output's yr_act | pooled flag: */
+#define YR_PW2_ACT_MASK     0xff
+#define YR_PW2_POOLED       0x100      /* bit 8: MaxPooling2D(2) of the second output's result */
+/* YR_OP_MBR / YR_OP_MBE, k = kernel size | form flags | nw << 8 | segs (weight-streaming form: rows) << 16: */
+#define YR_MBR_K_MASK       0x3f       /* the depthwise kernel size (3) */
+#define YR_MBR_STREAM       0x40       /* bit 6 (MBR only, with YR_MBR_SPLIT): the weight-streaming form (mbk.hip) */
+#define YR_MBR_SPLIT        0x80       /* bit 7: the split form - float16-plane fragments */
+#define YR_MBR_FORM_MASK    0xff       /* kernel size and form flags: the byte that belongs to the plan, never to a tuning word */
+#define YR_MBR_NW_SHIFT     8          /* waves per workgroup (0 = the library's choice) */
+#define YR_MBR_NW_MASK      0xff00
+#define YR_MBR_SEGS_SHIFT   16         /* row segments per strip (0 = the library's choice); weight-streaming form: rows per wave */
+#define YR_MBR_SEGS_MASK    0xff0000
+/* YR_OP_HEAD, k = kernel size | form flags | the conv's yr_act << 8 | cout tiles per workgroup << 16: */
+#define YR_HEAD_K_MASK      0x1f       /* the depthwise kernel size (3) */
+#define YR_HEAD_STREAM_BIT  0x20       /* bit 5: only together with YR_HEAD_WALK (= YR_HEAD_STREAM) */
+#define YR_HEAD_WALK        0x40       /* bit 6: the walking form (headwalk.hip, headwalk_h.hip) */
+#define YR_HEAD_PLANES      0x80       /* bit 7: `wgt` holds float16 planes in fragment order (the LDS-direct kernel) */
+#define YR_HEAD_STREAM      (YR_HEAD_WALK | YR_HEAD_STREAM_BIT)   /* bits 5 and 6: the weight-streaming form (headstream.hip) */
+#define YR_HEAD_ACT_SHIFT   8          /* yr_act of the 1x1 convolution (yr_op.act is the depthwise stage's) */
+#define YR_HEAD_ACT_MASK    0xff00
+#define YR_HEAD_TILES_SHIFT 16         /* cout tiles of 16 per workgroup (0 = the library's choice) */
+#define YR_HEAD_TILES_MASK  0xff0000
+/* YR_OP_MBH / YR_OP_MBX, k = kernel size | th << 8 | tw << 16 (the forced output tile; 0 = the library's choice): */
+#define YR_MBH_K_MASK       0xff       /* the depthwise kernel size (3 | 5) */
+#define YR_MBH_TH_SHIFT     8
+#define YR_MBH_TH_MASK      0xff00
+#define YR_MBH_TW_SHIFT     16
+#define YR_MBH_TW_MASK      0xff0000
+#define YR_MBH_TILE_LDS     254        /* th: force the LDS-tiled kernels' own choice (mbh.hip, mbn_h.hip), never the register-chained forms */
+#define YR_MBH_TILE_CHAINED 255        /* th: force the register-chained kernel (mbxr_h.hip); tw = row segments */
+/* YR_OP_STEMBLOCK, k = kernel size | entry form << 8: */
+#define YR_STEMBLOCK_K_MASK      0xff
+#define YR_STEMBLOCK_ENTRY_SHIFT 8
+#define YR_STEMBLOCK_ENTRY_MASK  0xff00
+#define YR_STEMBLOCK_ENTRY_MFMA  1     /* entry form: the matrix-pipe form of the stem + depthwise entry */
+/* The tuning word of an op (yr_set_tuning / yr_get_tuning) uses the positions of that op kind's `k`: MBH / MBX th << YR_MBH_TH_SHIFT |
+ * tw << YR_MBH_TW_SHIFT, MBR / MBE nw << YR_MBR_NW_SHIFT | segs << YR_MBR_SEGS_SHIFT, the low byte zero.
+ * ---- end of the launch-form bits */
 
 /* One fused operation.  Weight-like fields are float offsets into the weight
  * blob in plan ops (`wgt_off` etc.), or device pointers in yr_op_* calls. */
@@ -292,7 +344,7 @@ typedef struct {
      * k = h * w reading `gate` would have written (same values to float32 rounding), without the launch. */
     float* gate_out;  int32_t gate_out_buf;  int32_t gate_out_ld;   /* float32 [B][gate_out_ld], gate_out_ld >= round_up(cout, 4) */
     int32_t se_hidden;    /* hidden width R of the FC pair */
-    int32_t reserved0;    /* a two-output POINTWISE op (se_reduced bit 19): the second output's yr_act | pooled << 8; else 0 */
+    int32_t reserved0;    /* a two-output POINTWISE op (YR_PWF_TWO_OUT): the second output's yr_act | YR_PW2_POOLED; else 0 */
     const float* se_w;  int64_t se_w_off;   /* W1 [ldc][R4] (Keras kernel [1,1,C,R], rows padded to R4 = round_up(R, 4)) | W2 [R][ldc] | b1 [R4] | b2 [ldc], ldc = round_up(cout, 4) */
     uint32_t* sync;       /* [batch] arrival counters: zero before the launch, zero again after it.  Plan ops: assigned by yr_forward
                              from the tail of the workspace (cleared at the start of every pass); yr_op_run: the caller's */
@@ -350,8 +402,8 @@ int yr_forward_profile(yr_handle* h, const float* images, int batch, float* y1, 
                        void* workspace, size_t workspace_bytes, void* stream, int iters,
                        float* ms_per_op, const char** kernel_names);
 /* The same pass, instrumented: max_abs_per_op[n_ops] (host) receives the largest |value| among the float32 k-space sources each op
- * reads (+inf where a NaN was seen; 0 for ops without such sources).  A float32 plan's SPLIT-form ops (POINTWISE without se_reduced bit
- * 16, MBR / MBE with k bit 7, HEAD) carry their operands as two float16 planes and need |x| < 65504 - the reference's float32
+ * reads (+inf where a NaN was seen; 0 for ops without such sources).  A float32 plan's SPLIT-form ops (POINTWISE without
+ * YR_PWF_F32_MFMA, MBR / MBE with YR_MBR_SPLIT, HEAD) carry their operands as two float16 planes and need |x| < 65504 - the reference's float32
  * convolutions have no such bound (model.py:20-30; MobileNetV2's linear bottlenecks and residual sums are unclamped, override.py:290-341).
  * yoloret_amd's Model runs this once per set of weights on its first batch and rebuilds the plan with the ops beyond 60000 on the
  * float32-MFMA forms (Model.check_ranges); a host without it does the same through this call.  Synchronises the stream. */
@@ -363,7 +415,7 @@ int yr_forward_ranges(yr_handle* h, const float* images, int batch, float* y1, f
 int yr_autotune(yr_handle* h, const float* images, int batch, float* y1, float* y2, float* y3,
                 void* workspace, size_t workspace_bytes, void* stream, int iters);
 /* The autotuned table for `batch`: one int per plan op - POINTWISE: 0 = heuristic, else the 1-based tile shape;
- * MBH, MBX: 0 = heuristic, else the output tile as th << 8 | tw << 16; every other op kind: 0.  yr_get_tuning returns YR_ERR_STATE if that batch has not been tuned; yr_set_tuning installs a table
+ * MBH, MBX: 0 = heuristic, else the output tile as th << YR_MBH_TH_SHIFT | tw << YR_MBH_TW_SHIFT; every other op kind: 0.  yr_get_tuning returns YR_ERR_STATE if that batch has not been tuned; yr_set_tuning installs a table
  * saved from an earlier run (tune once, deploy many: n must equal yr_plan_num_launches). */
 int yr_get_tuning(const yr_handle* h, int batch, int32_t* cfg_per_op, int n);
 int yr_set_tuning(yr_handle* h, int batch, const int32_t* cfg_per_op, int n);
@@ -375,10 +427,10 @@ int yr_op_run(const yr_op* op, int batch, void* stream);
 /* How a YR_OP_HEAD launch cuts an h x w map into nsy x nsx regions (a function of the shape alone): the rows of the squeeze-excite
  * sums buffer such an op writes per image = nsy * nsx (its se_reduced). */
 int yr_head_regions(int h, int w, int32_t* nsy, int32_t* nsx);
-/* ... and of the WALKING form of YR_OP_HEAD (k bit 6): rows = strips of 14 columns x row segments (its se_reduced). */
+/* ... and of the WALKING form of YR_OP_HEAD (YR_HEAD_WALK): rows = strips of 14 columns x row segments (its se_reduced). */
 int yr_head_walk_rows(int h, int w, int32_t* rows);
-/* ... and of its WEIGHT-STREAMING form (k bits 5 and 6): rows = strips x row segments x waves per workgroup. */
-/* chunks of 32 channels the pixel-stationary POINTWISE form (se_reduced bit 18) runs a k space of kp channels with - what the plan
+/* ... and of its WEIGHT-STREAMING form (YR_HEAD_STREAM): rows = strips x row segments x waves per workgroup. */
+/* chunks of 32 channels the pixel-stationary POINTWISE form (YR_PWF_STATIONARY) runs a k space of kp channels with - what the plan
  * pads the weight planes to (1 .. 10, 12, 16); 0: the form does not take a k space this deep. */
 int yr_pwt_chunks(int kp);
 int yr_head_stream_rows(int h, int w, int32_t* rows);

@@ -180,9 +180,9 @@ def test_unfused_plan_matches_fused(dev):
         fused_kinds = {rt.OP_STEMBLOCK, rt.OP_MBLANE, rt.OP_MBR, rt.OP_MBE}
         # (at 96 x 96 the lane-per-pixel kernel's minimum map size keeps block_1..3 unfused: the matrix-pipe forms carry the test)
         if fuse == '1':     # block_7..15 in the weight-streaming form (k bit 6): no expand + depthwise op is left
-            assert {rt.OP_STEMBLOCK, rt.OP_MBR} <= kinds and rt.OP_MBE not in kinds and sum(1 for o in m.plan.ops if o.kind == rt.OP_MBR and o.k & 0x40) == 9
+            assert {rt.OP_STEMBLOCK, rt.OP_MBR} <= kinds and rt.OP_MBE not in kinds and sum(1 for o in m.plan.ops if o.kind == rt.OP_MBR and o.k & rt.MBR_STREAM) == 9
         elif fuse == '1e':
-            assert {rt.OP_STEMBLOCK, rt.OP_MBR, rt.OP_MBE} <= kinds and not any(o.kind == rt.OP_MBR and o.k & 0x40 for o in m.plan.ops)
+            assert {rt.OP_STEMBLOCK, rt.OP_MBR, rt.OP_MBE} <= kinds and not any(o.kind == rt.OP_MBR and o.k & rt.MBR_STREAM for o in m.plan.ops)
         else:
             assert not (fused_kinds & kinds)
         m.set_weights(P.values)
@@ -212,9 +212,9 @@ def test_tuning_table_round_trip(dev, tmp_path, monkeypatch):
     table = json.load(open(cache))
     (key, cfg), = table.items()
     assert key.endswith(':2') and len(cfg) == len(m.plan.ops)
-    # tuned entries: a pointwise tile shape, or the walk geometry of a register-chained block (waves << 8 | row segments << 16)
+    # tuned entries: a pointwise tile shape, or the walk geometry of a register-chained block (waves << rt.MBR_NW_SHIFT | row segments << rt.MBR_SEGS_SHIFT)
     assert all((c == 0) or (o.kind in (rt.OP_POINTWISE, rt.OP_MBR, rt.OP_MBE)) for c, o in zip(cfg, m.plan.ops)) and any(cfg)
-    assert all((c & 0xff) == 0 for c, o in zip(cfg, m.plan.ops) if o.kind in (rt.OP_MBR, rt.OP_MBE))
+    assert all((c & rt.MBR_FORM_MASK) == 0 for c, o in zip(cfg, m.plan.ops) if o.kind in (rt.OP_MBR, rt.OP_MBE))
     for a, b in zip(*outs):
         assert np.array_equal(a, b)
     bad = (ctypes.c_int32 * 3)(1, 2, 3)
@@ -228,11 +228,11 @@ def test_odd_grids_with_all_graph_rewrites(dev, name, size):
     """Input sizes whose grids are odd (352 -> 11/22/44, 224 -> 7/14/28): the hoisted (up2_add) and pooled-output
     convs, the lane-per-pixel blocks and the ragged tiles of every kernel against the oracle's torch-CPU graph."""
     from oracle import torch_ref
-    from yoloret_amd import layers as L
+    from yoloret_amd import layers as L, runtime as rt
     from yoloret_amd.yolo3.model import yolov3_body
     m = yolov3_body(L.Input(shape=[size, size, 3]), name, 3, num_classes=20)
     assert sum(o.name.endswith('_lowres') for o in m.plan.ops) == 2
-    assert sum((getattr(o, 'stride', 0) == 2) + ((getattr(o, 'reserved0', 0) >> 8) & 1) for o in m.plan.ops if o.kind == 2) == 3      # (... as a two-output conv's second output)
+    assert sum((getattr(o, 'stride', 0) == 2) + bool(getattr(o, 'reserved0', 0) & rt.PW2_POOLED) for o in m.plan.ops if o.kind == 2) == 3      # (... as a two-output conv's second output)
     P = params.ParamStore(77, 'conditioned')
     x = params.synthetic_images(2, size, size)
     ref = torch_ref.TorchReference(P, name, 3, 20)(x)
@@ -268,12 +268,12 @@ def test_small_batch_plan_of_float32_models(dev):
     m.mbk_batch = 6
     assert m.variant(5) == 'mid' and m.variant(6) == 'throughput'
     mid = [y.cpu().numpy() for y in m(xt[:5])]
-    k6 = lambda b_: sum(1 for o in m.plan_for(b_).ops if o.kind == rt.OP_MBR and o.k & 0x40)
+    k6 = lambda b_: sum(1 for o in m.plan_for(b_).ops if o.kind == rt.OP_MBR and o.k & rt.MBR_STREAM)
     assert k6(5) == 0 and k6(6) == 9 and [o.kind for o in m.plan_for(5).ops].count(rt.OP_HEAD) == 6 and all(k6(b_) == 0 for b_ in (1, 3))
     for i, r in enumerate(ref):
         assert_close(mid[i], r[:5], 1e-4, 'mid plan, output %d' % i)
-    flagged = [o.name for o in m.plan_for(2).ops if o.kind == rt.OP_POINTWISE and o.se_reduced & 0x20000]
-    assert flagged and not any(o.se_reduced & 0x20000 for b_ in (3, 6) for o in m.plan_for(b_).ops if o.kind == rt.OP_POINTWISE)
+    flagged = [o.name for o in m.plan_for(2).ops if o.kind == rt.OP_POINTWISE and o.se_reduced & rt.PWF_KSPLIT]
+    assert flagged and not any(o.se_reduced & rt.PWF_KSPLIT for b_ in (3, 6) for o in m.plan_for(b_).ops if o.kind == rt.OP_POINTWISE)
     ran = dict((r['name'], r['kernel']) for r in m.profile(xt[:2], iters=1))
     assert any(ran[n].startswith('pwk_kernel') for n in flagged), ran
     two = [y.cpu().numpy() for y in m(xt[:2])]

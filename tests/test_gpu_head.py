@@ -121,7 +121,7 @@ def run_head(dev, rng, b, h, w, segs, f, pre=False, gated=False, se=None, conv_a
     op.h, op.w, op.cin, op.cout, op.stride = h, w, cin, f, 1
     if form is None:
         form = 'walk' if walk_ok(segs, f, pre, gated, conv_act) else 'dma' if all(xf in ('identity', 'up2') for _, xf in segs) and len(segs) <= 3 else 'pws'
-    op.k = 3 | rt.ACT[conv_act] << 8 | cfg << 16 | {'walk': 0x40, 'stream': 0x60, 'dma': 0x80, 'pws': 0}[form]
+    op.k = 3 | rt.ACT[conv_act] << rt.HEAD_ACT_SHIFT | cfg << rt.HEAD_TILES_SHIFT | {'walk': rt.HEAD_WALK, 'stream': rt.HEAD_STREAM, 'dma': rt.HEAD_PLANES, 'pws': 0}[form]
     from yoloret_amd.compiler import head_pack
     if form == 'dma':
         wt = head_pack(wt, [c for c, _ in segs])
@@ -377,7 +377,7 @@ def run_head16(dev, dt, rng, b, h, w, segs, f, pre=False, gated=False, se=True, 
     op = rt.new_op(rt.OP_HEAD, dw_act)
     op.dtype = op.out_dtype = did
     op.h, op.w, op.cin, op.cout, op.stride = h, w, cin, f, 1
-    op.k = 3 | rt.ACT[conv_act] << 8 | 0x40
+    op.k = 3 | rt.ACT[conv_act] << rt.HEAD_ACT_SHIFT | rt.HEAD_WALK
     n = 0
     for t, c in zip(srcs_dev, segs):
         op.src[n] = rt.make_src(t, c=c, xform='identity')

@@ -133,12 +133,12 @@ def test_pointwise_with_pooled_output(dev, case):
 
 
 def test_compiler_pools_in_the_producer(dev):
-    from yoloret_amd import layers as L
+    from yoloret_amd import layers as L, runtime as rt
     from yoloret_amd.yolo3.model import yolov3_body
     m = yolov3_body(L.Input(shape=[128, 128, 3]), 'mobilenetv2x75', 3, num_classes=20)
     pooled = {o.name: (o.h, o.w) for o in m.plan.ops if getattr(o, 'stride', 0) == 2 and o.kind == 2}
     # (the throughput plan runs a down conv as the SECOND output of the launch that also computes the head's y conv: compiler.fuse_stream_pairs)
-    pooled.update({o.second_name: (o.gate_out.h, o.gate_out.w) for o in m.plan.ops if o.kind == 2 and (getattr(o, 'reserved0', 0) >> 8) & 1})
+    pooled.update({o.second_name: (o.gate_out.h, o.gate_out.w) for o in m.plan.ops if o.kind == 2 and getattr(o, 'reserved0', 0) & rt.PW2_POOLED})
     assert set(pooled) == {'bu3_down_conv', 'bu2_down_conv', 'rfcr_b3c'}
     assert pooled['bu3_down_conv'] == (8, 8)
     assert not any(s.xform == 'maxpool2' and s.buf.name.endswith('_pooled') for o in m.plan.ops for s in o.srcs)
@@ -166,7 +166,7 @@ def test_depthwise_folded_into_project_is_bit_identical(dev, name, size):
         folded = [o for o in m.plan.ops if o.kind == rt.OP_POINTWISE and o.srcs[0].xform == 'dw3']
         assert (len(folded) >= 5) == fold
         if fold:
-            assert {o.se_reduced & 0xff for o in folded} == {1, 2}
+            assert {o.se_reduced & rt.PWDW_STRIDE_MASK for o in folded} == {1, 2}
         m.set_weights(synthetic_weights(m, 7, 'conditioned'))
         x = torch.from_numpy(synthetic_images(3, size, size)).to(dev)
         outs[fold] = [y.cpu().numpy() for y in m(x)]
@@ -185,7 +185,7 @@ def test_compiler_folds_head_projections_into_their_1x1_consumers(dev):
     depthwise map; accounting unchanged; logits equal the unfolded plan's to rounding and the oracle's within 1e-4
     (reference: code/yolo3/model.py:98-114,296-308; efficientnet.py:517-533)."""
     from oracle import model as om, params
-    from yoloret_amd import compiler, layers as L
+    from yoloret_amd import compiler, layers as L, runtime as rt
     from yoloret_amd.yolo3.model import yolov3_body
     m = yolov3_body(L.Input(shape=[128, 128, 3]), 'mobilenetv2x75', 3, num_classes=20)
     names = [o.name for o in m.plan.ops]
@@ -195,7 +195,7 @@ def test_compiler_folds_head_projections_into_their_1x1_consumers(dev):
     pair = folded['bu3_y']       # bu3's y conv and down conv: one launch with two outputs (compiler.fuse_stream_pairs), both composed
     assert sorted(folded) == ['bu1_y', 'bu3_head', 'bu3_y'] and pair.second_name == 'bu3_down_conv' and all(f.folded_projection for f in pair.fused)      # (bu3_head: bu3_conv + its depthwise, YR_OP_HEAD)
     assert all((o.res if o.kind == 15 else o.gate) is not None and o.cin == o.srcs[0].c and o.srcs[0].buf.name.endswith('_mb_dw') for o in folded.values())
-    assert (pair.reserved0 >> 8) & 1    # the pooled store still rides on the (composed) conv
+    assert pair.reserved0 & rt.PW2_POOLED    # the pooled store still rides on the (composed) conv
     saved = compiler.FOLD_PROJ
     try:
         compiler.FOLD_PROJ = False

@@ -65,23 +65,23 @@ def _chained_built(cin, cexp, cout, k, act='relu6'):
 @pytest.mark.parametrize('dt', ['bf16', 'f16'])
 @pytest.mark.parametrize('case', CASES, ids=[str(i) for i in range(len(CASES))])
 def test_mbh(dev, case, dt, form):
-    """form 'lds': the LDS-tiled kernels (mbh.hip, mbn_h.hip; forced tile 254 = their own tile choice); 'chained': the
-    row-walking register-chained kernel (mbxr_h.hip: mbhr_kernel; forced tile 255, one or three row segments) where built."""
+    """form 'lds': the LDS-tiled kernels (mbh.hip, mbn_h.hip; forced tile rt.MBH_TILE_LDS = their own tile choice); 'chained': the
+    row-walking register-chained kernel (mbxr_h.hip: mbhr_kernel; forced tile rt.MBH_TILE_CHAINED, one or three row segments) where built."""
     from yoloret_amd import runtime as rt
     h, w, cin, cexp, cout, k, s, residual, act, tile = case
     if form == 'chained':
         if tile is not None or not _chained_built(cin, cexp, cout, k, act):
             pytest.skip('the register-chained form is not built for this shape')
-        tile = (255, 3 if h > 20 else 0)
+        tile = (rt.MBH_TILE_CHAINED, 3 if h > 20 else 0)
     elif tile is None:
-        tile = (254, 0)
+        tile = (rt.MBH_TILE_LDS, 0)
     rng = np.random.default_rng(zlib.crc32(str(case).encode()))
     b = 2
     x = q16(rng.standard_normal((b, h, w, cin)), dt)
     we = q16(rng.standard_normal((cin, cexp)) * np.sqrt(2.0 / cin), dt)
     se, he = rng.uniform(0.5, 1.5, cexp).astype(np.float32), rng.normal(0, 0.3, cexp).astype(np.float32)
     t = _act(nn.pointwise(x.astype(np.float64), we.astype(np.float64)) * se + he, act)
-    mbn = k == 3 and s == 2 and cin <= 32 and cin % 8 == 0 and cexp <= 192 and cout <= 32 and not residual and tile == (254, 0)
+    mbn = k == 3 and s == 2 and cin <= 32 and cin % 8 == 0 and cexp <= 192 and cout <= 32 and not residual and tile == (rt.MBH_TILE_LDS, 0)
     if mbn:
         # the narrow stride-2 block at the network's front runs on mbn_h.hip, which keeps the WHOLE expanded halo tile on chip
         # in the 16-bit type (the unfused chain's rounding point, oracle/model.py P.store); an expanded value on a rounding
@@ -116,7 +116,7 @@ def test_mbh(dev, case, dt, form):
     op.dtype = op.out_dtype = did
     ho, wo = ref.shape[1], ref.shape[2]
     op.h, op.w, op.cin, op.cout, op.stride, op.nsrc, op.se_reduced = ho, wo, cin, cout, s, 1, cexp
-    op.k = k | ((tile[0] << 8) | (tile[1] << 16) if tile else 0)
+    op.k = k | ((tile[0] << rt.MBH_TH_SHIFT) | (tile[1] << rt.MBH_TW_SHIFT) if tile else 0)
     op.src[0] = rt.make_src(xd, c=cin)
     op.wgt, op.wgt2, op.b1, op.b2 = [t_.data_ptr() for t_ in keep]
     if residual:
@@ -193,7 +193,7 @@ def test_mbx(dev, case, with_sums, dt):
     op = rt.new_op(rt.OP_MBX, act)
     op.dtype = op.out_dtype = did
     op.h, op.w, op.cin, op.cout, op.stride, op.nsrc = ho, wo, cin, cexp, s, 1
-    op.k = k | ((tile[0] << 8) | (tile[1] << 16) if tile else 0)
+    op.k = k | ((tile[0] << rt.MBH_TH_SHIFT) | (tile[1] << rt.MBH_TW_SHIFT) if tile else 0)
     op.src[0] = rt.make_src(xd, c=cin)
     op.wgt, op.wgt2 = keep[0].data_ptr(), keep[1].data_ptr()
     out = torch.full((b, ho, wo, ldo), float('nan'), dtype=rt.TORCH_DTYPE[did], device=dev)
@@ -226,7 +226,7 @@ def test_mbx_rejects_a_short_sum_buffer(dev):
     op = rt.new_op(rt.OP_MBX, 'swish')
     op.dtype = op.out_dtype = rt.DTYPE['bf16']
     op.h, op.w, op.cin, op.cout, op.stride, op.nsrc = 26, 26, 24, 144, 1, 1
-    op.k = 3 | (4 << 8) | (8 << 16)
+    op.k = 3 | (4 << rt.MBH_TH_SHIFT) | (8 << rt.MBH_TW_SHIFT)
     op.src[0] = rt.make_src(x, c=24)
     op.wgt = op.wgt2 = x.data_ptr()
     op.out, op.out_ld = out.data_ptr(), 144

@@ -58,7 +58,7 @@ def make_block(case, dev, b=2, seed=None, split=False):
     ho, wo = (h + s - 1) // s, (w + s - 1) // s
     op = rt.new_op(rt.OP_MBR, 'relu6')
     op.dtype = op.out_dtype = rt.dtype_id('f32')
-    op.h, op.w, op.cin, op.cout, op.k, op.stride, op.nsrc, op.se_reduced = ho, wo, cin, cout, 3 | int(split) << 7 | nw << 8 | segs << 16, s, 1, cexp
+    op.h, op.w, op.cin, op.cout, op.k, op.stride, op.nsrc, op.se_reduced = ho, wo, cin, cout, 3 | (rt.MBR_SPLIT if split else 0) | nw << rt.MBR_NW_SHIFT | segs << rt.MBR_SEGS_SHIFT, s, 1, cexp
     op.src[0] = rt.make_src(xd, c=cin)
     op.wgt, op.wgt2, op.b2 = [k.data_ptr() for k in keep]
     if residual:
@@ -143,7 +143,7 @@ def test_mbe(dev, case, split):
     ho, wo = ref.shape[1], ref.shape[2]
     op = rt.new_op(rt.OP_MBE, 'relu6')
     op.dtype = op.out_dtype = rt.dtype_id('f32')
-    op.h, op.w, op.cin, op.cout, op.k, op.stride, op.nsrc = ho, wo, cin, cexp, 3 | int(split) << 7 | segs << 16, s, 1
+    op.h, op.w, op.cin, op.cout, op.k, op.stride, op.nsrc = ho, wo, cin, cexp, 3 | (rt.MBR_SPLIT if split else 0) | segs << rt.MBR_SEGS_SHIFT, s, 1
     op.src[0] = rt.make_src(xd, c=cin)
     op.wgt, op.wgt2 = [k.data_ptr() for k in keep]
     out = torch.full((b, ho, wo, cexp), float('nan'), dtype=torch.float32, device=dev)
@@ -187,7 +187,7 @@ def make_block_k(case, dev, b=2, seed=None):
     ho, wo = (h + s - 1) // s, (w + s - 1) // s
     op = rt.new_op(rt.OP_MBR, 'relu6')
     op.dtype = op.out_dtype = rt.dtype_id('f32')
-    op.h, op.w, op.cin, op.cout, op.k, op.stride, op.nsrc, op.se_reduced = ho, wo, cin, cout, 3 | 0xc0 | nw << 8 | rows << 16, s, 1, cexp
+    op.h, op.w, op.cin, op.cout, op.k, op.stride, op.nsrc, op.se_reduced = ho, wo, cin, cout, 3 | rt.MBR_STREAM | rt.MBR_SPLIT | nw << rt.MBR_NW_SHIFT | rows << rt.MBR_SEGS_SHIFT, s, 1, cexp
     op.src[0] = rt.make_src(xd, c=cin)
     op.wgt, op.b2 = [k.data_ptr() for k in keep]
     if residual:

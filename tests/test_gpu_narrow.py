@@ -129,7 +129,7 @@ def run_pointwise16(dev, dt, rng, b, h, w, segs, cout, act='none', bn=True, resi
     op.out, op.out_ld = out.data_ptr(), out_ld
     op.k = cfg
     if ksplit:
-        op.se_reduced |= 0x20000      # the k-split form of the plans for one or two images (pointwise_h.hip: pwkh_kernel)
+        op.se_reduced |= rt.PWF_KSPLIT      # the k-split form of the plans for one or two images (pointwise_h.hip: pwkh_kernel)
     rt.run_op(op, b)
     torch.cuda.synchronize()
     if out_f32:
@@ -738,9 +738,9 @@ def test_se_model_results_do_not_depend_on_the_tuning_table_or_the_batch(dev, mo
     for segs in (1, 2, 3, 6):
         cfg = [0] * n
         for i in chained:
-            cfg[i] = 255 << 8 | segs << 16        # the register-chained form with this many row segments per strip
+            cfg[i] = rt.MBH_TILE_CHAINED << rt.MBH_TH_SHIFT | segs << rt.MBH_TW_SHIFT        # the register-chained form with this many row segments per strip
         arr = (ctypes.c_int32 * n)(*cfg)
-        if rt.lib().yr_set_tuning(hd, 3, arr, n) != 0:      # (an op the chained form is not built for refuses tile 255: leave those alone)
+        if rt.lib().yr_set_tuning(hd, 3, arr, n) != 0:      # (an op the chained form is not built for refuses that tile: leave those alone)
             for i in chained:
                 if m.plan.ops[i].kind == rt.OP_MBH:
                     cfg[i] = 0

@@ -85,7 +85,7 @@ def run_pointwise(dev, rng, b, h, w, segs, cout, act='none', bn=True, residual=F
     if stream:            # the pixel-stationary form (pointwise_stream.hip): se_reduced bit 18, the weights as float16 planes
         from yoloret_amd import compiler
         keep = [_dev_vec(compiler.head_pack(wt, [kp], nk=compiler.pwt_chunks(kp)), dev)]
-        op.se_reduced |= 0x40000
+        op.se_reduced |= rt.PWF_STATIONARY
     op.wgt = keep[0].data_ptr()
     if bn:
         keep += [_dev_vec(scale, dev), _dev_vec(shift, dev)]
@@ -100,7 +100,7 @@ def run_pointwise(dev, rng, b, h, w, segs, cout, act='none', bn=True, residual=F
         op.gate, op.gate_ld = g.data_ptr(), g.shape[3]
     op.out, op.out_ld = out.data_ptr(), out_ld
     if ksplit:
-        op.se_reduced |= 0x20000      # the k-split form of the few-image plans (pointwise_split.hip: pwk_kernel)
+        op.se_reduced |= rt.PWF_KSPLIT      # the k-split form of the few-image plans (pointwise_split.hip: pwk_kernel)
     op.k = cfg            # 0: heuristic tile shape; 1..yr_pointwise_num_cfgs(): forced (15..: the LDS-free direct kernel)
     rt.run_op(op, b)
     torch.cuda.synchronize()
@@ -244,8 +244,8 @@ def _two_outputs(dev, shape, gated):
     if gated:
         op.gate, op.gate_ld = g.data_ptr(), ld
     op.out, op.out_ld = out1.data_ptr(), n1
-    op.gate_out, op.gate_out_ld, op.se_hidden, op.reserved0 = out2.data_ptr(), round_up(n2, 4), n2, rt.ACT['relu6'] | 1 << 8
-    op.se_reduced |= 0xc0000
+    op.gate_out, op.gate_out_ld, op.se_hidden, op.reserved0 = out2.data_ptr(), round_up(n2, 4), n2, rt.ACT['relu6'] | rt.PW2_POOLED
+    op.se_reduced |= rt.PWF_STATIONARY | rt.PWF_TWO_OUT
     rt.run_op(op, b)
     torch.cuda.synchronize()
     assert np.array_equal(from_dev(out1, n1), ref1)
@@ -306,9 +306,9 @@ def test_pointwise_ksplit_pooled_output(dev):
             from yoloret_amd import compiler
             keep[0] = _dev_vec(compiler.head_pack(np.ascontiguousarray(wk.T), [cin], nk=compiler.pwt_chunks(cin)), dev)
             op.wgt = keep[0].data_ptr()
-            op.se_reduced |= 0x40000
+            op.se_reduced |= rt.PWF_STATIONARY
         elif ks:
-            op.se_reduced |= 0x20000
+            op.se_reduced |= rt.PWF_KSPLIT
         rt.run_op(op, b)
         torch.cuda.synchronize()
         outs.append(from_dev(out, cout))

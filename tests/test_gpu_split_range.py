@@ -84,7 +84,7 @@ def test_pointwise_split_vs_fp32_mfma(dev, shape, kind):
             op.src[i] = rt.make_src(t, c=c, xform=xf)
         op.wgt = keep[0].data_ptr()
         op.out, op.out_ld = out.data_ptr(), round_up(cout, 4)
-        op.se_reduced = {'split': 0, 'ksplit': 0x20000, 'fp32': 0x10000}[form]      # bit 16: keep the float32 MFMA; bit 17: k-split
+        op.se_reduced = {'split': 0, 'ksplit': rt.PWF_KSPLIT, 'fp32': rt.PWF_F32_MFMA}[form]
         rt.run_op(op, b)
         torch.cuda.synchronize()
         errs[form] = err_vs_fp64(from_dev(out, cout), ref)
@@ -155,7 +155,7 @@ def test_head_forms_under_adversarial_ranges(dev, kind):
         keep = [_dev_vec(wt, dev), _dev_vec(L['cs'], dev), _dev_vec(L['ch'], dev)]
         e = torch.full((b, h, w, f), float('nan'), dtype=torch.float32, device=dev)
         op = rt.new_op(rt.OP_POINTWISE, 'none')
-        op.h, op.w, op.cin, op.cout, op.nsrc, op.se_reduced = h, w, cin, f, len(segs), 0x10000
+        op.h, op.w, op.cin, op.cout, op.nsrc, op.se_reduced = h, w, cin, f, len(segs), rt.PWF_F32_MFMA
         for i, (t, (c, xf)) in enumerate(zip(devs, segs)):
             op.src[i] = rt.make_src(t, c=c, xform=xf)
         op.wgt, op.scale, op.shift = [k_.data_ptr() for k_ in keep]
@@ -178,7 +178,7 @@ def test_head_forms_under_adversarial_ranges(dev, kind):
 def test_check_ranges_moves_ops_off_the_split_forms(dev):
     """Model.check_ranges: with weights that blow an activation past 60000 the ops reading it leave the split forms (float32 MFMA,
     full range), the logits stay finite and equal to the plan that never used a split form; with ordinary weights nothing changes."""
-    from yoloret_amd import layers as L, compiler as C
+    from yoloret_amd import layers as L, compiler as C, runtime as rt
     from yoloret_amd.weights import synthetic_images, synthetic_weights
     from yoloret_amd.yolo3.model import yolov3_body
     m = yolov3_body(L.Input(shape=[64, 64, 3]), 'mobilenetv2x75', 3, num_classes=20)
@@ -199,7 +199,7 @@ def test_check_ranges_moves_ops_off_the_split_forms(dev):
     ys = m2(x)                      # the automatic guard: fallback
     assert m2._nosplit and all(np.isfinite(y.cpu().numpy()).all() for y in ys), m2._nosplit
     names = {o.name: o for o in m2.plan.ops}
-    assert all(not (names[n].k & 0x80) for n in m2._nosplit if n in names and names[n].kind in (13, 14))
+    assert all(not (names[n].k & rt.MBR_SPLIT) for n in m2._nosplit if n in names and names[n].kind in (13, 14))
     # ... and the values are those of a plan that never used a split form
     saved = C.MBR_SPLIT, C.FUSE_HEAD, C.PW_STREAM
     C.MBR_SPLIT, C.FUSE_HEAD, C.PW_STREAM = False, False, False     # (PW_STREAM: that form's weights are stored as float16 planes)
@@ -210,7 +210,7 @@ def test_check_ranges_moves_ops_off_the_split_forms(dev):
         C.MBR_SPLIT, C.FUSE_HEAD, C.PW_STREAM = saved
     for o in m3.plan.ops:
         if o.kind == 2:
-            o.se_reduced |= 0x10000
+            o.se_reduced |= rt.PWF_F32_MFMA
     m3.range_check = False
     m3.set_weights(big)
     y3 = m3(x)
@@ -224,7 +224,7 @@ def test_range_guard_holds_across_plan_variants_and_for_weights(dev):
     '<x>_conv', the throughput plan '<x>_head') keeps the offending op off the split forms - finite logits equal to the other
     variant's; (ii) a WEIGHT beyond the float16 range moves its op to the float32 MFMA instead of failing an assertion in the
     fragment packing; (iii) range_check_every re-arms the guard: an input that leaves the range LATER is caught."""
-    from yoloret_amd import layers as L, compiler as C
+    from yoloret_amd import layers as L, compiler as C, runtime as rt
     from yoloret_amd.weights import synthetic_images, synthetic_weights
     from yoloret_amd.yolo3.model import yolov3_body
     hw = 64
@@ -260,7 +260,7 @@ def test_range_guard_holds_across_plan_variants_and_for_weights(dev):
     m2.set_weights(heavy)
     y2 = m2(x[:8])
     assert 'block_3_mbr' in m2._nosplit and all(np.isfinite(y.cpu().numpy()).all() for y in y2)
-    assert not ({o.name: o for o in m2.plan.ops}['block_3_mbr'].k & 0x80)
+    assert not ({o.name: o for o in m2.plan.ops}['block_3_mbr'].k & rt.MBR_SPLIT)
     # (iii) ordinary weights: the guard measures the first call and, with range_check_every = 4, every 4th one after it.  (With these
     # architectures no INPUT can drive a later activation out of range - the stem's ReLU6 bounds what follows whatever the image holds,
     # x 1e6 included; what the periodic pass protects is a deployment whose weights are swapped in place or a float32 plan with an

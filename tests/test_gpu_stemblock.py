@@ -79,7 +79,7 @@ def test_stemblock(dev, hw, c1, cout, act, dt):
 def test_stem_plus_depthwise(dev, hw, c1, act, with_sums, dt):
     """YR_OP_STEMBLOCK without a projection (the entry of the squeeze-excite EfficientNets, efficientnet.py:636-645 + the
     first block's depthwise conv): the depthwise map, one rounding at the store, plus the per-tile channel sums of the
-    STORED values (the squeeze), every row of the sum buffer written.  '-mfma': the matrix-pipe form (k = 3 | 1 << 8,
+    STORED values (the squeeze), every row of the sum buffer written.  '-mfma': the matrix-pipe form (rt.STEMBLOCK_ENTRY_MFMA in k,
     mbxr_h.hip: stemxr_kernel): image and (BN-scaled) stem kernel are 16-bit MFMA operands - the reference rounds them."""
     from yoloret_amd import runtime as rt
     mfma = dt.endswith('-mfma')
@@ -114,7 +114,7 @@ def test_stem_plus_depthwise(dev, hw, c1, act, with_sums, dt):
     part = torch.full((b, rows, ldo), float('nan'), dtype=torch.float32, device=dev)
     op = rt.new_op(rt.OP_STEMBLOCK, act)
     op.dtype = op.out_dtype = did
-    op.h, op.w, op.cin, op.cout, op.k, op.stride, op.nsrc, op.se_reduced = ho, wo, 3, c1, 3 | (1 << 8 if mfma else 0), 2, 1, c1
+    op.h, op.w, op.cin, op.cout, op.k, op.stride, op.nsrc, op.se_reduced = ho, wo, 3, c1, 3 | (rt.STEMBLOCK_ENTRY_MFMA << rt.STEMBLOCK_ENTRY_SHIFT if mfma else 0), 2, 1, c1
     op.src[0] = rt.make_src(xd, c=3, ld=3)
     op.wgt, op.wgt2 = keep[0].data_ptr(), keep[1].data_ptr()
     op.out, op.out_ld = out.data_ptr(), ldo

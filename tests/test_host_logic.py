@@ -80,7 +80,7 @@ def test_fold_depthwise_plan_keeps_the_accounting():
     assert p.arena_bytes_per_image <= base.arena_bytes_per_image
     assert np.isfinite(p.build_blob(synthetic_weights(fm, 1, 'survey'))).all()
     b13 = next(o for o in folded if o.name == 'block_13_project')
-    assert b13.se_reduced == (2 | (rt.ACT['relu6'] << 8)) and (b13.srcs[0].buf.h, b13.h) == (26, 13)
+    assert b13.se_reduced == (2 | (rt.ACT['relu6'] << rt.PWDW_ACT_SHIFT)) and (b13.srcs[0].buf.h, b13.h) == (26, 13)
 
 
 def test_plan_variants(monkeypatch):
@@ -98,11 +98,11 @@ def test_plan_variants(monkeypatch):
     pw = [o for o in nh.ops if o.kind == rt.OP_POINTWISE]
     px = lambda o: o.h * o.w * (4 if getattr(o, 'stride', 0) == 2 else 1)
     assert _model().variant(2) == 'nohead_k' and _model().variant(3) == 'nohead'
-    assert pw and all(bool(o.se_reduced & 0x20000) == (px(o) <= 32 * 32) for o in pw if not (o.se_reduced & 0x10000))
-    assert any(o.se_reduced & 0x20000 for o in pw) and any(not (o.se_reduced & 0x20000) for o in pw)
-    assert not any(o.se_reduced & 0x20000 for o in _model().plan.ops + _model().plan_for(3).ops if o.kind == rt.OP_POINTWISE)
+    assert pw and all(bool(o.se_reduced & rt.PWF_KSPLIT) == (px(o) <= 32 * 32) for o in pw if not (o.se_reduced & rt.PWF_F32_MFMA))
+    assert any(o.se_reduced & rt.PWF_KSPLIT for o in pw) and any(not (o.se_reduced & rt.PWF_KSPLIT) for o in pw)
+    assert not any(o.se_reduced & rt.PWF_KSPLIT for o in _model().plan.ops + _model().plan_for(3).ops if o.kind == rt.OP_POINTWISE)
     monkeypatch.setattr(compiler, 'KSPLIT_MAX_PIXELS', 0)
-    assert not any(o.se_reduced & 0x20000 for o in _model().plan_for(2).ops if o.kind == rt.OP_POINTWISE)
+    assert not any(o.se_reduced & rt.PWF_KSPLIT for o in _model().plan_for(2).ops if o.kind == rt.OP_POINTWISE)
     monkeypatch.undo()
     monkeypatch.setenv('YOLORET_SMALL_BATCH', '4')
     monkeypatch.setenv('YOLORET_SMALL_VARIANT', 'latency')
@@ -247,6 +247,22 @@ def test_utils():
     a = get_anchors('model_data/yolo_anchors.txt')
     assert a.shape == (9, 2) and a.dtype == np.float32 and a[0].tolist() == [10, 13] and a[-1].tolist() == [373, 326]
     assert len(get_classes('model_data/voc_classes.txt')) == 20 and len(get_classes('model_data/coco_classes.txt')) == 80
+
+
+def test_launch_form_constants_mirror_the_header():
+    """yoloret_amd/runtime.py restates the launch-form bits of include/yoloret_hip.h (what is packed into yr_op.k / se_reduced /
+    reserved0): the same names without the YR_ prefix, the same values, nothing missing and nothing extra on either side."""
+    from yoloret_amd import runtime as rt
+    header = open(os.path.join(ROOT, 'include', 'yoloret_hip.h')).read()
+    block = re.search(r'/\* ---- LAUNCH-FORM BITS.*?---- end of the launch-form bits \*/', header, re.S).group(0)
+    block = re.sub(r'/\*.*?\*/', '', block, flags=re.S)
+    declared = {}
+    for name, expr in re.findall(r'^#define (YR_\w+)[ \t]+(\S.*?)[ \t]*$', block, re.M):
+        declared[name[len('YR_'):]] = eval(expr, {'__builtins__': {}}, {'YR_' + n: v for n, v in declared.items()})
+    assert len(declared) >= 30 and declared['HEAD_STREAM'] == declared['HEAD_WALK'] | declared['HEAD_STREAM_BIT'], declared
+    kinds = {n.split('_')[0] for n in declared}       # PWF, PWDW, PW2, MBR, HEAD, MBH, STEMBLOCK
+    mirrored = {n: v for n, v in vars(rt).items() if '_' in n and n.split('_')[0] in kinds and isinstance(v, int)}
+    assert mirrored == declared, sorted(set(mirrored.items()) ^ set(declared.items()))
 
 
 def test_c_abi_library_loads_and_exports_every_declared_symbol():
@@ -491,7 +507,7 @@ def test_head_blocks_of_the_16bit_plans_and_their_fragment_packing(monkeypatch):
         heads = {o.name: o for o in p.ops if o.kind == rt.OP_HEAD}
         assert sorted(heads) == ['bu2_head', 'bu3_head', 'td2_head', 'td3_head'], (name, sorted(heads))
         for o in heads.values():
-            assert o.k & 0x40 and o.dtype == p.dtype and o.out.dtype == p.dtype and o.gate is not None and o.gate.dtype == 0
+            assert o.k & rt.HEAD_WALK and o.dtype == p.dtype and o.out.dtype == p.dtype and o.gate is not None and o.gate.dtype == 0
             assert o.se_reduced == compiler.head_walk_rows(o.h, o.w) == o.gate.h
             nk = sum((s.c + 31) // 32 for s in o.srcs if s.xform != 'up2_add')
             assert nk <= 8 and o.params['wgt'][0] == ((o.cout // 16) * nk * 512,) and o.params['wgt'][2] == p.dtype
@@ -534,11 +550,11 @@ def test_stream_form_chunk_counts_agree_between_compiler_and_library():
     assert all(L.yr_pwt_chunks(kp) == compiler.pwt_chunks(kp) for kp in range(4, 700, 4))
     m = _model()
     tp = [o for o in m.plan_for(64).ops if o.kind == rt.OP_POINTWISE]
-    assert sum(bool(o.se_reduced & 0x40000) for o in tp) >= 10 and sorted(o.name for o in tp if o.se_reduced & 0x80000) == ['bu2_y', 'bu3_y']
-    assert all(o.gate_out is not None and o.se_hidden > 0 for o in tp if o.se_reduced & 0x80000)
+    assert sum(bool(o.se_reduced & rt.PWF_STATIONARY) for o in tp) >= 10 and sorted(o.name for o in tp if o.se_reduced & rt.PWF_TWO_OUT) == ['bu2_y', 'bu3_y']
+    assert all(o.gate_out is not None and o.se_hidden > 0 for o in tp if o.se_reduced & rt.PWF_TWO_OUT)
     m.small_batch, m.mbk_batch = 4, 24
     for b in (1, 3, 10):        # 'nohead_k', 'nohead', 'mid'
-        assert m.variant(b) != 'throughput' and not any(o.se_reduced & 0xc0000 for o in m.plan_for(b).ops if o.kind == rt.OP_POINTWISE)
+        assert m.variant(b) != 'throughput' and not any(o.se_reduced & (rt.PWF_STATIONARY | rt.PWF_TWO_OUT) for o in m.plan_for(b).ops if o.kind == rt.OP_POINTWISE)
 
 
 def test_nosplit_names_hold_in_every_plan_variant():
@@ -562,7 +578,7 @@ def test_nosplit_names_hold_in_every_plan_variant():
                 base = n[:-len('_head')]
                 assert base + '_head' not in split and base + '_conv' not in split, (variant, reported[0], split)
             conv = {o.name: o for o in plan.ops}
-            assert all(conv[n.replace('_head', '_conv')].se_reduced & 0x10000 for n in heads)       # the float32 MFMA, in every variant
+            assert all(conv[n.replace('_head', '_conv')].se_reduced & rt.PWF_F32_MFMA for n in heads)       # the float32 MFMA, in every variant
     # an inverted-residual block: one-launch form (weight-streaming / register-chained) <-> expand + depthwise | projection
     for reported in (['block_11_mbr'], ['block_11_mbe'], ['block_3_mbr']):
         for variant in (True, 'nohead'):
@@ -570,12 +586,12 @@ def test_nosplit_names_hold_in_every_plan_variant():
             base = reported[0].rsplit('_', 1)[0]
             ops = {o.name: o for o in plan.ops}
             blk = [o for n, o in ops.items() if n in (base + '_mbr', base + '_mbe')]
-            assert blk and all(not (o.k & 0x80) for o in blk), (reported, variant, [(o.name, hex(o.k)) for o in blk])
+            assert blk and all(not (o.k & rt.MBR_SPLIT) for o in blk), (reported, variant, [(o.name, hex(o.k)) for o in blk])
     saved = C.FUSE_MBK
     C.FUSE_MBK = False
     try:       # ... and with the weight-streaming form off, the name it would have had still binds the expand + depthwise op
         plan = C.compile_graph(m.inputs[0], m.outputs, True, 0, frozenset(['block_12_mbr']))
-        assert not ({o.name: o for o in plan.ops}['block_12_mbe'].k & 0x80)
+        assert not ({o.name: o for o in plan.ops}['block_12_mbe'].k & rt.MBR_SPLIT)
     finally:
         C.FUSE_MBK = saved
 
@@ -600,7 +616,7 @@ def test_head_stream_form_takes_only_identity_or_pooled_sources(monkeypatch, hoi
                 finally:
                     L.set_global_policy('float32')
                 for o in plan.ops:
-                    if o.kind == rt.OP_HEAD and (o.k & 0x60) == 0x60:
+                    if o.kind == rt.OP_HEAD and (o.k & rt.HEAD_STREAM) == rt.HEAD_STREAM:
                         streamed += 1
                         xs = [s.xform for s in o.srcs]
                         body = xs[:-1] if xs[-1] == 'up2_add' else xs
@@ -612,12 +628,13 @@ def test_autotune_candidate_mirror_matches_the_library():
     """tests/util.py restates yr_autotune's candidate lists (what the tuning-table tests of tests/test_gpu_invariance.py try per op);
     they must be the lists runtime.hip holds, and the pointwise config counts those of pointwise.hip / pointwise_h.hip."""
     from tests import util as U
+    from yoloret_amd import runtime as rt
     csrc = os.path.join(ROOT, 'yoloret_amd', 'csrc')
     src = open(os.path.join(csrc, 'runtime.hip')).read()
 
     def pairs(name):
         body = re.search(r'static const int %s\[\]\[2\] = \{(.*?)\};' % name, src, re.S).group(1)
-        return [(int(a), int(b)) for a, b in re.findall(r'\{\s*(\d+)\s*,\s*(\d+)\s*\}', body)]
+        return [(int(a) if a.isdigit() else getattr(rt, a[len('YR_'):]), int(b)) for a, b in re.findall(r'\{\s*(\w+)\s*,\s*(\d+)\s*\}', body)]
 
     assert pairs('tiles') == U.AUTOTUNE_MBH_TILES
     assert pairs('chained') == U.AUTOTUNE_MBH_CHAINED
@@ -632,7 +649,7 @@ def test_autotune_candidate_mirror_matches_the_library():
     nsq = int(re.search(r'constexpr int PWH_NSQ = (\d+);', ph).group(1))
     assert ncfg + nwalk + nsq == U.PW_NUM_CFGS[1] == U.PW_NUM_CFGS[2]
     # ... and the tuner skips exactly the forms the mirror skips
-    assert 'if (h->ops[i].dtype == YR_F32 && (h->ops[i].se_reduced & 0x40000)) continue;' in src
-    assert 'if (h->ops[i].kind == YR_OP_MBR && (h->ops[i].k & 0x40)) continue;' in src
-    assert 'if (segs_list[c] > h->ops[i].h) continue;' in src and 'best_cfg = (base & 0xff00) | (segs_list[c] << 16)' in src
-    assert 'const int cfg = c < 0 ? 0 : (cand[c][0] << 8) | (cand[c][1] << 16);' in src
+    assert 'if (h->ops[i].dtype == YR_F32 && (h->ops[i].se_reduced & YR_PWF_STATIONARY)) continue;' in src
+    assert 'if (h->ops[i].kind == YR_OP_MBR && (h->ops[i].k & YR_MBR_STREAM)) continue;' in src
+    assert 'if (segs_list[c] > h->ops[i].h) continue;' in src and 'best_cfg = (base & YR_MBR_NW_MASK) | (segs_list[c] << YR_MBR_SEGS_SHIFT)' in src
+    assert 'const int cfg = c < 0 ? 0 : (cand[c][0] << YR_MBH_TH_SHIFT) | (cand[c][1] << YR_MBH_TW_SHIFT);' in src

@@ -92,10 +92,10 @@ def assert_rounded_once(got, ref64, dt, what, slack=2e-5):
 
 def entry_on_matrix_pipe(model):
     """Whether the plan's network entry takes image and stem kernel as 16-bit MFMA operands (stemblock_h.hip: a STEMBLOCK op in
-    the matrix-pipe layout, which carries BN `scale` rows, or the stem + depthwise entry asked for in its matrix-pipe form, k = 3 | 1 << 8) - what QuantStore(round_entry=...) must emulate for this plan."""
+    the matrix-pipe layout, which carries BN `scale` rows, or the stem + depthwise entry asked for in its matrix-pipe form, rt.STEMBLOCK_ENTRY_MFMA in k) - what QuantStore(round_entry=...) must emulate for this plan."""
     rt = _rt()
     op = model.plan.ops[0]
-    return model.plan.dtype != 0 and op.kind == rt.OP_STEMBLOCK and ('scale' in op.params or ((op.k >> 8) & 0xff) == 1)
+    return model.plan.dtype != 0 and op.kind == rt.OP_STEMBLOCK and ('scale' in op.params or (op.k & rt.STEMBLOCK_ENTRY_MASK) >> rt.STEMBLOCK_ENTRY_SHIFT == rt.STEMBLOCK_ENTRY_MFMA)
 
 
 # ---- whole-plan invariance helpers (tests/test_gpu_invariance.py)
@@ -129,7 +129,7 @@ def nan_outputs(model, b):
 # Only these entries are dispatched by the tuner, so only these are what a tuning table can hold in practice.
 AUTOTUNE_MBH_TILES = [(4, 8), (8, 4), (7, 4), (7, 8), (8, 8), (13, 4), (4, 16), (8, 16), (7, 16), (13, 8),
                       (16, 8), (13, 16), (8, 12), (7, 12), (13, 12), (16, 12), (16, 16), (4, 12), (6, 8)]     # (th, tw)
-AUTOTUNE_MBH_CHAINED = [(255, 1), (255, 2), (255, 3), (255, 4), (255, 6)]       # the register-chained form: (255, row segments)
+AUTOTUNE_MBH_CHAINED = [(_rt().MBH_TILE_CHAINED, s) for s in (1, 2, 3, 4, 6)]    # the register-chained form: (forced tile, row segments)
 AUTOTUNE_MBR_SEGS = [0, 1, 2, 3, 4, 6, 8, 13, 18, 26]                           # row segments per strip of YR_OP_MBR / YR_OP_MBE
 PW_NUM_CFGS = {0: 29, 1: 26, 2: 26}        # == yr_pointwise_num_cfgs(dtype): entries 0 .. n are valid for a pointwise op
 
@@ -140,15 +140,15 @@ def autotune_candidates(op):
     choice by shape, which the caller finds by whether the op takes a chained entry."""
     rt = _rt()
     if op.kind == rt.OP_POINTWISE:
-        if op.dtype == 0 and op.se_reduced & 0x40000:       # the pixel-stationary form: nothing to tune
+        if op.dtype == 0 and op.se_reduced & rt.PWF_STATIONARY:       # the pixel-stationary form: nothing to tune
             return []
         return list(range(1, PW_NUM_CFGS[op.dtype] + 1))
-    if op.kind == rt.OP_MBR and op.k & 0x40:                # the weight-streaming block form: nothing to tune
+    if op.kind == rt.OP_MBR and op.k & rt.MBR_STREAM:                # the weight-streaming block form: nothing to tune
         return []
     if op.kind in (rt.OP_MBR, rt.OP_MBE):
-        base = op.k & 0xffff
-        return [(base & 0xff00) | (s << 16) for s in AUTOTUNE_MBR_SEGS if 0 < s <= op.h]
+        base = op.k & (rt.MBR_FORM_MASK | rt.MBR_NW_MASK)
+        return [(base & rt.MBR_NW_MASK) | (s << rt.MBR_SEGS_SHIFT) for s in AUTOTUNE_MBR_SEGS if 0 < s <= op.h]
     if op.kind in (rt.OP_MBH, rt.OP_MBX):
-        return [('chained', [th << 8 | tw << 16 for th, tw in AUTOTUNE_MBH_CHAINED]),
-                ('tiles', [th << 8 | tw << 16 for th, tw in AUTOTUNE_MBH_TILES])]
+        return [('chained', [th << rt.MBH_TH_SHIFT | tw << rt.MBH_TW_SHIFT for th, tw in AUTOTUNE_MBH_CHAINED]),
+                ('tiles', [th << rt.MBH_TH_SHIFT | tw << rt.MBH_TW_SHIFT for th, tw in AUTOTUNE_MBH_TILES])]
     return []

@@ -80,7 +80,7 @@ def main():
         op.gate_out, op.gate_out_ld, op.se_hidden, op.se_w, op.sync = gate.data_ptr(), f, r, par[4].data_ptr(), sync.data_ptr()
         moved = sum(t.numel() * 4 for t in keep) + out.numel() * 4
         for cfg in cfgs:
-            op.k = 3 | 1 << 8 | cfg << 16 | (0x80 if packed else 0x40 if walk else 0)
+            op.k = 3 | rt.ACT['relu6'] << rt.HEAD_ACT_SHIFT | cfg << rt.HEAD_TILES_SHIFT | (rt.HEAD_PLANES if packed else rt.HEAD_WALK if walk else 0)
             for _ in range(3):
                 rt.run_op(op, b)
             torch.cuda.synchronize()

@@ -40,7 +40,7 @@ if gated:
     keep.append(g)
     op.res, op.res_ld = g.data_ptr(), g.shape[1]
 op.h, op.w, op.cin, op.cout, op.stride = h, w, cin, f, 1
-op.k = 3 | rt.ACT['relu6'] << 8 | 0x60
+op.k = 3 | rt.ACT['relu6'] << rt.HEAD_ACT_SHIFT | rt.HEAD_STREAM
 rpw, nw, strips, nsegs = head_stream_geometry(h, w)
 rows = strips * nsegs * nw
 sums = torch.zeros((b, rows, f), dtype=torch.float32, device=dev)

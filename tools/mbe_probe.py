@@ -34,7 +34,7 @@ def main():
                 continue
             op = rt.new_op(rt.OP_MBE, 'relu6')
             op.dtype = op.out_dtype = 0
-            op.h, op.w, op.cin, op.cout, op.k, op.stride, op.nsrc = ho, wo, cin, cexp, 3 | segs << 16, s, 1
+            op.h, op.w, op.cin, op.cout, op.k, op.stride, op.nsrc = ho, wo, cin, cexp, 3 | segs << rt.MBR_SEGS_SHIFT, s, 1
             op.src[0] = rt.make_src(x, c=cin)
             op.wgt, op.wgt2 = [k.data_ptr() for k in keep]
             op.out, op.out_ld = out.data_ptr(), cexp

@@ -56,7 +56,7 @@ for name, h, cin, cexp, cout, k, s, res in BLOCKS:
     op.out, op.out_ld = out.data_ptr(), ldo
     rows = []
     for tile in ([None] if not os.environ.get('MBH_TILE') else []) + TILES:
-        op.k = k | (((tile[0] << 8) | (tile[1] << 16)) if tile else 0)
+        op.k = k | (((tile[0] << rt.MBH_TH_SHIFT) | (tile[1] << rt.MBH_TW_SHIFT)) if tile else 0)
         try:
             rt.run_op(op, B)
         except rt.YoloretHipError as e:

@@ -1,5 +1,5 @@
-"""Times YR_OP_MBH in its forms - the LDS-tiled kernels' own choice (tile 254) against the register-chained whole-block kernel
-(mbxr_h.hip: mbhr_kernel, tile 255, 0 .. 8 row segments) - on the front blocks of the 16-bit configurations.
+"""Times YR_OP_MBH in its forms - the LDS-tiled kernels' own choice (tile rt.MBH_TILE_LDS) against the register-chained whole-block kernel
+(mbxr_h.hip: mbhr_kernel, tile rt.MBH_TILE_CHAINED, 0 .. 8 row segments) - on the front blocks of the 16-bit configurations.
     python tools/mbhr_probe.py [bf16|f16]"""
 import sys
 
@@ -34,11 +34,11 @@ def main():
         pb = torch.cat([torch.ones(ldo, device=dev), torch.zeros(ldo, device=dev)])
         ho, wo = (h + s - 1) // s, (w + s - 1) // s
         out = torch.empty((b, ho, wo, ldo), dtype=tdt, device=dev)
-        for tile in [(254, 0), (255, 0), (255, 1), (255, 2), (255, 4), (255, 8)]:
+        for tile in [(rt.MBH_TILE_LDS, 0)] + [(rt.MBH_TILE_CHAINED, segs) for segs in (0, 1, 2, 4, 8)]:
             op = rt.new_op(rt.OP_MBH, 'relu6')
             op.dtype = op.out_dtype = did
             op.h, op.w, op.cin, op.cout, op.stride, op.nsrc, op.se_reduced = ho, wo, cin, cout, s, 1, cexp
-            op.k = 3 | tile[0] << 8 | tile[1] << 16
+            op.k = 3 | tile[0] << rt.MBH_TH_SHIFT | tile[1] << rt.MBH_TW_SHIFT
             op.src[0] = rt.make_src(x, c=cin)
             op.wgt, op.wgt2, op.b1, op.b2 = wet.data_ptr(), prm.data_ptr(), wpt.data_ptr(), pb.data_ptr()
             if res:

@@ -26,7 +26,7 @@ if gated:
     g = torch.rand((b, 1, 1, ld), device=dev)
     op.gate, op.gate_ld = g.data_ptr(), ld
 op.out, op.out_ld = out.data_ptr(), n
-op.se_reduced |= 0x40000
+op.se_reduced |= rt.PWF_STATIONARY
 for _ in range(3):
     rt.run_op(op, b)
 torch.cuda.synchronize()

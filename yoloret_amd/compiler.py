@@ -70,7 +70,7 @@ class OpRec:
         self.gate = None
         self.gate_out = None  # ABI 7, the SE tail: the gate vector this op writes itself (se_hidden = the FC pair's hidden width, params['se_w'])
         self.se_hidden = 0
-        self.reserved0 = 0    # (a two-output POINTWISE op: the second output's activation | pooled << 8)
+        self.reserved0 = 0    # (a two-output POINTWISE op: the second output's activation | rt.PW2_POOLED)
         self.params = {}      # role -> (shape, numpy builder fn(weights) -> float32 array[, yr_dtype it is stored as])
         self.offsets = {}     # role -> float offset in blob
         self.macs = 0
@@ -172,7 +172,7 @@ class Plan:
                 raise
             assert tuple(arr.shape) == tuple(shape), (op.name, role, arr.shape, shape)
             if dt == 0:
-                if (op.kind == rt.OP_POINTWISE and role == 'wgt' and op.dtype == 0 and PW_SPLIT and not (op.se_reduced & 0x50000)     # (bit 18: planes - head_pack has checked)
+                if (op.kind == rt.OP_POINTWISE and role == 'wgt' and op.dtype == 0 and PW_SPLIT and not (op.se_reduced & (rt.PWF_F32_MFMA | rt.PWF_STATIONARY))     # (PWF_STATIONARY: planes - head_pack has checked)
                         and arr.size and float(np.abs(arr).max()) >= 60000.0):
                     raise WeightRangeError(op.name, '%s: a weight of %.3g is beyond the float16 range the split pointwise form needs (YOLORET_PW_SPLIT=0 '
                                            'runs the float32-MFMA kernels)' % (op.name, float(np.abs(arr).max())))
@@ -233,7 +233,7 @@ class Plan:
                 p_ = producer.get(id(op.srcs[0].buf))
                 if p_ is not None and p_.kind == rt.OP_POINTWISE and p_.act in ('relu6', 'swish') and nreaders.get(id(p_.out), 0) == 1:
                     names.append(op.name)
-            elif op.kind == rt.OP_HEAD and not (op.k & 0xc0):
+            elif op.kind == rt.OP_HEAD and not (op.k & (rt.HEAD_WALK | rt.HEAD_PLANES)):
                 names.append(op.name)
         return names
 
@@ -357,13 +357,13 @@ MBS_SHAPES = {
     (24, 144, 32, 2, False): 3, (32, 192, 32, 1, True): 4, (32, 192, 48, 2, False): 4,     # MobileNetV2 x1.4
 }
 MBS_MBE_CINS = (48, 72, 88, 120, 136)      # YR_OP_MBE's split form is built for these block input widths
-# The WEIGHT-STREAMING form of YR_OP_MBR (mbk.hip, round 6; k bits 6 and 7): the blocks whose fragments do not fit one CU's register
+# The WEIGHT-STREAMING form of YR_OP_MBR (mbk.hip, round 6; rt.MBR_STREAM | rt.MBR_SPLIT): the blocks whose fragments do not fit one CU's register
 # file as ONE launch - the pixels stay in registers (a wave owns one or two input rows of a 16-column strip and the projection
 # accumulators of its output rows), the weights stream through LDS one pair of expanded tiles at a time.  (cin, cexp, cout, stride,
 # residual) -> (input rows per wave, waves per workgroup).  Before: YR_OP_MBE + a separate projection launch (the 6x-wide depthwise map
 # written and read back: block_11 87 + 100 MB).  YOLORET_FUSE_MBK=0 switches it off.
 FUSE_MBK = os.environ.get('YOLORET_FUSE_MBK', '1') != '0'
-# the pixel-stationary form of the float32 plans' 1x1 convs (pointwise_stream.hip; se_reduced bit 18, the weights stored as float16 planes)
+# the pixel-stationary form of the float32 plans' 1x1 convs (pointwise_stream.hip; rt.PWF_STATIONARY, the weights stored as float16 planes)
 PW_STREAM = os.environ.get('YOLORET_PW_STREAM', '1') != '0'
 PW_STREAM_MID = os.environ.get('YOLORET_PW_STREAM_MID', '0') != '0'     # ... in the 'mid' plan variant (batches below Model.mbk_batch) too
 PWT_CHUNKS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 16)      # (yr_pwt_chunks)
@@ -380,8 +380,8 @@ PW_STREAM_PAIRS = os.environ.get('YOLORET_PW_STREAM_PAIRS', '1') != '0'
 
 def fuse_stream_pairs(ops, output_buf_ids=()):
     """Two pixel-stationary POINTWISE ops over the SAME (gated) map - a head's y conv and the down conv of the bottom-up path (reference
-    code/yolo3/model.py:139-151) - become one launch with two outputs (se_reduced bit 19): the map is read once.  The first output is
-    the one a plan output aliases (if any); the second travels as gate_out / se_hidden (couts) / reserved0 (activation | pooled << 8),
+    code/yolo3/model.py:139-151) - become one launch with two outputs (rt.PWF_TWO_OUT): the map is read once.  The first output is
+    the one a plan output aliases (if any); the second travels as gate_out / se_hidden (couts) / reserved0 (activation | rt.PW2_POOLED),
     its tiles behind the first's in the weight planes, scale and shift padded to the tiles."""
     if not PW_STREAM_PAIRS:
         return ops
@@ -392,7 +392,7 @@ def fuse_stream_pairs(ops, output_buf_ids=()):
         return o.h * f, o.w * f
 
     def ok(o):
-        return (o.kind == rt.OP_POINTWISE and (o.se_reduced & 0xc0000) == 0x40000 and len(o.srcs) == 1 and o.srcs[0].xform == 'identity'
+        return (o.kind == rt.OP_POINTWISE and (o.se_reduced & (rt.PWF_STATIONARY | rt.PWF_TWO_OUT)) == rt.PWF_STATIONARY and len(o.srcs) == 1 and o.srcs[0].xform == 'identity'
                 and o.gate_out is None)
     i = 0
     while i < len(ops):
@@ -406,8 +406,8 @@ def fuse_stream_pairs(ops, output_buf_ids=()):
                     if second.out.external_slot >= 0 or second.out.id in output_buf_ids:
                         continue        # (two plan outputs: the second output is an arena buffer)
                     m = OpRec(rt.OP_POINTWISE, first.name, act=first.act, h=first.h, w=first.w, cin=first.cin, cout=first.cout, k=first.k, stride=first.stride,
-                              se_reduced=first.se_reduced | 0x80000, srcs=list(first.srcs), out=first.out, gate=first.gate, macs=first.macs + second.macs, dtype=0)
-                    m.gate_out, m.se_hidden, m.reserved0 = second.out, second.cout, rt.ACT[second.act] | ((1 if second.stride == 2 else 0) << 8)
+                              se_reduced=first.se_reduced | rt.PWF_TWO_OUT, srcs=list(first.srcs), out=first.out, gate=first.gate, macs=first.macs + second.macs, dtype=0)
+                    m.gate_out, m.se_hidden, m.reserved0 = second.out, second.cout, rt.ACT[second.act] | (rt.PW2_POOLED if second.stride == 2 else 0)
                     m.fused = [first, second]
                     m.second_name = second.name
                     if getattr(first, 'folded_projection', None):
@@ -436,8 +436,8 @@ def fuse_stream_pairs(ops, output_buf_ids=()):
 
 
 def pw_stream_form(o):
-    """Turn the float32 POINTWISE op o into its pixel-stationary form if it can take it: se_reduced bit 18, 'wgt' as head_pack planes."""
-    if (o.kind != rt.OP_POINTWISE or o.dtype != 0 or (o.se_reduced & 0x70000) or any(s_.xform in ('dw3', 'maxpool2', 'maxpool4', 'up2_add') for s_ in o.srcs)
+    """Turn the float32 POINTWISE op o into its pixel-stationary form if it can take it: rt.PWF_STATIONARY, 'wgt' as head_pack planes."""
+    if (o.kind != rt.OP_POINTWISE or o.dtype != 0 or (o.se_reduced & (rt.PWF_F32_MFMA | rt.PWF_KSPLIT | rt.PWF_STATIONARY)) or any(s_.xform in ('dw3', 'maxpool2', 'maxpool4', 'up2_add') for s_ in o.srcs)
             or o.res is not None or o.act not in ('none', 'relu6')
             or 'wgt' not in o.params or (len(o.params['wgt']) > 2 and o.params['wgt'][2] != 0)):
         return False
@@ -453,7 +453,7 @@ def pw_stream_form(o):
         return head_pack(np.asarray(fn(wd), np.float32).reshape(cout, kp), [kp], nk=nk)
     o.params = dict(o.params)
     o.params['wgt'] = ((nt * nk * 512,), planes, 0)
-    o.se_reduced |= 0x40000
+    o.se_reduced |= rt.PWF_STATIONARY
     return True
 MBK_SHAPES = {
     (48, 288, 48, 1, True): (2, 8),       # MobileNetV2 x0.75 block_7..9 (26 x 26): 35 us on the weight-stationary form (mbr.hip) -> 24
@@ -867,7 +867,7 @@ def fold_depthwise_into_project(ops, output_buf_ids, min_pixels=0):
                 and p.h * p.w >= min_pixels):
             f = OpRec(rt.OP_POINTWISE, p.name, act=p.act, h=p.h, w=p.w, cin=p.cin, cout=p.cout,
                       srcs=[Seg(d.srcs[0].buf, d.srcs[0].c, 'dw3')], out=p.out, res=p.res,
-                      se_reduced=d.stride | (rt.ACT[d.act] << 8), macs=p.macs + d.macs)
+                      se_reduced=d.stride | (rt.ACT[d.act] << rt.PWDW_ACT_SHIFT), macs=p.macs + d.macs)
             f.params = dict(p.params)
             f.params['wgt2'], f.params['b1'], f.params['b2'] = d.params['wgt'], d.params['scale'], d.params['shift']
             f.fused = [d, p]
@@ -894,7 +894,7 @@ SE_TAIL_LDS = 4608 - 1024 - 4      # == YR_SE_TAIL_LDS - 4 * 256 threads (se_tai
 HEAD_WALK_MAX_NK = min(7, int(os.environ.get('YOLORET_HEAD_WALK_MAX_NK', '4')))   # (measured, MobileNetV2 x0.75 @416 batch 64: 1 chunk 52 us against the LDS-direct kernel's 95, 4 chunks 96 | 124, 6 chunks 85 | 82, 7 chunks 96 | 84: one tile per wave and 250 registers from 5 chunks on)
 HEAD_WALK = os.environ.get('YOLORET_HEAD_WALK', '1') != '0'   # head blocks of at most 7 chunks of 32 identity-source channels on the walking kernel (headwalk.hip)
 HEAD_DMA = os.environ.get('YOLORET_HEAD_DMA', '1') != '0'   # head blocks without a pooled source on the LDS-direct kernel
-# Round 6: the WEIGHT-STREAMING form of YR_OP_HEAD (headstream.hip, k bits 5 and 6; mbk.hip's formulation - the pixels of a wave's one or
+# Round 6: the WEIGHT-STREAMING form of YR_OP_HEAD (headstream.hip, rt.HEAD_STREAM; mbk.hip's formulation - the pixels of a wave's one or
 # two rows stationary over the whole k space, the conv's output channels streaming past them in pairs of tiles): identity and 2 x 2
 # max-pooled sources (gathered once), up to 11 chunks of 32 channels at one row per wave (maps below 20 rows), 7 at two.
 # YOLORET_HEAD_STREAM=0 switches it off, a comma list of block names ('td2,bu2') restricts it.
@@ -951,7 +951,7 @@ def head_walk_rows(h, w):
 def head_pack(wt, seg_c, V=4, nk=None):
     """(nk: pad the chunk list with zero chunks to this length - the pixel-stationary pointwise form is built for some chunk counts only.)
     The 1x1 convolution's weights Wt [F][kp] (k space = the sources' channels, each padded to V) as the float16 planes the
-    LDS-direct head kernel reads (headblock.hip, YR_OP_HEAD with k bit 7): the k space cut into chunks of 32 channels PER SOURCE,
+    LDS-direct head kernel reads (headblock.hip, YR_OP_HEAD with rt.HEAD_PLANES): the k space cut into chunks of 32 channels PER SOURCE,
     [ceil(F / 16)][NK][2 planes][64 lanes][8 halves] - lane (m = l % 16, g = l / 16) of cout tile t, chunk j of source s:
     W[16 t + m][channel 32 j + 8 g + i of s], zero beyond the source / beyond F; h plane, then m = f16((w - h) 2^11).
     -> the float32 words that hold them."""
@@ -1016,7 +1016,7 @@ def _head_block16(c, d, readers, output_buf_ids):
           and d.res is None and d.gate_out is None and not (c.h == 1 and c.w == 1) and (d.gate is not None or FUSE_HEAD_ALL))
     if not ok:
         return None
-    m = OpRec(rt.OP_HEAD, c.name.rsplit('_', 1)[0] + '_head', act=d.act, h=d.h, w=d.w, cin=c.cin, cout=F, k=3 | rt.ACT[c.act] << 8 | 0x40, stride=1,
+    m = OpRec(rt.OP_HEAD, c.name.rsplit('_', 1)[0] + '_head', act=d.act, h=d.h, w=d.w, cin=c.cin, cout=F, k=3 | rt.ACT[c.act] << rt.HEAD_ACT_SHIFT | rt.HEAD_WALK, stride=1,
               srcs=list(c.srcs), out=d.out, res=c.gate, macs=c.macs + d.macs, dtype=c.dtype)
     m.fused = [c, d]
     if getattr(c, 'folded_projection', None):
@@ -1076,7 +1076,7 @@ def fuse_head_blocks(ops, bufs, output_buf_ids, nosplit=frozenset(), stream_ok=T
                 i += 1
             continue
         ok = (d is not None and c.kind == rt.OP_POINTWISE and c.dtype == 0 and c.act in ('relu6', 'none', 'swish', 'leaky') and 'scale' in c.params
-              and c.res is None and not getattr(c, 'stride', 0) and not (c.se_reduced & 0x10000) and not getattr(c, 'accounted_in', None)
+              and c.res is None and not getattr(c, 'stride', 0) and not (c.se_reduced & rt.PWF_F32_MFMA) and not getattr(c, 'accounted_in', None)
               and all(s_.xform in ('identity', 'up2', 'maxpool2', 'maxpool4', 'up2_add') for s_ in c.srcs)
               and (c.gate is None or (len(c.srcs) == 1 and c.srcs[0].xform == 'identity'))
               and kp >= 16 and c.cout % 4 == 0 and c.out.external_slot < 0 and c.out.id not in output_buf_ids and readers.get(id(c.out), 0) == 1
@@ -1086,12 +1086,12 @@ def fuse_head_blocks(ops, bufs, output_buf_ids, nosplit=frozenset(), stream_ok=T
               and c.name.rsplit('_', 1)[0] + '_head' not in nosplit)       # (the head kernels exist in the split form only)
         if not ok:
             if c.kind == rt.OP_POINTWISE and c.name.rsplit('_', 1)[0] + '_head' in nosplit:
-                c.se_reduced |= 0x10000      # the unfused conv of a head block that left the split form stays off it as well
+                c.se_reduced |= rt.PWF_F32_MFMA      # the unfused conv of a head block that left the split form stays off it as well
             out.append(c)
             i += 1
             continue
         F, ldf = c.cout, round_up(c.cout, 4)
-        m = OpRec(rt.OP_HEAD, c.name.rsplit('_', 1)[0] + '_head', act=d.act, h=d.h, w=d.w, cin=c.cin, cout=F, k=3 | rt.ACT[c.act] << 8, stride=1,
+        m = OpRec(rt.OP_HEAD, c.name.rsplit('_', 1)[0] + '_head', act=d.act, h=d.h, w=d.w, cin=c.cin, cout=F, k=3 | rt.ACT[c.act] << rt.HEAD_ACT_SHIFT, stride=1,
                   srcs=list(c.srcs), out=d.out, res=c.gate, macs=c.macs + d.macs, dtype=0)
         m.fused = [c, d]
         if getattr(c, 'folded_projection', None):
@@ -1119,9 +1119,9 @@ def fuse_head_blocks(ops, bufs, output_buf_ids, nosplit=frozenset(), stream_ok=T
         walk = (not stream and HEAD_WALK and all(s_.xform in ('identity', 'up2_add') for s_ in c.srcs) and len(kseg) <= 3 and nk <= HEAD_WALK_MAX_NK and F % 16 == 0 and (F // 16 // nt) % 4 == 0
                 and F // 16 % nt == 0 and c.act in ('relu6', 'none') and not (c.gate is not None and len(kseg) != len(c.srcs)) and F * 11 * 4 <= 64 * 1024)
         if walk or stream:
-            # the walking form (headwalk.hip, k bit 6) / the weight-streaming form (headstream.hip, k bits 5 and 6): weights as float16
+            # the walking form (headwalk.hip, rt.HEAD_WALK) / the weight-streaming form (headstream.hip, rt.HEAD_STREAM): weights as float16
             # planes with the conv's BN scale folded in, YR_OP_MBR's tap table
-            m.k |= 0x60 if stream else 0x40
+            m.k |= rt.HEAD_STREAM if stream else rt.HEAD_WALK
             cp = c.params
 
             def planes(wd, cp=cp, kseg=kseg, F=F):
@@ -1135,8 +1135,8 @@ def fuse_head_blocks(ops, bufs, output_buf_ids, nosplit=frozenset(), stream_ok=T
                 return o
             m.params = {'wgt': (((F // 16) * nk * 512,), planes), 'scale': c.params['scale'], 'wgt2': ((F // 16, 11, 16), tab)}
         elif all(s_.xform in ('identity', 'up2', 'up2_add') for s_ in c.srcs) and len(kseg) <= 3 and HEAD_DMA:
-            # no pooled source: the LDS-direct kernel, weights as float16 planes in fragment order (k bit 7)
-            m.k |= 0x80
+            # no pooled source: the LDS-direct kernel, weights as float16 planes in fragment order (rt.HEAD_PLANES)
+            m.k |= rt.HEAD_PLANES
             m.params['wgt'] = ((((F + 15) // 16) * nk * 512,), lambda wd, wf=c.params['wgt'][1], kseg=kseg: head_pack(wf(wd), kseg))
 
         def dw_rows(wd, dp=dp, F=F, ldf=ldf):
@@ -1170,7 +1170,7 @@ def se_tail_into_producers(ops):
         P = producer_of_sums.get(id(fc.srcs[0].buf))
         if P is None or P.gate_out is not None or fc.out.external_slot >= 0:
             continue
-        if P.kind == rt.OP_HEAD and (P.k & 0x60) == 0x60:      # (the weight-streaming head form has no tail: its waves never meet)
+        if P.kind == rt.OP_HEAD and (P.k & rt.HEAD_STREAM) == rt.HEAD_STREAM:      # (the weight-streaming head form has no tail: its waves never meet)
             continue
         C, R = fc.cin, fc.se_reduced
         ldc = round_up(C, 4)
@@ -1240,7 +1240,7 @@ def mbs_wave_pairs(T, nw):
 
 
 def mbs_pack(we_t, e_scale, e_shift, dw, d_scale, d_shift, wp_t, p_scale, p_shift, nw):
-    """Parameters of a YR_OP_MBR block in its SPLIT form (k bit 7; mbr.hip, SP): both 1x1 convolutions on the 16-bit matrix pipe
+    """Parameters of a YR_OP_MBR block in its SPLIT form (rt.MBR_SPLIT; mbr.hip, SP): both 1x1 convolutions on the 16-bit matrix pipe
     with every float32 operand cut into two float16 planes, w = h + 2^-11 m.  wgt = [T][NKE][2 planes][64 lanes][8 halves] for the
     expand conv (lane (m, g) of tile j, step c: We[16 j + m][32 c + 8 g + i] * BN scale, zero beyond cin), then per tile pair of
     mbs_wave_pairs(T, nw) [TO][2 planes][64][8]: Wp[16 t + m][16 tA + 4 g + i] (i < 4) | [16 tB + 4 g + i - 4] * BN scale - as the
@@ -1289,7 +1289,7 @@ def mbk_chunk_words(cin, cout):
 
 
 def mbk_pack(we_t, e_scale, e_shift, dw, d_scale, d_shift, wp_t, p_scale, p_shift):
-    """Parameters of a YR_OP_MBR block in its WEIGHT-STREAMING form (k bits 6, 7; mbk.hip): ceil(T / 2) chunks, chunk q = the pair of
+    """Parameters of a YR_OP_MBR block in its WEIGHT-STREAMING form (rt.MBR_STREAM | rt.MBR_SPLIT; mbk.hip): ceil(T / 2) chunks, chunk q = the pair of
     expanded tiles (2 q, 2 q + 1) = [2 tiles][NKE][2 planes][64 lanes][8 halves] expand fragments | [TO][2 planes][64][8] project
     fragments | [2 tiles][11][16] float32 (taps x BN scale | depthwise BN shift | expand BN shift) | zeros up to 2 KB - the fragments
     are mbs_pack's (one wave: consecutive tiles pair up), re-ordered so that a chunk is ONE contiguous piece of the blob.
@@ -1471,11 +1471,11 @@ def fuse_inverted_residuals(ops, output_buf_ids, blocks=True, dtype=0, bufs=None
                     part.h, part.elems = rows, rows * part.w * part.ld
                     part.bytes = part.elems * rt.ESIZE[part.dtype]
                 # the matrix-pipe form of this entry (mbxr_h.hip: stemxr_kernel; float32 image of even size, at most 48 stem channels):
-                # asked for by the PLAN (k = 3 | 1 << 8), so that every batch size rounds the same way
+                # asked for by the PLAN (rt.STEMBLOCK_ENTRY_MFMA in k), so that every batch size rounds the same way
                 src0 = e.srcs[0].buf
                 mfma_entry = (FUSE_STEMDW_MFMA and src0.dtype == 0 and src0.h % 2 == 0 and src0.w % 2 == 0 and c1 <= 48 and c1 % 4 == 0
                               and e.act in ('relu6', 'swish') and d.out.ld % 4 == 0)
-                m = OpRec(rt.OP_STEMBLOCK, e.name + '_dw', act=e.act, h=d.h, w=d.w, cin=3, cout=c1, k=3 | (1 << 8 if mfma_entry else 0), stride=2,
+                m = OpRec(rt.OP_STEMBLOCK, e.name + '_dw', act=e.act, h=d.h, w=d.w, cin=3, cout=c1, k=3 | (rt.STEMBLOCK_ENTRY_MFMA << rt.STEMBLOCK_ENTRY_SHIFT if mfma_entry else 0), stride=2,
                           se_reduced=c1, srcs=[e.srcs[0]], out=d.out, gate=part, macs=e.macs + d.macs, dtype=dtype)
                 m.fused = [e, d]
 
@@ -1514,7 +1514,7 @@ def fuse_inverted_residuals(ops, output_buf_ids, blocks=True, dtype=0, bufs=None
                 cin, cexp, cout = bi.c, d.cin, p.cout
                 rows, nw = MBK_SHAPES[key]
                 T, TO = cexp // 16, (cout + 15) // 16
-                m = OpRec(rt.OP_MBR, bname + '_mbr', act='relu6', h=p.h, w=p.w, cin=cin, cout=cout, k=3 | 0xc0 | nw << 8 | rows << 16,
+                m = OpRec(rt.OP_MBR, bname + '_mbr', act='relu6', h=p.h, w=p.w, cin=cin, cout=cout, k=3 | rt.MBR_STREAM | rt.MBR_SPLIT | nw << rt.MBR_NW_SHIFT | rows << rt.MBR_SEGS_SHIFT,
                           stride=d.stride, se_reduced=cexp, srcs=[bi], out=p.out, res=p.res, macs=exp.macs + d.macs + p.macs, dtype=0)
                 m.fused = [exp, d, p]
                 ep, dp, pp = exp.params, d.params, p.params
@@ -1539,7 +1539,7 @@ def fuse_inverted_residuals(ops, output_buf_ids, blocks=True, dtype=0, bufs=None
                 if split:
                     nw = MBS_SHAPES[key]
                 T, TO, KE = cexp // 16, (cout + 15) // 16, cin // 4
-                m = OpRec(rt.OP_MBR, bname + '_mbr', act='relu6', h=p.h, w=p.w, cin=cin, cout=cout, k=3 | (0x80 if split else 0) | nw << 8 | segs << 16,
+                m = OpRec(rt.OP_MBR, bname + '_mbr', act='relu6', h=p.h, w=p.w, cin=cin, cout=cout, k=3 | (rt.MBR_SPLIT if split else 0) | nw << rt.MBR_NW_SHIFT | segs << rt.MBR_SEGS_SHIFT,
                           stride=d.stride, se_reduced=cexp, srcs=[bi], out=p.out, res=p.res, macs=exp.macs + d.macs + p.macs, dtype=0)
                 m.fused = [exp, d, p]
                 ep, dp, pp = exp.params, d.params, p.params
@@ -1573,7 +1573,7 @@ def fuse_inverted_residuals(ops, output_buf_ids, blocks=True, dtype=0, bufs=None
             T, KE = cexp // 16, bi.c // 4
             mbe_split = (MBR_SPLIT and bi.c in MBS_MBE_CINS and exp.name.rsplit('_', 1)[0] + '_mbe' not in nosplit
                          and exp.name.rsplit('_', 1)[0] + '_mbr' not in nosplit)     # (... or the block's one-launch form was found out of range)
-            m = OpRec(rt.OP_MBE, exp.name.rsplit('_', 1)[0] + '_mbe', act='relu6', h=d.h, w=d.w, cin=bi.c, cout=cexp, k=3 | (0x80 if mbe_split else 0), stride=d.stride,
+            m = OpRec(rt.OP_MBE, exp.name.rsplit('_', 1)[0] + '_mbe', act='relu6', h=d.h, w=d.w, cin=bi.c, cout=cexp, k=3 | (rt.MBR_SPLIT if mbe_split else 0), stride=d.stride,
                       srcs=[bi], out=d.out, macs=exp.macs + d.macs, dtype=0)
             m.fused = [exp, d]
             ep, dp = exp.params, d.params
@@ -1959,29 +1959,29 @@ class Compiler:
             if latency and self.dtype == 0:
                 # the plan for a few images keeps the float32-MFMA pointwise kernels: at 169 ... 2704 pixels per map a conv waits for
                 # its round trips, not for the matrix pipe, and the split form's plane-cutting stage is pure overhead there
-                # (batch 1 @416: p50 0.64 ms against 0.68).  se_reduced bit 16 of a POINTWISE op = "not the split form".
+                # (batch 1 @416: p50 0.64 ms against 0.68).  rt.PWF_F32_MFMA on a POINTWISE op = "not the split form".
                 for o in ops:
                     if o.kind == rt.OP_POINTWISE and not any(s_.xform == 'dw3' for s_ in o.srcs):
-                        o.se_reduced |= 0x10000
+                        o.se_reduced |= rt.PWF_F32_MFMA
             if latency and self.dtype != 0 and KSPLIT_MAX_PIXELS > 0:
                 # the 16-bit plan for one or two images: its small maps' pointwise convs in the k-split form too (pointwise_h.hip: pwkh_kernel -
                 # a gated projection of 1152 channels is 36 chunks behind each other in pwh_kernel: 9.8 us at one image)
                 for o in ops:
                     if o.kind == rt.OP_POINTWISE and not any(s_.xform == 'dw3' for s_ in o.srcs):
                         if o.h * o.w * (4 if getattr(o, 'stride', 0) == 2 else 1) <= KSPLIT_MAX_PIXELS:
-                            o.se_reduced |= 0x20000
+                            o.se_reduced |= rt.PWF_KSPLIT
             if self.fuse == 'nohead_k' and self.dtype == 0 and KSPLIT_MAX_PIXELS > 0:
                 # fuse == 'nohead_k' (one or two images: Model.ksplit_batch): the 'nohead' plan whose small maps take the K-SPLIT form of the
-                # split pointwise kernel (se_reduced bit 17; pointwise_split.hip:
+                # split pointwise kernel (rt.PWF_KSPLIT; pointwise_split.hip:
                 # pwk_kernel): at 169 .. 2704 pixels a conv is a few workgroups, each one latency chain of k chunks - there a workgroup
                 # is one 16 x 16 tile and its four waves split the k range.  A property of the plan (the sums are grouped by wave).
                 for o in ops:
-                    if o.kind == rt.OP_POINTWISE and not any(s_.xform == 'dw3' for s_ in o.srcs) and not (o.se_reduced & 0x10000):
+                    if o.kind == rt.OP_POINTWISE and not any(s_.xform == 'dw3' for s_ in o.srcs) and not (o.se_reduced & rt.PWF_F32_MFMA):
                         if o.h * o.w * (4 if getattr(o, 'stride', 0) == 2 else 1) <= KSPLIT_MAX_PIXELS:
-                            o.se_reduced |= 0x20000
+                            o.se_reduced |= rt.PWF_KSPLIT
         for o in ops:     # (also without fusion: a float32 POINTWISE op named by Model.check_ranges keeps the float32 MFMA)
             if o.kind == rt.OP_POINTWISE and o.name in self.nosplit:
-                o.se_reduced |= 0x10000
+                o.se_reduced |= rt.PWF_F32_MFMA
         if PW_STREAM and PW_SPLIT and (self.fuse is True or (self.fuse == 'mid' and PW_STREAM_MID)) and self.dtype == 0:
             # the throughput plan's 1x1 convs in the pixel-stationary form (pointwise_stream.hip): HBM-bound launches that the tiled kernel
             # ran at a third of the memory rate
@@ -2257,19 +2257,19 @@ def nosplit_aliases(names):
     return frozenset(out)
 
 
+def in_split_form(o):
+    """Whether the GEMM operands of op `o` travel as float16 planes (|x| < 65504 required): a float32 POINTWISE op at least 16 channels
+    deep without rt.PWF_F32_MFMA (and no depthwise-folded source), MBR / MBE with rt.MBR_SPLIT, HEAD."""
+    if o.dtype != 0:
+        return False
+    if o.kind == rt.OP_POINTWISE:
+        kp = sum(round_up(s_.c, 4) for s_ in o.srcs if s_.xform != 'up2_add')
+        return bool(PW_SPLIT and kp >= 16 and not (o.se_reduced & rt.PWF_F32_MFMA) and not any(s_.xform == 'dw3' for s_ in o.srcs))
+    if o.kind in (rt.OP_MBR, rt.OP_MBE):
+        return bool(o.k & rt.MBR_SPLIT)
+    return o.kind == rt.OP_HEAD
+
+
 def split_form_ops(plan):
-    """Indices of the ops of a float32 plan whose GEMM operands travel as float16 planes (|x| < 65504 required): POINTWISE ops at
-    least 16 channels deep without the keep-float32 flag (and no depthwise-folded source), MBR / MBE with k bit 7, HEAD."""
-    idx = []
-    for i, o in enumerate(plan.ops):
-        if o.dtype != 0:
-            continue
-        if o.kind == rt.OP_POINTWISE:
-            kp = sum(round_up(s_.c, 4) for s_ in o.srcs if s_.xform != 'up2_add')
-            if PW_SPLIT and kp >= 16 and not (o.se_reduced & 0x10000) and not any(s_.xform == 'dw3' for s_ in o.srcs):
-                idx.append(i)
-        elif o.kind in (rt.OP_MBR, rt.OP_MBE) and o.k & 0x80:
-            idx.append(i)
-        elif o.kind == rt.OP_HEAD:
-            idx.append(i)
-    return idx
+    """Indices of the ops of a float32 plan that are in a split form (in_split_form)."""
+    return [i for i, o in enumerate(plan.ops) if in_split_form(o)]

@@ -20,7 +20,7 @@
 // move the F-wide map twice.
 //
 // Two GEMM front ends feed the same finish (head_finish):
-//   * head2_kernel (k bit 7: the plan packed the weights as float16 planes in fragment order, compiler.head_pack): the
+//   * head2_kernel (YR_HEAD_PLANES: the plan packed the weights as float16 planes in fragment order, compiler.head_pack): the
 //     activations of a 32-channel chunk travel global memory -> LDS by LDS-DIRECT loads (no staging registers, no address
 //     arithmetic per element, no ds_write pass: round 5's profile of the first version showed ~50 VALU instructions per 16 bytes
 //     fetched and the k loop VALU-bound at 2 workgroups per CU), XOR-swizzled on the source side so the fragment reads are
@@ -497,12 +497,12 @@ static int launch_head(const HeadArgs& h, int batch, hipStream_t s) {
 }
 
 int yr_launch_head(const yr_op& op, int batch, hipStream_t s) {
-    if ((op.k & 0x60) == 0x60 && op.dtype == YR_F32) return yr_launch_head_stream(op, batch, s);   // the weight-streaming form (headstream.hip)
-    if (op.k & 0x40) return yr_launch_head_walk(op, batch, s);   // the walking form (headwalk.hip; headwalk_h.hip for the 16-bit plans)
+    if ((op.k & YR_HEAD_STREAM) == YR_HEAD_STREAM && op.dtype == YR_F32) return yr_launch_head_stream(op, batch, s);   // the weight-streaming form (headstream.hip)
+    if (op.k & YR_HEAD_WALK) return yr_launch_head_walk(op, batch, s);   // the walking form (headwalk.hip; headwalk_h.hip for the 16-bit plans)
     YR_REQUIRE(op.dtype == YR_F32 && op.out_dtype == YR_F32, "head: the LDS-tiled forms are float32 only (16-bit plans: the walking form, k bit 6)");
-    YR_REQUIRE((op.k & 0x7f) == 3 && op.stride == 1, "head: depthwise 3x3, stride 1");
+    YR_REQUIRE((op.k & (YR_HEAD_K_MASK | YR_HEAD_STREAM)) == 3 && op.stride == 1, "head: depthwise 3x3, stride 1");
     YR_REQUIRE(op.out && op.wgt && op.wgt2, "head: null pointer");
-    const bool v2 = (op.k & 0x80) != 0;     // the weights are float16 planes in fragment order (compiler.head_pack)
+    const bool v2 = (op.k & YR_HEAD_PLANES) != 0;     // the weights are float16 planes in fragment order (compiler.head_pack)
     HeadArgs h;
     PwArgs& a = h.p;
     // ---- the convolution's sources, as yr_launch_pointwise reads them
@@ -537,7 +537,7 @@ int yr_launch_head(const yr_op& op, int batch, hipStream_t s) {
     }
     a.out = (float*)op.out; a.out_ld = op.out_ld;
     a.H = op.h; a.W = op.w; a.N = op.cout; a.M = batch * op.h * op.w;
-    a.act = (op.k >> 8) & 0xff; a.pool = 0;
+    a.act = (op.k & YR_HEAD_ACT_MASK) >> YR_HEAD_ACT_SHIFT; a.pool = 0;
     a.dw_w = nullptr; a.dw_scale = a.dw_shift = nullptr; a.dw_stride = a.dw_act = a.dw_pad_t = a.dw_pad_l = 0; a.out_f32 = 1;
     YR_REQUIRE(op.out_ld % 4 == 0 && op.out_ld >= op.cout && op.cout % 4 == 0 && ((uintptr_t)op.out % 16) == 0, "head: output stride / width");
     if (a.pre) YR_REQUIRE(op.h % 2 == 0 && op.w % 2 == 0, "head: an up-sampled addend needs even dims");
@@ -552,7 +552,7 @@ int yr_launch_head(const yr_op& op, int batch, hipStream_t s) {
     if (rc) return rc;
     h.sums = const_cast<float*>(op.gate); h.ld_sums = op.gate_ld;
     if (exp & 32) h.se.w = nullptr;   // (probing: arrival without the FC pair)
-    const int cfg = (op.k >> 16) & 0xff;   // 0: the library's choice (a function of the shape); else the cout tiles of 16 per workgroup
+    const int cfg = (op.k & YR_HEAD_TILES_MASK) >> YR_HEAD_TILES_SHIFT;   // 0: the library's choice (a function of the shape); else the cout tiles of 16 per workgroup
     const int ct = cfg ? cfg : op.cout >= 64 ? 4 : op.cout >= 32 ? 2 : 1;
     if (v2) {
         if (ct >= 4) return launch_head<4, true>(h, batch, s);

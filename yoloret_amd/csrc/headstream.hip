@@ -1,4 +1,4 @@
-// YR_OP_HEAD, WEIGHT-STREAMING form (k bits 5 and 6; round 6): the detection-head block's Concatenate + 1x1 conv + BN + ReLU6 ->
+// YR_OP_HEAD, WEIGHT-STREAMING form (YR_HEAD_STREAM; round 6): the detection-head block's Concatenate + 1x1 conv + BN + ReLU6 ->
 // depthwise 3x3 + BN + Swish -> squeeze-excite sums (reference code/yolo3/model.py:91-115, efficientnet.py:406-438,467-536) in mbk.hip's
 // formulation: the PIXELS are stationary, the weights stream.
 //   * a workgroup owns a strip of 16 columns x NW * ROWS rows of the map; a wave owns ROWS (1 | 2) of those rows for the whole kernel: the
@@ -440,15 +440,15 @@ static int launch_hstream(HsArgs& a, int batch, hipStream_t s) {
     return YR_OK;
 }
 
-// op fields as the walking form of YR_OP_HEAD (headwalk.hip) with k bit 5 as well: wgt = the float16 planes of compiler.head_pack with the
+// op fields as the walking form of YR_OP_HEAD (headwalk.hip) with YR_HEAD_STREAM_BIT as well: wgt = the float16 planes of compiler.head_pack with the
 // conv's BN scale folded in ([T][NK][2 planes][64][8]); scale = the conv's BN scale [F]; wgt2 = [T = F / 16][11][16] (YR_OP_MBR's table);
 // se_reduced = yr_head_stream_rows(h, w); sources: one to three float32 sources, identity or maxpool2, an up2_add addend last; res = the SE
 // gate of the single source.  F a multiple of 32.
 int yr_launch_head_stream(const yr_op& op, int batch, hipStream_t s) {
     YR_REQUIRE(op.dtype == YR_F32 && op.out_dtype == YR_F32 && op.out && op.wgt && op.wgt2 && op.scale, "head (weight-streaming form): float32, non-null parameters");
-    YR_REQUIRE((op.k & 0x1f) == 3 && op.stride == 1 && op.cout % 32 == 0 && op.out_ld % 4 == 0 && op.out_ld >= op.cout, "head (weight-streaming form): 3x3 stride 1, F a multiple of 32");
+    YR_REQUIRE((op.k & YR_HEAD_K_MASK) == 3 && op.stride == 1 && op.cout % 32 == 0 && op.out_ld % 4 == 0 && op.out_ld >= op.cout, "head (weight-streaming form): 3x3 stride 1, F a multiple of 32");
     YR_REQUIRE(op.gate_out == nullptr, "head (weight-streaming form): the squeeze-excite tail is not built for this form");
-    const int act = (op.k >> 8) & 0xff;
+    const int act = (op.k & YR_HEAD_ACT_MASK) >> YR_HEAD_ACT_SHIFT;
     YR_REQUIRE(act == YR_ACT_RELU6 || act == YR_ACT_NONE, "head (weight-streaming form): conv activation ReLU6 or none");
     HsArgs a;
     int nsrc = op.nsrc;

@@ -1,4 +1,4 @@
-// YR_OP_HEAD, WALKING form (k bit 6; round 5): the detection-head block's 1x1 conv + BN + ReLU6 -> depthwise 3x3 + BN + Swish ->
+// YR_OP_HEAD, WALKING form (YR_HEAD_WALK; round 5): the detection-head block's 1x1 conv + BN + ReLU6 -> depthwise 3x3 + BN + Swish ->
 // squeeze-excite sums (reference code/yolo3/model.py:91-115, efficientnet.py:406-438,467-536) as mbe_kernel (mbr.hip) does the
 // first two thirds of a MobileNetV2 block: a WAVE owns a strip of 16 input columns x a run of rows x NT output-channel tiles of 16
 // and walks down the rows -
@@ -292,14 +292,14 @@ static int launch_hwalk(HwArgs& a, int batch, hipStream_t s) {
     return YR_OK;
 }
 
-// op fields as YR_OP_HEAD (headblock.hip) with k bit 6: wgt = the float16 planes of compiler.head_pack with the conv's BN scale
+// op fields as YR_OP_HEAD (headblock.hip) with YR_HEAD_WALK: wgt = the float16 planes of compiler.head_pack with the conv's BN scale
 // folded in; scale = the conv's BN scale [F] (for the pre-BN addend); wgt2 = [T = F / 16][11][16]: depthwise taps x BN scale |
 // depthwise BN shift | conv BN shift (YR_OP_MBR's table); se_reduced = yr_head_walk_rows(h, w).
 int yr_launch_head_walk(const yr_op& op, int batch, hipStream_t s) {
     if (op.dtype != YR_F32) return yr_launch_head_walk_h(op, batch, s);   // the 16-bit plans' twin (headwalk_h.hip)
     YR_REQUIRE(op.dtype == YR_F32 && op.out_dtype == YR_F32 && op.out && op.wgt && op.wgt2 && op.scale, "head (walking form): float32, non-null parameters");
-    YR_REQUIRE((op.k & 0x3f) == 3 && op.stride == 1 && op.cout % 16 == 0 && op.out_ld % 4 == 0 && op.out_ld >= op.cout, "head (walking form): 3x3 stride 1, F a multiple of 16");
-    const int act = (op.k >> 8) & 0xff;
+    YR_REQUIRE((op.k & (YR_HEAD_K_MASK | YR_HEAD_STREAM_BIT)) == 3 && op.stride == 1 && op.cout % 16 == 0 && op.out_ld % 4 == 0 && op.out_ld >= op.cout, "head (walking form): 3x3 stride 1, F a multiple of 16");
+    const int act = (op.k & YR_HEAD_ACT_MASK) >> YR_HEAD_ACT_SHIFT;
     YR_REQUIRE(act == YR_ACT_RELU6 || act == YR_ACT_NONE, "head (walking form): conv activation ReLU6 or none");
     HwArgs a;
     int nsrc = op.nsrc;

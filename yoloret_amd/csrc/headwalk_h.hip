@@ -1,4 +1,4 @@
-// YR_OP_HEAD, WALKING form, 16-BIT plans (k bit 6, dtype bf16 / f16; round 5): the detection-head block's 1x1 conv + BN + ReLU6 ->
+// YR_OP_HEAD, WALKING form, 16-BIT plans (YR_HEAD_WALK, dtype bf16 / f16; round 5): the detection-head block's 1x1 conv + BN + ReLU6 ->
 // depthwise 3x3 + BN + Swish -> squeeze-excite sums (reference code/yolo3/model.py:91-115, efficientnet.py:406-438,467-536) in one
 // launch, for the EfficientNet configurations (BASELINE c3 / c5 and the SE EfficientNets), the 16-bit twin of headwalk.hip:
 //   * a WAVE owns a strip of 16 input columns x a run of rows x NT = 2 output-channel tiles of 16 and walks down the rows; the conv
@@ -247,14 +247,14 @@ static int launch_head_walk_h(HwhArgs& a, int nk, int batch, hipStream_t s) {
     return YR_ERR_ARG;
 }
 
-// op fields as YR_OP_HEAD (include/yoloret_hip.h) with k bit 6 and dtype = out_dtype = bf16 | f16: wgt = the 16-bit weight fragments
+// op fields as YR_OP_HEAD (include/yoloret_hip.h) with YR_HEAD_WALK and dtype = out_dtype = bf16 | f16: wgt = the 16-bit weight fragments
 // [F / 16][NK][64 lanes][8] (compiler.head_pack16: the conv's weights as they are, no BN scale), scale = conv BN scale [F] float32,
 // wgt2 = [F / 16][11][16] float32: depthwise taps x BN scale | depthwise BN shift | conv BN shift; se_reduced = yr_head_walk_rows(h, w).
 int yr_launch_head_walk_h(const yr_op& op, int batch, hipStream_t s) {
     YR_REQUIRE((op.dtype == YR_BF16 || op.dtype == YR_F16) && op.out_dtype == op.dtype && op.out && op.wgt && op.wgt2 && op.scale, "head (walking form, 16-bit): bf16 / f16, non-null parameters");
-    YR_REQUIRE((op.k & 0x3f) == 3 && op.stride == 1 && op.cout % 16 == 0 && op.out_ld % 4 == 0 && op.out_ld >= op.cout && ((uintptr_t)op.out % 8) == 0, "head (walking form, 16-bit): 3x3 stride 1, F a multiple of 16");
+    YR_REQUIRE((op.k & (YR_HEAD_K_MASK | YR_HEAD_STREAM_BIT)) == 3 && op.stride == 1 && op.cout % 16 == 0 && op.out_ld % 4 == 0 && op.out_ld >= op.cout && ((uintptr_t)op.out % 8) == 0, "head (walking form, 16-bit): 3x3 stride 1, F a multiple of 16");
     YR_REQUIRE(op.gate_out == nullptr, "head (walking form, 16-bit): the squeeze-excite tail is not built (an SE_FC op finishes the sums)");
-    const int act = (op.k >> 8) & 0xff;
+    const int act = (op.k & YR_HEAD_ACT_MASK) >> YR_HEAD_ACT_SHIFT;
     YR_REQUIRE(act == YR_ACT_RELU6 || act == YR_ACT_NONE, "head (walking form, 16-bit): conv activation ReLU6 or none");
     HwhArgs a;
     int nsrc = op.nsrc;

@@ -541,7 +541,7 @@ static int launch_mbh_shape(const MbhArgs& a, int cp, int ng, int batch, hipStre
 // 128 outputs per group slot, i.e. 128 for NG = 1, 256 for NG = 2): few wasted pixels in ragged edge tiles, a small
 // halo-to-output ratio (the expand GEMM and its epilogue run on halo pixels), whole groups of 8 runs for the four waves,
 // an LDS footprint that leaves several workgroups per CU, and enough workgroups to fill 256 CUs.  The constants were
-// fitted to tools/mbh_probe.py on the MobileNetV2 block shapes.  op.k may force a choice: k = K | th << 8 | tw << 16.
+// fitted to tools/mbh_probe.py on the MobileNetV2 block shapes.  op.k may force a choice: k = K | th << YR_MBH_TH_SHIFT | tw << YR_MBH_TW_SHIFT.
 // cp == 0: the expand + depthwise form; max_tiles > 0 bounds the tiles per image (rows of its partial-sum buffer).
 static void mbh_pick_tile(int ho, int wo, int batch, int k, int s, int kp, int cp, int max_tiles, int* th_out, int* tw_out) {
     double best = 1e30;
@@ -571,7 +571,7 @@ static void mbh_pick_tile(int ho, int wo, int batch, int k, int s, int kp, int c
 }
 
 // op fields (YR_OP_MBH): src[0] = block input (16-bit, ld % 8 == 0); cin; se_reduced = expanded width Cexp; cout <= 128;
-// k = K (3 | 5), optionally | th << 8 | tw << 16 to force the output tile (tw % 4 == 0); stride 1 | 2; act = expand / depthwise
+// k = K (3 | 5), optionally | th << YR_MBH_TH_SHIFT | tw << YR_MBH_TW_SHIFT to force the output tile (tw % 4 == 0); stride 1 | 2; act = expand / depthwise
 // activation; res (optional) = the block input itself (stride 1, cin == cout).  With CexpP = round_up(Cexp, 32),
 // KP = round_up(cin, 32), everything zero padded:
 //   wgt  = expand Wt[CexpP][KP] (16-bit, in the blob: CexpP*KP/2 floats);
@@ -582,15 +582,15 @@ static void mbh_pick_tile(int ho, int wo, int batch, int k, int s, int kp, int c
 // (se_reduced = rows of the buffer >= tiles per image; the rows no tile owns are zeroed).
 template <class T>
 static int launch_mbh_t(const yr_op& op_in, int batch, hipStream_t s) {
-    // forced tile th = 254: this file's (and mbn_h.hip's) own choice, never the register-chained forms - the tuner's way to
+    // forced tile th = YR_MBH_TILE_LDS: this file's (and mbn_h.hip's) own choice, never the register-chained forms - the tuner's way to
     // time both, and the A/B switch of the tests
-    const bool legacy = ((op_in.k >> 8) & 0xff) == 254;
+    const bool legacy = ((op_in.k & YR_MBH_TH_MASK) >> YR_MBH_TH_SHIFT) == YR_MBH_TILE_LDS;
     yr_op op = op_in;
-    if (legacy) op.k &= 0xff;
+    if (legacy) op.k &= YR_MBH_K_MASK;
     const bool full = op.kind == YR_OP_MBH;
     YR_REQUIRE(op.nsrc == 1 && op.src[0].xform == YR_X_IDENTITY, "mbh: needs one identity source");
     const yr_src& in = op.src[0];
-    const int K = op.k & 0xff, fth = (op.k >> 8) & 0xff, ftw = (op.k >> 16) & 0xff;
+    const int K = op.k & YR_MBH_K_MASK, fth = (op.k & YR_MBH_TH_MASK) >> YR_MBH_TH_SHIFT, ftw = (op.k & YR_MBH_TW_MASK) >> YR_MBH_TW_SHIFT;
     YR_REQUIRE((K == 3 || K == 5) && (op.stride == 1 || op.stride == 2), "mbh: depthwise %dx%d stride %d is not fused", K, K, op.stride);
     YR_REQUIRE(in.ptr && op.out && op.wgt && op.wgt2 && (!full || (op.b1 && op.b2)), "mbh: null pointer");
     YR_REQUIRE(in.dtype == op.dtype && op.out_dtype == op.dtype, "mbh: input and output have the op's 16-bit dtype");
@@ -599,14 +599,14 @@ static int launch_mbh_t(const yr_op& op_in, int batch, hipStream_t s) {
     YR_REQUIRE(((uintptr_t)in.ptr | (uintptr_t)op.out | (uintptr_t)op.wgt | (uintptr_t)op.b1 | (uintptr_t)op.wgt2) % 16 == 0, "mbh: pointers must be 16-byte aligned");
     YR_REQUIRE(op.cout >= 1 && op.cin >= 1 && op.cin <= 128, "mbh: widths out of range (cin <= 128)");
     if (full) {
-        // the whole block in the register-chained form (mbxr_h.hip: mbhr_kernel): forced tile th = 255 (tw = row segments);
+        // the whole block in the register-chained form (mbxr_h.hip: mbhr_kernel): forced tile th = YR_MBH_TILE_CHAINED (tw = row segments);
         // without a forced tile it is the default where it is built (YOLORET_MBHR=0: the kernels below, for A/B runs)
         if (!legacy && yr_mbh_prefers_chained(op) && yr_mbhr_built(op)) {
             YR_REQUIRE(op.res == nullptr || (op.res == in.ptr && op.stride == 1 && in.c == op.cout), "mbh: the residual must be the block input (stride 1, cin == cout)");
             YR_REQUIRE((in.h + op.stride - 1) / op.stride == op.h && (in.w + op.stride - 1) / op.stride == op.w, "mbh: output dims mismatch");
-            return yr_launch_mbhr(op, batch, fth == 255 ? ftw : 0, s);
+            return yr_launch_mbhr(op, batch, fth == YR_MBH_TILE_CHAINED ? ftw : 0, s);
         }
-        YR_REQUIRE(fth != 255, "mbh: the register-chained whole-block form (tile 255) is not built for this op");
+        YR_REQUIRE(fth != YR_MBH_TILE_CHAINED, "mbh: the register-chained whole-block form (tile 255) is not built for this op");
     }
     {   // the narrow stride-2 3x3 block at the network's front: its own kernel (mbn_h.hip; YOLORET_MBN=0: this one, for A/B runs)
         static const bool mbn_on = !(getenv("YOLORET_MBN") && atoi(getenv("YOLORET_MBN")) == 0);
@@ -641,10 +641,10 @@ static int launch_mbh_t(const yr_op& op_in, int batch, hipStream_t s) {
     if (a.has_res) YR_REQUIRE(op.res == in.ptr && op.stride == 1 && in.c == op.cout, "mbh: the residual must be the block input (stride 1, cin == cout)");
     a.act = op.act;
     if (!full) {
-        // the expand + depthwise form has a second kernel (mbxr_h.hip): forced tile th = 255 selects it (tw = row segments),
+        // the expand + depthwise form has a second kernel (mbxr_h.hip): forced tile th = YR_MBH_TILE_CHAINED selects it (tw = row segments),
         // no forced tile: it is the default where it is built (YOLORET_MBXR=0: the LDS-tiled form below, for A/B runs)
-        if (!legacy && yr_mbh_prefers_chained(op) && yr_mbxr_takes(op)) return yr_launch_mbxr(op, batch, fth == 255 ? ftw : 0, s);
-        YR_REQUIRE(fth != 255, "mbx: the register-chained form (tile 255) is not built for this op");
+        if (!legacy && yr_mbh_prefers_chained(op) && yr_mbxr_takes(op)) return yr_launch_mbxr(op, batch, fth == YR_MBH_TILE_CHAINED ? ftw : 0, s);
+        YR_REQUIRE(fth != YR_MBH_TILE_CHAINED, "mbx: the register-chained form (tile 255) is not built for this op");
     }
     const int cp = !full ? 0 : op.cout <= 32 ? 1 : (op.cout <= 64 ? 2 : 4);
     if (fth && ftw) { a.th = fth; a.tw = ftw; }

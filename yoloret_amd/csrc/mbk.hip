@@ -1,4 +1,4 @@
-// Fused inverted-residual block, float32 (split form), WEIGHT-STREAMING formulation (YR_OP_MBR with k bit 6: the blocks whose
+// Fused inverted-residual block, float32 (split form), WEIGHT-STREAMING formulation (YR_OP_MBR with YR_MBR_STREAM: the blocks whose
 // two 1x1 convolutions do not fit one CU's register file - MobileNetV2 x0.75 block_11..15: 72 -> 432 -> 72 | 120, 120 -> 720 -> 120;
 // x1.4: 88 -> 528 -> 88 | 136, 136 -> 816 -> 136; [3P] via reference code/yolo3/override.py:290-341):
 //   expand 1x1 + BN + ReLU6 -> depthwise 3x3 (stride 1|2, TF SAME) + BN + ReLU6 -> project 1x1 + BN (+ residual)
@@ -490,8 +490,8 @@ static int launch_mbk(const MbkArgs& a0, int batch, hipStream_t s) {
     return YR_OK;
 }
 
-// YR_OP_MBR with k bit 6 (and bit 7: the operands are float16 planes): the weight-streaming form.  Op fields as YR_OP_MBR; k bits 8-15 =
-// waves per workgroup, bits 16-23 = rows per wave (both fixed by the plan: compiler.MBK_SHAPES).  wgt = NQ = ceil(Cexp / 32) chunks, one per
+// YR_OP_MBR with YR_MBR_STREAM (and YR_MBR_SPLIT: the operands are float16 planes): the weight-streaming form.  Op fields as YR_OP_MBR; YR_MBR_NW_MASK =
+// waves per workgroup, YR_MBR_SEGS_MASK = rows per wave (both fixed by the plan: compiler.MBK_SHAPES).  wgt = NQ = ceil(Cexp / 32) chunks, one per
 // pair of expanded tiles (2 q, 2 q + 1), each [2 tiles][NKE][2 planes][64 lanes][8 halves] expand fragments (mbs_pack's) |
 // [TO][2 planes][64][8] project fragments of the pair | [2 tiles][11][16] float32 (taps x BN scale | depthwise BN shift | expand BN shift)
 // | zeros up to a multiple of 1 KB;  b2 = project BN shift [16 TO];  wgt2 unused.
@@ -499,7 +499,7 @@ int yr_launch_mbk(const yr_op& op, int batch, hipStream_t s) {
     YR_REQUIRE(op.dtype == YR_F32 && op.out_dtype == YR_F32, "mbk: float32 plans only");
     YR_REQUIRE(op.nsrc == 1 && op.src[0].xform == YR_X_IDENTITY && op.src[0].dtype == YR_F32, "mbk: needs one float32 identity source");
     const yr_src& in = op.src[0];
-    YR_REQUIRE((op.k & 0x3f) == 3 && (op.k & 0xc0) == 0xc0 && (op.stride == 1 || op.stride == 2) && op.act == YR_ACT_RELU6, "mbk: 3x3, stride 1|2, ReLU6, split + streamed form");
+    YR_REQUIRE((op.k & YR_MBR_K_MASK) == 3 && (op.k & (YR_MBR_STREAM | YR_MBR_SPLIT)) == (YR_MBR_STREAM | YR_MBR_SPLIT) && (op.stride == 1 || op.stride == 2) && op.act == YR_ACT_RELU6, "mbk: 3x3, stride 1|2, ReLU6, split + streamed form");
     YR_REQUIRE(in.ptr && op.out && op.wgt && op.b2, "mbk: null pointer");
     YR_REQUIRE(in.ld % 4 == 0 && op.out_ld % 4 == 0 && in.c == op.cin && in.ld >= in.c && op.out_ld >= op.cout, "mbk: channel strides");
     YR_REQUIRE(((uintptr_t)in.ptr) % 16 == 0 && ((uintptr_t)op.out) % 16 == 0 && ((uintptr_t)op.wgt) % 16 == 0, "mbk: pointers must be 16-byte aligned");
@@ -513,7 +513,7 @@ int yr_launch_mbk(const yr_op& op, int batch, hipStream_t s) {
     const bool res = op.res != nullptr;
     if (res) YR_REQUIRE(op.res == in.ptr && op.stride == 1 && in.c == op.cout, "mbk: the residual must be the block input (stride 1, Cin == Cout)");
     a.strips = a.segs = 0; a.wa_bytes = 0;
-    const int nw = (op.k >> 8) & 0xff, rows = (op.k >> 16) & 0xff;
+    const int nw = (op.k & YR_MBR_NW_MASK) >> YR_MBR_NW_SHIFT, rows = (op.k & YR_MBR_SEGS_MASK) >> YR_MBR_SEGS_SHIFT;
 #ifdef MBK_EXPERIMENT
     if (const char* e = getenv("YR_MBK_EXP")) {
         switch (atoi(e)) {

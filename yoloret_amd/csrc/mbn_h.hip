@@ -194,7 +194,7 @@ static int launch_mbn(const MbnArgs& a, int batch, hipStream_t s) {
 // Whether yr_launch_mbh hands the op over (its checks have passed): the whole block, 3x3 stride 2, at most 32 inputs in whole
 // 16-byte vectors, at most 192 expanded channels (two passes of 96), at most 32 outputs, no residual, ReLU6 or swish.
 bool yr_mbn_takes(const yr_op& op) {
-    return op.kind == YR_OP_MBH && (op.k & 0xff) == 3 && (op.k >> 8) == 0 && op.stride == 2 && op.src[0].c <= 32 && op.src[0].c % 8 == 0 && op.se_reduced <= 192 &&
+    return op.kind == YR_OP_MBH && (op.k & YR_MBH_K_MASK) == 3 && (op.k & ~YR_MBH_K_MASK) == 0 && op.stride == 2 && op.src[0].c <= 32 && op.src[0].c % 8 == 0 && op.se_reduced <= 192 &&
            op.cout <= 32 && op.res == nullptr && (op.act == YR_ACT_RELU6 || op.act == YR_ACT_SWISH);
 }
 

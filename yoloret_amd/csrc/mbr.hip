@@ -619,13 +619,13 @@ static int launch_mbe(const MbeArgs& a0, int batch, int want_segs, hipStream_t s
 }
 
 // op fields: src[0] = block input (float32, c % 16 in {0, 8}); cout = Cexp = width of the stored depthwise map (multiple of 16);
-// k = 3 | segs << 16; stride 1 | 2; act = ReLU6 (both activations).  wgt = expand A fragments [T][KE][64] (register order of
+// k = 3 | segs << YR_MBR_SEGS_SHIFT; stride 1 | 2; act = ReLU6 (both activations).  wgt = expand A fragments [T][KE][64] (register order of
 // YR_OP_MBR, rho < KE); wgt2 = [T][11][16] as YR_OP_MBR.
 int yr_launch_mbe(const yr_op& op, int batch, hipStream_t s) {
     YR_REQUIRE(op.dtype == YR_F32 && op.out_dtype == YR_F32, "mbe: float32 plans only");
     YR_REQUIRE(op.nsrc == 1 && op.src[0].xform == YR_X_IDENTITY && op.src[0].dtype == YR_F32, "mbe: needs one float32 identity source");
     const yr_src& in = op.src[0];
-    YR_REQUIRE((op.k & 0x7f) == 3 && (op.stride == 1 || op.stride == 2) && op.act == YR_ACT_RELU6, "mbe: 3x3, stride 1|2, ReLU6");
+    YR_REQUIRE((op.k & (YR_MBR_K_MASK | YR_MBR_STREAM)) == 3 && (op.stride == 1 || op.stride == 2) && op.act == YR_ACT_RELU6, "mbe: 3x3, stride 1|2, ReLU6");
     YR_REQUIRE(in.ptr && op.out && op.wgt && op.wgt2 && op.res == nullptr, "mbe: null pointer (or a residual)");
     YR_REQUIRE(in.ld % 4 == 0 && op.out_ld % 4 == 0 && in.c == op.cin && in.ld >= in.c && op.out_ld >= op.cout && op.cout % 16 == 0, "mbe: channel strides / widths");
     YR_REQUIRE(((uintptr_t)in.ptr) % 16 == 0 && ((uintptr_t)op.out) % 16 == 0, "mbe: pointers must be 16-byte aligned");
@@ -637,11 +637,11 @@ int yr_launch_mbe(const yr_op& op, int batch, hipStream_t s) {
     const int pth = (a.Ho - 1) * op.stride + 3 - in.h, ptw = (a.Wo - 1) * op.stride + 3 - in.w;
     a.pad_t = (pth > 0 ? pth : 0) / 2; a.pad_l = (ptw > 0 ? ptw : 0) / 2;
     a.strips = a.segs = a.seg_rows = a.groups = a.nwaves = 0;
-    const int segs = (op.k >> 16) & 0xff;
-    // k bit 7: the SPLIT form - wgt holds the float16 planes [T][NKE][2][64 lanes][8 halves] of YR_OP_MBR's split form (expand part)
+    const int segs = (op.k & YR_MBR_SEGS_MASK) >> YR_MBR_SEGS_SHIFT;
+    // YR_MBR_SPLIT: the SPLIT form - wgt holds the float16 planes [T][NKE][2][64 lanes][8 halves] of YR_OP_MBR's split form (expand part)
     // (NTS: tiles per wave of the split form - its two rows of pixel operands are 16 registers per K = 32 step)
 #define MBE_CASE(CIN, NT, NTS)                                                                \
-    if (in.c == CIN && (op.k & 0x80)) return op.stride == 1 ? launch_mbe<CIN, 1, NTS, true>(a, batch, segs, s) : launch_mbe<CIN, 2, NTS, true>(a, batch, segs, s); \
+    if (in.c == CIN && (op.k & YR_MBR_SPLIT)) return op.stride == 1 ? launch_mbe<CIN, 1, NTS, true>(a, batch, segs, s) : launch_mbe<CIN, 2, NTS, true>(a, batch, segs, s); \
     if (in.c == CIN) return op.stride == 1 ? launch_mbe<CIN, 1, NT>(a, batch, segs, s) : launch_mbe<CIN, 2, NT>(a, batch, segs, s);
     MBE_CASE(48, 3, 3)
     MBE_CASE(72, 3, 2)      // MobileNetV2 x0.75 block_11..13
@@ -649,12 +649,12 @@ int yr_launch_mbe(const yr_op& op, int batch, hipStream_t s) {
     MBE_CASE(120, 2, 2)     // x0.75 block_14, 15
     MBE_CASE(136, 2, 1)     // x1.4 block_11..13
 #undef MBE_CASE
-    if (in.c == 224 && !(op.k & 0x80)) return op.stride == 1 ? launch_mbe<224, 1, 1>(a, batch, segs, s) : launch_mbe<224, 2, 1>(a, batch, segs, s);   // x1.4 block_14, 15
+    if (in.c == 224 && !(op.k & YR_MBR_SPLIT)) return op.stride == 1 ? launch_mbe<224, 1, 1>(a, batch, segs, s) : launch_mbe<224, 2, 1>(a, batch, segs, s);   // x1.4 block_14, 15
     yr_set_error("mbe: block input width %d is not built", in.c);
     return YR_ERR_ARG;
 }
 
-// op fields: src[0] = block input (float32, c % 8 == 0, c % 16 in {0, 8}); se_reduced = Cexp (multiple of 16); k = 3 | split << 7 | nw << 8 | segs << 16
+// op fields: src[0] = block input (float32, c % 8 == 0, c % 16 in {0, 8}); se_reduced = Cexp (multiple of 16); k = 3 | YR_MBR_SPLIT | nw << YR_MBR_NW_SHIFT | segs << YR_MBR_SEGS_SHIFT
 // (nw: waves per workgroup, segs: row segments per strip; 0 = the library's choice); stride 1 | 2; act = ReLU6; res (optional) = the block input.  Parameters (float32):
 //   wgt  = A fragments [T = Cexp/16][KE + 4 TO][64]: register rho of lane (m = l % 16, g = l / 16) of tile j:
 //          rho < KE (expand step q = rho): We[16 j + m][kperm(q, g)] * expand BN scale, kperm(4 c + s, g) = 16 c + 4 g + s for the
@@ -671,7 +671,7 @@ int yr_launch_mbr(const yr_op& op, int batch, hipStream_t s) {
     YR_REQUIRE(op.dtype == YR_F32 && op.out_dtype == YR_F32, "mbr: float32 plans only");
     YR_REQUIRE(op.nsrc == 1 && op.src[0].xform == YR_X_IDENTITY && op.src[0].dtype == YR_F32, "mbr: needs one float32 identity source");
     const yr_src& in = op.src[0];
-    YR_REQUIRE((op.k & 0x7f) == 3 && (op.stride == 1 || op.stride == 2) && op.act == YR_ACT_RELU6, "mbr: 3x3, stride 1|2, ReLU6");
+    YR_REQUIRE((op.k & (YR_MBR_K_MASK | YR_MBR_STREAM)) == 3 && (op.stride == 1 || op.stride == 2) && op.act == YR_ACT_RELU6, "mbr: 3x3, stride 1|2, ReLU6");
     YR_REQUIRE(in.ptr && op.out && op.wgt && op.wgt2 && op.b2, "mbr: null pointer");
     YR_REQUIRE(in.ld % 4 == 0 && op.out_ld % 4 == 0 && in.c == op.cin && in.ld >= in.c && op.out_ld >= op.cout, "mbr: channel strides");
     YR_REQUIRE(((uintptr_t)in.ptr) % 16 == 0 && ((uintptr_t)op.out) % 16 == 0, "mbr: pointers must be 16-byte aligned");
@@ -685,11 +685,11 @@ int yr_launch_mbr(const yr_op& op, int batch, hipStream_t s) {
     const bool res = op.res != nullptr;
     if (res) YR_REQUIRE(op.res == in.ptr && op.stride == 1 && in.c == op.cout, "mbr: the residual must be the block input (stride 1, Cin == Cout)");
     a.strips = a.segs = a.seg_rows = 0;
-    const int nw = (op.k >> 8) & 0xff;
-    if (op.k & 0x80) {   // the SPLIT form (bit 7 of k): wgt holds float16 planes packed for exactly this many waves (compiler.mbs_pack)
+    const int nw = (op.k & YR_MBR_NW_MASK) >> YR_MBR_NW_SHIFT;
+    if (op.k & YR_MBR_SPLIT) {   // the SPLIT form: wgt holds float16 planes packed for exactly this many waves (compiler.mbs_pack)
 #define MBS_CASE(CIN, CEXP, COUT, S, NW, RES)                                                              \
     if (in.c == CIN && op.se_reduced == CEXP && op.cout == COUT && op.stride == S && res == RES && nw == NW) \
-        return launch_mbr<CIN, CEXP, COUT, S, NW, RES, true>(a, batch, (op.k >> 16) & 0xff, s);
+        return launch_mbr<CIN, CEXP, COUT, S, NW, RES, true>(a, batch, (op.k & YR_MBR_SEGS_MASK) >> YR_MBR_SEGS_SHIFT, s);
         MBS_CASE(16, 96, 24, 2, 3, false)
         MBS_CASE(16, 96, 24, 2, 2, false)     // (block_1 @208: 0.188 ms against 0.195-0.204 with three waves - one partner less at the row barrier)
         MBS_CASE(24, 144, 24, 1, 3, true)
@@ -706,7 +706,7 @@ int yr_launch_mbr(const yr_op& op, int batch, hipStream_t s) {
     }
 #define MBR_CASE(CIN, CEXP, COUT, S, NW, RES)                                                              \
     if (in.c == CIN && op.se_reduced == CEXP && op.cout == COUT && op.stride == S && res == RES && (nw == 0 || nw == NW)) \
-        return launch_mbr<CIN, CEXP, COUT, S, NW, RES>(a, batch, (op.k >> 16) & 0xff, s);
+        return launch_mbr<CIN, CEXP, COUT, S, NW, RES>(a, batch, (op.k & YR_MBR_SEGS_MASK) >> YR_MBR_SEGS_SHIFT, s);
     MBR_CASE(16, 96, 24, 2, 2, false)      // MobileNetV2 x0.75 block_1
     MBR_CASE(16, 96, 24, 2, 3, false)
     MBR_CASE(24, 144, 24, 1, 3, true)      // block_2, 4, 5

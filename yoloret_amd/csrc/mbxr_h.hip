@@ -14,7 +14,7 @@
 //   * expand weights (A fragments), BN parameters and the K x K taps of the wave's tiles are STATIONARY in registers;
 //   * the matrix pipe is its own pipe for 16-bit operands, so the kernel is bound by the depthwise VALU work alone:
 //     K*K multiply-adds + two activations + the rounding per value - what the arithmetic itself costs.
-// Same op, same parameter layouts as mbh.hip MODE 1 (yoloret_hip.h: YR_OP_MBX); the forced "tile" th = 255 selects this form
+// Same op, same parameter layouts as mbh.hip MODE 1 (yoloret_hip.h: YR_OP_MBX); the forced "tile" th = YR_MBH_TILE_CHAINED selects this form
 // and tw = row segments per strip (0: the launcher's choice) - yr_autotune times it next to the LDS-tiled tiles.
 // Numerics: expand accumulates in float32, BN in float32, activation (swish: hardware exp2 + rcp, as mbh.hip), the expanded
 // value stays float32 (never rounded), depthwise in float32 with the BN scale folded into the taps, one rounding at the store.
@@ -1787,7 +1787,7 @@ static int launch_mbhq_shape(const MbhrArgs& a, int k, int batch, int segs, hipS
 
 // the whole-block register-chained form is built for: 3x3, at most 16 expanded tiles, cin <= 64, cout <= 80
 bool yr_mbhr_takes(const yr_op& op) {
-    return op.kind == YR_OP_MBH && (op.dtype == YR_BF16 || op.dtype == YR_F16) && (op.k & 0xff) == 3 && (op.stride == 1 || op.stride == 2) &&
+    return op.kind == YR_OP_MBH && (op.dtype == YR_BF16 || op.dtype == YR_F16) && (op.k & YR_MBH_K_MASK) == 3 && (op.stride == 1 || op.stride == 2) &&
            (op.act == YR_ACT_RELU6 || op.act == YR_ACT_SWISH) && op.cin % 8 == 0 && op.cin <= 64 && op.se_reduced % 16 == 0 && op.se_reduced <= 256 &&
            op.cout % 4 == 0 && op.cout <= 80 && op.nsrc == 1 && op.out_ld % 4 == 0;
 }
@@ -1817,7 +1817,7 @@ static bool mbhr_pair_built(const yr_op& op) {
 // the tile-wise form (mbhq_kernel): 3x3 / 5x5, ReLU6, the shapes of MBHQ_SHAPES
 static bool mbhq_built(const yr_op& op) {
     static const bool on = !(getenv("YOLORET_MBHQ") && atoi(getenv("YOLORET_MBHQ")) == 0);
-    const int K = op.k & 0xff;
+    const int K = op.k & YR_MBH_K_MASK;
     return on && op.kind == YR_OP_MBH && (op.dtype == YR_BF16 || op.dtype == YR_F16) && (K == 3 || K == 5) && (op.stride == 1 || op.stride == 2) &&
            op.act == YR_ACT_RELU6 && op.cin % 8 == 0 && op.cin <= 64 && op.se_reduced % 16 == 0 && op.cout % 4 == 0 && op.nsrc == 1 &&
            op.out_ld % 4 == 0 && mbhq_shape(K, op.stride, op.cin, op.se_reduced, op.cout) != nullptr;
@@ -1831,7 +1831,7 @@ static int launch_mbhr_t(const yr_op& op, int batch, int segs, hipStream_t s) {
     a.x = in.ptr; a.out = op.out; a.we = op.wgt; a.prm = op.wgt2; a.wp = op.b1; a.sp = op.b2; a.hp = op.b2 + yr_round_up(op.cout, 8);
     a.H = in.h; a.W = in.w; a.Ho = op.h; a.Wo = op.w; a.Cin = in.c; a.CexpP = yr_round_up(op.se_reduced, 32); a.KP = yr_round_up(in.c, 32);
     a.Cout = op.cout; a.ld_in = in.ld; a.ld_out = op.out_ld; a.T = op.se_reduced / 16; a.has_res = op.res != nullptr;
-    const int K = op.k & 0xff;
+    const int K = op.k & YR_MBH_K_MASK;
     const int pth = (a.Ho - 1) * op.stride + K - in.h, ptw = (a.Wo - 1) * op.stride + K - in.w;
     a.pad_t = (pth > 0 ? pth : 0) / 2; a.pad_l = (ptw > 0 ? ptw : 0) / 2;
     a.strips = a.segs = a.seg_rows = 0;
@@ -1847,7 +1847,7 @@ bool yr_mbxr_takes(const yr_op& op);
 bool yr_mbh_prefers_chained(const yr_op& op) {
     static const bool mbxr_on = !(getenv("YOLORET_MBXR") && atoi(getenv("YOLORET_MBXR")) == 0);
     static const bool mbhr_on = !(getenv("YOLORET_MBHR") && atoi(getenv("YOLORET_MBHR")) == 0);
-    if (((op.k >> 8) & 0xff) != 0) return ((op.k >> 8) & 0xff) == 255;
+    if ((op.k & YR_MBH_TH_MASK) != 0) return ((op.k & YR_MBH_TH_MASK) >> YR_MBH_TH_SHIFT) == YR_MBH_TILE_CHAINED;
     return op.kind == YR_OP_MBX ? (mbxr_on && yr_mbxr_takes(op)) : (mbhr_on && yr_mbhr_built(op));
 }
 
@@ -1858,7 +1858,7 @@ int yr_launch_mbhr(const yr_op& op, int batch, int segs, hipStream_t s) {
 
 // whether the register-chained form is built for this YR_OP_MBX op (mbh.hip asks before it dispatches here)
 bool yr_mbxr_takes(const yr_op& op) {
-    const int K = op.k & 0xff;
+    const int K = op.k & YR_MBH_K_MASK;
     return op.kind == YR_OP_MBX && (op.dtype == YR_BF16 || op.dtype == YR_F16) && (K == 3 || K == 5) && (op.stride == 1 || op.stride == 2) &&
            (op.act == YR_ACT_RELU6 || op.act == YR_ACT_SWISH) && op.cin % 8 == 0 && op.cin <= 128 && op.cout % 16 == 0 && op.nsrc == 1 &&
            op.out_ld % 4 == 0 && (op.gate == nullptr || op.gate_ld % 4 == 0);
@@ -1867,7 +1867,7 @@ bool yr_mbxr_takes(const yr_op& op) {
 template <class T>
 static int launch_mbxr_t(const yr_op& op, int batch, int segs, hipStream_t s) {
     const yr_src& in = op.src[0];
-    const int K = op.k & 0xff;
+    const int K = op.k & YR_MBH_K_MASK;
     MbxrArgs a;
     a.x = in.ptr; a.out = op.out; a.we = op.wgt; a.prm = op.wgt2;
     a.part = const_cast<float*>(op.gate); a.ld_part = op.gate ? op.gate_ld : 0; a.rows_cap = op.gate ? op.se_reduced : 0;

@@ -197,8 +197,8 @@ int yr_launch_pointwise(const yr_op& op_in, int batch, hipStream_t s) {
                    "pointwise: dw3 source needs 16-byte aligned wgt2 / b1 / b2");
         YR_REQUIRE(11ll * a.S.kp * (long long)sizeof(float) <= 48 * 1024, "pointwise: dw3 source with %d channels does not fit LDS", e.c);
         a.dw_w = op.wgt2; a.dw_scale = op.b1; a.dw_shift = op.b2;
-        a.dw_stride = op.se_reduced & 0xff;
-        a.dw_act = (op.se_reduced >> 8) & 0xff;
+        a.dw_stride = op.se_reduced & YR_PWDW_STRIDE_MASK;
+        a.dw_act = (op.se_reduced & YR_PWDW_ACT_MASK) >> YR_PWDW_ACT_SHIFT;
         // TF 'SAME': pad_total = max((out-1)*s + k - in, 0); before = total/2 (extra goes bottom/right)
         const int pth = (op.h - 1) * a.dw_stride + 3 - e.h, ptw = (op.w - 1) * a.dw_stride + 3 - e.w;
         a.dw_pad_t = (pth > 0 ? pth : 0) / 2;
@@ -245,7 +245,7 @@ int yr_launch_pointwise(const yr_op& op_in, int batch, hipStream_t s) {
                                {128, 32, launch_direct<2, 2>}, {128, 48, launch_direct<2, 3>}, {128, 64, launch_direct<2, 4>},
                                {128, 80, launch_direct<2, 5>}, {128, 96, launch_direct<2, 6>},
                                {256, 32, launch_direct<4, 2>}, {256, 48, launch_direct<4, 3>}, {256, 64, launch_direct<4, 4>}};
-    if (narrow && (op.se_reduced & 0x20000) && a.S.kp >= 2 * 32 && a.dw_w == nullptr) return yr_pwh_launch_ksplit(op.dtype, a, s);   // (the plan asks for the k-split form)
+    if (narrow && (op.se_reduced & YR_PWF_KSPLIT) && a.S.kp >= 2 * 32 && a.dw_w == nullptr) return yr_pwh_launch_ksplit(op.dtype, a, s);   // (the plan asks for the k-split form)
     if (narrow) return yr_pw_launch_h(op.dtype, op.k - 1, a, s);   // bf16 / f16: pointwise_h.hip (its own tile table)
     constexpr int NLDS = 14;  // the first NLDS entries are the LDS-staged kernel (the heuristic below only ranks those)
     constexpr int NCFG = sizeof(cfgs) / sizeof(cfgs[0]);
@@ -260,19 +260,19 @@ int yr_launch_pointwise(const yr_op& op_in, int batch, hipStream_t s) {
     // by one).  The tuner's index picks the tile shape (the direct kernels' indices map onto the LDS shapes).  YOLORET_PW_SPLIT=0:
     // the float32-MFMA kernels.
     static const bool split_on = !(getenv("YOLORET_PW_SPLIT") && atoi(getenv("YOLORET_PW_SPLIT")) == 0);
-    const bool split = split_on && a.S.kp >= 16 && !(op.se_reduced & 0x10000);   // (bit 16 of se_reduced: the plan asks for the float32 MFMA - its few-image form)   // (a 16- or 24-deep conv pads its one step with zeros: the MFMAs are not what it waits for)
-    // bit 17 of se_reduced: the plan asks for the k-split form (the 'nohead' variant's small maps; pointwise_split.hip) - a property of the
+    const bool split = split_on && a.S.kp >= 16 && !(op.se_reduced & YR_PWF_F32_MFMA);   // (the plan asks for the float32 MFMA - its few-image form)   // (a 16- or 24-deep conv pads its one step with zeros: the MFMAs are not what it waits for)
+    // YR_PWF_KSPLIT: the plan asks for the k-split form (the 'nohead' variant's small maps; pointwise_split.hip) - a property of the
     // PLAN like the split form itself, so the tuner's index is not looked at
-    if (op.se_reduced & 0x40000) {     // bit 18: the pixel-stationary form - op.wgt holds float16 planes, no other kernel can read them
+    if (op.se_reduced & YR_PWF_STATIONARY) {     // op.wgt holds float16 planes, no other kernel can read them
         YR_REQUIRE(split, "pointwise: the plan stores this op's weights as float16 planes (se_reduced bit 18) but the split form is off");
-        if (op.se_reduced & 0x80000) {     // bit 19: a second conv of the same source in the same launch (its output: gate_out, its width: se_hidden)
+        if (op.se_reduced & YR_PWF_TWO_OUT) {     // a second conv of the same source in the same launch (its output: gate_out, its width: se_hidden)
             YR_REQUIRE(op.gate_out != nullptr && op.se_hidden >= 1 && op.gate_out_ld >= op.se_hidden, "pointwise: the second output of a two-output op is missing or too narrow");
             a.out2 = op.gate_out; a.out2_ld = op.gate_out_ld; a.N2 = op.se_hidden;
-            a.act2 = op.reserved0 & 0xff; a.pool2 = (op.reserved0 >> 8) & 1;
+            a.act2 = op.reserved0 & YR_PW2_ACT_MASK; a.pool2 = (op.reserved0 & YR_PW2_POOLED) ? 1 : 0;
         }
         return yr_pw_launch_stream(a, s);
     }
-    if (split && (op.se_reduced & 0x20000) && a.S.kp >= 2 * 32) return yr_pw_launch_ksplit(a, s);
+    if (split && (op.se_reduced & YR_PWF_KSPLIT) && a.S.kp >= 2 * 32) return yr_pw_launch_ksplit(a, s);
     if (split && op.k >= 1 && op.k <= NCFG) return yr_pw_launch_split((op.k - 1) % NLDS, a, s);
     if (op.k >= 1 && op.k <= NCFG) return cfgs[op.k - 1].fn(a, s);
     // tuning override: YR_PW_CFG="BMxBN" forces one tile shape for every layer (experiments only)

@@ -441,7 +441,7 @@ static int launch_h_cfg(int cfg, const PwArgs& a, hipStream_t s) {
     }
 }
 
-// The K-SPLIT form for the passes of one or two images (se_reduced bit 17 of a POINTWISE op, set by the compiler's 'latency' variant of
+// The K-SPLIT form for the passes of one or two images (YR_PWF_KSPLIT on a POINTWISE op, set by the compiler's 'latency' variant of
 // a 16-bit plan for its small maps; the float32 twin is pointwise_split.hip's pwk_kernel).  pwh_kernel gives a wave 16 pixels x 32
 // couts and the whole k range: at 169 .. 1024 pixels a gated projection of 1152 channels is 36 chunks behind each other (9.8 us at
 // one image).  Here a workgroup is ONE such tile and its four waves take the chunks w, w + 4, ... (PWKH_G of them in flight per wave);

@@ -110,7 +110,7 @@ static int launch_split_cfg(const PwArgs& a, hipStream_t s) {
     return YR_OK;
 }
 
-// The K-SPLIT form (round 5, the passes of one or two images: se_reduced bit 17 of a POINTWISE op, set by the compiler's 'nohead_k'
+// The K-SPLIT form (round 5, the passes of one or two images: YR_PWF_KSPLIT on a POINTWISE op, set by the compiler's 'nohead_k'
 // variant for the maps of the heads and the last backbone stages).  At 169 .. 2704 pixels a conv is a handful of workgroups, each ONE latency
 // chain: pws_kernel walks its k chunks one barrier pair at a time, ~165 instructions of staging per chunk and wave for three MFMAs
 // (block_14_project, 720 deep: 23 chunks, 15 us; several chunks per barrier pair with all their loads in flight - built, bit-identical,

@@ -1,4 +1,4 @@
-// Pointwise (1x1) convolution of float32 plans, PIXEL-STATIONARY form of the split arithmetic (round 6; se_reduced bit 18 of a
+// Pointwise (1x1) convolution of float32 plans, PIXEL-STATIONARY form of the split arithmetic (round 6; YR_PWF_STATIONARY in se_reduced of a
 // POINTWISE op - a property of the plan: the op's weights are stored as float16 planes in fragment order, compiler.head_pack).
 // The 1x1 convs of the neck and the heads (reference code/yolo3/model.py:91-157: Concatenate + Conv2D 1x1 + BN (+ ReLU6), the SE
 // block's projection, the y convs) are HBM-bound - 14 .. 140 MB per launch at 64 images, worth 3 .. 28 us of memory time - and

@@ -47,7 +47,7 @@ struct PwArgs {
     // 16-bit ops (pointwise_h.hip; the float32 kernels ignore it): sources, weights and residual are bf16 / f16 behind the
     // type-erased pointers above; out_f32 = 1: `out` is float32 all the same (logit outputs, hoisted partial sums)
     int out_f32;
-    // the pixel-stationary form's SECOND output (se_reduced bit 19 of a POINTWISE op; null: none): another 1x1 conv of the same (gated) source -
+    // the pixel-stationary form's SECOND output (YR_PWF_TWO_OUT on a POINTWISE op; null: none): another 1x1 conv of the same (gated) source -
     // its couts follow the first one's in the weight planes and in scale / shift (each padded to a multiple of 16)
     float* out2;
     int out2_ld, N2, act2, pool2;
@@ -336,16 +336,16 @@ __device__ __forceinline__ float4 pw_finish(float4 v, const float4& gt, int cval
 int yr_pw_launch_lds(int shape, const PwArgs& a, hipStream_t s);
 // the same tile shapes on the 16-bit matrix pipe with float32-grade operands (pointwise_split.hip: two float16 planes per operand)
 int yr_pw_launch_split(int shape, const PwArgs& a, hipStream_t s);
-// its k-split form for the passes of a few images (a workgroup = one 16 x 16 tile, the four waves split the k range; se_reduced bit 17)
+// its k-split form for the passes of a few images (a workgroup = one 16 x 16 tile, the four waves split the k range; YR_PWF_KSPLIT)
 int yr_pw_launch_ksplit(const PwArgs& a, hipStream_t s);
-// its pixel-stationary form (pointwise_stream.hip; se_reduced bit 18: a.wt holds the weights' float16 planes, compiler.head_pack over
+// its pixel-stationary form (pointwise_stream.hip; YR_PWF_STATIONARY: a.wt holds the weights' float16 planes, compiler.head_pack over
 // yr_pwt_chunks(kp) chunks of 32 channels); yr_pwt_chunks: 0 = the form does not take a k space this deep
 int yr_pw_launch_stream(const PwArgs& a, hipStream_t s);
 extern "C" int yr_pwt_chunks(int kp);
 // 16-bit kernel (pointwise_h.hip): cfg = tile shape index 0..yr_pwh_num_cfgs()-1, or -1 for its heuristic
 int yr_pw_launch_h(int dtype, int cfg, const PwArgs& a, hipStream_t s);
 int yr_pwh_num_cfgs();
-// its k-split form for the passes of one or two images (se_reduced bit 17; a workgroup = one 16 x 32 tile, four waves split the k range)
+// its k-split form for the passes of one or two images (YR_PWF_KSPLIT; a workgroup = one 16 x 32 tile, four waves split the k range)
 int yr_pwh_launch_ksplit(int dtype, const PwArgs& a, hipStream_t s);
 // its activation-stationary (pointwise_hs.hip) and all-couts k-streaming (pointwise_hq.hip) forms, variant 0..3 each;
 // -1: the form does not take this op (nothing launched, no error set)

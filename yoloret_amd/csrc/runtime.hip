@@ -44,7 +44,7 @@ static int dispatch(const yr_op& op, int batch, hipStream_t s) {
         case YR_OP_STEMBLOCK: return yr_launch_stemblock(op, batch, s);
         case YR_OP_MBLANE: return yr_launch_mblane(op, batch, s);
         case YR_OP_MBH: case YR_OP_MBX: return yr_launch_mbh(op, batch, s);
-        case YR_OP_MBR: return (op.k & 0x40) ? yr_launch_mbk(op, batch, s) : yr_launch_mbr(op, batch, s);
+        case YR_OP_MBR: return (op.k & YR_MBR_STREAM) ? yr_launch_mbk(op, batch, s) : yr_launch_mbr(op, batch, s);
         case YR_OP_MBE: return yr_launch_mbe(op, batch, s);
         case YR_OP_HEAD: return yr_launch_head(op, batch, s);
         default: yr_set_error("unknown op kind %d", op.kind); return YR_ERR_ARG;
@@ -127,9 +127,9 @@ extern "C" int yr_create(const yr_op* ops, int n_ops, const yr_buf* bufs, int n_
             else if (op.kind != YR_OP_HEAD && op.res_buf >= 0 && (op.res_ld < op.cout || !fits(op.res_buf, (int64_t)op.h * op.w * op.res_ld, op.dtype))) why = "the residual";
             else if (op.gate_buf >= 0 && op.gate_ld <= 0) why = "the gate";
             else if (op.kind == YR_OP_POINTWISE && op.gate_out_buf >= 0) {
-                // the second output of a two-output conv (se_reduced bits 18 + 19): se_hidden couts, its own pooling in reserved0
-                const int64_t ch = (int64_t)op.h * (op.stride == 2 ? 2 : 1), cw = (int64_t)op.w * (op.stride == 2 ? 2 : 1), p2 = ((op.reserved0 >> 8) & 1) ? 2 : 1;
-                if ((op.se_reduced & 0xc0000) != 0xc0000 || op.dtype != YR_F32 || op.se_hidden < 1 || op.gate_out_ld < op.se_hidden || !fits(op.gate_out_buf, (ch / p2) * (cw / p2) * op.gate_out_ld, YR_F32))
+                // the second output of a two-output conv (YR_PWF_STATIONARY | YR_PWF_TWO_OUT): se_hidden couts, its own pooling in reserved0
+                const int64_t ch = (int64_t)op.h * (op.stride == 2 ? 2 : 1), cw = (int64_t)op.w * (op.stride == 2 ? 2 : 1), p2 = (op.reserved0 & YR_PW2_POOLED) ? 2 : 1;
+                if ((op.se_reduced & (YR_PWF_STATIONARY | YR_PWF_TWO_OUT)) != (YR_PWF_STATIONARY | YR_PWF_TWO_OUT) || op.dtype != YR_F32 || op.se_hidden < 1 || op.gate_out_ld < op.se_hidden || !fits(op.gate_out_buf, (ch / p2) * (cw / p2) * op.gate_out_ld, YR_F32))
                     why = "the second output";
             }
             else if (op.gate_out_buf >= 0 && (op.gate_buf < 0 || op.se_hidden < 1 || op.se_w_off < 0 || op.gate_out_ld < op.cout || !fits(op.gate_out_buf, op.gate_out_ld, YR_F32) ||
@@ -171,8 +171,8 @@ static int64_t param_floats(const yr_op& op, int role) {   // role: 0 wgt, 1 sca
     }
     switch (op.kind) {
         case YR_OP_HEAD:
-            if (role == 3) return (op.k & 0x40) ? (int64_t)(op.cout / 16) * 176 : 10 * ru(op.cout, 4);
-            if (role == 0 && (op.k & 0xc0)) {   // float16 planes in fragment order, 32-channel chunks per source
+            if (role == 3) return (op.k & YR_HEAD_WALK) ? (int64_t)(op.cout / 16) * 176 : 10 * ru(op.cout, 4);
+            if (role == 0 && (op.k & (YR_HEAD_WALK | YR_HEAD_PLANES))) {   // float16 planes in fragment order, 32-channel chunks per source
                 int64_t nk = 0;
                 for (int i = 0; i < op.nsrc; ++i)
                     if (op.src[i].xform != YR_X_UP2_ADD) nk += (op.src[i].c + 31) / 32;
@@ -183,10 +183,10 @@ static int64_t param_floats(const yr_op& op, int role) {   // role: 0 wgt, 1 sca
             int64_t kp = 0;
             for (int i = 0; i < op.nsrc; ++i)
                 if (op.src[i].xform != YR_X_UP2_ADD) kp += ru(op.src[i].c, V);
-            if (op.kind == YR_OP_POINTWISE && op.dtype == YR_F32 && (op.se_reduced & 0x40000)) {     // the pixel-stationary form: float16 planes (pointwise_stream.hip)
-                const int64_t tiles = ru(op.cout, 16) / 16 + ((op.se_reduced & 0x80000) ? ru(op.se_hidden, 16) / 16 : 0);      // (bit 19: the second output's tiles behind the first's)
+            if (op.kind == YR_OP_POINTWISE && op.dtype == YR_F32 && (op.se_reduced & YR_PWF_STATIONARY)) {     // the pixel-stationary form: float16 planes (pointwise_stream.hip)
+                const int64_t tiles = ru(op.cout, 16) / 16 + ((op.se_reduced & YR_PWF_TWO_OUT) ? ru(op.se_hidden, 16) / 16 : 0);      // (the second output's tiles behind the first's)
                 if (role == 0) return tiles * (int64_t)yr_pwt_chunks((int)kp) * 512;
-                if ((role == 1 || role == 2) && (op.se_reduced & 0x80000)) return 16 * tiles;
+                if ((role == 1 || role == 2) && (op.se_reduced & YR_PWF_TWO_OUT)) return 16 * tiles;
             }
             if (role == 0) return op.dtype == YR_F32 ? (int64_t)op.cout * kp : ((int64_t)op.cout * kp + 1) / 2;
             if (role == 1 || role == 2) return op.cout;
@@ -210,7 +210,7 @@ static int64_t param_floats(const yr_op& op, int role) {   // role: 0 wgt, 1 sca
         }
         case YR_OP_WSUM: return role == 0 ? 4 : 0;
         case YR_OP_MBH: case YR_OP_MBX: {
-            const int64_t cexp = ru(op.kind == YR_OP_MBH ? op.se_reduced : op.cout, 32), kp = ru(op.cin, 32), kk = (op.k & 0xff) * (op.k & 0xff);
+            const int64_t cexp = ru(op.kind == YR_OP_MBH ? op.se_reduced : op.cout, 32), kp = ru(op.cin, 32), kk = (op.k & YR_MBH_K_MASK) * (op.k & YR_MBH_K_MASK);
             if (role == 0) return cexp * kp / 2;
             if (role == 3) return (kk + 4) * cexp;
             if (op.kind == YR_OP_MBH && role == 4) return (int64_t)op.cout * cexp / 2;
@@ -240,20 +240,20 @@ static int64_t param_floats(const yr_op& op, int role) {   // role: 0 wgt, 1 sca
         }
         case YR_OP_MBE: {
             const int64_t t = op.cout / 16, ke = op.cin / 4;
-            if (role == 0 && (op.k & 0x80)) return t * ((op.cin + 31) / 32) * 2 * 64 * 4;   // the split form: float16 planes
+            if (role == 0 && (op.k & YR_MBR_SPLIT)) return t * ((op.cin + 31) / 32) * 2 * 64 * 4;   // the split form: float16 planes
             if (role == 0) return t * ke * 64;
             if (role == 3) return t * 176;
             return 0;
         }
         case YR_OP_MBR: {
             const int64_t t = op.se_reduced / 16, to = ru(op.cout, 16) / 16, ke = op.cin / 4;
-            if (op.k & 0x40) {   // the weight-streaming form (mbk.hip): one chunk per pair of expanded tiles, no wgt2
+            if (op.k & YR_MBR_STREAM) {   // the weight-streaming form (mbk.hip): one chunk per pair of expanded tiles, no wgt2
                 if (role == 0) return (t + 1) / 2 * ((4 * ((op.cin + 31) / 32) + 2 * to) * 1024 + 2048) / 4;
                 if (role == 5) return 16 * to;
                 return 0;
             }
-            if (role == 0 && (op.k & 0x80)) {   // the split form: float16 planes, projection fragments per tile pair of the nw waves
-                const int64_t nw = (op.k >> 8) & 0xff, nke = (op.cin + 31) / 32;
+            if (role == 0 && (op.k & YR_MBR_SPLIT)) {   // the split form: float16 planes, projection fragments per tile pair of the nw waves
+                const int64_t nw = (op.k & YR_MBR_NW_MASK) >> YR_MBR_NW_SHIFT, nke = (op.cin + 31) / 32;
                 if (nw < 1 || nw > t) return -1;
                 const int64_t ntl = t / nw, r = t % nw;
                 const int64_t pairs = r * ((ntl + 2) / 2) + (nw - r) * ((ntl + 1) / 2);
@@ -378,13 +378,13 @@ extern "C" int yr_set_tuning(yr_handle* h, int batch, const int32_t* cfg, int n)
     for (int i = 0; i < n; ++i) {
         const int ncfg = yr_pointwise_num_cfgs(h->ops[i].dtype);
         const bool pw_ok = cfg[i] >= 0 && cfg[i] <= ncfg && (cfg[i] == 0 || h->ops[i].kind == YR_OP_POINTWISE);
-        const bool mbh_ok = (h->ops[i].kind == YR_OP_MBH || h->ops[i].kind == YR_OP_MBX || h->ops[i].kind == YR_OP_MBR || h->ops[i].kind == YR_OP_MBE) && cfg[i] >= 0 && (cfg[i] & 0xff) == 0 && cfg[i] < (1 << 24);   // th << 8 | tw << 16
+        const bool mbh_ok = (h->ops[i].kind == YR_OP_MBH || h->ops[i].kind == YR_OP_MBX || h->ops[i].kind == YR_OP_MBR || h->ops[i].kind == YR_OP_MBE) && cfg[i] >= 0 && (cfg[i] & ~(YR_MBH_TH_MASK | YR_MBH_TW_MASK)) == 0;   // th | tw, or nw | segs: the same two bytes
         YR_REQUIRE(pw_ok || mbh_ok, "yr_set_tuning: entry %d = %d is not a valid tile shape for that op", i, cfg[i]);
         // a split-form block's fragments are packed for ONE nw: a table tuned for another form of the plan (YOLORET_MBR_SPLIT=0) is refused
-        YR_REQUIRE(!(h->ops[i].kind == YR_OP_MBR && (h->ops[i].k & 0x40)) || cfg[i] == 0, "yr_set_tuning: entry %d: the weight-streaming block form has nothing to tune (must be 0)", i);
-        const bool split_block = (h->ops[i].kind == YR_OP_MBR || h->ops[i].kind == YR_OP_MBE) && (h->ops[i].k & 0x80);
-        YR_REQUIRE(!split_block || (cfg[i] & 0xff00) == 0 || (cfg[i] & 0xff00) == (h->ops[i].k & 0xff00),
-                   "yr_set_tuning: entry %d asks for %d waves per workgroup, the split-form fragments of that op are packed for %d", i, (cfg[i] >> 8) & 0xff, (h->ops[i].k >> 8) & 0xff);
+        YR_REQUIRE(!(h->ops[i].kind == YR_OP_MBR && (h->ops[i].k & YR_MBR_STREAM)) || cfg[i] == 0, "yr_set_tuning: entry %d: the weight-streaming block form has nothing to tune (must be 0)", i);
+        const bool split_block = (h->ops[i].kind == YR_OP_MBR || h->ops[i].kind == YR_OP_MBE) && (h->ops[i].k & YR_MBR_SPLIT);
+        YR_REQUIRE(!split_block || (cfg[i] & YR_MBR_NW_MASK) == 0 || (cfg[i] & YR_MBR_NW_MASK) == (h->ops[i].k & YR_MBR_NW_MASK),
+                   "yr_set_tuning: entry %d asks for %d waves per workgroup, the split-form fragments of that op are packed for %d", i, (cfg[i] & YR_MBR_NW_MASK) >> YR_MBR_NW_SHIFT, (h->ops[i].k & YR_MBR_NW_MASK) >> YR_MBR_NW_SHIFT);
         t[i] = cfg[i];
     }
     h->tuned[batch] = t;
@@ -412,15 +412,15 @@ static int resolve_op(const yr_handle* h, size_t i, int batch, float* const ext[
     if (op.kind == YR_OP_POINTWISE) {
         auto it = h->tuned.find(batch);
         op.k = it != h->tuned.end() ? it->second[i] : 0;
-    } else if (op.kind == YR_OP_MBH || op.kind == YR_OP_MBX) {   // the tuned output tile (th << 8 | tw << 16) rides in the upper bytes of k
+    } else if (op.kind == YR_OP_MBH || op.kind == YR_OP_MBX) {   // the tuned output tile (YR_MBH_TH_MASK | YR_MBH_TW_MASK) rides in the upper bytes of k
         auto it = h->tuned.find(batch);
-        if (it != h->tuned.end()) op.k = (op.k & 0xff) | it->second[i];
-    } else if (op.kind == YR_OP_MBR || op.kind == YR_OP_MBE) {   // (waves per workgroup << 8 | row segments << 16: the tuned walk geometry)
+        if (it != h->tuned.end()) op.k = (op.k & YR_MBH_K_MASK) | it->second[i];
+    } else if (op.kind == YR_OP_MBR || op.kind == YR_OP_MBE) {   // (YR_MBR_NW_MASK | YR_MBR_SEGS_MASK: the tuned walk geometry)
         auto it = h->tuned.find(batch);
-        if (it != h->tuned.end() && it->second[i] != 0 && !(op.k & 0x40)) {   // (k bit 6, the weight-streaming form: its geometry is the plan's)
+        if (it != h->tuned.end() && it->second[i] != 0 && !(op.k & YR_MBR_STREAM)) {   // (the weight-streaming form: its geometry is the plan's)
             // the SPLIT form's fragments are packed for the plan's nw (compiler.mbs_pack): only the row segments are tunable there
-            if (op.k & 0x80) op.k = (op.k & 0xffff) | (it->second[i] & 0xff0000);
-            else op.k = (op.k & 0xff) | it->second[i];
+            if (op.k & YR_MBR_SPLIT) op.k = (op.k & (YR_MBR_FORM_MASK | YR_MBR_NW_MASK)) | (it->second[i] & YR_MBR_SEGS_MASK);
+            else op.k = (op.k & YR_MBR_FORM_MASK) | it->second[i];
         }
     }
     *out = op;
@@ -611,11 +611,11 @@ extern "C" int yr_autotune(yr_handle* h, const float* images, int batch, float* 
             static const int tiles[][2] = {{4, 8}, {8, 4}, {7, 4}, {7, 8}, {8, 8}, {13, 4}, {4, 16}, {8, 16}, {7, 16}, {13, 8},
                                            {16, 8}, {13, 16}, {8, 12}, {7, 12}, {13, 12}, {16, 12}, {16, 16}, {4, 12}, {6, 8}};
             // ops that run the row-walking register-chained form (mbxr_h.hip; chosen by shape): 1 .. 6 row segments per strip
-            static const int chained[][2] = {{255, 1}, {255, 2}, {255, 3}, {255, 4}, {255, 6}};
+            static const int chained[][2] = {{YR_MBH_TILE_CHAINED, 1}, {YR_MBH_TILE_CHAINED, 2}, {YR_MBH_TILE_CHAINED, 3}, {YR_MBH_TILE_CHAINED, 4}, {YR_MBH_TILE_CHAINED, 6}};
             yr_op op;
             rc = resolve_op(h, i, batch, ext, static_cast<char*>(workspace), &op);
             if (rc) break;
-            const int kk = op.k & 0xff;
+            const int kk = op.k & YR_MBH_K_MASK;
             float best_ms = 1e30f;
             int best_cfg = 0;
             const bool ch = yr_mbh_prefers_chained(op);
@@ -623,7 +623,7 @@ extern "C" int yr_autotune(yr_handle* h, const float* images, int batch, float* 
             const int ncand = ch ? (int)(sizeof(chained) / sizeof(chained[0])) : (int)(sizeof(tiles) / sizeof(tiles[0]));
             for (int pass = 0; pass < 2; ++pass)                 // two passes, minimum: one noisy sample must not decide
                 for (int c = -1; c < ncand; ++c) {
-                    const int cfg = c < 0 ? 0 : (cand[c][0] << 8) | (cand[c][1] << 16);
+                    const int cfg = c < 0 ? 0 : (cand[c][0] << YR_MBH_TH_SHIFT) | (cand[c][1] << YR_MBH_TW_SHIFT);
                     op.k = kk | cfg;
                     if (dispatch(op, batch, s) != YR_OK) continue;          // warm-up / validity
                     YR_CHECK_HIP(hipEventRecord(e0, s));
@@ -637,7 +637,7 @@ extern "C" int yr_autotune(yr_handle* h, const float* images, int batch, float* 
             best[i] = best_cfg;
             continue;
         }
-        if (h->ops[i].kind == YR_OP_MBR && (h->ops[i].k & 0x40)) continue;   // the weight-streaming form (mbk.hip): nothing to tune
+        if (h->ops[i].kind == YR_OP_MBR && (h->ops[i].k & YR_MBR_STREAM)) continue;   // the weight-streaming form (mbk.hip): nothing to tune
         if (h->ops[i].kind == YR_OP_MBR || h->ops[i].kind == YR_OP_MBE) {
             // register-chained float32 blocks: row segments per strip (how many waves the walk is cut into; each segment
             // recomputes two halo rows), IN CONTEXT - right behind the predecessor, whose output is what the caches hold (in
@@ -653,17 +653,17 @@ extern "C" int yr_autotune(yr_handle* h, const float* images, int batch, float* 
                 rc = resolve_op(h, i - 1, batch, ext, static_cast<char*>(workspace), &prev);
                 if (rc) break;
                 if (h->ops[i - 1].kind == YR_OP_POINTWISE) prev.k = best[i - 1];
-                else if (prev.kind == YR_OP_MBR && (prev.k & 0x40)) {}
-                else if (best[i - 1] != 0 && (prev.k & 0x80)) prev.k = (prev.k & 0xffff) | (best[i - 1] & 0xff0000);
-                else if (best[i - 1] != 0) prev.k = (prev.k & 0xff) | best[i - 1];
+                else if (prev.kind == YR_OP_MBR && (prev.k & YR_MBR_STREAM)) {}
+                else if (best[i - 1] != 0 && (prev.k & YR_MBR_SPLIT)) prev.k = (prev.k & (YR_MBR_FORM_MASK | YR_MBR_NW_MASK)) | (best[i - 1] & YR_MBR_SEGS_MASK);
+                else if (best[i - 1] != 0) prev.k = (prev.k & YR_MBR_FORM_MASK) | best[i - 1];
             }
             static const int segs_list[] = {0, 1, 2, 3, 4, 6, 8, 13, 18, 26};   // (13 .. 26: the few-image passes, where a strip's walk is the whole launch)
-            const int base = op.k & 0xffff;     // 3 | nw << 8: the workgroup shape the plan asks for
+            const int base = op.k & (YR_MBR_FORM_MASK | YR_MBR_NW_MASK);     // 3 | nw: the workgroup shape the plan asks for
             float best_ms = 1e30f;
             int best_cfg = 0;
             for (int c = 0; c < (int)(sizeof(segs_list) / sizeof(segs_list[0])); ++c) {
                 if (segs_list[c] > h->ops[i].h) continue;
-                op.k = base | (segs_list[c] << 16);
+                op.k = base | (segs_list[c] << YR_MBR_SEGS_SHIFT);
                 if (dispatch(op, batch, s) != YR_OK) continue;
                 float ms = 1e30f;
                 for (int it = 0; it < 2 * iters + 1; ++it) {
@@ -676,13 +676,13 @@ extern "C" int yr_autotune(yr_handle* h, const float* images, int batch, float* 
                     YR_CHECK_HIP(hipEventElapsedTime(&t, e0, e1));
                     if (t < ms) ms = t;
                 }
-                if (ms < best_ms * 0.98f) { best_ms = ms; best_cfg = (base & 0xff00) | (segs_list[c] << 16); }
+                if (ms < best_ms * 0.98f) { best_ms = ms; best_cfg = (base & YR_MBR_NW_MASK) | (segs_list[c] << YR_MBR_SEGS_SHIFT); }
             }
             best[i] = best_cfg;
             continue;
         }
         if (h->ops[i].kind != YR_OP_POINTWISE) continue;
-        if (h->ops[i].dtype == YR_F32 && (h->ops[i].se_reduced & 0x40000)) continue;   // the pixel-stationary form (pointwise_stream.hip): nothing to tune
+        if (h->ops[i].dtype == YR_F32 && (h->ops[i].se_reduced & YR_PWF_STATIONARY)) continue;   // the pixel-stationary form (pointwise_stream.hip): nothing to tune
         const int ncfg = yr_pointwise_num_cfgs(h->ops[i].dtype);
         yr_op op;
         rc = resolve_op(h, i, batch, ext, static_cast<char*>(workspace), &op);

@@ -52,12 +52,12 @@ bool yr_stemxp_takes(const yr_op& op);                                  // mbxr_
 int yr_launch_stemxp(const yr_op& op, int batch, hipStream_t s);   // mbxr_h.hip: a plain launch of this MBH / MBX op runs the register-chained form
 int yr_launch_mbr(const yr_op& op, int batch, hipStream_t s);
 int yr_launch_mbe(const yr_op& op, int batch, hipStream_t s);
-int yr_launch_mbk(const yr_op& op, int batch, hipStream_t s);   // YR_OP_MBR with k bit 6: the weight-streaming form (mbk.hip)
+int yr_launch_mbk(const yr_op& op, int batch, hipStream_t s);   // YR_OP_MBR with YR_MBR_STREAM: the weight-streaming form (mbk.hip)
 int yr_launch_head(const yr_op& op, int batch, hipStream_t s);      // headblock.hip
 int yr_launch_absmax(const float* p, long long rows, int c, int ld, unsigned* out, hipStream_t s);   // elementwise.hip
-int yr_launch_head_walk(const yr_op& op, int batch, hipStream_t s); // headwalk.hip (YR_OP_HEAD with k bit 6)
+int yr_launch_head_walk(const yr_op& op, int batch, hipStream_t s); // headwalk.hip (YR_OP_HEAD with YR_HEAD_WALK)
 int yr_launch_head_walk_h(const yr_op& op, int batch, hipStream_t s); // headwalk_h.hip (... of a 16-bit plan)
-int yr_launch_head_stream(const yr_op& op, int batch, hipStream_t s); // headstream.hip (YR_OP_HEAD with k bits 5 and 6: the weight-streaming form)
+int yr_launch_head_stream(const yr_op& op, int batch, hipStream_t s); // headstream.hip (YR_OP_HEAD with YR_HEAD_STREAM: the weight-streaming form)
 int yr_pointwise_num_cfgs(int dtype);
 extern "C" int yr_pwt_chunks(int kp);   // chunks of 32 channels the pixel-stationary pointwise form (pointwise_stream.hip) runs a k space with; 0: not taken
 
@@ -282,7 +282,7 @@ static inline int yr_make_srcset(const yr_op& op, DSrcSet* S) {
         else if (s.xform == YR_X_MAXPOOL2) { eh /= 2; ew /= 2; }
         else if (s.xform == YR_X_MAXPOOL4) { eh /= 4; ew /= 4; }
         else if (s.xform == YR_X_DW3) {  // POINTWISE only (checked there): read through a 3x3 depthwise conv, TF 'SAME'
-            const int st = op.se_reduced & 0xff;
+            const int st = op.se_reduced & YR_PWDW_STRIDE_MASK;
             if (op.nsrc != 1 || (st != 1 && st != 2)) { yr_set_error("dw3 source: must be the only source, stride 1 or 2"); return YR_ERR_ARG; }
             eh = (eh + st - 1) / st; ew = (ew + st - 1) / st;
         }

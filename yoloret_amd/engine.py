@@ -304,7 +304,7 @@ class Model:
     # (tune once, deploy many; also keeps profiler runs free of the tuner's trial launches)
     def _tune_key(self, b):
         import zlib
-        sig = zlib.crc32(' '.join('%s:%d:%d:%d:%d:%d' % (o.name, o.kind, o.cin, o.cout, o.dtype, o.k & 0xffff) for o in self.plan_for(b).ops).encode())   # (k: kernel size, split bit, waves per workgroup the fragments are packed for)
+        sig = zlib.crc32(' '.join('%s:%d:%d:%d:%d:%d' % (o.name, o.kind, o.cin, o.cout, o.dtype, o.k & (rt.MBR_FORM_MASK | rt.MBR_NW_MASK)) for o in self.plan_for(b).ops).encode())   # (k: kernel size, split bit, waves per workgroup the fragments are packed for)
         return '%08x:%d' % (sig, b)
 
     def _load_tuning(self, hd, b):
@@ -417,10 +417,10 @@ class Model:
                 if op.kind == rt.OP_POINTWISE:
                     m16 = op.macs
                 elif op.kind in (rt.OP_MBH, rt.OP_MBX):
-                    kk = (op.k & 0xff) ** 2
+                    kk = (op.k & rt.MBH_K_MASK) ** 2
                     cexp = op.se_reduced if op.kind == rt.OP_MBH else op.cout
                     m16 = max(op.macs - op.h * op.w * kk * cexp, 0)
-            elif op.kind in (rt.OP_MBE, rt.OP_MBR) and op.k & 0x80:
+            elif op.kind in (rt.OP_MBE, rt.OP_MBR) and op.k & rt.MBR_SPLIT:
                 # the split form: the 1x1 convolutions run on the 16-bit pipe as THREE float16 products per multiply-add (what that
                 # pipe executes), the depthwise stage on the float32 pipe
                 m32 = op.h * op.w * 9 * (op.cout if op.kind == rt.OP_MBE else op.se_reduced)

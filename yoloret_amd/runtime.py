@@ -18,6 +18,19 @@ ACT = {'none': 0, None: 0, 'relu6': 1, 'swish': 2, 'sigmoid': 3, 'leaky': 4}
 XFORM = {'identity': 0, 'up2': 1, 'maxpool2': 2, 'maxpool4': 3, 'up2_add': 4, 'dw3': 5}
 OP_STEM, OP_POINTWISE, OP_DEPTHWISE, OP_SE_MEAN, OP_SE_FC, OP_WSUM, OP_GATHER, OP_MBCONV = 1, 2, 3, 4, 5, 6, 7, 8
 OP_STEMBLOCK, OP_MBLANE, OP_MBH, OP_MBX, OP_MBR, OP_MBE, OP_HEAD = 9, 10, 11, 12, 13, 14, 15
+# launch-form bits packed into yr_op.k / se_reduced / reserved0, per op kind: the constant block of include/yoloret_hip.h, name by
+# name without the YR_ prefix (tests/test_host_logic.py compares the two)
+PWF_F32_MFMA, PWF_KSPLIT, PWF_STATIONARY, PWF_TWO_OUT = 0x10000, 0x20000, 0x40000, 0x80000      # POINTWISE se_reduced
+PWDW_STRIDE_MASK, PWDW_ACT_SHIFT, PWDW_ACT_MASK = 0xff, 8, 0xff00                               # ... of an op with a 'dw3' source
+PW2_ACT_MASK, PW2_POOLED = 0xff, 0x100                                                          # POINTWISE reserved0 (two outputs)
+MBR_K_MASK, MBR_STREAM, MBR_SPLIT, MBR_FORM_MASK = 0x3f, 0x40, 0x80, 0xff                       # MBR / MBE k
+MBR_NW_SHIFT, MBR_NW_MASK, MBR_SEGS_SHIFT, MBR_SEGS_MASK = 8, 0xff00, 16, 0xff0000
+HEAD_K_MASK, HEAD_STREAM_BIT, HEAD_WALK, HEAD_PLANES = 0x1f, 0x20, 0x40, 0x80                   # HEAD k
+HEAD_STREAM = HEAD_WALK | HEAD_STREAM_BIT
+HEAD_ACT_SHIFT, HEAD_ACT_MASK, HEAD_TILES_SHIFT, HEAD_TILES_MASK = 8, 0xff00, 16, 0xff0000
+MBH_K_MASK, MBH_TH_SHIFT, MBH_TH_MASK, MBH_TW_SHIFT, MBH_TW_MASK = 0xff, 8, 0xff00, 16, 0xff0000    # MBH / MBX k
+MBH_TILE_LDS, MBH_TILE_CHAINED = 254, 255
+STEMBLOCK_K_MASK, STEMBLOCK_ENTRY_SHIFT, STEMBLOCK_ENTRY_MASK, STEMBLOCK_ENTRY_MFMA = 0xff, 8, 0xff00, 1     # STEMBLOCK k
 # yr_dtype: element type of activation tensors / pointwise weights (include/yoloret_hip.h)
 DTYPE = {'f32': 0, 'float32': 0, None: 0, 'bf16': 1, 'bfloat16': 1, 'f16': 2, 'float16': 2, 'u8': 3, 'uint8': 3}   # (u8: images only)
 DTYPE_NAME = {0: 'f32', 1: 'bf16', 2: 'f16', 3: 'u8'}
