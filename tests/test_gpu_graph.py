@@ -168,14 +168,14 @@ def test_unfused_plan_matches_fused(dev):
     from yoloret_amd import compiler
     for fuse in ('1', '1e', '0'):     # ('1e': the deep blocks as expand + depthwise | projection - what they ran before the weight-streaming form)
         os.environ['YOLORET_FUSE'] = fuse[0]
-        saved = compiler.FUSE_MAX_CIN, compiler.FUSE_MIN_PIXELS, compiler.FUSE_MBK
-        compiler.FUSE_MAX_CIN, compiler.FUSE_MIN_PIXELS = 1 << 20, 0  # fuse every eligible block, also the deep ones
+        saved = compiler.FUSE_MAX_CIN, compiler.FUSE_MBK
+        compiler.FUSE_MAX_CIN = 1 << 20  # fuse every eligible block, also the deep ones
         compiler.FUSE_MBK = fuse == '1'
         try:
             m = yolov3_body(L.Input(shape=[hw[0], hw[1], 3]), 'mobilenetv2x75', 3, num_classes=20)
         finally:
             os.environ.pop('YOLORET_FUSE', None)
-            compiler.FUSE_MAX_CIN, compiler.FUSE_MIN_PIXELS, compiler.FUSE_MBK = saved
+            compiler.FUSE_MAX_CIN, compiler.FUSE_MBK = saved
         kinds = set(o.kind for o in m.plan.ops)
         fused_kinds = {rt.OP_STEMBLOCK, rt.OP_MBLANE, rt.OP_MBR, rt.OP_MBE}
         # (at 96 x 96 the lane-per-pixel kernel's minimum map size keeps block_1..3 unfused: the matrix-pipe forms carry the test)

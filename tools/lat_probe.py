@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Batch-1 latency of the full step (forward + decode + NMS + pack) under the current fusion knobs (env):
-    YOLORET_FUSE_MAX_CIN=1000 YOLORET_FUSE_MIN_PIXELS=1 python tools/lat_probe.py [model] [size] [f32|bf16|f16]"""
+    YOLORET_FUSE_MAX_CIN=1000 YOLORET_FUSE_LANE_MIN_PIXELS=1 python tools/lat_probe.py [model] [size] [f32|bf16|f16]"""
 import os, sys, time
 import numpy as np
 import torch

@@ -78,6 +78,22 @@ class OpRec:
         self.__dict__.update(kw)
 
 
+def block_name(name):
+    """'block_3_expand' -> 'block_3': the block a lowered op belongs to.  Fused ops are named after it ('block_3_mbr'), and
+    nosplit_aliases relies on that."""
+    return name.rsplit('_', 1)[0]
+
+
+def count_readers(ops):
+    """{id(buf): how many times the ops read buf - as a source, a residual or a gate}."""
+    readers = {}
+    for op in ops:
+        for b in [s.buf for s in op.srcs] + [op.res, op.gate]:
+            if b is not None:
+                readers[id(b)] = readers.get(id(b), 0) + 1
+    return readers
+
+
 class WeightRangeError(ValueError):
     """A weight of a split-form op (float16 planes) is beyond the float16 range.  `op_name`: the plan op."""
 
@@ -223,7 +239,7 @@ class Plan:
         1x1 convolution's private output (an inverted-residual or head block no fused kernel's shape list took), and HEAD blocks on
         the register-staged front end (pooled sources).  bench.py prints the list: a shape that is on no whitelist must not go unnoticed."""
         producer = {id(op.out): op for op in self.ops}
-        nreaders = {}
+        nreaders = {}      # (reads as a SOURCE only: not count_readers)
         for op in self.ops:
             for s_ in op.srcs:
                 nreaders[id(s_.buf)] = nreaders.get(id(s_.buf), 0) + 1
@@ -311,12 +327,10 @@ class Plan:
 # 81 % of the traffic; on the deep 26x26 / 13x13 blocks its 8x8 tiles under-fill the chip and the
 # unfused GEMMs win, so those stay unfused until the kernel grows a large-M variant.
 FUSE_MAX_CIN = int(os.environ.get('YOLORET_FUSE_MAX_CIN', '32'))
-FUSE_MIN_PIXELS = int(os.environ.get('YOLORET_FUSE_MIN_PIXELS', '1600'))  # output H*W of the block
-FUSE_NO_EXPAND = os.environ.get('YOLORET_FUSE_NO_EXPAND', '0') != '0'    # also fuse DW+project blocks without expand
-FUSE_LANE_NO_EXPAND = os.environ.get('YOLORET_FUSE_LANE_NO_EXPAND', '1') != '0'   # ... in the lane-per-pixel kernel (any dtype)
+FUSE_LANE_NO_EXPAND = os.environ.get('YOLORET_FUSE_LANE_NO_EXPAND', '1') != '0'   # also fuse depthwise + project blocks without expand conv (any dtype)
 MBLANE_IDENT_WIDTHS = {(4, 16), (6, 24), (8, 32)}     # (Cin quads, padded Cout) of launch_ml_ident
 FUSE_STEM = os.environ.get('YOLORET_FUSE_STEM', '1') != '0'              # stem + first (expand-free) block in one kernel
-FUSE_LANE = os.environ.get('YOLORET_FUSE_LANE', '1') != '0'              # narrow fused blocks use mblane.hip instead of mbconv.hip
+FUSE_LANE = os.environ.get('YOLORET_FUSE_LANE', '1') != '0'              # the lane-per-pixel block kernel (mblane.hip); 0: no block runs on it
 FUSE_LANE_MIN_PIXELS = int(os.environ.get('YOLORET_FUSE_LANE_MIN_PIXELS', '600'))  # mblane still wins on 26x26 outputs (block_6)
 MBLANE_WIDTHS = {(4, 16), (4, 24), (6, 24), (6, 32), (6, 40), (6, 48), (8, 32), (8, 40), (8, 48)}  # (CINP/4, round_up(cout,8)) built in mblane.hip
 STEMBLOCK_WIDTHS ={(12, 16), (16, 16), (16, 24), (20, 24), (24, 16), (24, 24)}  # (C1p/2, round_up(cout,8)) built in stemblock.hip
@@ -556,7 +570,7 @@ FOLD_PROJ_MAX_RATIO = float(os.environ.get('YOLORET_FOLD_PROJ_MAX_RATIO', '1.1')
 
 
 def fold_projection_into_consumers(ops, output_buf_ids):
-    readers = {}
+    readers = {}      # (the reading ops and segments themselves, not their number: not count_readers)
     for op in ops:
         for s in op.srcs:
             readers.setdefault(id(s.buf), []).append((op, s))
@@ -622,13 +636,7 @@ FOLD_WSUM = os.environ.get('YOLORET_FOLD_WSUM', '1') != '0'
 
 def fold_weighted_sum(ops, output_buf_ids, V=4):
     producer = {id(op.out): op for op in ops}
-    nreaders = {}
-    for op in ops:
-        for sg in op.srcs:
-            nreaders[id(sg.buf)] = nreaders.get(id(sg.buf), 0) + 1
-        for b in (op.res, op.gate):
-            if b is not None:
-                nreaders[id(b)] = nreaders.get(id(b), 0) + 1
+    nreaders = count_readers(ops)
     drop, repl = set(), {}
     for W in ops:
         if W.kind != rt.OP_WSUM or len(W.srcs) != 4 or W.out.id in output_buf_ids:
@@ -682,7 +690,7 @@ def merge_se_mean(ops, only_after_depthwise=False):
     se_partials_from_depthwise will then turn the pooling into partial sums of the depthwise kernel - a merged launch
     that pools a whole map in one workgroup is what that plan avoids."""
     producer = {id(op.out): op for op in ops}
-    readers = {}
+    readers = {}      # (the reading ops themselves, not their number: not count_readers)
     for op in ops:
         for s in op.srcs:
             readers.setdefault(id(s.buf), []).append(op)
@@ -808,7 +816,7 @@ def pool_into_producers(ops, bufs, output_buf_ids):
     take the maximum of four loads per element, the producing pointwise op stores the pooled map itself (op.stride =
     2: GEMM rows in 2x2-quad-major order, window maximum across four lanes): a quarter of the bytes written, a
     quarter read.  Arithmetic is unchanged (max of the same finished values)."""
-    readers = {}
+    readers = {}      # (the reading ops and segments themselves, not their number: not count_readers)
     for op in ops:
         for s in op.srcs:
             readers.setdefault(id(s.buf), []).append((op, s))
@@ -847,13 +855,7 @@ def fold_depthwise_into_project(ops, output_buf_ids, min_pixels=0):
     depthwise INPUT through xform 'dw3' and computes the depthwise stage in its loader (pointwise_lds.hip, PwDwRow),
     bit-identically; the depthwise output - as wide as the expand output - never reaches HBM.  Only where the
     projection has a single cout tile (cout <= FOLD_DW_MAX_COUT), so the depthwise work is not repeated."""
-    readers = {}
-    for op in ops:
-        for s in op.srcs:
-            readers[s.buf.id] = readers.get(s.buf.id, 0) + 1
-        for b in (op.res, op.gate):
-            if b is not None:
-                readers[b.id] = readers.get(b.id, 0) + 1
+    readers = count_readers(ops)
     out, i = [], 0
     while i < len(ops):
         d = ops[i]
@@ -862,7 +864,7 @@ def fold_depthwise_into_project(ops, output_buf_ids, min_pixels=0):
                 and len(d.srcs) == 1 and d.srcs[0].xform == 'identity' and d.srcs[0].c == d.srcs[0].buf.c
                 and p.kind == rt.OP_POINTWISE and len(p.srcs) == 1 and p.srcs[0].buf is d.out
                 and p.srcs[0].xform == 'identity' and p.gate is None and not getattr(p, 'stride', 0)
-                and readers.get(d.out.id, 0) == 1 and d.out.id not in output_buf_ids
+                and readers.get(id(d.out), 0) == 1 and d.out.id not in output_buf_ids
                 and p.cout <= FOLD_DW_MAX_COUT and d.cout <= FOLD_DW_MAX_C and 'scale' in p.params
                 and p.h * p.w >= min_pixels):
             f = OpRec(rt.OP_POINTWISE, p.name, act=p.act, h=p.h, w=p.w, cin=p.cin, cout=p.cout,
@@ -1016,7 +1018,7 @@ def _head_block16(c, d, readers, output_buf_ids):
           and d.res is None and d.gate_out is None and not (c.h == 1 and c.w == 1) and (d.gate is not None or FUSE_HEAD_ALL))
     if not ok:
         return None
-    m = OpRec(rt.OP_HEAD, c.name.rsplit('_', 1)[0] + '_head', act=d.act, h=d.h, w=d.w, cin=c.cin, cout=F, k=3 | rt.ACT[c.act] << rt.HEAD_ACT_SHIFT | rt.HEAD_WALK, stride=1,
+    m = OpRec(rt.OP_HEAD, block_name(c.name) + '_head', act=d.act, h=d.h, w=d.w, cin=c.cin, cout=F, k=3 | rt.ACT[c.act] << rt.HEAD_ACT_SHIFT | rt.HEAD_WALK, stride=1,
               srcs=list(c.srcs), out=d.out, res=c.gate, macs=c.macs + d.macs, dtype=c.dtype)
     m.fused = [c, d]
     if getattr(c, 'folded_projection', None):
@@ -1054,13 +1056,7 @@ HEAD_WALK16_MAX_NK = min(8, int(os.environ.get('YOLORET_HEAD_WALK16_MAX_NK', '2'
 
 
 def fuse_head_blocks(ops, bufs, output_buf_ids, nosplit=frozenset(), stream_ok=True):
-    readers = {}
-    for op in ops:
-        for s_ in op.srcs:
-            readers[id(s_.buf)] = readers.get(id(s_.buf), 0) + 1
-        for b in (op.res, op.gate):
-            if b is not None:
-                readers[id(b)] = readers.get(id(b), 0) + 1
+    readers = count_readers(ops)
     out, i = [], 0
     while i < len(ops):
         c = ops[i]
@@ -1083,15 +1079,15 @@ def fuse_head_blocks(ops, bufs, output_buf_ids, nosplit=frozenset(), stream_ok=T
               and d.kind == rt.OP_DEPTHWISE and d.dtype == 0 and d.k == 3 and d.stride == 1 and len(d.srcs) == 1 and d.srcs[0].buf is c.out
               and d.srcs[0].xform == 'identity' and d.srcs[0].c == c.cout and d.act in ('swish', 'relu6', 'none') and d.out.ld % 4 == 0
               and d.out.dtype == 0 and not (c.h == 1 and c.w == 1) and (d.gate is not None or FUSE_HEAD_ALL)
-              and c.name.rsplit('_', 1)[0] + '_head' not in nosplit)       # (the head kernels exist in the split form only)
+              and block_name(c.name) + '_head' not in nosplit)       # (the head kernels exist in the split form only)
         if not ok:
-            if c.kind == rt.OP_POINTWISE and c.name.rsplit('_', 1)[0] + '_head' in nosplit:
+            if c.kind == rt.OP_POINTWISE and block_name(c.name) + '_head' in nosplit:
                 c.se_reduced |= rt.PWF_F32_MFMA      # the unfused conv of a head block that left the split form stays off it as well
             out.append(c)
             i += 1
             continue
         F, ldf = c.cout, round_up(c.cout, 4)
-        m = OpRec(rt.OP_HEAD, c.name.rsplit('_', 1)[0] + '_head', act=d.act, h=d.h, w=d.w, cin=c.cin, cout=F, k=3 | rt.ACT[c.act] << rt.HEAD_ACT_SHIFT, stride=1,
+        m = OpRec(rt.OP_HEAD, block_name(c.name) + '_head', act=d.act, h=d.h, w=d.w, cin=c.cin, cout=F, k=3 | rt.ACT[c.act] << rt.HEAD_ACT_SHIFT, stride=1,
                   srcs=list(c.srcs), out=d.out, res=c.gate, macs=c.macs + d.macs, dtype=0)
         m.fused = [c, d]
         if getattr(c, 'folded_projection', None):
@@ -1101,7 +1097,7 @@ def fuse_head_blocks(ops, bufs, output_buf_ids, nosplit=frozenset(), stream_ok=T
         kseg = [s_.c for s_ in c.srcs if s_.xform != 'up2_add']
         nk = sum((c_ + 31) // 32 for c_ in kseg)
         nt = 2 if nk <= 4 else 1
-        bname_h = c.name.rsplit('_', 1)[0]
+        bname_h = block_name(c.name)
         ksrc = [s_ for s_ in c.srcs if s_.xform != 'up2_add']
         # ... where it measured ahead (MobileNetV2 x0.75 @416, 64 images, us, streaming | before): the 26 x 26 heads - td2 48 | 69, bu2 46 | 73 -; not the
         # 13 x 13 ones (two workgroups per image on half the chip: td1 50 | 51, bu1 56 | 37) nor the 52 x 52 ones (four generations of
@@ -1333,436 +1329,435 @@ def mbk_segs(stride, h, pad_t, nw, rows):
         s += 1
 
 
+def pad_to(fn, n, ld):
+    """Builder of fn(weights)[:n], zero-padded to ld floats."""
+    def f(wd):
+        o = np.zeros(ld, np.float32)
+        o[:n] = fn(wd)[:n]
+        return o
+    return f
+
+
+def bn_pair(prm, n, ld):
+    """Builder of [BN scale | BN shift] of the op with params prm, each zero-padded from n to ld floats."""
+    return lambda wd: np.concatenate([pad_to(prm['scale'][1], n, ld)(wd), pad_to(prm['shift'][1], n, ld)(wd)])
+
+
+def block_arrays(wd, ep, dp, pp=None):
+    """The nine arrays mbr_pack / mbs_pack / mbk_pack take, from the params of a block's expand, depthwise 3x3 and project ops (pp None: MBE)."""
+    proj = (pp['wgt'][1](wd), pp['scale'][1](wd), pp['shift'][1](wd)) if pp is not None else (None, None, None)
+    return (ep['wgt'][1](wd), ep['scale'][1](wd), ep['shift'][1](wd), dp['wgt'][1](wd).reshape(9, -1), dp['scale'][1](wd), dp['shift'][1](wd)) + proj
+
+
+def packed(pack, which, ep, dp, pp=None, *extra):
+    """Builder of element `which` of pack(*block_arrays, *extra)."""
+    return lambda wd: pack(*block_arrays(wd, ep, dp, pp), *extra)[which]
+
+
+def stem_pair_rows(prm, taps, c1p):
+    """params entry of stemblock.hip: [taps][c1p] weights + scale/shift [c1p]  ->  [c1p/2][taps x 2, times the scale | 1 1 | shift 2]
+    (the kernel adds the shift to the sum of products: one float32 rounding of w * scale per weight)"""
+    def f(wd):
+        sc = pad_to(prm['scale'][1], c1p, c1p)(wd)
+        w = (prm['wgt'][1](wd).reshape(taps, -1)[:, :c1p] * sc[None]).astype(np.float32)
+        rows = np.concatenate([w, np.ones((1, c1p), np.float32), pad_to(prm['shift'][1], c1p, c1p)(wd)[None]])     # [taps+2][c1p]
+        return np.ascontiguousarray(rows.reshape(taps + 2, c1p // 2, 2).transpose(1, 0, 2)).reshape(c1p // 2, -1)
+    return ((c1p // 2, (taps + 2) * 2), f)
+
+
+def stemblock_params(e, d, p):
+    """params of stem e + depthwise d + projection p on the float32-pipe kernel (stemblock.hip)."""
+    c1p, cout, cop = round_up(e.cout, 4), p.cout, round_up(p.cout, 8)
+
+    def proj_w(wd, pw=p.params['wgt'][1]):
+        o = np.zeros((c1p, cop), np.float32)
+        o[:, :cout] = pw(wd)[:, :c1p].T       # pointwise layout is Wt[cout][kp]
+        return o
+    return {'wgt': stem_pair_rows(e.params, 27, c1p), 'wgt2': stem_pair_rows(d.params, 9, c1p), 'b1': ((c1p, cop), proj_w),
+            'b2': ((2 * cop,), bn_pair(p.params, cout, cop))}
+
+
+def stemblock_mfma_params(e, d, p, dtype):
+    """params of stem e + depthwise d + projection p in the matrix-pipe form of the 16-bit plans (stemblock_h.hip).  Stem weights as
+    the plan's type, [C1P][32] with the k space in the kernel's order: image rows 0..2 x values 0..7 of the row's 9 (kx, c) | value 8
+    of rows 0..2 | 0 x 5"""
+    c1, cout = e.cout, p.cout
+    c1m, com = round_up(c1, 32), round_up(cout, 16)
+    korder = [g * 9 + i_ for g in range(3) for i_ in range(8)] + [i_ * 9 + 8 for i_ in range(3)]
+
+    def stem_w(wd, ew=e.params['wgt'][1]):
+        o = np.zeros((c1m, 32), np.float32)
+        o[:c1, :27] = ew(wd)[korder, :c1].T
+        return o
+
+    def dw_rows(wd, dp=d.params):
+        o = np.zeros((10, c1m), np.float32)
+        sc = dp['scale'][1](wd)[:c1]
+        o[:9, :c1] = (dp['wgt'][1](wd).reshape(9, -1)[:, :c1] * sc[None]).astype(np.float32)
+        o[9, :c1] = dp['shift'][1](wd)[:c1]
+        return o
+
+    def proj_m(wd, pw=p.params['wgt'][1]):
+        o = np.zeros((com, c1m), np.float32)
+        o[:cout, :c1] = pw(wd)[:cout, :c1]       # pointwise layout is Wt[cout][kp]
+        return o
+    return {'wgt': ((c1m, 32), stem_w, dtype), 'scale': ((c1m,), pad_to(e.params['scale'][1], c1, c1m)),
+            'shift': ((c1m,), pad_to(e.params['shift'][1], c1, c1m)), 'wgt2': ((10, c1m), dw_rows), 'b1': ((com, c1m), proj_m, dtype),
+            'b2': ((2 * com,), bn_pair(p.params, cout, com))}
+
+
+def mbh_params(ep, dp, pp, cin, cexp, cout, k, dtype):
+    """params of an MBH op, or (pp None: no projection) of an MBX op, over whole 32-channel chunks; the matrices as the plan's type."""
+    kk, cexp_p, kp, ldo = k * k, round_up(cexp, 32), round_up(cin, 32), round_up(cout, 8)
+
+    def expand_wt(wd):
+        o = np.zeros((cexp_p, kp), np.float32)
+        o[:cexp, :cin] = ep['wgt'][1](wd)[:, :cin]            # pointwise layout Wt[cexp][k-space], one source
+        return o
+
+    def chunk_params(wd):
+        o = np.zeros((kk + 4, cexp_p), np.float32)            # taps | dw scale | dw shift | expand scale | expand shift
+        o[:kk, :cexp] = dp['wgt'][1](wd)[:, :cexp]
+        o[kk, :cexp], o[kk + 1, :cexp] = dp['scale'][1](wd)[:cexp], dp['shift'][1](wd)[:cexp]
+        o[kk + 2, :cexp], o[kk + 3, :cexp] = ep['scale'][1](wd)[:cexp], ep['shift'][1](wd)[:cexp]
+        return o
+
+    def project_wt(wd):
+        o = np.zeros((cout, cexp_p), np.float32)
+        o[:, :cexp] = pp['wgt'][1](wd)[:, :cexp]
+        return o
+
+    def project_bn(wd):
+        o = np.zeros((2, ldo), np.float32)
+        o[0, :cout], o[1, :cout] = pp['scale'][1](wd)[:cout], pp['shift'][1](wd)[:cout]
+        return o.ravel()
+    params = {'wgt': ((cexp_p, kp), expand_wt, dtype), 'wgt2': ((kk + 4, cexp_p), chunk_params)}
+    if pp is not None:
+        params.update({'b1': ((cout, cexp_p), project_wt, dtype), 'b2': ((2 * ldo,), project_bn)})
+    return params
+
+
+def mblane_params(exp, dw, proj):
+    """params of the lane-per-pixel formulation (mblane.hip): everything packed per expanded-channel pair."""
+    cin, cexp, cout = (exp if exp is not None else dw).srcs[0].c, dw.cin, proj.cout
+    cinp, cop, npair = round_up(cin, 4), round_up(cout, 8), round_up((cexp + 1) // 2, 8)
+    e2 = 2 * npair
+    ep, dwp, pp = (exp.params if exp is not None else None), dw.params, proj.params
+
+    def pairs(rows, scale, shift):
+        """rows [K][>=cexp] + BN [>=cexp]  ->  [P][K x 2, times the BN scale | 1 1 | shift 2]  (the kernels add
+        the shift to the sum of products; the scale slot stays in the layout).  Zero beyond cexp, the 1 1 too: not stem_pair_rows."""
+        full = np.zeros((rows.shape[0] + 2, e2), np.float32)
+        full[:-2, :cexp] = (rows[:, :cexp] * scale[None, :cexp]).astype(np.float32)
+        full[-2, :cexp], full[-1, :cexp] = 1.0, shift[:cexp]
+        return np.ascontiguousarray(full.reshape(-1, e2 // 2, 2).transpose(1, 0, 2)).reshape(e2 // 2, -1)
+
+    def expand_w(wd):
+        wt = ep['wgt'][1](wd)                      # pointwise layout Wt[cexp][kp]
+        rows = np.zeros((cinp, wt.shape[0]), np.float32)
+        rows[:wt.shape[1]] = wt.T[:cinp]
+        return pairs(rows, ep['scale'][1](wd), ep['shift'][1](wd))
+
+    def proj_w(wd):
+        o = np.zeros((e2, cop), np.float32)
+        o[:cexp, :cout] = pp['wgt'][1](wd)[:, :cexp].T
+        return o
+    params = {}
+    if exp is not None:          # (without expand conv the op has no `wgt`: the kernel copies the input pairs)
+        params['wgt'] = ((npair, cinp * 2 + 4), expand_w)
+    params['wgt2'] = ((npair, 22), lambda wd: pairs(dwp['wgt'][1](wd), dwp['scale'][1](wd), dwp['shift'][1](wd)))
+    params['b1'] = ((e2, cop), proj_w)
+    params['b2'] = ((2 * cop,), bn_pair(pp, cout, cop))
+    return params
+
+
+def se_fc_of(ops, d):
+    """The SE_FC op that finishes the squeeze of depthwise op d's map - it reads the map itself (merged mean) or the partial sums d
+    already writes -, or None."""
+    return next((o for o in ops if o.kind == rt.OP_SE_FC and getattr(o, 'merged_mean', 0) and len(o.srcs) == 1
+                 and (o.srcs[0].buf is d.out or (d.gate is not None and o.srcs[0].buf is d.gate))), None)
+
+
+def attach_se_sums(d, fc, rows, c, ld, bufs):
+    """`rows` rows of c per-workgroup channel sums for the fused op that replaces depthwise op d: the buffer d already writes, resized,
+    or a new one that SE_FC op fc then reads instead of the map.  -> the buffer.  (Changes bufs and fc: call it once the match is sure.)"""
+    part = d.gate
+    if part is None:
+        part = Buf(len(bufs), rows, 1, c, ld, name=d.name + ':se_sums', dtype=0)
+        bufs.append(part)
+        fc.srcs = [Seg(part, c, 'identity')]
+        fc.k = d.h * d.w
+    else:
+        part.h, part.elems = rows, rows * part.w * part.ld
+        part.bytes = part.elems * rt.ESIZE[part.dtype]
+    return part
+
+
+def plain1(op):
+    return len(op.srcs) == 1 and op.srcs[0].xform == 'identity' and op.gate is None
+
+
+class FuseContext:
+    """What the matchers of fuse_inverted_residuals share: reader counts and the properties of the plan being compiled."""
+
+    def __init__(self, ops, output_buf_ids, dtype, bufs, nosplit, mbk):
+        self.readers = count_readers(ops)
+        self.output_buf_ids, self.dtype, self.bufs, self.nosplit, self.mbk = output_buf_ids, dtype, bufs, nosplit, mbk
+
+    def internal(self, buf):  # not a model output
+        return buf.id not in self.output_buf_ids and buf.external_slot < 0
+
+    def private(self, buf):  # read by exactly one op and not a model output
+        return self.readers.get(id(buf), 0) == 1 and self.internal(buf)
+
+
+class Block:
+    """The ops at position i read as an inverted-residual block, [exp: POINTWISE expand conv + BN + act ->] d: DEPTHWISE [-> p: POINTWISE
+    project conv], recognised once for all the matchers; each adds only its own limits.
+    exp: the expand conv (a plain conv with BN and ReLU6 / Swish whose output has one reader) or None; d: the op behind it - a matcher
+    checks its kind and size -; p: the op behind d or None; nd: ops up to and including d; bi: the block's input; name: the block's."""
+
+    def __init__(self, ops, i, cx):
+        e = ops[i]
+        self.exp = exp = e if (e.kind == rt.OP_POINTWISE and plain1(e) and e.res is None and e.act in ('relu6', 'swish') and cx.private(e.out)
+                               and 'scale' in e.params and not (e.h == 1 and e.w == 1) and i + 1 < len(ops)) else None
+        self.nd = 1 if exp is None else 2
+        self.d = d = ops[i + self.nd - 1]
+        self.p = p = ops[i + self.nd] if i + self.nd < len(ops) else None
+        first = exp if exp is not None else d
+        self.bi = bi = first.srcs[0] if first.srcs else None
+        self.name = block_name(first.name)
+        dw = d.kind == rt.OP_DEPTHWISE
+        # expand -> depthwise: d reads exp's output as it is and has exp's activation
+        self.chained = (exp is not None and dw and len(d.srcs) == 1 and d.srcs[0].xform == 'identity' and d.srcs[0].buf is exp.out
+                        and d.act == exp.act)
+        # private intermediate: d's map has one reader, is no output of the plan, and d writes no squeeze-excite sums
+        self.closed = dw and d.gate is None and cx.private(d.out)
+        # depthwise -> project: a linear 1x1 conv with BN reads d's map and nothing else; its residual, if any, is the block input
+        self.projected = (dw and p is not None and p.kind == rt.OP_POINTWISE and plain1(p) and p.srcs[0].buf is d.out and p.act == 'none'
+                          and 'scale' in p.params and (p.res is None or (p.res is bi.buf and d.stride == 1 and p.cout == bi.c)))
+
+
+def lane_ok(exp, block_in, proj, dw=None):  # the lane-per-pixel kernel (mblane.hip) is built for this block shape
+    widths = (round_up(block_in.c, 4) // 4, round_up(proj.cout, 8))
+    if exp is None:   # a block without expand conv (expand ratio 1): stride 1, a few widths (launch_ml_ident)
+        return (FUSE_LANE and FUSE_LANE_NO_EXPAND and dw is not None and dw.stride == 1 and proj.out.ld % 2 == 0
+                and widths in MBLANE_IDENT_WIDTHS)
+    return FUSE_LANE and proj.out.ld % 2 == 0 and widths in MBLANE_WIDTHS
+
+
+def match_stem_block0(ops, i, cx):
+    """Network entry: STEM -> DEPTHWISE 3x3 s1 -> POINTWISE project (MobileNetV2 Conv1 + block 0) as one STEMBLOCK op, on the
+    float32-pipe kernel or, in 16-bit plans, in its matrix-pipe form."""
+    e = ops[i]
+    if not (FUSE_STEM and e.kind == rt.OP_STEM and cx.private(e.out) and i + 2 < len(ops) and e.act in ('relu6', 'swish')):
+        return None
+    d, p = ops[i + 1], ops[i + 2]
+    if not (d.kind == rt.OP_DEPTHWISE and d.k == 3 and d.stride == 1 and plain1(d) and d.srcs[0].buf is e.out
+            and d.act == e.act and cx.private(d.out) and p.kind == rt.OP_POINTWISE and plain1(p)
+            and p.srcs[0].buf is d.out and p.act == 'none' and p.res is None and 'scale' in p.params
+            and (round_up(e.cout, 4) // 2, round_up(p.cout, 8)) in STEMBLOCK_WIDTHS):
+        return None
+    m = OpRec(rt.OP_STEMBLOCK, e.name + '_block0', act=e.act, h=p.h, w=p.w, cin=3, cout=p.cout, k=3, stride=2,
+              se_reduced=e.cout, srcs=[e.srcs[0]], out=p.out, macs=e.macs + d.macs + p.macs, dtype=cx.dtype, fused=[e, d, p])
+    img = e.srcs[0].buf
+    if STEM_MFMA and cx.dtype != 0 and img.h % 2 == 0 and img.w % 2 == 0 and e.cout <= STEM_MFMA_MAX_C1 and p.cout <= 32:
+        m.params = stemblock_mfma_params(e, d, p, cx.dtype)
+    else:
+        m.params = stemblock_params(e, d, p)
+    return m, 3
+
+
+def match_stem_depthwise(ops, i, cx):
+    """Network entry of the squeeze-excite EfficientNets: STEM -> DEPTHWISE 3x3 s1 whose map feeds an SE block (the projection waits
+    for the gate): stem + depthwise as one kernel, the depthwise map and its per-tile channel sums out.
+    16-bit plans only: measured (B0 @416, 128 images) 0.53 vs 0.23 + 0.34 ms with bf16 maps - the kernel is bound by its
+    two swish passes, the 708 MB it no longer moves buy 7 % - and 0.77 vs 0.36 + 0.39 ms in float32 (pinned expf)"""
+    e = ops[i]
+    if not (FUSE_STEM and FUSE_STEMDW and cx.dtype != 0 and cx.bufs is not None and e.kind == rt.OP_STEM and cx.private(e.out)
+            and i + 1 < len(ops) and e.act in ('relu6', 'swish') and round_up(e.cout, 4) // 2 in (16, 20, 24)):
+        return None
+    d = ops[i + 1]
+    if not (d.kind == rt.OP_DEPTHWISE and d.k == 3 and d.stride == 1 and len(d.srcs) == 1 and d.srcs[0].xform == 'identity'
+            and d.srcs[0].buf is e.out and d.act == e.act and cx.internal(d.out) and d.out.ld % 4 == 0):
+        return None
+    fc = se_fc_of(ops, d)
+    if fc is None:
+        return None
+    c1 = e.cout
+    rows = ((d.h + 13) // 14) * ((d.w + 13) // 14)           # one row per 14 x 14 output tile (stemblock.hip)
+    part = attach_se_sums(d, fc, rows, c1, round_up(c1, 4), cx.bufs)
+    # the matrix-pipe form of this entry (mbxr_h.hip: stemxr_kernel; float32 image of even size, at most 48 stem channels):
+    # asked for by the PLAN (rt.STEMBLOCK_ENTRY_MFMA in k), so that every batch size rounds the same way
+    src0 = e.srcs[0].buf
+    mfma_entry = (FUSE_STEMDW_MFMA and src0.dtype == 0 and src0.h % 2 == 0 and src0.w % 2 == 0 and c1 <= 48 and c1 % 4 == 0
+                  and e.act in ('relu6', 'swish') and d.out.ld % 4 == 0)
+    m = OpRec(rt.OP_STEMBLOCK, e.name + '_dw', act=e.act, h=d.h, w=d.w, cin=3, cout=c1, k=3 | (rt.STEMBLOCK_ENTRY_MFMA << rt.STEMBLOCK_ENTRY_SHIFT if mfma_entry else 0), stride=2,
+              se_reduced=c1, srcs=[e.srcs[0]], out=d.out, gate=part, macs=e.macs + d.macs, dtype=cx.dtype, fused=[e, d])
+    m.params = {'wgt': stem_pair_rows(e.params, 27, round_up(c1, 4)), 'wgt2': stem_pair_rows(d.params, 9, round_up(c1, 4))}
+    return m, 2
+
+
+def mbr_key(blk, cx):
+    """The key of MBR_SHAPES / MBS_SHAPES / MBK_SHAPES - (cin, cexp, cout, stride, residual) - of a block that mbr.hip / mbk.hip can run as ONE
+    launch, or None: expand -> depthwise 3x3 -> project with ReLU6 in a float32 plan, input and output in whole 16-byte pixels."""
+    d, p, bi = blk.d, blk.p, blk.bi
+    if not (FUSE_MBR and cx.dtype == 0 and blk.chained and blk.closed and blk.projected and d.k == 3 and d.stride in (1, 2) and d.act == 'relu6'
+            and bi.xform == 'identity' and bi.buf.ld % 4 == 0 and p.out.ld % 4 == 0 and bi.buf.dtype == 0 and p.out.dtype == 0):
+        return None
+    return (bi.c, d.cin, p.cout, d.stride, p.res is not None)
+
+
+def mbr_op(blk, form):
+    """The YR_OP_MBR op of block blk (mbr_key) with the launch-form bits `form` in k; its params are the caller's."""
+    exp, d, p = blk.exp, blk.d, blk.p
+    return OpRec(rt.OP_MBR, blk.name + '_mbr', act='relu6', h=p.h, w=p.w, cin=blk.bi.c, cout=p.cout, k=3 | form, stride=d.stride,
+                 se_reduced=d.cin, srcs=[blk.bi], out=p.out, res=p.res, macs=exp.macs + d.macs + p.macs, dtype=0, fused=[exp, d, p])
+
+
+def match_mbr_stream(ops, blk, cx):
+    """The weight-streaming form of YR_OP_MBR: one launch, the expanded tensor and the depthwise map stay on the CU (mbk.hip)."""
+    key = mbr_key(blk, cx)
+    if key is None or not (FUSE_MBK and cx.mbk and MBR_SPLIT and key in MBK_SHAPES and blk.name + '_mbr' not in cx.nosplit):
+        return None
+    cin, cexp, cout = key[:3]
+    rows, nw = MBK_SHAPES[key]
+    m = mbr_op(blk, rt.MBR_STREAM | rt.MBR_SPLIT | nw << rt.MBR_NW_SHIFT | rows << rt.MBR_SEGS_SHIFT)
+    ep, dp, pp = blk.exp.params, blk.d.params, blk.p.params
+    m.params = {'wgt': (((cexp // 16 + 1) // 2 * mbk_chunk_words(cin, cout),), packed(mbk_pack, 0, ep, dp, pp)),
+                'b2': ((16 * ((cout + 15) // 16),), packed(mbk_pack, 1, ep, dp, pp))}
+    return m, blk.nd + 1
+
+
+def match_mbr(ops, blk, cx):
+    """YR_OP_MBR on the row-walking register-chained kernel (mbr.hip), in its split form where the shape is built for it."""
+    key = mbr_key(blk, cx)
+    if (key is None or key not in MBR_SHAPES or (MBR_BLOCKS and blk.name not in MBR_BLOCKS)
+            or not (len(MBR_SHAPES[key]) < 3 or blk.p.h * blk.p.w <= MBR_SHAPES[key][2])):
+        return None
+    cin, cexp, cout = key[:3]
+    nw, segs = MBR_SHAPES[key][:2]
+    split = MBR_SPLIT and key in MBS_SHAPES and blk.name + '_mbr' not in cx.nosplit     # (nosplit: Model.check_ranges found operands beyond the float16 range)
+    if split:
+        nw = MBS_SHAPES[key]
+    T, TO, KE = cexp // 16, (cout + 15) // 16, cin // 4
+    m = mbr_op(blk, (rt.MBR_SPLIT if split else 0) | nw << rt.MBR_NW_SHIFT | segs << rt.MBR_SEGS_SHIFT)
+    ep, dp, pp = blk.exp.params, blk.d.params, blk.p.params
+    wshape, pack, extra = (((T * ((cin + 31) // 32) + len(mbs_wave_pairs(T, nw)) * TO) * 512,), mbs_pack, (nw,)) if split else ((T, KE + 4 * TO, 64), mbr_pack, ())
+    m.params = {'wgt': (wshape, packed(pack, 0, ep, dp, pp, *extra)), 'wgt2': ((T, 11, 16), packed(pack, 1, ep, dp, pp, *extra)),
+                'b2': ((16 * TO,), packed(pack, 2, ep, dp, pp, *extra))}
+    return m, blk.nd + 1
+
+
+def match_mbe(ops, blk, cx):
+    """Blocks too wide for mbr.hip's one-workgroup form: expand + depthwise 3x3 as YR_OP_MBE, the projection stays a pointwise op
+    (the depthwise map is written: it need not be private)."""
+    exp, d, bi = blk.exp, blk.d, blk.bi
+    if not (FUSE_MBE and cx.dtype == 0 and blk.chained and d.gate is None and d.k == 3 and d.stride in (1, 2) and d.act == 'relu6'
+            and bi.c in MBE_CINS and d.cin % 16 == 0 and d.cin * 11 * 4 <= 64 * 1024 and bi.xform == 'identity'
+            and bi.buf.ld % 4 == 0 and d.out.ld % 4 == 0 and bi.buf.dtype == 0 and d.out.dtype == 0 and d.out.ld == round_up(d.cin, 4)):
+        return None
+    cexp = d.cin
+    T, KE = cexp // 16, bi.c // 4
+    split = (MBR_SPLIT and bi.c in MBS_MBE_CINS and blk.name + '_mbe' not in cx.nosplit
+             and blk.name + '_mbr' not in cx.nosplit)     # (... or the block's one-launch form was found out of range)
+    m = OpRec(rt.OP_MBE, blk.name + '_mbe', act='relu6', h=d.h, w=d.w, cin=bi.c, cout=cexp, k=3 | (rt.MBR_SPLIT if split else 0), stride=d.stride,
+              srcs=[bi], out=d.out, macs=exp.macs + d.macs, dtype=0, fused=[exp, d])
+    wshape, pack, extra = ((T * ((bi.c + 31) // 32) * 512,), mbs_pack, (0,)) if split else ((T, KE, 64), mbr_pack, ())
+    m.params = {'wgt': (wshape, packed(pack, 0, exp.params, d.params, None, *extra)), 'wgt2': ((T, 11, 16), packed(pack, 1, exp.params, d.params, None, *extra))}
+    return m, blk.nd
+
+
+def match_mbh(ops, blk, cx):
+    """16-bit plans: the MFMA block kernel (mbh.hip) takes every expand -> depthwise 3x3 | 5x5 -> project block with up
+    to 128 input / output channels, whatever the map size (measured: it beats the unfused chain on every
+    MobileNetV2 block at batch 64 and the float32 lane kernels where both apply)"""
+    exp, d, p, bi, dtype = blk.exp, blk.d, blk.p, blk.bi, cx.dtype
+    if not (FUSE_MBH and dtype != 0 and blk.chained and blk.closed and blk.projected and d.k in (3, 5) and d.stride in (1, 2)
+            and '%d%d' % (d.k, d.stride) not in MBH_SKIP
+            and not (d.k == 5 and d.stride == 1 and (d.cin > MBH_K5_MAX_CEXP or (d.cin > MBH_K5_SMALL_CEXP and d.h * d.w <= MBH_K5_SMALL_MAP)))
+            and not (d.k == 3 and d.stride == 1 and d.cin > MBH_K3_MAX_CEXP) and d.act in MBH_ACTS
+            and p.out.dtype == dtype and bi.c <= 128 and p.cout <= 128 and bi.xform == 'identity' and bi.buf.dtype == dtype):
+        return None
+    # measured (tools/mbh_probe.py, batch 64): only on the first, stride-2 block (16 -> 96 -> 24 channels,
+    # 208 x 208 -> 104 x 104) the float32 lane-per-pixel kernel is still ahead (0.223 vs 0.253 ms: its 17 x 17
+    # halo tile leaves two workgroups per CU); from block_2 on (0.205 vs 0.138 ms) everything goes to mbh.  With 24
+    # block inputs the lane kernel loses there too (EfficientNet-lite3 stage 2 entry, 320 x 320 -> 160 x 160, 32 images:
+    # 0.48 vs 0.41 ms): only blocks of at most 16 inputs stay on it
+    # round 3: that block has its own matrix-pipe kernel (mbn_h.hip, dispatched by yr_launch_mbh: 3x3 stride 2, at most 32
+    # inputs in whole 16-byte vectors, at most 192 expanded channels, at most 32 outputs)
+    mbn = MBN and d.k == 3 and d.stride == 2 and bi.c <= 32 and bi.c % 8 == 0 and d.cin <= 192 and p.cout <= 32 and p.res is None
+    if not mbn and lane_ok(exp, bi, p) and d.k == 3 and d.stride == 2 and p.h * p.w >= MBH_LANE_MIN_PIXELS and bi.c <= MBH_LANE_MAX_CIN:
+        return None
+    cin, cexp, cout = bi.c, d.cin, p.cout
+    m = OpRec(rt.OP_MBH, blk.name + '_mbh', act=d.act, h=p.h, w=p.w, cin=cin, cout=cout, k=d.k,
+              stride=d.stride, se_reduced=cexp, srcs=[bi], out=p.out, res=p.res, macs=exp.macs + d.macs + p.macs, dtype=dtype, fused=[exp, d, p])
+    m.params = mbh_params(exp.params, d.params, p.params, cin, cexp, cout, d.k, dtype)
+    return m, blk.nd + 1
+
+
+def match_mbx(ops, blk, cx):
+    """16-bit plans, blocks with squeeze-excite (the projection needs the gate of the complete depthwise map): POINTWISE expand ->
+    DEPTHWISE becomes one MBX op that stores the depthwise map and the per-tile channel sums the SE_FC op finishes the squeeze from."""
+    exp, d, bi, dtype = blk.exp, blk.d, blk.bi, cx.dtype
+    if not (FUSE_MBX and cx.bufs is not None and dtype != 0 and blk.chained and d.k in (3, 5) and d.stride in (1, 2)
+            and '%d%d' % (d.k, d.stride) not in MBX_SKIP and not (d.k == 5 and d.stride == 1 and d.cin > MBX_K5_MAX_CEXP)
+            and d.out.dtype == dtype and bi.buf.dtype == dtype and bi.c <= 128 and cx.internal(d.out)):
+        return None
+    # the squeeze of this depthwise map: an SE_FC op reading it (merged mean) or the partial sums it already writes
+    fc = se_fc_of(ops, d)
+    if fc is None:
+        return None
+    cin, cexp = bi.c, d.cin
+    # partial-sum rows: enough for a 4 x 8 output tile (4 x 4 on small maps, where wide blocks need small tiles)
+    rows = ((d.h + 3) // 4) * ((d.w + 7) // 8 if d.h * d.w > 1000 else (d.w + 3) // 4)
+    part = attach_se_sums(d, fc, rows, cexp, round_up(cexp, rt.VEC[dtype]), cx.bufs)
+    m = OpRec(rt.OP_MBX, blk.name + '_mbx', act=d.act, h=d.h, w=d.w, cin=cin, cout=cexp, k=d.k,
+              stride=d.stride, se_reduced=rows, srcs=[bi], out=d.out, gate=part, macs=exp.macs + d.macs, dtype=dtype, fused=[exp, d])
+    m.params = mbh_params(exp.params, d.params, None, cin, cexp, 0, d.k, dtype)
+    return m, blk.nd
+
+
+def match_mblane(ops, blk, cx):
+    """[expand ->] depthwise 3x3 -> project on the lane-per-pixel kernel (mblane.hip; it computes in float32 from registers, so it takes
+    the 16-bit plans' maps too): the narrow, high-resolution blocks (FUSE_MAX_CIN, FUSE_LANE_MIN_PIXELS)."""
+    exp, d, p, bi = blk.exp, blk.d, blk.p, blk.bi
+    if not (blk.projected and blk.closed and (blk.chained if exp is not None else plain1(d)) and d.k == 3 and d.act in ('relu6', 'swish')
+            and d.srcs[0].buf.ld == round_up(d.cin, rt.VEC[cx.dtype]) and lane_ok(exp, bi, p, d) and p.cout <= 224
+            and bi.buf.ld % 4 == 0 and bi.c <= FUSE_MAX_CIN and p.h * p.w >= FUSE_LANE_MIN_PIXELS):
+        return None
+    m = OpRec(rt.OP_MBLANE, blk.name + '_mblane', act=d.act, h=p.h, w=p.w, cin=bi.c, cout=p.cout, k=3, stride=d.stride,
+              se_reduced=d.cin, srcs=[bi], out=p.out, res=p.res, macs=(exp.macs if exp is not None else 0) + d.macs + p.macs, dtype=cx.dtype,
+              fused=[o for o in (exp, d, p) if o is not None])
+    m.params = mblane_params(exp, d, p)
+    return m, blk.nd + 1
+
+
 def fuse_inverted_residuals(ops, output_buf_ids, blocks=True, dtype=0, bufs=None, nosplit=frozenset(), mbk=True):
-    """Peephole over the lowered op list: [POINTWISE expand+act ->] DEPTHWISE 3x3+act -> POINTWISE
-    project (+residual == block input) becomes one MBCONV op whose expanded tensors never reach HBM.
-    blocks=False (the small-batch plan) keeps only the network-entry fusion (stem + first block).
-    16-bit plans (dtype != 0): the lane-per-pixel kernels (stemblock, mblane) take 16-bit inputs / outputs - they
-    compute in float32 from registers, so only their loads and stores change; the MFMA block kernel (mbconv.hip) is
-    float32 only and is not selected.  Blocks with squeeze-excite (the projection needs the gate of the complete depthwise
-    map) get their first two thirds fused instead: POINTWISE expand -> DEPTHWISE becomes one MBX op that stores the
-    depthwise map and the per-tile channel sums the SE_FC op finishes the squeeze from."""
-    max_cin = FUSE_MAX_CIN if blocks else 0
-    readers = {}
-    for op in ops:
-        for s in op.srcs:
-            readers[s.buf.id] = readers.get(s.buf.id, 0) + 1
-        for b in (op.res, op.gate):
-            if b is not None:
-                readers[b.id] = readers.get(b.id, 0) + 1
-
-    def private(buf):  # read by exactly one op and not a model output
-        return readers.get(buf.id, 0) == 1 and buf.id not in output_buf_ids and buf.external_slot < 0
-
-    def plain1(op):
-        return len(op.srcs) == 1 and op.srcs[0].xform == 'identity' and op.gate is None
-
-    def lane_ok(exp, block_in, proj, dw=None):  # the lane-per-pixel kernel (mblane.hip) is built for this block shape
-        widths = (round_up(block_in.c, 4) // 4, round_up(proj.cout, 8))
-        if exp is None:   # a block without expand conv (expand ratio 1): stride 1, a few widths (launch_ml_ident)
-            return (FUSE_LANE and FUSE_LANE_NO_EXPAND and dw is not None and dw.stride == 1 and proj.out.ld % 2 == 0
-                    and widths in MBLANE_IDENT_WIDTHS)
-        return FUSE_LANE and proj.out.ld % 2 == 0 and widths in MBLANE_WIDTHS
-
-    def pad_to(fn, n, ld):
-        def f(wd):
-            o = np.zeros(ld, np.float32)
-            o[:n] = fn(wd)[:n]
-            return o
-        return f
-
+    """Peephole over the lowered op list: the network entry (STEM -> DEPTHWISE 3x3 [-> POINTWISE project]) and the inverted-residual
+    blocks ([POINTWISE expand+act ->] DEPTHWISE+act -> POINTWISE project (+residual == block input)) become one fused op each, whose
+    expanded tensors never reach HBM.  At each position the first matcher that answers takes the ops; a matcher that declines
+    changes nothing.  blocks=False (the small-batch plan) keeps only the fusion of stem + first block.
+    float32 plans run their blocks on the register-chained matrix-pipe kernels (mbr.hip, mbk.hip; mbe: expand + depthwise only),
+    16-bit plans (dtype != 0) on the MFMA block kernel (mbh.hip; mbx: expand + depthwise of a squeeze-excite block, whose
+    projection waits for the gate); the lane-per-pixel kernels (stemblock.hip, mblane.hip) serve both - they compute in float32
+    from registers, only their loads and stores change."""
+    cx = FuseContext(ops, output_buf_ids, dtype, bufs, nosplit, mbk)
     out, i = [], 0
     while i < len(ops):
-        e = ops[i]
-        # ---- network entry: STEM -> DEPTHWISE 3x3 s1 -> POINTWISE project (MobileNetV2 Conv1 + block 0)
-        if FUSE_STEM and e.kind == rt.OP_STEM and private(e.out) and i + 2 < len(ops) and e.act in ('relu6', 'swish'):
-            d, p = ops[i + 1], ops[i + 2]
-            if (d.kind == rt.OP_DEPTHWISE and d.k == 3 and d.stride == 1 and plain1(d) and d.srcs[0].buf is e.out
-                    and d.act == e.act and private(d.out) and p.kind == rt.OP_POINTWISE and plain1(p)
-                    and p.srcs[0].buf is d.out and p.act == 'none' and p.res is None and 'scale' in p.params
-                    and (round_up(e.cout, 4) // 2, round_up(p.cout, 8)) in STEMBLOCK_WIDTHS):
-                c1, cout = e.cout, p.cout
-                c1p, cop = round_up(c1, 4), round_up(cout, 8)
-                m = OpRec(rt.OP_STEMBLOCK, e.name + '_block0', act=e.act, h=p.h, w=p.w, cin=3, cout=cout, k=3, stride=2,
-                          se_reduced=c1, srcs=[e.srcs[0]], out=p.out, macs=e.macs + d.macs + p.macs, dtype=dtype)
-                m.fused = [e, d, p]
-
-                def per_pair(prm, taps, c1p=c1p):
-                    """[taps][c1p] weights + scale/shift [c1p]  ->  [c1p/2][taps x 2, times the scale | 1 1 | shift 2]
-                    (the kernel adds the shift to the sum of products: one float32 rounding of w * scale per weight)"""
-                    def f(wd):
-                        sc = pad_to(prm['scale'][1], c1p, c1p)(wd)
-                        w = (prm['wgt'][1](wd).reshape(taps, -1)[:, :c1p] * sc[None]).astype(np.float32)
-                        rows = np.concatenate([w, np.ones((1, c1p), np.float32),
-                                               pad_to(prm['shift'][1], c1p, c1p)(wd)[None]])     # [taps+2][c1p]
-                        return np.ascontiguousarray(rows.reshape(taps + 2, c1p // 2, 2).transpose(1, 0, 2)).reshape(c1p // 2, -1)
-                    return ((c1p // 2, (taps + 2) * 2), f)
-
-                def proj_w(wd, pw=p.params['wgt'][1], c1p=c1p, cop=cop, cout=cout):
-                    o = np.zeros((c1p, cop), np.float32)
-                    o[:, :cout] = pw(wd)[:, :c1p].T       # pointwise layout is Wt[cout][kp]
-                    return o
-                pp2 = p.params
-                img = e.srcs[0].buf
-                if STEM_MFMA and dtype != 0 and img.h % 2 == 0 and img.w % 2 == 0 and c1 <= STEM_MFMA_MAX_C1 and cout <= 32:
-                    # 16-bit plans: the matrix-pipe form (stemblock_h.hip).  Stem weights as the plan's type, [C1P][32] with the k
-                    # space in the kernel's order: image rows 0..2 x values 0..7 of the row's 9 (kx, c) | value 8 of rows 0..2 | 0 x 5
-                    c1m, com = round_up(c1, 32), round_up(cout, 16)
-                    korder = [g * 9 + i_ for g in range(3) for i_ in range(8)] + [i_ * 9 + 8 for i_ in range(3)]
-
-                    def stem_w(wd, ew=e.params['wgt'][1], c1=c1, c1m=c1m, korder=korder):
-                        o = np.zeros((c1m, 32), np.float32)
-                        o[:c1, :27] = ew(wd)[korder, :c1].T
-                        return o
-
-                    def dw_rows(wd, dp=d.params, c1=c1, c1m=c1m):
-                        o = np.zeros((10, c1m), np.float32)
-                        sc = dp['scale'][1](wd)[:c1]
-                        o[:9, :c1] = (dp['wgt'][1](wd).reshape(9, -1)[:, :c1] * sc[None]).astype(np.float32)
-                        o[9, :c1] = dp['shift'][1](wd)[:c1]
-                        return o
-
-                    def proj_m(wd, pw=p.params['wgt'][1], c1=c1, c1m=c1m, com=com, cout=cout):
-                        o = np.zeros((com, c1m), np.float32)
-                        o[:cout, :c1] = pw(wd)[:cout, :c1]       # pointwise layout is Wt[cout][kp]
-                        return o
-                    m.params['wgt'] = ((c1m, 32), stem_w, dtype)
-                    m.params['scale'] = ((c1m,), pad_to(e.params['scale'][1], c1, c1m))
-                    m.params['shift'] = ((c1m,), pad_to(e.params['shift'][1], c1, c1m))
-                    m.params['wgt2'] = ((10, c1m), dw_rows)
-                    m.params['b1'] = ((com, c1m), proj_m, dtype)
-                    m.params['b2'] = ((2 * com,), lambda wd, pp2=pp2, cout=cout, com=com: np.concatenate(
-                        [pad_to(pp2['scale'][1], cout, com)(wd), pad_to(pp2['shift'][1], cout, com)(wd)]))
-                    out.append(m)
-                    i += 3
-                    continue
-                m.params['wgt'] = per_pair(e.params, 27)
-                m.params['wgt2'] = per_pair(d.params, 9)
-                m.params['b1'] = ((c1p, cop), proj_w)
-                m.params['b2'] = ((2 * cop,), lambda wd, pp2=pp2, cout=cout, cop=cop: np.concatenate(
-                    [pad_to(pp2['scale'][1], cout, cop)(wd), pad_to(pp2['shift'][1], cout, cop)(wd)]))
-                out.append(m)
-                i += 3
-                continue
-        # ---- network entry of the squeeze-excite EfficientNets: STEM -> DEPTHWISE 3x3 s1 whose map feeds an SE block (the
-        # projection waits for the gate): stem + depthwise as one kernel, the depthwise map and its per-tile channel sums out.
-        # 16-bit plans only: measured (B0 @416, 128 images) 0.53 vs 0.23 + 0.34 ms with bf16 maps - the kernel is bound by its
-        # two swish passes, the 708 MB it no longer moves buy 7 % - and 0.77 vs 0.36 + 0.39 ms in float32 (pinned expf)
-        if (FUSE_STEM and FUSE_STEMDW and dtype != 0 and blocks and bufs is not None and e.kind == rt.OP_STEM and private(e.out) and i + 1 < len(ops)
-                and e.act in ('relu6', 'swish') and round_up(e.cout, 4) // 2 in (16, 20, 24)):
-            d = ops[i + 1]
-            fc = None
-            if (d.kind == rt.OP_DEPTHWISE and d.k == 3 and d.stride == 1 and len(d.srcs) == 1 and d.srcs[0].xform == 'identity'
-                    and d.srcs[0].buf is e.out and d.act == e.act and d.out.external_slot < 0 and d.out.id not in output_buf_ids
-                    and d.out.ld % 4 == 0):
-                fc = next((o for o in ops if o.kind == rt.OP_SE_FC and getattr(o, 'merged_mean', 0) and len(o.srcs) == 1
-                           and (o.srcs[0].buf is d.out or (d.gate is not None and o.srcs[0].buf is d.gate))), None)
-            if fc is not None:
-                c1 = e.cout
-                c1p = round_up(c1, 4)
-                rows = ((d.h + 13) // 14) * ((d.w + 13) // 14)           # one row per 14 x 14 output tile (stemblock.hip)
-                part = d.gate
-                if part is None:
-                    part = Buf(len(bufs), rows, 1, c1, round_up(c1, 4), name=d.name + ':se_sums', dtype=0)
-                    bufs.append(part)
-                    fc.srcs = [Seg(part, c1, 'identity')]
-                    fc.k = d.h * d.w
-                else:
-                    part.h, part.elems = rows, rows * part.w * part.ld
-                    part.bytes = part.elems * rt.ESIZE[part.dtype]
-                # the matrix-pipe form of this entry (mbxr_h.hip: stemxr_kernel; float32 image of even size, at most 48 stem channels):
-                # asked for by the PLAN (rt.STEMBLOCK_ENTRY_MFMA in k), so that every batch size rounds the same way
-                src0 = e.srcs[0].buf
-                mfma_entry = (FUSE_STEMDW_MFMA and src0.dtype == 0 and src0.h % 2 == 0 and src0.w % 2 == 0 and c1 <= 48 and c1 % 4 == 0
-                              and e.act in ('relu6', 'swish') and d.out.ld % 4 == 0)
-                m = OpRec(rt.OP_STEMBLOCK, e.name + '_dw', act=e.act, h=d.h, w=d.w, cin=3, cout=c1, k=3 | (rt.STEMBLOCK_ENTRY_MFMA << rt.STEMBLOCK_ENTRY_SHIFT if mfma_entry else 0), stride=2,
-                          se_reduced=c1, srcs=[e.srcs[0]], out=d.out, gate=part, macs=e.macs + d.macs, dtype=dtype)
-                m.fused = [e, d]
-
-                def per_pair2(prm, taps, c1p=c1p):
-                    def f(wd):
-                        sc = pad_to(prm['scale'][1], c1p, c1p)(wd)
-                        w = (prm['wgt'][1](wd).reshape(taps, -1)[:, :c1p] * sc[None]).astype(np.float32)
-                        rows_ = np.concatenate([w, np.ones((1, c1p), np.float32), pad_to(prm['shift'][1], c1p, c1p)(wd)[None]])
-                        return np.ascontiguousarray(rows_.reshape(taps + 2, c1p // 2, 2).transpose(1, 0, 2)).reshape(c1p // 2, -1)
-                    return ((c1p // 2, (taps + 2) * 2), f)
-                m.params['wgt'] = per_pair2(e.params, 27)
-                m.params['wgt2'] = per_pair2(d.params, 9)
-                out.append(m)
-                i += 2
-                continue
-        exp = dw = proj = None
-        j = i
-        if (e.kind == rt.OP_POINTWISE and plain1(e) and e.res is None and e.act in ('relu6', 'swish')
-                and private(e.out) and 'scale' in e.params and not (e.h == 1 and e.w == 1) and j + 1 < len(ops)):
-            exp, j = e, j + 1
-        d = ops[j] if j < len(ops) else None
-        # 16-bit plans: the MFMA block kernel (mbh.hip) takes every expand -> depthwise 3x3 | 5x5 -> project block with up
-        # to 128 input / output channels, whatever the map size (measured: it beats the unfused chain on every
-        # MobileNetV2 block at batch 64 and the float32 lane kernels where both apply)
-        if (FUSE_MBR and dtype == 0 and blocks and exp is not None and d is not None and d.kind == rt.OP_DEPTHWISE and d.k == 3
-                and d.stride in (1, 2) and plain1(d) and private(d.out) and d.srcs[0].buf is exp.out and d.act == exp.act == 'relu6'
-                and j + 1 < len(ops)):
-            p, bi = ops[j + 1], exp.srcs[0]
-            key = (bi.c, d.cin, p.cout if p.kind == rt.OP_POINTWISE else 0, d.stride, p.res is not None)
-            bname = exp.name.rsplit('_', 1)[0]
-            if (FUSE_MBK and mbk and MBR_SPLIT and key in MBK_SHAPES and bname + '_mbr' not in nosplit and p.kind == rt.OP_POINTWISE and plain1(p)
-                    and p.srcs[0].buf is d.out and p.act == 'none' and 'scale' in p.params and bi.xform == 'identity'
-                    and bi.buf.ld % 4 == 0 and p.out.ld % 4 == 0 and bi.buf.dtype == 0 and p.out.dtype == 0
-                    and (p.res is None or (p.res is bi.buf and d.stride == 1 and p.cout == bi.c))):
-                # the weight-streaming form: one launch, the expanded tensor and the depthwise map stay on the CU (mbk.hip)
-                cin, cexp, cout = bi.c, d.cin, p.cout
-                rows, nw = MBK_SHAPES[key]
-                T, TO = cexp // 16, (cout + 15) // 16
-                m = OpRec(rt.OP_MBR, bname + '_mbr', act='relu6', h=p.h, w=p.w, cin=cin, cout=cout, k=3 | rt.MBR_STREAM | rt.MBR_SPLIT | nw << rt.MBR_NW_SHIFT | rows << rt.MBR_SEGS_SHIFT,
-                          stride=d.stride, se_reduced=cexp, srcs=[bi], out=p.out, res=p.res, macs=exp.macs + d.macs + p.macs, dtype=0)
-                m.fused = [exp, d, p]
-                ep, dp, pp = exp.params, d.params, p.params
-
-                def packed_k(which, ep=ep, dp=dp, pp=pp):
-                    def f(wd):
-                        return mbk_pack(ep['wgt'][1](wd), ep['scale'][1](wd), ep['shift'][1](wd), dp['wgt'][1](wd).reshape(9, -1),
-                                        dp['scale'][1](wd), dp['shift'][1](wd), pp['wgt'][1](wd), pp['scale'][1](wd), pp['shift'][1](wd))[which]
-                    return f
-                m.params = {'wgt': (((T + 1) // 2 * mbk_chunk_words(cin, cout),), packed_k(0)), 'b2': ((16 * TO,), packed_k(1))}
-                out.append(m)
-                i = j + 2
-                continue
-            if (key in MBR_SHAPES and (not MBR_BLOCKS or bname in MBR_BLOCKS) and p.kind == rt.OP_POINTWISE and plain1(p)
-                    and (len(MBR_SHAPES[key]) < 3 or p.h * p.w <= MBR_SHAPES[key][2])
-                    and p.srcs[0].buf is d.out and p.act == 'none' and 'scale' in p.params and bi.xform == 'identity'
-                    and bi.buf.ld % 4 == 0 and p.out.ld % 4 == 0 and bi.buf.dtype == 0 and p.out.dtype == 0
-                    and (p.res is None or (p.res is bi.buf and d.stride == 1 and p.cout == bi.c))):
-                cin, cexp, cout = bi.c, d.cin, p.cout
-                nw, segs = MBR_SHAPES[key][:2]
-                split = MBR_SPLIT and key in MBS_SHAPES and bname + '_mbr' not in nosplit     # (nosplit: Model.check_ranges found operands beyond the float16 range)
-                if split:
-                    nw = MBS_SHAPES[key]
-                T, TO, KE = cexp // 16, (cout + 15) // 16, cin // 4
-                m = OpRec(rt.OP_MBR, bname + '_mbr', act='relu6', h=p.h, w=p.w, cin=cin, cout=cout, k=3 | (rt.MBR_SPLIT if split else 0) | nw << rt.MBR_NW_SHIFT | segs << rt.MBR_SEGS_SHIFT,
-                          stride=d.stride, se_reduced=cexp, srcs=[bi], out=p.out, res=p.res, macs=exp.macs + d.macs + p.macs, dtype=0)
-                m.fused = [exp, d, p]
-                ep, dp, pp = exp.params, d.params, p.params
-                if split:
-                    def packed_s(which, ep=ep, dp=dp, pp=pp, nw=nw):
-                        def f(wd):
-                            return mbs_pack(ep['wgt'][1](wd), ep['scale'][1](wd), ep['shift'][1](wd), dp['wgt'][1](wd).reshape(9, -1),
-                                            dp['scale'][1](wd), dp['shift'][1](wd), pp['wgt'][1](wd), pp['scale'][1](wd), pp['shift'][1](wd), nw)[which]
-                        return f
-                    nwords = (T * ((cin + 31) // 32) + len(mbs_wave_pairs(T, nw)) * TO) * 512
-                    m.params = {'wgt': ((nwords,), packed_s(0)), 'wgt2': ((T, 11, 16), packed_s(1)), 'b2': ((16 * TO,), packed_s(2))}
-                    out.append(m)
-                    i = j + 2
-                    continue
-
-                def packed(which, ep=ep, dp=dp, pp=pp, cexp=cexp):
-                    def f(wd):
-                        return mbr_pack(ep['wgt'][1](wd), ep['scale'][1](wd), ep['shift'][1](wd), dp['wgt'][1](wd).reshape(9, -1),
-                                        dp['scale'][1](wd), dp['shift'][1](wd), pp['wgt'][1](wd), pp['scale'][1](wd), pp['shift'][1](wd))[which]
-                    return f
-                m.params = {'wgt': ((T, KE + 4 * TO, 64), packed(0)), 'wgt2': ((T, 11, 16), packed(1)), 'b2': ((16 * TO,), packed(2))}
-                out.append(m)
-                i = j + 2
-                continue
-        if (FUSE_MBE and dtype == 0 and blocks and exp is not None and d is not None and d.kind == rt.OP_DEPTHWISE and d.k == 3
-                and d.stride in (1, 2) and plain1(d) and d.gate is None and d.srcs[0].buf is exp.out and d.act == exp.act == 'relu6'
-                and exp.srcs[0].c in MBE_CINS and d.cin % 16 == 0 and d.cin * 11 * 4 <= 64 * 1024 and exp.srcs[0].xform == 'identity'
-                and exp.srcs[0].buf.ld % 4 == 0 and d.out.ld % 4 == 0 and exp.srcs[0].buf.dtype == 0 and d.out.dtype == 0
-                and d.out.ld == round_up(d.cin, 4)):
-            bi, cexp = exp.srcs[0], d.cin
-            T, KE = cexp // 16, bi.c // 4
-            mbe_split = (MBR_SPLIT and bi.c in MBS_MBE_CINS and exp.name.rsplit('_', 1)[0] + '_mbe' not in nosplit
-                         and exp.name.rsplit('_', 1)[0] + '_mbr' not in nosplit)     # (... or the block's one-launch form was found out of range)
-            m = OpRec(rt.OP_MBE, exp.name.rsplit('_', 1)[0] + '_mbe', act='relu6', h=d.h, w=d.w, cin=bi.c, cout=cexp, k=3 | (rt.MBR_SPLIT if mbe_split else 0), stride=d.stride,
-                      srcs=[bi], out=d.out, macs=exp.macs + d.macs, dtype=0)
-            m.fused = [exp, d]
-            ep, dp = exp.params, d.params
-            if mbe_split:
-                def packed_es(which, ep=ep, dp=dp):
-                    def f(wd):
-                        wa, tab, _ = mbs_pack(ep['wgt'][1](wd), ep['scale'][1](wd), ep['shift'][1](wd), dp['wgt'][1](wd).reshape(9, -1),
-                                              dp['scale'][1](wd), dp['shift'][1](wd), None, None, None, 0)
-                        return wa if which == 0 else tab
-                    return f
-                m.params = {'wgt': ((T * ((bi.c + 31) // 32) * 512,), packed_es(0)), 'wgt2': ((T, 11, 16), packed_es(1))}
-                out.append(m)
-                i = j + 1
-                continue
-
-            def packed_e(which, ep=ep, dp=dp):
-                def f(wd):
-                    wa, tab, _ = mbr_pack(ep['wgt'][1](wd), ep['scale'][1](wd), ep['shift'][1](wd), dp['wgt'][1](wd).reshape(9, -1),
-                                          dp['scale'][1](wd), dp['shift'][1](wd), None, None, None)
-                    return wa if which == 0 else tab
-                return f
-            m.params = {'wgt': ((T, KE, 64), packed_e(0)), 'wgt2': ((T, 11, 16), packed_e(1))}
-            out.append(m)
-            i = j + 1
-            continue
-        mbh = None
-        if (FUSE_MBH and dtype != 0 and blocks and exp is not None and d is not None and d.kind == rt.OP_DEPTHWISE and d.k in (3, 5)
-                and d.stride in (1, 2) and '%d%d' % (d.k, d.stride) not in MBH_SKIP and not (d.k == 5 and d.stride == 1 and (d.cin > MBH_K5_MAX_CEXP or (d.cin > MBH_K5_SMALL_CEXP and d.h * d.w <= MBH_K5_SMALL_MAP))) and not (d.k == 3 and d.stride == 1 and d.cin > MBH_K3_MAX_CEXP) and plain1(d) and private(d.out) and d.srcs[0].buf is exp.out and d.act == exp.act
-                and d.act in MBH_ACTS and j + 1 < len(ops)):
-            p = ops[j + 1]
-            bi = exp.srcs[0]
-            if (p.kind == rt.OP_POINTWISE and plain1(p) and p.srcs[0].buf is d.out and p.act == 'none' and 'scale' in p.params
-                    and p.out.dtype == dtype and bi.c <= 128 and p.cout <= 128 and bi.xform == 'identity' and bi.buf.dtype == dtype
-                    and (p.res is None or (p.res is bi.buf and d.stride == 1 and p.cout == bi.c))):
-                mbh = (d, p)
-                # measured (tools/mbh_probe.py, batch 64): only on the first, stride-2 block (16 -> 96 -> 24 channels,
-                # 208 x 208 -> 104 x 104) the float32 lane-per-pixel kernel is still ahead (0.223 vs 0.253 ms: its 17 x 17
-                # halo tile leaves two workgroups per CU); from block_2 on (0.205 vs 0.138 ms) everything goes to mbh.  With 24
-                # block inputs the lane kernel loses there too (EfficientNet-lite3 stage 2 entry, 320 x 320 -> 160 x 160, 32 images:
-                # 0.48 vs 0.41 ms): only blocks of at most 16 inputs stay on it
-                # round 3: that block has its own matrix-pipe kernel (mbn_h.hip, dispatched by yr_launch_mbh: 3x3 stride 2, at most 32
-                # inputs in whole 16-byte vectors, at most 192 expanded channels, at most 32 outputs)
-                mbn = MBN and d.k == 3 and d.stride == 2 and bi.c <= 32 and bi.c % 8 == 0 and d.cin <= 192 and p.cout <= 32 and p.res is None
-                if not mbn and lane_ok(exp, bi, p) and d.k == 3 and d.stride == 2 and p.h * p.w >= MBH_LANE_MIN_PIXELS and bi.c <= MBH_LANE_MAX_CIN:
-                    mbh = None
-        mbx = None
-        if (FUSE_MBX and mbh is None and bufs is not None and dtype != 0 and blocks and exp is not None and d is not None
-                and d.kind == rt.OP_DEPTHWISE and d.k in (3, 5) and d.stride in (1, 2) and '%d%d' % (d.k, d.stride) not in MBX_SKIP and not (d.k == 5 and d.stride == 1 and d.cin > MBX_K5_MAX_CEXP) and len(d.srcs) == 1
-                and d.srcs[0].xform == 'identity' and d.srcs[0].buf is exp.out and d.act == exp.act and d.out.dtype == dtype
-                and exp.srcs[0].buf.dtype == dtype and exp.srcs[0].c <= 128 and d.out.external_slot < 0 and d.out.id not in output_buf_ids):
-            # the squeeze of this depthwise map: an SE_FC op reading it (merged mean) or the partial sums it already writes
-            mbx = next((o for o in ops if o.kind == rt.OP_SE_FC and getattr(o, 'merged_mean', 0) and len(o.srcs) == 1
-                        and (o.srcs[0].buf is d.out or (d.gate is not None and o.srcs[0].buf is d.gate))), None)
-        if mbx is not None:
-            fc, bi = mbx, exp.srcs[0]
-            cin, cexp, kk = bi.c, d.cin, d.k * d.k
-            cexp_p, kp = round_up(cexp, 32), round_up(cin, 32)
-            # partial-sum rows: enough for a 4 x 8 output tile (4 x 4 on small maps, where wide blocks need small tiles)
-            rows = ((d.h + 3) // 4) * ((d.w + 7) // 8 if d.h * d.w > 1000 else (d.w + 3) // 4)
-            part = d.gate
-            if part is None:
-                part = Buf(len(bufs), rows, 1, cexp, round_up(cexp, rt.VEC[dtype]), name=d.name + ':se_sums', dtype=0)
-                bufs.append(part)
-                fc.srcs = [Seg(part, cexp, 'identity')]
-                fc.k = d.h * d.w
-            else:
-                part.h, part.elems = rows, rows * part.w * part.ld
-                part.bytes = part.elems * rt.ESIZE[part.dtype]
-            m = OpRec(rt.OP_MBX, exp.name.rsplit('_', 1)[0] + '_mbx', act=d.act, h=d.h, w=d.w, cin=cin, cout=cexp, k=d.k,
-                      stride=d.stride, se_reduced=rows, srcs=[bi], out=d.out, gate=part, macs=exp.macs + d.macs, dtype=dtype)
-            m.fused = [exp, d]
-            ep, dp = exp.params, d.params
-
-            def expand_wt(wd, ep=ep, cexp=cexp, cin=cin, cexp_p=cexp_p, kp=kp):
-                o = np.zeros((cexp_p, kp), np.float32)
-                o[:cexp, :cin] = ep['wgt'][1](wd)[:, :cin]            # pointwise layout Wt[cexp][k-space], one source
-                return o
-
-            def chunk_params(wd, ep=ep, dp=dp, cexp=cexp, cexp_p=cexp_p, kk=kk):
-                o = np.zeros((kk + 4, cexp_p), np.float32)            # taps | dw scale | dw shift | expand scale | expand shift
-                o[:kk, :cexp] = dp['wgt'][1](wd)[:, :cexp]
-                o[kk, :cexp], o[kk + 1, :cexp] = dp['scale'][1](wd)[:cexp], dp['shift'][1](wd)[:cexp]
-                o[kk + 2, :cexp], o[kk + 3, :cexp] = ep['scale'][1](wd)[:cexp], ep['shift'][1](wd)[:cexp]
-                return o
-            m.params = {'wgt': ((cexp_p, kp), expand_wt, dtype), 'wgt2': ((kk + 4, cexp_p), chunk_params)}
-            out.append(m)
-            i = j + 1
-            continue
-        if mbh is not None:
-            d, p = mbh
-            bi = exp.srcs[0]
-            cin, cexp, cout, kk = bi.c, d.cin, p.cout, d.k * d.k
-            cexp_p, kp, ldo = round_up(cexp, 32), round_up(cin, 32), round_up(cout, 8)
-            m = OpRec(rt.OP_MBH, exp.name.rsplit('_', 1)[0] + '_mbh', act=d.act, h=p.h, w=p.w, cin=cin, cout=cout, k=d.k,
-                      stride=d.stride, se_reduced=cexp, srcs=[bi], out=p.out, res=p.res, macs=exp.macs + d.macs + p.macs, dtype=dtype)
-            m.fused = [exp, d, p]
-            ep, dp, pp = exp.params, d.params, p.params
-
-            def expand_wt(wd, ep=ep, cexp=cexp, cin=cin, cexp_p=cexp_p, kp=kp):
-                o = np.zeros((cexp_p, kp), np.float32)
-                o[:cexp, :cin] = ep['wgt'][1](wd)[:, :cin]            # pointwise layout Wt[cexp][k-space], one source
-                return o
-
-            def chunk_params(wd, ep=ep, dp=dp, cexp=cexp, cexp_p=cexp_p, kk=kk):
-                o = np.zeros((kk + 4, cexp_p), np.float32)            # taps | dw scale | dw shift | expand scale | expand shift
-                o[:kk, :cexp] = dp['wgt'][1](wd)[:, :cexp]
-                o[kk, :cexp], o[kk + 1, :cexp] = dp['scale'][1](wd)[:cexp], dp['shift'][1](wd)[:cexp]
-                o[kk + 2, :cexp], o[kk + 3, :cexp] = ep['scale'][1](wd)[:cexp], ep['shift'][1](wd)[:cexp]
-                return o
-
-            def project_wt(wd, pp=pp, cexp=cexp, cexp_p=cexp_p, cout=cout):
-                o = np.zeros((cout, cexp_p), np.float32)
-                o[:, :cexp] = pp['wgt'][1](wd)[:, :cexp]
-                return o
-
-            def project_bn(wd, pp=pp, cout=cout, ldo=ldo):
-                o = np.zeros((2, ldo), np.float32)
-                o[0, :cout], o[1, :cout] = pp['scale'][1](wd)[:cout], pp['shift'][1](wd)[:cout]
-                return o.ravel()
-            m.params = {'wgt': ((cexp_p, kp), expand_wt, dtype), 'wgt2': ((kk + 4, cexp_p), chunk_params),
-                        'b1': ((cout, cexp_p), project_wt, dtype), 'b2': ((2 * ldo,), project_bn)}
-            out.append(m)
-            i = j + 2
-            continue
-        if (d is not None and d.kind == rt.OP_DEPTHWISE and d.k == 3 and plain1(d) and private(d.out)
-                and (exp is None or (d.srcs[0].buf is exp.out and d.act == exp.act)) and d.act in ('relu6', 'swish')
-                and d.srcs[0].buf.ld == round_up(d.cin, rt.VEC[dtype]) and j + 1 < len(ops)):
-            p = ops[j + 1]
-            block_in = exp.srcs[0] if exp is not None else d.srcs[0]
-            lane = lane_ok(exp, block_in, p, d)
-            if (lane and p.kind == rt.OP_POINTWISE and plain1(p) and p.srcs[0].buf is d.out and p.act == 'none'
-                    and 'scale' in p.params and p.cout <= 224 and block_in.buf.ld % 4 == 0
-                    and (exp is not None or FUSE_NO_EXPAND or lane) and block_in.c <= max_cin
-                    and p.h * p.w >= (FUSE_LANE_MIN_PIXELS if lane else FUSE_MIN_PIXELS)
-                    and (p.res is None or (p.res is block_in.buf and d.stride == 1 and p.cout == block_in.c))):
-                dw, proj = d, p
-        if proj is None:
-            out.append(e)
-            i += 1
-            continue
-        block_in = exp.srcs[0] if exp is not None else dw.srcs[0]
-        cexp, cout = dw.cin, proj.cout
-        lde, ldo = round_up(cexp, 4), round_up(cout, 4)
-        m = OpRec(rt.OP_MBLANE, (exp or dw).name.rsplit('_', 1)[0] + '_mblane', act=dw.act, h=proj.h, w=proj.w,
-                  cin=block_in.c, cout=cout, k=3, stride=dw.stride, se_reduced=cexp, srcs=[block_in], out=proj.out,
-                  res=proj.res, macs=(exp.macs if exp else 0) + dw.macs + proj.macs, dtype=dtype)
-        m.fused = [o for o in (exp, dw, proj) if o is not None]
-
-        def padded(fn, n, ld):
-            def f(wd):
-                o = np.zeros(ld, np.float32)
-                o[:n] = fn(wd)[:n]
-                return o
-            return f
-        cinp, cop = round_up(block_in.c, 4), round_up(cout, 8)
-        if lane_ok(exp, block_in, proj, dw):
-            # lane-per-pixel formulation (mblane.hip): everything packed per expanded-channel pair
-            npair = round_up((cexp + 1) // 2, 8)
-            e2 = 2 * npair
-
-            def pairs(rows, scale, shift, e2=e2, cexp=cexp):
-                """rows [K][>=cexp] + BN [>=cexp]  ->  [P][K x 2, times the BN scale | 1 1 | shift 2]  (the kernels add
-                the shift to the sum of products; the scale slot stays in the layout)"""
-                full = np.zeros((rows.shape[0] + 2, e2), np.float32)
-                full[:-2, :cexp] = (rows[:, :cexp] * scale[None, :cexp]).astype(np.float32)
-                full[-2, :cexp], full[-1, :cexp] = 1.0, shift[:cexp]
-                return np.ascontiguousarray(full.reshape(-1, e2 // 2, 2).transpose(1, 0, 2)).reshape(e2 // 2, -1)
-            ep, dwp, pp_ = (exp.params if exp is not None else None), dw.params, proj.params
-
-            def expand_w(wd, ep=ep, cinp=cinp, pairs=pairs):
-                wt = ep['wgt'][1](wd)                      # pointwise layout Wt[cexp][kp]
-                rows = np.zeros((cinp, wt.shape[0]), np.float32)
-                rows[:wt.shape[1]] = wt.T[:cinp]
-                return pairs(rows, ep['scale'][1](wd), ep['shift'][1](wd))
-
-            def proj_w(wd, pp_=pp_, e2=e2, cop=cop, cout=cout, cexp=cexp):
-                o = np.zeros((e2, cop), np.float32)
-                o[:cexp, :cout] = pp_['wgt'][1](wd)[:, :cexp].T
-                return o
-            if exp is not None:          # (without expand conv the op has no `wgt`: the kernel copies the input pairs)
-                m.params['wgt'] = ((npair, cinp * 2 + 4), expand_w)
-            m.params['wgt2'] = ((npair, 22), lambda wd, dwp=dwp, pairs=pairs: pairs(dwp['wgt'][1](wd), dwp['scale'][1](wd), dwp['shift'][1](wd)))
-            m.params['b1'] = ((e2, cop), proj_w)
-            m.params['b2'] = ((2 * cop,), lambda wd, pp_=pp_, cout=cout, cop=cop: np.concatenate(
-                [padded(pp_['scale'][1], cout, cop)(wd), padded(pp_['shift'][1], cout, cop)(wd)]))
-            out.append(m)
-            i = j + 2
-            continue
-        raise AssertionError('a fused float32 block that the lane-per-pixel kernel does not take (mbconv.hip was removed)')
+        hit = match_stem_block0(ops, i, cx)             # stem + block 0: float32-pipe form | matrix-pipe form (16-bit plans)
+        if hit is None and blocks:
+            blk = Block(ops, i, cx)
+            hit = (match_stem_depthwise(ops, i, cx)     # stem + depthwise with squeeze-excite sums
+                   or match_mbr_stream(ops, blk, cx)    # mbr, weight-streaming (mbk.hip)
+                   or match_mbr(ops, blk, cx)           # mbr, split | plain
+                   or match_mbe(ops, blk, cx)           # mbe, split | plain
+                   or match_mbh(ops, blk, cx)           # mbh (its own mbn kernel, else mblane, takes the narrow stride-2 first block)
+                   or match_mbx(ops, blk, cx)           # mbx
+                   or match_mblane(ops, blk, cx))       # mblane, with | without expand conv
+        m, n = hit or (ops[i], 1)
+        out.append(m)
+        i += n
     return out
 
 
