@@ -490,6 +490,25 @@ int yr_pack_detections(const float* boxes, const float* scores, const int32_t* n
                        const int32_t* nms_count, int batch, int n, int num_classes, int max_boxes,
                        int32_t* det, int32_t* det_count, void* stream);
 
+/* ---- YoloLoss.call, GIOU branch (model.py:607-671, with yolo_head(calc_loss=True) :344-369 and do_giou_calculate,
+ * utils.py:9-53) for ONE scale, forward only; added under ABI 9 (additive: no struct or existing entry changed).
+ *   feats     [B,gh,gw,A,5+C] raw logits, dense float32;  y_true: same shape, the rows preprocess_true_boxes
+ *             (utils.py:298-376) writes: (x, y, w, h) relative to the input, object flag, class bits
+ *   anchors   host, the A x (w,h) anchors of THIS scale (model.py:605);  in_h, in_w = grid * grid_step (:628)
+ *   out5      device float32 {loss, giou_loss, confidence_loss, class_loss, ignore_sum}: the three sums divided by B
+ *             (:662-668), their total, and sum(ignore_mask) over every cell (:671)
+ * As in the reference, the labelled boxes are gathered over the WHOLE batch (:643): a prediction of one image is
+ * compared with the labelled boxes of every image of the call; with no labelled box at all every cell is ignored.
+ * Per-element arithmetic is float32 in the reference's order; the sums are float64 in a fixed order, rounded once:
+ * the same call gives the same bits.  Non-finite logits are outside the contract.  Three launches on `stream`, no
+ * host synchronisation.  `workspace`: device memory, 16-byte aligned, at least the number of bytes the first
+ * entry returns (0 for bad sizes); its contents before the call do not matter. */
+size_t yr_yolo_loss_workspace_bytes(int batch, int gh, int gw, int num_anchors);
+int yr_yolo_loss(const float* feats, const float* y_true, int batch, int gh, int gw, int num_anchors,
+                 int num_classes, const float* anchors_host /*A x (w,h)*/, int in_h, int in_w,
+                 float ignore_thresh, void* workspace, size_t workspace_bytes,
+                 float* out5 /*device*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,250 @@
+// YoloLoss forward, GIOU branch, for ONE scale.  Replaces the TF graph behind reference code/yolo3/model.py: YoloLoss.call
+// :607-671 with yolo_head(calc_loss=True) :344-369 and do_giou_calculate (code/yolo3/utils.py:9-53).  Forward only: no gradients.
+//
+// What is reproduced, quirks included:
+//   * masked_true_box (:643) is gathered over the WHOLE batch of the call: a prediction of image 0 is compared with the labelled
+//     boxes of every image.  That is what the reference computes, so that is what is computed here.
+//   * with no labelled box in the call, the maximum over the empty set is below every threshold: every cell is ignored (:648-649).
+//   * the true boxes are clipped to [0,1] (:640), the predicted ones are not.
+// Per-element arithmetic is float32 in the reference's operation order with no FMA contraction (library built with
+// -ffp-contract=off); exp through yr_expf and sigmoid through yr_sigmoid, so pred_xy / pred_wh are bit-identical to what
+// yolo_head_kernel (postprocess.hip) writes; log1p is the device library's float32 log1pf.  The sums are float64 in a FIXED order
+// (lane -> wave butterfly -> waves in index order -> one row per workgroup -> rows in a fixed order) and rounded to float32 once:
+// no float atomics and no in-launch hand-off between workgroups, so a call is bit-reproducible whatever the arrival order.
+// Non-finite logits or labels are outside the contract (a NaN would make the maximum depend on the order of the box list).
+//
+// Three launches on the caller's stream, no host round trip:
+//   1. loss_compact_kernel  appends the clipped box of every object cell (y_true[..., 4] != 0) to a list in the workspace;
+//   2. loss_main_kernel     one lane per prediction: decode, best IoU over the list (LDS-resident chunks), the lane's terms;
+//   3. loss_final_kernel    sums the workgroup rows, divides by B, writes {loss, giou, conf, class, ignore_sum}.
+// Workspace: [0,256) header (word 0: the number of listed boxes), then the list (float4 per box, room for every cell), then one
+// LossRow per workgroup of the main pass.  Nothing in it is read before this call has written it.
+#include "yr_common.h"
+
+#define LOSS_T 256          // lanes per workgroup = boxes per LDS chunk
+#define LOSS_HEADER 256     // bytes in front of the box list
+
+struct LossRow {
+    double giou, conf, cls;
+    long long ignore;
+};
+
+struct LossArgs {
+    const float* feats;     // [B,gh,gw,A,5+C] logits
+    const float* y_true;    // same shape: (x, y, w, h, object, class bits)
+    float anchors[8][2];
+    int gh, gw, A, C, in_h, in_w, batch;
+    int total;              // B*gh*gw*A
+    float ignore_thresh;
+    unsigned* count;        // listed boxes
+    float4* list;           // (y_min, x_min, y_max, x_max), clipped
+    LossRow* rows;
+    int nrows;
+    float* out5;
+};
+
+// model.py:631-633 / :637-639: (y_min, x_min, y_max, x_max) from centre and size
+__device__ __forceinline__ float4 loss_box(float x, float y, float w, float h) {
+    const float hw = w / 2.0f, hh = h / 2.0f;
+    return make_float4(y - hh, x - hw, y + hh, x + hw);
+}
+
+// tf.clip_by_value(v, 0, 1)
+__device__ __forceinline__ float loss_clip01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
+
+// utils.py:24-29
+__device__ __forceinline__ float loss_area(float4 b) { return fmaxf(0.0f, b.w - b.y) * fmaxf(0.0f, b.z - b.x); }
+
+// tf.math.divide_no_nan: a zero denominator gives 0
+__device__ __forceinline__ float loss_div_no_nan(float a, float b) { return b == 0.0f ? 0.0f : a / b; }
+
+// tf.nn.sigmoid_cross_entropy_with_logits(labels=z, logits=x) = (max(x,0) - x*z) + log1p(exp(-|x|))
+__device__ __forceinline__ float loss_sce(float z, float x) { return (fmaxf(x, 0.0f) - x * z) + log1pf(yr_expf(-fabsf(x))); }
+
+__global__ __launch_bounds__(LOSS_T) void loss_compact_kernel(LossArgs a) {
+    const int gid = (int)blockIdx.x * LOSS_T + (int)threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const float* t = a.y_true + (size_t)min(gid, a.total - 1) * (a.C + 5);
+    const bool obj = gid < a.total && t[4] != 0.0f;
+    const unsigned long long mask = __ballot(obj);
+    if (!mask) return;   // wave-uniform
+    // One atomic per wave.  The list's order is arrival order, which is harmless BECAUSE THE ONLY THING COMPUTED FROM THE LIST IS A
+    // MAXIMUM (best_iou, :648): a maximum of finite floats does not depend on the order of its operands.
+    unsigned base = 0;
+    if (lane == 0) base = atomicAdd(a.count, (unsigned)__popcll(mask));
+    base = __shfl(base, 0);
+    if (obj) {
+        float4 b = loss_box(t[0], t[1], t[2], t[3]);
+        b = make_float4(loss_clip01(b.x), loss_clip01(b.y), loss_clip01(b.z), loss_clip01(b.w));   // :640
+        a.list[base + (unsigned)__popcll(mask & ((1ull << lane) - 1ull))] = b;   // < total: at most one entry per cell
+    }
+}
+
+__global__ __launch_bounds__(LOSS_T) void loss_main_kernel(LossArgs a) {
+    __shared__ float4 sbox[LOSS_T];
+    __shared__ float sarea[LOSS_T];
+    __shared__ LossRow swave[LOSS_T / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int gid = (int)blockIdx.x * LOSS_T + tid;
+    const bool valid = gid < a.total;
+    const int row = a.C + 5;
+    const size_t off = (size_t)min(gid, a.total - 1) * row;
+    const float* t = a.feats + off;
+    const float* yt = a.y_true + off;
+    const int an = gid % a.A;
+    const int cell = gid / a.A;
+    const int w = cell % a.gw, h = (cell / a.gw) % a.gh;
+    // yolo_head (model.py:363-366), the expressions of yolo_head_kernel
+    const float px = (yr_sigmoid(t[0]) + (float)w) / (float)a.gw;
+    const float py = (yr_sigmoid(t[1]) + (float)h) / (float)a.gh;
+    const float pw = yr_expf(t[2]) * a.anchors[an][0] / (float)a.in_w;
+    const float ph = yr_expf(t[3]) * a.anchors[an][1] / (float)a.in_h;
+    const float4 pb = loss_box(px, py, pw, ph);
+    const float parea = loss_area(pb);
+
+    // best_iou (:644-648) over the listed boxes of the whole call.  A chunk of the list sits in LDS; every lane reads the same
+    // address (a broadcast).  The maximum over an empty list is -inf: every cell is then ignored.
+    const unsigned n = *a.count;
+    float best = -__builtin_inff();
+    for (unsigned c0 = 0; c0 < n; c0 += LOSS_T) {
+        __syncthreads();
+        if (c0 + tid < n) {
+            const float4 b = a.list[c0 + tid];
+            sbox[tid] = b;
+            sarea[tid] = loss_area(b);
+        }
+        __syncthreads();
+        const int m = (int)min((unsigned)LOSS_T, n - c0);
+        for (int k = 0; k < m; ++k) {
+            const float4 tb = sbox[k];
+            // utils.py:31-40
+            const float iw = fmaxf(0.0f, fminf(pb.w, tb.w) - fmaxf(pb.y, tb.y));
+            const float ih = fmaxf(0.0f, fminf(pb.z, tb.z) - fmaxf(pb.x, tb.x));
+            const float inter = iw * ih;
+            // a zero intersection gives 0 / union = 0, or 0 by divide_no_nan: the division is only needed where boxes meet
+            float iou = 0.0f;
+            if (inter > 0.0f) iou = loss_div_no_nan(inter, parea + sarea[k] - inter);
+            best = fmaxf(best, iou);
+        }
+    }
+    const float ignore = best < a.ignore_thresh ? 1.0f : 0.0f;   // :649, strict
+
+    double giou_t = 0.0, conf_t = 0.0, cls_t = 0.0;
+    long long ign_t = 0;
+    if (valid) {
+        const float om = yt[4];
+        const float ce = loss_sce(om, t[4]);
+        conf_t = (double)(om * ce + (1.0f - om) * ce * ignore);   // :653-657
+        ign_t = best < a.ignore_thresh ? 1 : 0;                   // :671 counts object cells too
+        if (om != 0.0f) {   // other cells contribute exactly 0 to the class and GIoU terms
+            for (int c = 0; c < a.C; ++c) cls_t += (double)(om * loss_sce(yt[5 + c], t[5 + c]));   // :658-659
+            float4 tb = loss_box(yt[0], yt[1], yt[2], yt[3]);
+            tb = make_float4(loss_clip01(tb.x), loss_clip01(tb.y), loss_clip01(tb.z), loss_clip01(tb.w));
+            // utils.py:24-53 with b1 = pred_box, b2 = true_box
+            const float tarea = loss_area(tb);
+            const float iw = fmaxf(0.0f, fminf(pb.w, tb.w) - fmaxf(pb.y, tb.y));
+            const float ih = fmaxf(0.0f, fminf(pb.z, tb.z) - fmaxf(pb.x, tb.x));
+            const float inter = iw * ih;
+            const float uni = parea + tarea - inter;
+            const float iou = loss_div_no_nan(inter, uni);
+            const float ew = fmaxf(0.0f, fmaxf(pb.w, tb.w) - fminf(pb.y, tb.y));
+            const float eh = fmaxf(0.0f, fmaxf(pb.z, tb.z) - fminf(pb.x, tb.x));
+            const float earea = ew * eh;
+            const float giou = iou - loss_div_no_nan(earea - uni, earea);
+            giou_t = (double)(om * (1.0f - giou));   // :667
+        }
+    }
+    // wave butterfly, then the waves in index order: a fixed order
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        giou_t += __shfl_xor(giou_t, o);
+        conf_t += __shfl_xor(conf_t, o);
+        cls_t += __shfl_xor(cls_t, o);
+        ign_t += __shfl_xor(ign_t, o);
+    }
+    if (lane == 0) { swave[wave].giou = giou_t; swave[wave].conf = conf_t; swave[wave].cls = cls_t; swave[wave].ignore = ign_t; }
+    __syncthreads();
+    if (tid == 0) {
+        LossRow r = swave[0];
+        for (int k = 1; k < LOSS_T / 64; ++k) { r.giou += swave[k].giou; r.conf += swave[k].conf; r.cls += swave[k].cls; r.ignore += swave[k].ignore; }
+        a.rows[blockIdx.x] = r;
+    }
+}
+
+// One workgroup.  Lane i adds rows i, i+256, ... in ascending order, then the same fixed tree as above; divide by B (:662-668),
+// round once to float32.  `loss` is rounded from the float64 sum of the three terms, not from their float32 values.
+__global__ __launch_bounds__(LOSS_T) void loss_final_kernel(LossArgs a) {
+    __shared__ LossRow swave[LOSS_T / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double g = 0.0, c = 0.0, k = 0.0;
+    long long ig = 0;
+    for (int r = tid; r < a.nrows; r += LOSS_T) {
+        const LossRow v = a.rows[r];
+        g += v.giou; c += v.conf; k += v.cls; ig += v.ignore;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        g += __shfl_xor(g, o);
+        c += __shfl_xor(c, o);
+        k += __shfl_xor(k, o);
+        ig += __shfl_xor(ig, o);
+    }
+    if (lane == 0) { swave[wave].giou = g; swave[wave].conf = c; swave[wave].cls = k; swave[wave].ignore = ig; }
+    __syncthreads();
+    if (tid == 0) {
+        LossRow r = swave[0];
+        for (int i = 1; i < LOSS_T / 64; ++i) { r.giou += swave[i].giou; r.conf += swave[i].conf; r.cls += swave[i].cls; r.ignore += swave[i].ignore; }
+        const double mf = (double)a.batch;
+        const double gl = r.giou / mf, cl = r.conf / mf, kl = r.cls / mf;
+        a.out5[0] = (float)(gl + cl + kl);
+        a.out5[1] = (float)gl;
+        a.out5[2] = (float)cl;
+        a.out5[3] = (float)kl;
+        a.out5[4] = (float)r.ignore;
+    }
+}
+
+static inline size_t loss_rows_offset(long long total) { return LOSS_HEADER + (size_t)total * sizeof(float4); }
+
+extern "C" size_t yr_yolo_loss_workspace_bytes(int batch, int gh, int gw, int num_anchors) {
+    if (batch <= 0 || gh <= 0 || gw <= 0 || num_anchors <= 0) return 0;
+    const long long total = (long long)batch * gh * gw * num_anchors;
+    return loss_rows_offset(total) + (size_t)((total + LOSS_T - 1) / LOSS_T) * sizeof(LossRow);
+}
+
+extern "C" int yr_yolo_loss(const float* feats, const float* y_true, int batch, int gh, int gw, int num_anchors,
+                            int num_classes, const float* anchors_host, int in_h, int in_w, float ignore_thresh,
+                            void* workspace, size_t workspace_bytes, float* out5, void* stream) {
+    YR_REQUIRE(feats && y_true && anchors_host && workspace && out5, "yolo_loss: null pointer");
+    YR_REQUIRE(num_anchors >= 1 && num_anchors <= 8, "yolo_loss: num_anchors must be 1..8");
+    YR_REQUIRE(batch > 0 && gh > 0 && gw > 0 && num_classes >= 0 && in_h > 0 && in_w > 0, "yolo_loss: bad sizes");
+    const long long total = (long long)batch * gh * gw * num_anchors;
+    YR_REQUIRE(total * (num_classes + 5) < (1ll << 31), "yolo_loss: more than 2^31 logits");
+    const size_t need = yr_yolo_loss_workspace_bytes(batch, gh, gw, num_anchors);
+    YR_REQUIRE(workspace_bytes >= need, "yolo_loss: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    YR_REQUIRE(((uintptr_t)workspace) % 16 == 0, "yolo_loss: workspace not 16-byte aligned");
+    LossArgs a;
+    a.feats = feats; a.y_true = y_true;
+    for (int k = 0; k < 8; ++k) {
+        a.anchors[k][0] = k < num_anchors ? anchors_host[k * 2] : 0.0f;
+        a.anchors[k][1] = k < num_anchors ? anchors_host[k * 2 + 1] : 0.0f;
+    }
+    a.gh = gh; a.gw = gw; a.A = num_anchors; a.C = num_classes; a.in_h = in_h; a.in_w = in_w; a.batch = batch;
+    a.total = (int)total;
+    a.ignore_thresh = ignore_thresh;
+    char* ws = (char*)workspace;
+    a.count = (unsigned*)ws;
+    a.list = (float4*)(ws + LOSS_HEADER);
+    a.rows = (LossRow*)(ws + loss_rows_offset(total));
+    a.nrows = (int)((total + LOSS_T - 1) / LOSS_T);
+    a.out5 = out5;
+    hipStream_t s = (hipStream_t)stream;
+    YR_CHECK_HIP(hipMemsetAsync(a.count, 0, sizeof(unsigned), s));
+    hipLaunchKernelGGL(loss_compact_kernel, dim3(a.nrows), dim3(LOSS_T), 0, s, a);
+    YR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(loss_main_kernel, dim3(a.nrows), dim3(LOSS_T), 0, s, a);
+    YR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(LOSS_T), 0, s, a);
+    YR_LAUNCH_CHECK();
+    return YR_OK;
+}

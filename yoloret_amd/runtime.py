@@ -106,7 +106,7 @@ class YrBuf(ctypes.Structure):
 ABI_VERSION = 9   # == YR_ABI_VERSION of include/yoloret_hip.h
 EXPORTS = ['yr_last_error', 'yr_abi_version', 'yr_abi_sizeof', 'yr_create', 'yr_create_from_blob', 'yr_plan_io_dims', 'yr_destroy', 'yr_load_weights', 'yr_workspace_bytes',
            'yr_forward', 'yr_forward_profile', 'yr_forward_ranges', 'yr_autotune', 'yr_get_tuning', 'yr_set_tuning', 'yr_plan_num_launches', 'yr_op_run', 'yr_head_regions', 'yr_head_walk_rows', 'yr_head_stream_rows', 'yr_pwt_chunks', 'yr_decode', 'yr_decode_zoom', 'yr_yolo_head', 'yr_correct_boxes',
-           'yr_nms', 'yr_pack_detections', 'yr_letterbox', 'yr_letterbox_batch']
+           'yr_nms', 'yr_pack_detections', 'yr_letterbox', 'yr_letterbox_batch', 'yr_yolo_loss_workspace_bytes', 'yr_yolo_loss']
 
 _lib = None
 
@@ -163,6 +163,11 @@ def lib():
                                    ctypes.c_int, ctypes.c_void_p]
         L.yr_letterbox_batch.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                          ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+        L.yr_yolo_loss_workspace_bytes.restype = ctypes.c_size_t
+        L.yr_yolo_loss_workspace_bytes.argtypes = [ctypes.c_int] * 4
+        L.yr_yolo_loss.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                                                            ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t,
+                                                                                            ctypes.c_void_p, ctypes.c_void_p]
         if L.yr_abi_version() != ABI_VERSION:
             raise YoloretHipError('libyoloret_hip.so ABI version mismatch')
         L.yr_abi_sizeof.argtypes = [ctypes.c_int]
@@ -340,6 +345,41 @@ def yolo_head(feats, anchors, input_hw, with_scores=False):
                                  int(input_hw[0]), int(input_hw[1]), _ptr(xy), _ptr(wh), _ptr(conf), _ptr(probs),
                                  _ptr(scores), stream_ptr(dev)))
     return (xy, wh, conf, probs, scores) if with_scores else (xy, wh, conf, probs)
+
+
+def yolo_loss_workspace_bytes(batch, gh, gw, num_anchors):
+    return int(lib().yr_yolo_loss_workspace_bytes(int(batch), int(gh), int(gw), int(num_anchors)))
+
+
+def yolo_loss(feats, y_true, anchors, input_hw, ignore_thresh=.5, workspace=None):
+    """YoloLoss.call, GIOU branch (model.py:607-671) for one scale.  feats, y_true [B,gh,gw,A,5+C] float32 on one device,
+    anchors: the A (w,h) anchors of this scale -> float32 [5] on that device: loss, giou_loss, confidence_loss, class_loss,
+    ignore_sum.  Launches only; nothing is copied to the host.  workspace: a uint8 tensor of at least
+    yolo_loss_workspace_bytes(B, gh, gw, A) bytes on that device to work in (its contents do not matter); default: a fresh one."""
+    _require_cuda_f32(feats, 'feats')
+    _require_cuda_f32(y_true, 'y_true')
+    if feats.dim() != 5 or feats.shape[-1] < 5 or feats.numel() == 0:
+        raise ValueError('yolo_loss: feats has shape %s, expected [B,gh,gw,A,5+C]' % (tuple(feats.shape),))
+    if y_true.shape != feats.shape or y_true.device != feats.device:
+        raise ValueError('yolo_loss: y_true %s on %s, expected the logits\' %s on %s'
+                         % (tuple(y_true.shape), y_true.device, tuple(feats.shape), feats.device))
+    b, gh, gw, a, ch = feats.shape
+    anchors = np.ascontiguousarray(np.asarray(anchors, np.float32).reshape(-1, 2))
+    if anchors.shape[0] != a:
+        raise ValueError('yolo_loss: %d anchors for %d anchor slots' % (anchors.shape[0], a))
+    if not 1 <= a <= 8:
+        raise ValueError('yolo_loss: 1..8 anchor slots per cell, not %d' % a)
+    dev = feats.device
+    out = torch.empty((5,), dtype=torch.float32, device=dev)
+    need = yolo_loss_workspace_bytes(b, gh, gw, a)
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev) if workspace is None else workspace
+    if not (isinstance(ws, torch.Tensor) and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.device == dev and ws.numel() >= need):
+        raise ValueError('yolo_loss: workspace must be a contiguous uint8 tensor of at least %d bytes on %s' % (need, dev))
+    with torch.cuda.device(dev):
+        check(lib().yr_yolo_loss(_ptr(feats), _ptr(y_true), b, gh, gw, a, ch - 5, anchors.ctypes.data_as(ctypes.c_void_p),
+                                 int(input_hw[0]), int(input_hw[1]), float(ignore_thresh), _ptr(ws), ws.numel(), _ptr(out),
+                                 stream_ptr(dev)))
+    return out
 
 
 def correct_boxes(box_xy, box_wh, input_hw, image_hw):

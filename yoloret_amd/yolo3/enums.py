@@ -1,4 +1,4 @@
-"""Backbone names (reference code/yolo3/enums.py:25-28)."""
+"""Backbone names (reference code/yolo3/enums.py:25-28) and box-loss kinds (:32-34)."""
 from enum import Enum, unique
 
 
@@ -7,3 +7,9 @@ class BACKBONE(Enum):
     MOBILENETV2x75 = 0
     MOBILENETV2x14 = 1
     EFFICIENTNETB3 = 2
+
+
+@unique
+class BOX_LOSS(Enum):
+    MSE = 0
+    GIOU = 1

@@ -11,6 +11,7 @@ Graph builders (record a ``yoloret_amd.layers`` graph, lowered by ``yoloret_amd.
   rfcr_module :146-168, yolov3_body :170-342.
 Post-processing (launch HIP kernels): yolo_head :344-371, yolo_correct_boxes :374-399,
   yolo_boxes_and_scores :402-428, yolo_eval :431-491, YoloEval :494-526.
+Loss forward (validation loss from device logits; no gradients): YoloLoss :585-691 (GIOU branch), yolo_loss.
 
 Batch semantics: the reference folds the batch axis into the box list before NMS
 (:425-427) and pins inference to batch 1 (yolo.py:84).  Here a batch means "the
@@ -25,6 +26,7 @@ from .. import runtime as rt
 from ..engine import Model
 from ..layers import WeightedSum  # model.py:117-137
 from . import efficientnet as _effnet
+from .enums import BOX_LOSS
 from .efficientnet import BlockArgs, EfficientNetB0, EfficientNetB3, MBConvBlock, get_model_params
 from .override import mobilenet_v2
 from .utils import compose
@@ -173,10 +175,16 @@ def _hw(shape):
 
 def yolo_head(feats, anchors, input_shape, calc_loss=False):
     """Convert final layer features to bounding box parameters (model.py:344-371).
-    feats [B,G,G,A,C+5] CUDA f32; returns (box_xy, box_wh, box_confidence, box_class_probs)."""
+    feats [B,G,G,A,C+5] CUDA f32; returns (box_xy, box_wh, box_confidence, box_class_probs), or with calc_loss
+    (grid, box_xy, box_wh, box_confidence) (:368-369): grid [gh,gw,1,2] float32 holds (x, y) of each cell."""
+    box_xy, box_wh, box_confidence, box_class_probs = rt.yolo_head(feats.contiguous(), anchors, _hw(input_shape))
     if calc_loss:
-        raise NotImplementedError('calc_loss=True is the training path (out of scope)')
-    return rt.yolo_head(feats.contiguous(), anchors, _hw(input_shape))
+        gh, gw = feats.shape[1:3]
+        grid = torch.empty((gh, gw, 1, 2), dtype=torch.float32, device=feats.device)   # :355-360, indices only
+        grid[..., 0] = torch.arange(gw, dtype=torch.float32, device=feats.device).reshape(1, gw, 1)
+        grid[..., 1] = torch.arange(gh, dtype=torch.float32, device=feats.device).reshape(gh, 1, 1)
+        return grid, box_xy, box_wh, box_confidence
+    return box_xy, box_wh, box_confidence, box_class_probs
 
 
 def yolo_correct_boxes(box_xy, box_wh, input_shape, image_shape):
@@ -268,3 +276,66 @@ class YoloEval:
         return {'name': self.name, 'anchors': self.anchors, 'num_scales': self.num_scales,
                 'num_classes': self.num_classes, 'max_boxes': self.max_boxes,
                 'score_threshold': self.score_threshold, 'iou_threshold': self.iou_threshold}
+
+
+# ----------------------------------------------------------------------------- loss forward
+class YoloLoss:
+    """The loss of one output scale (model.py:585-691), forward only: the GIoU / confidence / class sums of the GIOU
+    branch (:623-671) from the logits on the device, in one call of the HIP kernels behind ``yr_yolo_loss``.
+
+    ``call(y_true, yolo_output)``: both [B,gh,gw,A,5+C] float32 CUDA tensors (``y_true`` as ``preprocess_true_boxes``
+    writes it; a NumPy array is copied to the logits' device) -> the 0-d float32 device tensor ``loss``.
+    ``last_terms`` keeps the device tensor [5] = (loss, giou_loss, confidence_loss, class_loss, ignore_sum) of the last
+    call.  As in the reference, the labelled boxes a prediction is compared with are those of the whole batch (:643).
+    ``print_loss`` prints the reference's line "<idx>: giou conf class ignore_sum" (:671); reading the four numbers
+    SYNCHRONISES with the device, so pass ``print_loss=False`` where the loss is evaluated inside a pipeline.
+    ``box_loss=BOX_LOSS.MSE`` raises NotImplementedError: the reference's MSE branch reads names that do not exist
+    in its scope (:676, :688) and cannot run there either."""
+
+    def __init__(self, idx, anchors, num_scales, ignore_thresh=.5, box_loss=BOX_LOSS.GIOU, print_loss=True):
+        if box_loss != BOX_LOSS.GIOU:
+            raise NotImplementedError('box_loss=%r: only BOX_LOSS.GIOU runs (the reference\'s MSE branch does not either)' % (box_loss,))
+        grid_steps = [32, 16, 8]
+        anchor_masks = [[6, 7, 8], [3, 4, 5], [0, 1, 2]][-1 * num_scales:]     # :597-598
+        self.idx = idx
+        self.ignore_thresh = ignore_thresh
+        self.box_loss = box_loss
+        self.print_loss = print_loss
+        self.grid_step = grid_steps[self.idx]
+        self.anchor = np.asarray(anchors, np.float32).reshape(-1, 2)[anchor_masks[idx]]
+        self.last_terms = None
+
+    def call(self, y_true, yolo_output):
+        if not isinstance(yolo_output, torch.Tensor):
+            raise ValueError('yolo_output must be a CUDA tensor (the logits of yolov3_body)')
+        if not isinstance(y_true, torch.Tensor):
+            y_true = torch.as_tensor(np.ascontiguousarray(y_true, np.float32), device=yolo_output.device)
+        if yolo_output.dim() == 4 and yolo_output.shape[3] % len(self.anchor) == 0:    # [B,gh,gw,A*(5+C)], as a serialised plan emits it
+            yolo_output = yolo_output.reshape(tuple(yolo_output.shape[:3]) + (len(self.anchor), -1))
+        if yolo_output.dim() != 5:
+            raise ValueError('yolo_output has shape %s, expected [B,gh,gw,A,5+C]' % (tuple(yolo_output.shape),))
+        if y_true.dim() == 4 and y_true.numel() == yolo_output.numel():
+            y_true = y_true.reshape(yolo_output.shape)
+        input_hw = (yolo_output.shape[1] * self.grid_step, yolo_output.shape[2] * self.grid_step)   # :628
+        terms = rt.yolo_loss(yolo_output.contiguous(), y_true.contiguous(), self.anchor, input_hw, self.ignore_thresh)
+        self.last_terms = terms
+        if self.print_loss:
+            t = terms.tolist()   # (synchronises)
+            print('%d: %s %s %s %s' % ((self.idx,) + tuple(str(np.float32(v)) for v in t[1:])))
+        return terms[0]
+
+    __call__ = call
+
+
+def yolo_loss(yolo_outputs, y_trues, anchors, num_scales, ignore_thresh=.5):
+    """The sum the reference forms over its list of per-scale losses: -> (total 0-d float32 device tensor,
+    terms [num_scales,5] device tensor, one row of (loss, giou, conf, class, ignore_sum) per scale)."""
+    if len(yolo_outputs) < num_scales or len(y_trues) < num_scales:
+        raise ValueError('yolo_loss: %d logit tensors and %d label tensors for %d scales' % (len(yolo_outputs), len(y_trues), num_scales))
+    rows = []
+    for idx in range(num_scales):
+        layer = YoloLoss(idx, anchors, num_scales, ignore_thresh, BOX_LOSS.GIOU, print_loss=False)
+        layer(y_trues[idx], yolo_outputs[idx])
+        rows.append(layer.last_terms)
+    terms = torch.stack(rows)
+    return terms[:, 0].sum(), terms

@@ -39,3 +39,78 @@ def get_classes(classes_path):
     with open(_resolve(classes_path)) as f:
         class_names = f.readlines()
     return [c.strip() for c in class_names]
+
+
+def _divide_no_nan(a, b):
+    """tf.math.divide_no_nan: 0 where the denominator is 0."""
+    a, b = np.broadcast_arrays(a, b)
+    out = np.zeros(a.shape, a.dtype)
+    np.divide(a, b, out=out, where=b != 0)
+    return out
+
+
+def do_giou_calculate(b1, b2, mode='giou'):
+    """IoU / GIoU of boxes (y_min, x_min, y_max, x_max) on the last axis, broadcasting over the others (utils.py:9-53).
+    Host NumPy in the dtype of ``b1`` - the label encoding below uses it; the loss itself runs in the HIP kernels."""
+    b1 = np.asarray(b1)
+    b2 = np.asarray(b2, b1.dtype)
+    zero = b1.dtype.type(0)
+    b1_ymin, b1_xmin, b1_ymax, b1_xmax = (b1[..., i] for i in range(4))
+    b2_ymin, b2_xmin, b2_ymax, b2_xmax = (b2[..., i] for i in range(4))
+    b1_area = np.maximum(zero, b1_xmax - b1_xmin) * np.maximum(zero, b1_ymax - b1_ymin)
+    b2_area = np.maximum(zero, b2_xmax - b2_xmin) * np.maximum(zero, b2_ymax - b2_ymin)
+    intersect_width = np.maximum(zero, np.minimum(b1_xmax, b2_xmax) - np.maximum(b1_xmin, b2_xmin))
+    intersect_height = np.maximum(zero, np.minimum(b1_ymax, b2_ymax) - np.maximum(b1_ymin, b2_ymin))
+    intersect_area = intersect_width * intersect_height
+    union_area = b1_area + b2_area - intersect_area
+    iou = _divide_no_nan(intersect_area, union_area)
+    if mode == 'iou':
+        return iou
+    enclose_width = np.maximum(zero, np.maximum(b1_xmax, b2_xmax) - np.minimum(b1_xmin, b2_xmin))
+    enclose_height = np.maximum(zero, np.maximum(b1_ymax, b2_ymax) - np.minimum(b1_ymin, b2_ymin))
+    enclose_area = enclose_width * enclose_height
+    return iou - _divide_no_nan(enclose_area - union_area, enclose_area)
+
+
+def preprocess_true_boxes(true_boxes, input_shape, anchors, num_classes, num_scales):
+    """Labelled boxes of ONE image -> the y_true arrays the loss reads (utils.py:298-376).
+
+    true_boxes [T,5]: x_min, y_min, x_max, y_max, class id, in pixels of the network input; input_shape (h,w), multiples of
+    32; anchors [9,2] (w,h).  Returns float32 arrays [gh,gw,3,5+num_classes], one per scale (a single array for
+    num_scales == 1, else a tuple): (x, y, w, h) relative to the input, object flag, one class bit.  Stack them over the batch.
+
+    The reference's behaviour is kept where it is peculiar: centres come from a floor division (:321), a box is valid when its
+    WIDTH is positive (:342), argmax ties go to the first anchor, the last writer of a (cell, slot) wins, and the index that
+    runs over the valid boxes addresses the unfiltered array (:356-366) - right when the zero padding rows come last, which is
+    how the reference's pipeline pads."""
+    anchor_mask = [[6, 7, 8], [3, 4, 5], [0, 1, 2]][-1 * num_scales:]
+    true_boxes = np.array(true_boxes, dtype='float32')
+    input_shape = np.array(input_shape, dtype='int32')
+    boxes_xy = (true_boxes[..., 0:2] + true_boxes[..., 2:4]) // 2
+    boxes_wh = true_boxes[..., 2:4] - true_boxes[..., 0:2]
+    true_boxes[..., 0:2] = boxes_xy / input_shape[::-1]
+    true_boxes[..., 2:4] = boxes_wh / input_shape[::-1]
+    grid_steps = [32, 16, 8]
+    grid_shapes = [np.round(input_shape / grid_steps[l]).astype(np.int32) for l in range(num_scales)]
+    y_true = [np.zeros((grid_shapes[l][0], grid_shapes[l][1], len(anchor_mask[l]), 5 + num_classes), dtype='float32')
+              for l in range(num_scales)]
+    # the anchor whose shape, centred on the box, overlaps it most
+    anchor_maxes = np.expand_dims(np.asarray(anchors), 0) / 2.
+    wh = np.expand_dims(boxes_wh[boxes_wh[..., 0] > 0], -2)
+    box_maxes = wh / 2.
+    anchor_box = np.stack([-anchor_maxes[..., 1], -anchor_maxes[..., 0], anchor_maxes[..., 1], anchor_maxes[..., 0]], axis=-1)
+    bbox = np.stack([-box_maxes[..., 1], -box_maxes[..., 0], box_maxes[..., 1], box_maxes[..., 0]], axis=-1)
+    best_anchor = np.argmax(do_giou_calculate(anchor_box, bbox, mode='iou'), axis=-1)
+    slot_of = {n: (l, k) for l, mask in enumerate(anchor_mask) for k, n in enumerate(mask)}   # anchor -> (scale, slot)
+    for t, n in enumerate(best_anchor):      # t counts the VALID boxes but indexes the unfiltered rows (see above)
+        if int(n) not in slot_of:
+            continue                         # (an anchor of a scale that num_scales leaves out)
+        l, k = slot_of[int(n)]
+        gh, gw = grid_shapes[l]
+        col = int(np.floor(true_boxes[t, 0] * gw))
+        row = int(np.floor(true_boxes[t, 1] * gh))
+        entry = y_true[l][row, col, k]       # a later box of the same cell and slot overwrites the box; class bits accumulate
+        entry[0:4] = true_boxes[t, 0:4]
+        entry[4] = 1.
+        entry[5 + int(true_boxes[t, 4])] = 1.
+    return y_true[0] if num_scales == 1 else tuple(y_true)
