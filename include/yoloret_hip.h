@@ -301,7 +301,19 @@ typedef enum {
  * ---- end of the launch-form bits */
 
 /* One fused operation.  Weight-like fields are float offsets into the weight
- * blob in plan ops (`wgt_off` etc.), or device pointers in yr_op_* calls. */
+ * blob in plan ops (`wgt_off` etc.), or device pointers in yr_op_* calls.
+ *
+ * Where an op touches memory (tests/fence.py holds every op of the suite to this, between guard bytes):
+ *   - it writes only the bytes of its outputs.  Of `out` (and of the second output of a two-output POINTWISE op) these are, per
+ *     pixel row of out_ld elements, elements [0, round_up(cout, V)) - V = 4 for a float32 output, 8 for a 16-bit one - or
+ *     [0, cout) where the row is dense (out_ld == cout); elements behind them, up to out_ld, keep what they held.  The other
+ *     outputs are written whole, as sized at their fields: the channel-sum rows behind `gate` (B x se_reduced x gate_ld), the
+ *     SE tail's gate_out (B x gate_out_ld), `sync` (B words, zero again after the launch), SE_MEAN's and SE_FC's `out` (B x out_ld);
+ *   - no byte outside a source's B x h x w x ld elements (nor outside a gate's B x gate_ld, a residual's B x h x w x res_ld, a
+ *     parameter array's documented extent) influences a result: a kernel may fetch a halo row, a k-tail quad or a pooled window
+ *     past a tensor's end only if the value never reaches an output;
+ *   - 16-byte alignment of every pointer suffices (4-byte where a field is documented as dwords: `sync`); nothing may rely on the
+ *     larger alignment an allocator happens to give. */
 typedef struct {
     int32_t kind;         /* yr_op_kind */
     int32_t act;          /* yr_act */
@@ -316,7 +328,10 @@ typedef struct {
                              the low-resolution partial sums of a hoisted conv); SE_MEAN / SE_FC always write float32 */
     yr_src src[YR_MAX_SRC];
     /* output */
-    void* out;  int32_t out_buf;  int32_t out_ld;
+    void* out;  int32_t out_buf;  int32_t out_ld;    /* out_ld may exceed the padded width (a multiple of V): the elements behind round_up(cout, V) are
+                                                         left alone (tests: *_wide_rows).  Refused with YR_ERR_ARG: YR_OP_MBX in its LDS-tiled
+                                                         form (mbh.hip: a forced tile, or a shape the register-chained form is not built for),
+                                                         which needs out_ld == round_up(cout, 8); no other kind refuses a wider row */
     /* optional residual added after BN (same shape as output, element type `dtype`) */
     const void* res;  int32_t res_buf;  int32_t res_ld;
     /* optional SE gate [B, gate_ld] (float32) multiplied onto the (single) source on load */
@@ -392,7 +407,12 @@ int yr_load_weights(yr_handle* h, const float* host_blob, size_t n_floats);
 /* Bytes of caller-owned device workspace yr_forward needs for `batch` images (the arena of intermediate tensors followed by the
  * SE-tail arrival counters of the plan's ops, 4 * batch bytes each). */
 size_t yr_workspace_bytes(const yr_handle* h, int batch);
-/* images [B,H,W,3] -> y1,y2,y3 raw logits [B,G,G,A*(C+5)], G = H/32, H/16, H/8. */
+/* images [B,H,W,3] -> y1,y2,y3 raw logits [B,G,G,A*(C+5)], G = H/32, H/16, H/8.
+ * The pass (and yr_autotune, yr_forward_ranges, yr_forward_profile, which take the same buffers) writes only the B x G x G x A*(C+5)
+ * floats of each output and the first yr_workspace_bytes(h, batch) bytes of `workspace`; no byte outside the B x H x W x 3 image
+ * elements, and nothing the workspace held before the call, influences a logit; images, outputs and workspace need 16-byte
+ * alignment and no more (inside the arena a buffer of image b starts at a multiple of 16 bytes - an odd batch gives its ops
+ * pointers aligned to just that). */
 int yr_forward(yr_handle* h, const float* images, int batch, float* y1, float* y2, float* y3,
                void* workspace, size_t workspace_bytes, void* stream);
 /* Measurement aid: the same replay with a hipEvent pair around every op, `iters` times.

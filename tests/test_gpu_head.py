@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from oracle import nn
+from tests import fence
 from tests.util import assert_close, from_dev, round_up, to_dev
 from tests.test_gpu_ops import _act_np, _dev_vec, _src_dims, _xform_np
 
@@ -68,11 +69,12 @@ def se_gate_ref(y, w1, b1, w2, b2):
     return 1.0 / (1.0 + np.exp(-(hid @ w2.astype(np.float64) + b2)))
 
 
-def run_head(dev, rng, b, h, w, segs, f, pre=False, gated=False, se=None, conv_act='relu6', dw_act='swish', tail=True, scale_x=1.0, cfg=0, tile=False, form=None, xgen=None):
+def run_head(dev, rng, b, h, w, segs, f, pre=False, gated=False, se=None, conv_act='relu6', dw_act='swish', tail=True, scale_x=1.0, cfg=0, tile=False, form=None, xgen=None, wide=0):
     """segs: [(channels, xform)] of the conv's concatenated sources; pre: an up-sampled pre-BN addend (YR_X_UP2_ADD);
     gated: SE gate on the (single identity) source; se: hidden width R (None: no squeeze-excite sums at all); tail: the op also
     runs the FC pair (False: sums only); tile: every image of the batch is the same image (drawn once); form: 'walk' (headwalk.hip),
-    'dma' (headblock.hip, LDS-direct), 'pws' (headblock.hip, register-staged gathers) or None = what the compiler would pick.
+    'dma' (headblock.hip, LDS-direct), 'pws' (headblock.hip, register-staged gathers) or None = what the compiler would pick;
+    wide: elements by which the rows of the map are wider than the op may write.
     -> (map, gate | None)"""
     rt = _rt()
     nb = b
@@ -116,7 +118,7 @@ def run_head(dev, rng, b, h, w, segs, f, pre=False, gated=False, se=None, conv_a
     dwp[:9, :f] = (dk.reshape(9, f) * ds[None]).astype(np.float32)
     dwp[9, :f] = dh
 
-    out = torch.full((b, h, w, ldf), float('nan'), dtype=torch.float32, device=dev)
+    out = torch.full((b, h, w, ldf + wide), float('nan'), dtype=torch.float32, device=dev)
     op = rt.new_op(rt.OP_HEAD, dw_act)
     op.h, op.w, op.cin, op.cout, op.stride = h, w, cin, f, 1
     if form is None:
@@ -148,7 +150,7 @@ def run_head(dev, rng, b, h, w, segs, f, pre=False, gated=False, se=None, conv_a
         g = to_dev(gate_np.reshape(b, 1, 1, cin), dev)
         keep.append(g)
         op.res, op.res_ld = g.data_ptr(), g.shape[3]
-    op.out, op.out_ld = out.data_ptr(), ldf
+    op.out, op.out_ld = out.data_ptr(), ldf + wide
     sums = gate_out = None
     if se is not None:
         nsy, nsx = ctypes.c_int32(), ctypes.c_int32(1)
@@ -169,8 +171,9 @@ def run_head(dev, rng, b, h, w, segs, f, pre=False, gated=False, se=None, conv_a
             keep += [_dev_vec(se_pack(*sp), dev), torch.zeros(b, dtype=torch.int32, device=dev)]
             op.gate_out, op.gate_out_ld, op.se_hidden = gate_out.data_ptr(), ldf, se
             op.se_w, op.sync = keep[-2].data_ptr(), keep[-1].data_ptr()
+    writes = [out] + ([sums] if sums is not None else []) + ([gate_out, keep[-1]] if gate_out is not None else [])
     for rep in range(2):      # twice: the arrival counters must be back at zero after a launch
-        rt.run_op(op, b)
+        fence.run_op(op, b, writes=writes, reads=srcs_dev + (keep[:-1] if gate_out is not None else keep), cols=ldf)
     torch.cuda.synchronize()
     got = from_dev(out, f)
     assert_close(got, y, TOL, 'head %s -> %d' % (segs, f))
@@ -221,6 +224,16 @@ def test_head_block(dev, case, form):
         pytest.skip('pooled sources stay on the register-staged form')
     rng = np.random.default_rng(zlib.crc32(str(case).encode()))
     run_head(dev, rng, 3, h, w, segs, f, pre=pre, gated=gated, se=r, form=form, tail=form != 'stream')
+
+
+@pytest.mark.parametrize('form', ['stream', 'walk', 'dma', 'pws'])
+def test_head_block_wide_rows(dev, form):
+    """out_ld two vectors wider than F (three sources, a partial last quad, a map of 15 columns - a shape every form takes): the
+    elements past F of every row keep their bytes."""
+    h, w, segs, f, pre, gated, r = HEAD_CASES[13]
+    assert stream_ok(h, segs, f, pre, gated, 'relu6') and walk_ok(segs, f, pre, gated, 'relu6')
+    rng = np.random.default_rng(zlib.crc32(str(HEAD_CASES[13]).encode()))
+    run_head(dev, rng, 3, h, w, segs, f, pre=pre, gated=gated, se=r, form=form, tail=form != 'stream', wide=8)
 
 
 def test_head_stream_form_variants_and_batch_independence(dev):
@@ -309,7 +322,7 @@ def test_se_tail_of_depthwise(dev):
         op.gate_out, op.gate_out_ld, op.se_hidden = gate.data_ptr(), ldc, r
         op.se_w, op.sync = keep[3].data_ptr(), keep[4].data_ptr()
         for rep in range(3):
-            rt.run_op(op, b)
+            fence.run_op(op, b, writes=[out, sums, gate, keep[4]], reads=[xd] + keep[:4])
         torch.cuda.synchronize()
         assert_close(from_dev(out, c), ref, 2e-5, 'depthwise (SE tail)')
         assert int(keep[4].abs().sum().item()) == 0
@@ -322,7 +335,7 @@ def test_se_tail_of_depthwise(dev):
 # rounded once: half an ulp of the type + float32 noise).  The F-wide conv output is NOT rounded in between (the unfused pair of
 # launches rounds it: the fused op is the more accurate one).
 
-def run_head16(dev, dt, rng, b, h, w, segs, f, pre=False, gated=False, se=True, conv_act='relu6', dw_act='swish', tile=False):
+def run_head16(dev, dt, rng, b, h, w, segs, f, pre=False, gated=False, se=True, conv_act='relu6', dw_act='swish', tile=False, wide=0):
     from tests.util import assert_rounded_once, from_dev16, q16, to_dev16
     from yoloret_amd.compiler import head_pack16
     rt = _rt()
@@ -373,7 +386,7 @@ def run_head16(dev, dt, rng, b, h, w, segs, f, pre=False, gated=False, se=True, 
     frag = head_pack16(wt, segs)
     wd = torch.from_numpy(rt.to_bits16(frag, dt).view(np.int16)).to(dev)
     ldf = round_up(f, 8)
-    out = to_dev16(np.full((b, h, w, ldf), np.nan, np.float32), dev, dt)
+    out = to_dev16(np.full((b, h, w, ldf + wide), np.nan, np.float32), dev, dt)
     op = rt.new_op(rt.OP_HEAD, dw_act)
     op.dtype = op.out_dtype = did
     op.h, op.w, op.cin, op.cout, op.stride = h, w, cin, f, 1
@@ -394,14 +407,14 @@ def run_head16(dev, dt, rng, b, h, w, segs, f, pre=False, gated=False, se=True, 
         g = to_dev(gate_np.reshape(b, 1, 1, cin), dev)
         keep.append(g)
         op.res, op.res_ld = g.data_ptr(), g.shape[3]
-    op.out, op.out_ld = out.data_ptr(), ldf
+    op.out, op.out_ld = out.data_ptr(), ldf + wide
     sums = None
     if se:
         rows = ctypes.c_int32()
         rt.check(rt.lib().yr_head_walk_rows(h, w, ctypes.byref(rows)))
         sums = torch.full((b, rows.value, ldf), float('nan'), dtype=torch.float32, device=dev)
         op.gate, op.gate_ld, op.se_reduced = sums.data_ptr(), ldf, rows.value
-    rt.run_op(op, b)
+    fence.run_op(op, b, writes=[out] + ([sums] if se else []), reads=srcs_dev + keep, cols=ldf)
     torch.cuda.synchronize()
     got = from_dev16(out, dt, f)
     # float32 noise of two chained stages (conv accumulation over up to 256 channels, nine taps): 1e-4 of slack beside the half ulp
@@ -436,6 +449,13 @@ def test_head_block_16bit(dev, dt, case):
     h, w, segs, f, pre, gated = case
     rng = np.random.default_rng(zlib.crc32((str(case) + dt).encode()))
     run_head16(dev, dt, rng, 3, h, w, segs, f, pre=pre, gated=gated)
+
+
+@pytest.mark.parametrize('dt', ['bf16', 'f16'])
+def test_head_block_16bit_wide_rows(dev, dt):
+    h, w, segs, f, pre, gated = HEAD16_CASES[6]
+    rng = np.random.default_rng(zlib.crc32((str(HEAD16_CASES[6]) + dt).encode()))
+    run_head16(dev, dt, rng, 3, h, w, segs, f, pre=pre, gated=gated, wide=16)
 
 
 def test_head_block_16bit_variants(dev):

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from oracle import nn
+from tests import fence
 from tests.util import assert_close, from_dev, round_up, to_dev
 
 pytestmark = pytest.mark.gpu
@@ -26,7 +27,7 @@ def _pw(rt, dev, srcs, wt, cout, h, w, b, act='none', scale=None, shift=None, cf
         op.scale, op.shift = keep[1].data_ptr(), keep[2].data_ptr()
     out = torch.full((b, h, w, round_up(cout, 4)), float('nan'), dtype=torch.float32, device=dev)
     op.out, op.out_ld, op.k = out.data_ptr(), out.shape[3], cfg
-    rt.run_op(op, b)
+    fence.run_op(op, b, writes=[out], reads=[t for t, _, _ in srcs] + keep)
     torch.cuda.synchronize()
     return out
 
@@ -122,7 +123,7 @@ def test_pointwise_with_pooled_output(dev, case):
         op.wgt, op.scale, op.shift = [t.data_ptr() for t in keep]
         out = torch.full((b, h // 2, w // 2, round_up(cout, 4)), float('nan'), dtype=torch.float32, device=dev)
         op.out, op.out_ld = out.data_ptr(), out.shape[3]
-        rt.run_op(op, b)
+        fence.run_op(op, b, writes=[out], reads=[xd] + keep)
         torch.cuda.synchronize()
         outs.append(from_dev(out, cout))
         assert_close(outs[-1], ref, 3e-5, 'pooled conv %s cfg %d' % (case, cfg))

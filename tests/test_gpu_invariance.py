@@ -18,6 +18,7 @@ import pytest
 import torch
 
 from oracle import params
+from tests import fence
 from yoloret_amd.weights import synthetic_weights
 from tests.util import POISON_PATTERNS, assert_close, autotune_candidates, nan_outputs, poison_workspace
 
@@ -128,6 +129,88 @@ def _workspace_case(dev, name, size, dt, variant, b):
 @pytest.mark.parametrize('name,size,dt,variant,b', A_CASES, ids=['%s-%d-%s-%s-b%d' % c for c in A_CASES])
 def test_logits_do_not_depend_on_the_workspace(dev, name, size, dt, variant, b):
     _workspace_case(dev, name, size, dt, variant, b)
+
+
+def _fenced_buffers(m, xd, pattern, seed):
+    """A workspace of exactly m.workspace_bytes(b) bytes holding `pattern`, and NaN outputs: what a fenced pass works in."""
+    b = xd.shape[0]
+    ws = torch.empty(m.workspace_bytes(b), dtype=torch.uint8, device=xd.device)
+    if pattern == 'random':
+        g = torch.Generator(device=xd.device)
+        g.manual_seed(seed)
+        ws.random_(0, 256, generator=g)
+    else:
+        ws.fill_(int(pattern))
+    return ws, nan_outputs(m, b)
+
+
+def _fenced_forward(m, xd, pattern, seed=0):
+    """yr_autotune + yr_forward (Model.__call__ on a batch size it has not tuned) with the input batch, the three outputs and the
+    workspace each between the guards of tests/fence.py, in both of its variants: -> [y1, y2, y3] numpy."""
+    b, idx = xd.shape[0], xd.device.index
+    assert m.autotune
+    ws, ys = _fenced_buffers(m, xd, pattern, seed)
+    saved = m._workspace.get(idx)
+
+    def call(moved):
+        m._workspace[idx] = moved(ws)                   # (a view of exactly workspace_bytes(b) bytes: Model.__call__ takes it as it is)
+        m._tuned.discard((idx, b))                      # the tuner's trial launches run on the fenced buffers too
+        m(moved(xd), out=[moved(y) for y in ys])
+        assert m._workspace[idx].data_ptr() == moved(ws).data_ptr()
+    try:
+        fence.run(call, writes=ys, reads=[xd], scratch=[ws], batch=b)
+    finally:
+        m._workspace[idx] = saved
+    torch.cuda.synchronize()
+    return [y.cpu().numpy() for y in ys]
+
+
+@pytest.mark.parametrize('name,size,dt,variant,b', A_CASES, ids=['%s-%d-%s-%s-b%d' % c for c in A_CASES])
+def test_plans_stay_inside_their_buffers(dev, name, size, dt, variant, b):
+    """Every plan variant of section A (batches of 2, 3, 6, 24 and config 2's 64: at an odd batch the arena's per-op pointers are
+    16-byte aligned and no more) with input, outputs and workspace fenced, once per poison pattern: no byte around any of the five
+    buffers changes during yr_autotune + yr_forward, nothing around the input reaches the logits, and the logits are those of the
+    unfenced pass bit for bit (which section A holds to the oracle's bar on image 0)."""
+    m, runs = _workspace_case(dev, name, size, dt, variant, b)
+    xd = torch.from_numpy(params.synthetic_images(b, size, size)).to(dev)
+    what = '%s@%d %s %s B=%d, fenced' % (name, size, dt, variant, b)
+    for n, pat in enumerate(POISON_PATTERNS):
+        got = _fenced_forward(m, xd, pat, seed=n)
+        for k, (g, w) in enumerate(zip(got, runs[0])):
+            g = g.reshape(w.shape)
+            assert np.isfinite(g).all() and np.array_equal(g, w), '%s (pattern %r) y%d differs from the unfenced pass (%d elements)' % (
+                what, pat, k + 1, int((g != w).sum()))
+
+
+def test_ranges_and_profile_passes_stay_inside_their_buffers(dev):
+    """yr_forward_ranges and yr_forward_profile, the other two entries that walk a whole plan, through the C ABI with fenced buffers
+    (an odd batch): guards intact, logits those of yr_forward."""
+    import ctypes
+    from yoloret_amd import runtime as rt
+    name, size, b = 'mobilenetv2x75', 160, 3
+    m = _model(name, size, 'f32')
+    m.small_batch = m.mbk_batch = 0
+    m.set_weights(synthetic_weights(m, 1234, 'conditioned'))
+    xd = torch.from_numpy(params.synthetic_images(b, size, size)).to(dev)
+    want = [y.cpu().numpy() for y in m(xd)]
+    idx, hd = m._handle(xd.device, b)
+    n = len(m.plan_for(b).ops)
+    for entry in ('ranges', 'profile'):
+        ws, ys = _fenced_buffers(m, xd, 0xFF, 0)
+        mx, ms, names = (ctypes.c_float * n)(), (ctypes.c_float * n)(), (ctypes.c_char_p * n)()
+
+        def call(moved):
+            p = [rt._ptr(moved(t)) for t in [xd] + ys + [ws]]
+            if entry == 'ranges':
+                rt.check(rt.lib().yr_forward_ranges(hd, p[0], b, p[1], p[2], p[3], p[4], ws.numel(), rt.stream_ptr(dev), mx))
+            else:
+                rt.check(rt.lib().yr_forward_profile(hd, p[0], b, p[1], p[2], p[3], p[4], ws.numel(), rt.stream_ptr(dev), 1, ms, names))
+        fence.run(call, writes=ys, reads=[xd], scratch=[ws], batch=b)
+        torch.cuda.synchronize()
+        for k, (y, w) in enumerate(zip(ys, want)):
+            assert np.array_equal(y.cpu().numpy().reshape(w.shape), w), 'yr_forward_%s y%d differs from yr_forward' % (entry, k + 1)
+        if entry == 'ranges':
+            assert all(np.isfinite(v) and v >= 0 for v in mx) and max(mx) > 0
 
 
 def test_se_tail_plan_clears_its_arrival_counters(dev, monkeypatch):

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from oracle import nn
+from tests import fence
 from tests.util import assert_rounded_once, from_dev16, q16, round_up, to_dev16
 
 pytestmark = pytest.mark.gpu
@@ -67,6 +68,18 @@ def _chained_built(cin, cexp, cout, k, act='relu6'):
 def test_mbh(dev, case, dt, form):
     """form 'lds': the LDS-tiled kernels (mbh.hip, mbn_h.hip; forced tile rt.MBH_TILE_LDS = their own tile choice); 'chained': the
     row-walking register-chained kernel (mbxr_h.hip: mbhr_kernel; forced tile rt.MBH_TILE_CHAINED, one or three row segments) where built."""
+    _mbh(dev, case, dt, form)
+
+
+@pytest.mark.parametrize('form', ['lds', 'chained'])
+@pytest.mark.parametrize('dt', ['bf16', 'f16'])
+@pytest.mark.parametrize('ci', [4, 9], ids=['ragged_tiles', 'narrow_front_block'])
+def test_mbh_wide_rows(dev, ci, dt, form):
+    """out_ld two vectors wider than the padded width: the elements past round_up(cout, 8) of every row keep their bytes."""
+    _mbh(dev, CASES[ci], dt, form, wide=16)
+
+
+def _mbh(dev, case, dt, form, wide=0):
     from yoloret_amd import runtime as rt
     h, w, cin, cexp, cout, k, s, residual, act, tile = case
     if form == 'chained':
@@ -121,9 +134,9 @@ def test_mbh(dev, case, dt, form):
     op.wgt, op.wgt2, op.b1, op.b2 = [t_.data_ptr() for t_ in keep]
     if residual:
         op.res, op.res_ld = xd.data_ptr(), xd.shape[3]
-    out = torch.full((b, ho, wo, ldo), float('nan'), dtype=rt.TORCH_DTYPE[did], device=dev)
-    op.out, op.out_ld = out.data_ptr(), ldo
-    rt.run_op(op, b)
+    out = torch.full((b, ho, wo, ldo + wide), float('nan'), dtype=rt.TORCH_DTYPE[did], device=dev)
+    op.out, op.out_ld = out.data_ptr(), ldo + wide
+    fence.run_op(op, b, writes=[out], reads=[xd] + keep, cols=ldo)
     torch.cuda.synchronize()
     assert_rounded_once(from_dev16(out, dt, cout), ref, dt, 'mbh %s %s' % (dt, case), slack={'bf16': 4e-3, 'f16': 5e-4}[dt] * (2 if mbn else 1))
 
@@ -139,10 +152,10 @@ def test_mbh_rejects_what_it_is_not_built_for(dev):
     op.wgt = op.wgt2 = op.b1 = op.b2 = x.data_ptr()
     op.out, op.out_ld = out.data_ptr(), 160
     with pytest.raises(rt.YoloretHipError, match='widths out of range'):
-        rt.run_op(op, 1)
+        fence.run_op(op, 1, writes=[out], reads=[x])
     op.dtype = op.out_dtype = 0
     with pytest.raises(rt.YoloretHipError, match='16-bit'):
-        rt.run_op(op, 1)
+        fence.run_op(op, 1, writes=[out], reads=[x])
 
 
 MBX_CASES = [
@@ -169,6 +182,27 @@ MBX_CASES = [
 def test_mbx(dev, case, with_sums, dt):
     """YR_OP_MBX: expand 1x1 + BN + act -> depthwise + BN + act, the depthwise map stored once (16-bit) and its per-tile
     channel sums (the squeeze of squeeze-excite) written beside it."""
+    _mbx(dev, case, with_sums, dt)
+
+
+@pytest.mark.parametrize('dt', ['bf16', 'f16'])
+def test_mbx_wide_rows(dev, dt):
+    """out_ld two vectors wider than the padded width (the sums keep their own stride), register-chained form (5x5 stride 2, ragged
+    tiles): the elements past round_up(cexp, 8) of every row of the map keep their bytes."""
+    _mbx(dev, MBX_CASES[2], True, dt, wide=16)
+
+
+@pytest.mark.parametrize('dt', ['bf16', 'f16'])
+@pytest.mark.parametrize('ci', [10, 11], ids=['two_groups_per_wave', 'pad_lanes'])
+def test_mbx_lds_tiled_form_refuses_wide_rows(dev, ci, dt):
+    """The LDS-tiled form (forced tiles) masks its channel quads by out_ld, so in a wider row it would write the zero quads of its
+    last 32-channel chunk behind round_up(cexp, 8) (cexp = 52: elements 56 .. 63): its launcher refuses such a row."""
+    from yoloret_amd import runtime as rt
+    with pytest.raises(rt.YoloretHipError, match='LDS-tiled form needs out_ld == round_up'):
+        _mbx(dev, MBX_CASES[ci], True, dt, wide=16)
+
+
+def _mbx(dev, case, with_sums, dt, wide=0):
     from yoloret_amd import runtime as rt
     h, w, cin, cexp, k, s, act, tile = case
     rng = np.random.default_rng(zlib.crc32(str(case).encode()))
@@ -196,12 +230,12 @@ def test_mbx(dev, case, with_sums, dt):
     op.k = k | ((tile[0] << rt.MBH_TH_SHIFT) | (tile[1] << rt.MBH_TW_SHIFT) if tile else 0)
     op.src[0] = rt.make_src(xd, c=cin)
     op.wgt, op.wgt2 = keep[0].data_ptr(), keep[1].data_ptr()
-    out = torch.full((b, ho, wo, ldo), float('nan'), dtype=rt.TORCH_DTYPE[did], device=dev)
-    op.out, op.out_ld = out.data_ptr(), ldo
+    out = torch.full((b, ho, wo, ldo + wide), float('nan'), dtype=rt.TORCH_DTYPE[did], device=dev)
+    op.out, op.out_ld = out.data_ptr(), ldo + wide
     part = torch.full((b, rows, ldo), float('nan'), dtype=torch.float32, device=dev)
     if with_sums:
         op.gate, op.gate_ld, op.se_reduced = part.data_ptr(), ldo, rows
-    rt.run_op(op, b)
+    fence.run_op(op, b, writes=[out] + ([part] if with_sums else []), reads=[xd] + keep, cols=ldo)
     torch.cuda.synchronize()
     got = from_dev16(out, dt, cexp)
     # hardware exp2 / reciprocal in the swish (about 1e-6 relative) on top of the half ulp of the one rounding
@@ -232,4 +266,4 @@ def test_mbx_rejects_a_short_sum_buffer(dev):
     op.out, op.out_ld = out.data_ptr(), 144
     op.gate, op.gate_ld, op.se_reduced = part.data_ptr(), 144, 4
     with pytest.raises(rt.YoloretHipError, match='exceed the 4 rows'):
-        rt.run_op(op, 1)
+        fence.run_op(op, 1, writes=[out, part], reads=[x])

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from oracle import nn
+from tests import fence
 from tests.util import assert_close, assert_rounded_once, from_dev, from_dev16, q16, round_up, to_dev, to_dev16
 
 pytestmark = pytest.mark.gpu
@@ -43,6 +44,17 @@ def _pairs(rows, scale, shift, e2):
 def test_mblane(dev, case, dt):
     """dt: element type of the block's input and output (16-bit: the block computes in float32 from registers and
     rounds once at the store; the residual is the 16-bit input widened)."""
+    _mblane(dev, case, dt)
+
+
+@pytest.mark.parametrize('dt', ['f32', 'bf16', 'f16'])
+@pytest.mark.parametrize('ci', [4, 8], ids=['ragged_tiles', 'pad_lanes'])
+def test_mblane_wide_rows(dev, ci, dt):
+    """out_ld two vectors wider than the padded width: the elements past it keep their bytes in every row."""
+    _mblane(dev, CASES[ci], dt, wide=True)
+
+
+def _mblane(dev, case, dt, wide=False):
     from yoloret_amd import runtime as rt
     h, w, cin, cexp, cout, s, residual, act = case
     rng = np.random.default_rng(zlib.crc32(str(case).encode()))
@@ -81,9 +93,12 @@ def test_mblane(dev, case, dt):
         op.res, op.res_ld = xd.data_ptr(), xd.shape[3]
     if dt != 'f32':
         ldo = round_up(cout, 8)
+    cols = ldo
+    if wide:
+        ldo += 2 * rt.VEC[rt.dtype_id(dt)]
     out = torch.full((b, ref.shape[1], ref.shape[2], ldo), float('nan'), dtype=rt.TORCH_DTYPE[rt.dtype_id(dt)], device=dev)
     op.out, op.out_ld = out.data_ptr(), ldo
-    rt.run_op(op, b)
+    fence.run_op(op, b, writes=[out], reads=[xd] + keep, cols=cols)
     torch.cuda.synchronize()
     if dt == 'f32':
         assert_close(from_dev(out, cout), ref, 5e-5, 'mblane %s' % (case,))
@@ -136,7 +151,7 @@ def test_mblane_without_expand(dev, case, dt):
     ldo = round_up(cout, 4) if dt == 'f32' else round_up(cout, 8)
     out = torch.full((b, h, w, ldo), float('nan'), dtype=rt.TORCH_DTYPE[rt.dtype_id(dt)], device=dev)
     op.out, op.out_ld = out.data_ptr(), ldo
-    rt.run_op(op, b)
+    fence.run_op(op, b, writes=[out], reads=[xd] + keep)
     torch.cuda.synchronize()
     if dt == 'f32':
         assert_close(from_dev(out, cout), ref, 5e-5, 'mblane without expand %s' % (case,))
@@ -154,4 +169,4 @@ def test_mblane_rejects_unsupported_widths(dev):
     out = torch.zeros((1, 8, 8, 64), dtype=torch.float32, device=dev)
     op.out, op.out_ld = out.data_ptr(), 64
     with pytest.raises(rt.YoloretHipError, match='unsupported'):
-        rt.run_op(op, 1)
+        fence.run_op(op, 1, writes=[out], reads=[x])

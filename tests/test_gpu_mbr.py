@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from oracle import nn
+from tests import fence
 from tests.util import assert_close, from_dev, to_dev
 
 pytestmark = pytest.mark.gpu
@@ -39,7 +40,7 @@ def _reference(x, we, se, he, wd, sd, hd, wp, sp, hp, s, residual):
     return ref + x if residual else ref
 
 
-def make_block(case, dev, b=2, seed=None, split=False):
+def make_block(case, dev, b=2, seed=None, split=False, wide=0):
     from yoloret_amd import runtime as rt
     from yoloret_amd.compiler import mbr_pack, mbs_pack
     h, w, cin, cexp, cout, s, residual, nw, segs = case
@@ -63,8 +64,8 @@ def make_block(case, dev, b=2, seed=None, split=False):
     op.wgt, op.wgt2, op.b2 = [k.data_ptr() for k in keep]
     if residual:
         op.res, op.res_ld = xd.data_ptr(), xd.shape[3]
-    out = torch.full((b, ho, wo, cout), float('nan'), dtype=torch.float32, device=dev)
-    op.out, op.out_ld = out.data_ptr(), cout
+    out = torch.full((b, ho, wo, cout + wide), float('nan'), dtype=torch.float32, device=dev)     # wide: elements of a row the op leaves alone
+    op.out, op.out_ld = out.data_ptr(), cout + wide
     return op, out, (x, we, se, he, wd, sd, hd, wp, sp, hp, s, residual), keep + [xd]
 
 
@@ -73,7 +74,7 @@ def test_mbr(dev, case):
     from yoloret_amd import runtime as rt
     op, out, params, keep = make_block(case, dev)
     ref = _reference(*params)
-    rt.run_op(op, 2)
+    fence.run_op(op, 2, writes=[out], reads=keep)
     torch.cuda.synchronize()
     assert_close(from_dev(out), ref, 5e-5, 'mbr %s' % (case,))
 
@@ -100,7 +101,7 @@ def test_mbr_split_form(dev, case):
     from yoloret_amd import runtime as rt
     op, out, params, keep = make_block(case, dev, split=True)
     ref = _reference(*params)
-    rt.run_op(op, 2)
+    fence.run_op(op, 2, writes=[out], reads=keep)
     torch.cuda.synchronize()
     assert_close(from_dev(out), ref, 5e-5, 'mbr split %s' % (case,))
 
@@ -122,6 +123,17 @@ MBE_CASES = [
 @pytest.mark.parametrize('split', [False, True], ids=['f32', 'split'])
 @pytest.mark.parametrize('case', MBE_CASES, ids=[str(i) for i in range(len(MBE_CASES))])
 def test_mbe(dev, case, split):
+    _mbe(dev, case, split)
+
+
+@pytest.mark.parametrize('split', [False, True], ids=['f32', 'split'])
+def test_mbe_wide_rows(dev, split):
+    """out_ld two vectors wider than the map: the elements past cexp of every row keep their bytes (ragged case: two strips, a short
+    tile group)."""
+    _mbe(dev, MBE_CASES[4], split, wide=8)
+
+
+def _mbe(dev, case, split, wide=0):
     from yoloret_amd import runtime as rt
     from yoloret_amd.compiler import mbr_pack, mbs_pack
     h, w, cin, cexp, s, segs = case
@@ -146,11 +158,11 @@ def test_mbe(dev, case, split):
     op.h, op.w, op.cin, op.cout, op.k, op.stride, op.nsrc = ho, wo, cin, cexp, 3 | (rt.MBR_SPLIT if split else 0) | segs << rt.MBR_SEGS_SHIFT, s, 1
     op.src[0] = rt.make_src(xd, c=cin)
     op.wgt, op.wgt2 = [k.data_ptr() for k in keep]
-    out = torch.full((b, ho, wo, cexp), float('nan'), dtype=torch.float32, device=dev)
-    op.out, op.out_ld = out.data_ptr(), cexp
-    rt.run_op(op, b)
+    out = torch.full((b, ho, wo, cexp + wide), float('nan'), dtype=torch.float32, device=dev)
+    op.out, op.out_ld = out.data_ptr(), cexp + wide
+    fence.run_op(op, b, writes=[out], reads=keep + [xd], cols=cexp)
     torch.cuda.synchronize()
-    assert_close(from_dev(out), ref, 5e-5, 'mbe %s' % (case,))
+    assert_close(from_dev(out, cexp), ref, 5e-5, 'mbe %s' % (case,))
 
 
 MBK_CASES = [
@@ -169,7 +181,7 @@ MBK_CASES = [
 ]
 
 
-def make_block_k(case, dev, b=2, seed=None):
+def make_block_k(case, dev, b=2, seed=None, wide=0):
     from yoloret_amd import runtime as rt
     from yoloret_amd.compiler import mbk_pack
     h, w, cin, cexp, cout, s, residual, rows, nw = case
@@ -192,8 +204,8 @@ def make_block_k(case, dev, b=2, seed=None):
     op.wgt, op.b2 = [k.data_ptr() for k in keep]
     if residual:
         op.res, op.res_ld = xd.data_ptr(), xd.shape[3]
-    out = torch.full((b, ho, wo, cout), float('nan'), dtype=torch.float32, device=dev)
-    op.out, op.out_ld = out.data_ptr(), cout
+    out = torch.full((b, ho, wo, cout + wide), float('nan'), dtype=torch.float32, device=dev)     # wide: elements of a row the op leaves alone
+    op.out, op.out_ld = out.data_ptr(), cout + wide
     return op, out, (x, we, se, he, wd, sd, hd, wp, sp, hp, s, residual), keep + [xd]
 
 
@@ -204,7 +216,7 @@ def test_mbr_streaming_form(dev, case):
     from yoloret_amd import runtime as rt
     op, out, params, keep = make_block_k(case, dev)
     ref = _reference(*params)
-    rt.run_op(op, 2)
+    fence.run_op(op, 2, writes=[out], reads=keep)
     torch.cuda.synchronize()
     assert_close(from_dev(out), ref, 5e-5, 'mbr streaming %s' % (case,))
 
@@ -214,7 +226,7 @@ def test_mbr_streaming_form_is_batch_independent(dev):
     from yoloret_amd import runtime as rt
     case = MBK_CASES[2]
     op, out, params, keep = make_block_k(case, dev, b=5, seed=3)
-    rt.run_op(op, 5)
+    fence.run_op(op, 5, writes=[out], reads=keep)
     torch.cuda.synchronize()
     full = from_dev(out).copy()
     x = params[0]
@@ -223,6 +235,20 @@ def test_mbr_streaming_form_is_batch_independent(dev):
         xd1 = to_dev(x[i:i + 1], dev)
         op1.src[0] = rt.make_src(xd1, c=case[2])
         op1.res = xd1.data_ptr()
-        rt.run_op(op1, 1)
+        fence.run_op(op1, 1, writes=[out1], reads=keep1[:-1] + [xd1])
         torch.cuda.synchronize()
         assert np.array_equal(from_dev(out1)[0], full[i])
+
+
+@pytest.mark.parametrize('form', ['f32', 'split', 'streaming'])
+def test_mbr_wide_rows(dev, form):
+    """out_ld two vectors wider than cout: the elements past cout of every row keep their bytes, and the result is the oracle's (odd
+    sizes, ragged strips and segments; the streaming form at its ragged three-segment case)."""
+    from tests.util import round_up
+    case = {'f32': CASES[2], 'split': MBS_CASES[2], 'streaming': MBK_CASES[4]}[form]
+    op, out, params, keep = (make_block_k(case, dev, wide=8) if form == 'streaming' else make_block(case, dev, split=form == 'split', wide=8))
+    cout = case[4]
+    ref = _reference(*params)
+    fence.run_op(op, 2, writes=[out], reads=keep, cols=round_up(cout, 4))
+    torch.cuda.synchronize()
+    assert_close(from_dev(out, cout), ref, 5e-5, 'mbr %s, wide rows %s' % (form, case,))

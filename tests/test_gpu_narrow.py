@@ -18,6 +18,7 @@ import pytest
 import torch
 
 from oracle import nn
+from tests import fence
 from tests.util import assert_rounded_once, from_dev16, q16, round_up, to_dev16
 
 pytestmark = pytest.mark.gpu
@@ -51,9 +52,10 @@ def _src_dims(h, w, xf):
 
 
 def run_pointwise16(dev, dt, rng, b, h, w, segs, cout, act='none', bn=True, residual=False, gate=False, out_f32=False,
-                    dense_out=False, pool=False, pre=False, cfg=0, ksplit=False):
+                    dense_out=False, pool=False, pre=False, cfg=0, ksplit=False, wide=False):
     """One 16-bit POINTWISE op through yr_op_run against float64 NumPy on the same (exactly representable) operands.
-    h, w: the conv's resolution (pool=True: the output is its 2x2 max)."""
+    h, w: the conv's resolution (pool=True: the output is its 2x2 max).  wide: rows two vectors wider than the padded width, which
+    the op must leave alone."""
     rt = _rt()
     did = rt.dtype_id(dt)
     srcs_np, srcs_dev = [], []
@@ -121,16 +123,18 @@ def run_pointwise16(dev, dt, rng, b, h, w, segs, cout, act='none', bn=True, resi
     op.wgt = wd.data_ptr()
     op.h, op.w, op.cin, op.cout, op.nsrc = oh, ow, cin, cout, nsrc
     if out_f32:
-        out_ld = cout if dense_out else round_up(cout, 4)
+        cols = cout if dense_out else round_up(cout, 4)
+        out_ld = cols + (8 if wide else 0)
         out = torch.full((b, oh, ow, out_ld), float('nan'), dtype=torch.float32, device=dev)
     else:
-        out_ld = round_up(cout, 8)
+        cols = round_up(cout, 8)
+        out_ld = cols + (16 if wide else 0)
         out = torch.full((b, oh, ow, out_ld), float('nan'), dtype=rt.TORCH_DTYPE[did], device=dev)
     op.out, op.out_ld = out.data_ptr(), out_ld
     op.k = cfg
     if ksplit:
         op.se_reduced |= rt.PWF_KSPLIT      # the k-split form of the plans for one or two images (pointwise_h.hip: pwkh_kernel)
-    rt.run_op(op, b)
+    fence.run_op(op, b, writes=[out], reads=srcs_dev + keep, cols=cols)
     torch.cuda.synchronize()
     if out_f32:
         got = out.cpu().numpy()[..., :cout]
@@ -178,6 +182,16 @@ def test_pointwise16(dev, dt, case):
 
 
 @pytest.mark.parametrize('dt', DTYPES)
+@pytest.mark.parametrize('ci', [8, 12, 16, 18], ids=['pooled_source', 'f32_out_255', 'pooled_out_203', 'f32_out_75'])
+def test_pointwise16_wide_rows(dev, dt, ci):
+    """out_ld two vectors wider than the padded width, 16-bit outputs and the float32 outputs of a 16-bit op (padded rows): the
+    elements past the padded width of every row keep their bytes."""
+    h, w, segs, cout, act, bn, residual, gate, out_f32, dense, pool, pre = PW16[ci]
+    rng = np.random.default_rng(zlib.crc32(str(PW16[ci]).encode()))
+    run_pointwise16(dev, dt, rng, 3, h, w, segs, cout, act, bn, residual, gate, out_f32, False, pool, pre, wide=True)
+
+
+@pytest.mark.parametrize('dt', DTYPES)
 @pytest.mark.parametrize('case', PW16, ids=[str(i) for i in range(len(PW16))])
 def test_pointwise16_ksplit_form(dev, dt, case):
     """The k-split form (se_reduced bit 17: a workgroup = one 16 x 32 tile, its four waves split the k range and meet in LDS in wave
@@ -217,6 +231,18 @@ def test_pointwise16_tile_shapes_are_bit_identical(dev, dt, ci):
                                            (3, 1, 52, 52, 128, 'swish'), (3, 1, 26, 26, 256, 'relu6'), (3, 1, 13, 13, 512, 'swish'), (3, 1, 7, 45, 64, 'none'),
                                            (3, 1, 37, 9, 100, 'leaky'), (3, 1, 2, 2, 72, 'relu6')])
 def test_depthwise16(dev, dt, k, s, h, w, c, act):
+    _depthwise16(dev, dt, k, s, h, w, c, act)
+
+
+@pytest.mark.parametrize('dt', DTYPES)
+@pytest.mark.parametrize('k,s,h,w,c,act', [(5, 2, 14, 14, 75, 'swish'), (5, 1, 37, 9, 100, 'swish'), (3, 1, 37, 9, 100, 'leaky'), (3, 1, 5, 7, 10, 'none')])
+def test_depthwise16_wide_rows(dev, dt, k, s, h, w, c, act):
+    """out_ld two vectors wider than the padded width (the plain and the LDS-tiled forms, channel tails): the elements past
+    round_up(c, 8) of every row keep their bytes."""
+    _depthwise16(dev, dt, k, s, h, w, c, act, wide=16)
+
+
+def _depthwise16(dev, dt, k, s, h, w, c, act, wide=0):
     rt = _rt()
     did = rt.dtype_id(dt)
     rng = np.random.default_rng(k * 1000 + s * 100 + c)
@@ -232,7 +258,7 @@ def test_depthwise16(dev, dt, k, s, h, w, c, act):
     pad = lambda v: np.concatenate([v, np.zeros(ldc - c, np.float32)])
     xd = to_dev16(x, dev, dt)
     ho, wo = -(-h // s), -(-w // s)
-    out = torch.full((b, ho, wo, round_up(c, 8)), float('nan'), dtype=rt.TORCH_DTYPE[did], device=dev)
+    out = torch.full((b, ho, wo, round_up(c, 8) + wide), float('nan'), dtype=rt.TORCH_DTYPE[did], device=dev)
     keep = [_dev_vec(wp, dev), _dev_vec(pad(scale), dev), _dev_vec(pad(shift), dev)]
     op = rt.new_op(rt.OP_DEPTHWISE, act)
     op.dtype = op.out_dtype = did
@@ -240,7 +266,7 @@ def test_depthwise16(dev, dt, k, s, h, w, c, act):
     op.src[0] = rt.make_src(xd, c=c)
     op.wgt, op.scale, op.shift = [t.data_ptr() for t in keep]
     op.out, op.out_ld = out.data_ptr(), out.shape[3]
-    rt.run_op(op, b)
+    fence.run_op(op, b, writes=[out], reads=[xd] + keep, cols=round_up(c, 8))
     torch.cuda.synchronize()
     assert_rounded_once(from_dev16(out, dt, c), ref, dt, 'depthwise16 k%d s%d' % (k, s))
 
@@ -276,7 +302,7 @@ def test_stem16(dev, dt, cout, act, pairs):
         keep.append(_dev_vec(_stem_pairs(wp, scale, shift, ldw), dev))
         op.wgt2 = keep[-1].data_ptr()
     op.out, op.out_ld = out.data_ptr(), out.shape[3]
-    rt.run_op(op, b)
+    fence.run_op(op, b, writes=[out], reads=[xd] + keep)
     torch.cuda.synchronize()
     assert_rounded_once(from_dev16(out, dt, cout), ref, dt, 'stem16 %d' % cout)
 
@@ -304,7 +330,7 @@ def test_weighted_sum_and_gather16(dev, dt):
         op.src[i] = rt.make_src(t, c=c, xform=xf)
     op.wgt = ad.data_ptr()
     op.out, op.out_ld = out.data_ptr(), out.shape[3]
-    rt.run_op(op, b)
+    fence.run_op(op, b, writes=[out], reads=devs + [ad])
     torch.cuda.synchronize()
     assert_rounded_once(from_dev16(out, dt, c), ref, dt, 'wsum16')
     # gather: concat of three sources with ragged widths
@@ -320,7 +346,7 @@ def test_weighted_sum_and_gather16(dev, dt):
     for i, ((xf, a), t) in enumerate(zip(gs, gd)):
         op.src[i] = rt.make_src(t, c=a.shape[-1], xform=xf)
     op.out, op.out_ld = outg.data_ptr(), outg.shape[3]
-    rt.run_op(op, b)
+    fence.run_op(op, b, writes=[outg], reads=gd)
     torch.cuda.synchronize()
     assert np.array_equal(from_dev16(outg, dt, ctot), refg)
 
@@ -359,7 +385,7 @@ def test_squeeze_excite16(dev, dt, h, w, c, r, merged):
         op.nsrc = 1
         op.src[0] = src
         op.out, op.out_ld = mean_d.data_ptr(), ldc
-        rt.run_op(op, b)
+        fence.run_op(op, b, writes=[mean_d], reads=[xd])
         got_mean = mean_d.cpu().numpy().reshape(b, ldc)[:, :c]
         assert np.abs(got_mean - mean).max() <= 2e-6 * max(1.0, np.abs(mean).max())
         src = rt.make_src(mean_d, c=c)
@@ -372,7 +398,7 @@ def test_squeeze_excite16(dev, dt, h, w, c, r, merged):
     op.src[0] = src
     op.wgt, op.b1, op.wgt2, op.b2 = [t.data_ptr() for t in keep]
     op.out, op.out_ld = gate.data_ptr(), ldg
-    rt.run_op(op, b)
+    fence.run_op(op, b, writes=[gate], reads=[xd if merged else mean_d] + keep)
     torch.cuda.synchronize()
     g = gate.cpu().numpy()
     assert np.abs(g[:, :c] - ref).max() <= 2e-5
@@ -393,11 +419,11 @@ def test_dtype_mismatches_are_refused(dev):
     op.wgt = wgt.data_ptr()
     op.out, op.out_ld = out.data_ptr(), 16
     with pytest.raises(rt.YoloretHipError, match='out_dtype'):
-        rt.run_op(op, 1)
+        fence.run_op(op, 1, writes=[out], reads=[x, wgt])
     op.out_dtype = rt.DTYPE['bf16']
     op.src[0].dtype = rt.DTYPE['f32']
     with pytest.raises(rt.YoloretHipError, match='dtype'):
-        rt.run_op(op, 1)
+        fence.run_op(op, 1, writes=[out], reads=[x, wgt])
 
 
 # ------------------------------------------------------------------------------------------------ whole graph
@@ -590,7 +616,7 @@ def test_depthwise_se_form(dev, dt, k, s, h, w, c, r):
         op.out, op.out_ld = out.data_ptr(), ldc
         if gate is not None:
             op.gate, op.gate_ld, op.se_reduced = gate.data_ptr(), gate.shape[2], rows
-        rt.run_op(op, b)
+        fence.run_op(op, b, writes=[out] + ([gate] if gate is not None else []), reads=[xd] + keep)
         torch.cuda.synchronize()
         return out
     plain = dw()
@@ -630,7 +656,7 @@ def test_depthwise_se_form(dev, dt, k, s, h, w, c, r):
     op.src[0] = rt.make_src(part.view(b, rows, 1, ldc), c=c)
     op.wgt, op.b1, op.wgt2, op.b2 = [t.data_ptr() for t in k2]
     op.out, op.out_ld = gate.data_ptr(), ldc
-    rt.run_op(op, b)
+    fence.run_op(op, b, writes=[gate], reads=[part] + k2)
     torch.cuda.synchronize()
     assert np.abs(gate.cpu().numpy()[:, :c] - ref).max() <= 2e-5
 
@@ -668,7 +694,7 @@ def test_depthwise_walk_is_batch_independent(dev, dt):
             op.wgt, op.scale, op.shift = [t.data_ptr() for t in keep]
             op.out, op.out_ld = out.data_ptr(), c
             op.gate, op.gate_ld, op.se_reduced = part.data_ptr(), c, ntx * nty
-            rt.run_op(op, b)
+            fence.run_op(op, b, writes=[out, part], reads=[xd[:b]] + keep)
             torch.cuda.synchronize()
             return out, part
         out_big, part_big = run(big)
@@ -712,7 +738,7 @@ def test_depthwise_lds_form_geometry_mirror(dev):
             op.wgt, op.scale, op.shift = [t.data_ptr() for t in keep]
             op.out, op.out_ld = out.data_ptr(), c
             op.gate, op.gate_ld, op.se_reduced = part.data_ptr(), c, ntx * nty
-            rt.run_op(op, 1)     # raises if the launcher's tile differs from the mirror's
+            fence.run_op(op, 1, writes=[out, part], reads=[x] + keep)     # raises if the launcher's tile differs from the mirror's
             torch.cuda.synchronize()
             sums = part.sum(dim=1).double().cpu().numpy()
             ref = out.double().sum(dim=(1, 2)).cpu().numpy()

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from oracle import nn
+from tests import fence
 from tests.util import assert_close, from_dev, round_up, to_dev
 
 pytestmark = pytest.mark.gpu
@@ -42,7 +43,7 @@ def _src_dims(h, w, xf):
     return {'identity': (h, w), 'up2': (h // 2, w // 2), 'maxpool2': (h * 2, w * 2), 'maxpool4': (h * 4, w * 4)}[xf]
 
 
-def run_pointwise(dev, rng, b, h, w, segs, cout, act='none', bn=True, residual=False, gate=False, out_ld=None, cfg=0, ksplit=False, stream=False):
+def run_pointwise(dev, rng, b, h, w, segs, cout, act='none', bn=True, residual=False, gate=False, out_ld=None, cfg=0, ksplit=False, stream=False, f32_mfma=False):
     rt = _rt()
     srcs_np, srcs_dev = [], []
     for c, xf in segs:
@@ -101,8 +102,10 @@ def run_pointwise(dev, rng, b, h, w, segs, cout, act='none', bn=True, residual=F
     op.out, op.out_ld = out.data_ptr(), out_ld
     if ksplit:
         op.se_reduced |= rt.PWF_KSPLIT      # the k-split form of the few-image plans (pointwise_split.hip: pwk_kernel)
+    if f32_mfma:
+        op.se_reduced |= rt.PWF_F32_MFMA    # full-range operands on the float32 matrix pipe
     op.k = cfg            # 0: heuristic tile shape; 1..yr_pointwise_num_cfgs(): forced (15..: the LDS-free direct kernel)
-    rt.run_op(op, b)
+    fence.run_op(op, b, writes=[out], reads=srcs_dev + keep, cols=min(out_ld, round_up(cout, 4)))
     torch.cuda.synchronize()
     got = from_dev(out, cout)
     assert_close(got, ref, TOL, 'pointwise %s cfg %d' % (segs, cfg))
@@ -134,6 +137,19 @@ def test_pointwise(dev, case):
     h, w, segs, cout, act, bn, residual, gate, dense = case
     rng = np.random.default_rng(zlib.crc32(str(case).encode()))
     run_pointwise(dev, rng, 3, h, w, segs, cout, act, bn, residual, gate, out_ld=cout if dense else None)
+
+
+@pytest.mark.parametrize('form', ['split', 'f32_mfma', 'ksplit', 'stream'])
+@pytest.mark.parametrize('ci', [8, 9], ids=['pooled_and_partial_quad', 'gated_75_couts'])
+def test_pointwise_wide_rows(dev, ci, form):
+    """out_ld = padded width + two vectors: the elements past round_up(cout, 4) of every row keep their bytes, in the tiled split
+    form, on the float32 matrix pipe, in the k-split form and in the pixel-stationary form (which takes no pooled source)."""
+    h, w, segs, cout, act, bn, residual, gate, dense = PW_CASES[ci]
+    if form == 'stream' and any(xf.startswith('maxpool') for _, xf in segs):
+        segs = [(c, 'identity') for c, _ in segs]
+    rng = np.random.default_rng(zlib.crc32(str(PW_CASES[ci]).encode()))
+    run_pointwise(dev, rng, 3, h, w, segs, cout, act, bn, residual, gate, out_ld=round_up(cout, 4) + 8,
+                  ksplit=form == 'ksplit', stream=form == 'stream', f32_mfma=form == 'f32_mfma')
 
 
 @pytest.mark.parametrize('case', PW_CASES, ids=[str(i) for i in range(len(PW_CASES))])
@@ -194,7 +210,12 @@ def test_pointwise_stream_two_outputs(dev, shape, gated):
     _two_outputs(dev, shape, gated)
 
 
-def _two_outputs(dev, shape, gated):
+def test_pointwise_stream_two_outputs_wide_rows(dev):
+    """Both outputs with rows two vectors wider than their padded widths (the ragged small case, gated)."""
+    _two_outputs(dev, (8, 12, 40, 20, 48, 5), True, wide=8)
+
+
+def _two_outputs(dev, shape, gated, wide=0):
     """The two-output form (se_reduced bits 18 + 19: a head's y conv and the bottom-up path's down conv read the same gated map in ONE
     launch - first output dense and unpooled, second ReLU6 + MaxPooling2D(2)) == each conv run alone on the tiled split kernel, bit
     for bit (bu3_y + bu3_down_conv and bu2_y + bu2_down_conv of MobileNetV2 x0.75 @416, and a ragged small case)."""
@@ -224,7 +245,7 @@ def _two_outputs(dev, shape, gated):
         if gated:
             op.gate, op.gate_ld = g.data_ptr(), ld
         op.out, op.out_ld = out.data_ptr(), out_ld
-        rt.run_op(op, b)
+        fence.run_op(op, b, writes=[out], reads=[xd] + keep + ([g] if gated else []))
         torch.cuda.synchronize()
         return from_dev(out, n)
     ref1 = single(w1, sc1, sh1, n1, 'none', False, n1)
@@ -234,8 +255,9 @@ def _two_outputs(dev, shape, gated):
     planes = np.concatenate([compiler.head_pack(w1, [ld], nk=nk), compiler.head_pack(w2, [ld], nk=nk)])
     sc, sh = np.ones(16 * (ta + tb), np.float32), np.zeros(16 * (ta + tb), np.float32)
     sc[:n1], sc[16 * ta:16 * ta + n2], sh[:n1], sh[16 * ta:16 * ta + n2] = sc1, sc2, sh1, sh2
-    out1 = torch.full((b, h, w, n1), float('nan'), dtype=torch.float32, device=dev)
-    out2 = torch.full((b, h // 2, w // 2, round_up(n2, 4)), float('nan'), dtype=torch.float32, device=dev)
+    ld1, ld2 = (round_up(n1, 4) + wide if wide else n1), round_up(n2, 4) + wide      # (first output dense unless the rows are wide)
+    out1 = torch.full((b, h, w, ld1), float('nan'), dtype=torch.float32, device=dev)
+    out2 = torch.full((b, h // 2, w // 2, ld2), float('nan'), dtype=torch.float32, device=dev)
     op = rt.new_op(rt.OP_POINTWISE, 'none')
     op.h, op.w, op.cin, op.cout, op.nsrc = h, w, cin, n1, 1
     op.src[0] = rt.make_src(xd, c=cin)
@@ -243,10 +265,11 @@ def _two_outputs(dev, shape, gated):
     op.wgt, op.scale, op.shift = keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr()
     if gated:
         op.gate, op.gate_ld = g.data_ptr(), ld
-    op.out, op.out_ld = out1.data_ptr(), n1
-    op.gate_out, op.gate_out_ld, op.se_hidden, op.reserved0 = out2.data_ptr(), round_up(n2, 4), n2, rt.ACT['relu6'] | rt.PW2_POOLED
+    op.out, op.out_ld = out1.data_ptr(), ld1
+    op.gate_out, op.gate_out_ld, op.se_hidden, op.reserved0 = out2.data_ptr(), ld2, n2, rt.ACT['relu6'] | rt.PW2_POOLED
     op.se_reduced |= rt.PWF_STATIONARY | rt.PWF_TWO_OUT
-    rt.run_op(op, b)
+    fence.run_op(op, b, writes=[out1, out2], reads=[xd] + keep + ([g] if gated else []),
+                 cols=[min(ld1, round_up(n1, 4)), round_up(n2, 4)])
     torch.cuda.synchronize()
     assert np.array_equal(from_dev(out1, n1), ref1)
     assert np.array_equal(from_dev(out2, n2), ref2)
@@ -309,7 +332,7 @@ def test_pointwise_ksplit_pooled_output(dev):
             op.se_reduced |= rt.PWF_STATIONARY
         elif ks:
             op.se_reduced |= rt.PWF_KSPLIT
-        rt.run_op(op, b)
+        fence.run_op(op, b, writes=[out], reads=[xd] + keep)
         torch.cuda.synchronize()
         outs.append(from_dev(out, cout))
         assert_close(outs[-1], ref, TOL, 'pooled output, ksplit %s' % ks)
@@ -328,6 +351,16 @@ DW_CASES = [(3, 1, 13, 13, 24), (3, 2, 26, 26, 96), (3, 2, 14, 10, 144), (5, 1, 
 @pytest.mark.parametrize('k,s,h,w,c', DW_CASES)
 @pytest.mark.parametrize('act', ['relu6', 'swish'])
 def test_depthwise(dev, k, s, h, w, c, act):
+    _depthwise(dev, k, s, h, w, c, act)
+
+
+@pytest.mark.parametrize('k,s,h,w,c', [(3, 2, 14, 10, 144), (5, 2, 9, 9, 20), (3, 1, 7, 5, 75)])
+def test_depthwise_wide_rows(dev, k, s, h, w, c):
+    """out_ld two vectors wider than the padded width: the elements past round_up(c, 4) of every row keep their bytes."""
+    _depthwise(dev, k, s, h, w, c, 'relu6', wide=8)
+
+
+def _depthwise(dev, k, s, h, w, c, act, wide=0):
     rt = _rt()
     rng = np.random.default_rng(k * 1000 + s * 100 + h + c)
     b = 2
@@ -342,13 +375,13 @@ def test_depthwise(dev, k, s, h, w, c, act):
     wd[:, :c] = wk.reshape(k * k, c)
     keep = [_dev_vec(wd, dev), _dev_vec(scale, dev, ldc), _dev_vec(shift, dev, ldc)]
     ho, wo = ref.shape[1:3]
-    out = torch.full((b, ho, wo, ldc), float('nan'), dtype=torch.float32, device=dev)
+    out = torch.full((b, ho, wo, ldc + wide), float('nan'), dtype=torch.float32, device=dev)
     op = rt.new_op(rt.OP_DEPTHWISE, act)
     op.h, op.w, op.cin, op.cout, op.k, op.stride, op.nsrc = ho, wo, c, c, k, s, 1
     op.src[0] = rt.make_src(xd, c=c)
     op.wgt, op.scale, op.shift = keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr()
-    op.out, op.out_ld = out.data_ptr(), ldc
-    rt.run_op(op, b)
+    op.out, op.out_ld = out.data_ptr(), ldc + wide
+    fence.run_op(op, b, writes=[out], reads=[xd] + keep, cols=ldc)
     torch.cuda.synchronize()
     assert_close(from_dev(out, c), ref, TOL, 'depthwise')
 
@@ -387,7 +420,7 @@ def test_stem(dev, hw, cout, act, pairs):
         keep.append(_dev_vec(_stem_pairs(wd, scale, shift, ldw), dev))
         op.wgt2 = keep[-1].data_ptr()
     op.out, op.out_ld = out.data_ptr(), ldw
-    rt.run_op(op, b)
+    fence.run_op(op, b, writes=[out], reads=[xd] + keep)
     torch.cuda.synchronize()
     assert_close(from_dev(out, cout), ref, TOL, 'stem')
 
@@ -411,7 +444,7 @@ def test_squeeze_excite(dev, h, w, c, r):
     op.h, op.w, op.cin, op.cout, op.nsrc = 1, 1, c, c, 1
     op.src[0] = rt.make_src(xd, c=c)
     op.out, op.out_ld = md.data_ptr(), ldc
-    rt.run_op(op, b)
+    fence.run_op(op, b, writes=[md], reads=[xd])
     torch.cuda.synchronize()
     assert_close(from_dev(md, c), mean, TOL, 'se_mean')
     w1t = np.zeros((ldc, round_up(r, 4)), np.float32)      # (ABI 7: W1 [ldc][R4] - the Keras kernel as it is, b1 [R4])
@@ -425,14 +458,14 @@ def test_squeeze_excite(dev, h, w, c, r):
     op.src[0] = rt.make_src(md, c=c)
     op.wgt, op.b1, op.wgt2, op.b2 = [k.data_ptr() for k in keep]
     op.out, op.out_ld = gd.data_ptr(), ldc
-    rt.run_op(op, b)
+    fence.run_op(op, b, writes=[gd], reads=[md] + keep)
     torch.cuda.synchronize()
     assert_close(from_dev(gd, c), gate, TOL, 'se_fc')
     # the merged form (SE_FC pools the full map itself; its own fixed summation order)
     g2 = torch.full((b, 1, 1, ldc), float('nan'), dtype=torch.float32, device=dev)
     op.src[0] = rt.make_src(xd, c=c)
     op.out = g2.data_ptr()
-    rt.run_op(op, b)
+    fence.run_op(op, b, writes=[g2], reads=[xd] + keep)
     torch.cuda.synchronize()
     assert_close(from_dev(g2, c), gate, TOL, 'se_fc with the mean merged in')
 
@@ -457,7 +490,7 @@ def test_weighted_sum_bit_exact(dev):
         op.src[i] = rt.make_src(t, c=c, xform=xf)
     op.wgt = ad.data_ptr()
     op.out, op.out_ld = out.data_ptr(), c
-    rt.run_op(op, b)
+    fence.run_op(op, b, writes=[out], reads=ts + [ad])
     torch.cuda.synchronize()
     assert np.array_equal(from_dev(out), ref)
 
@@ -481,7 +514,7 @@ def test_gather_concat_bit_exact(dev):
     for i, (t, (c, xf)) in enumerate(zip(ts, segs)):
         op.src[i] = rt.make_src(t, c=c, xform=xf)
     op.out, op.out_ld = out.data_ptr(), ctot
-    rt.run_op(op, b)
+    fence.run_op(op, b, writes=[out], reads=ts)
     torch.cuda.synchronize()
     assert np.array_equal(from_dev(out), ref)
 
@@ -494,13 +527,13 @@ def test_bad_arguments_report_errors(dev):
     rc = rt.lib().yr_op_run(ctypes.byref(op), 1, None)
     assert rc == -1 and b'nsrc' in rt.lib().yr_last_error()
     with pytest.raises(rt.YoloretHipError):
-        rt.run_op(op, 1)
+        fence.run_op(op, 1, writes=[], reads=[])
     x = torch.zeros((1, 4, 4, 6), device=dev)  # ld not a multiple of 4
     op = rt.new_op(rt.OP_POINTWISE)
     op.h, op.w, op.cin, op.cout, op.nsrc = 4, 4, 6, 8, 1
     op.src[0] = rt.make_src(x, c=6)
     with pytest.raises(rt.YoloretHipError, match='multiple of 4'):
-        rt.run_op(op, 1)
+        fence.run_op(op, 1, writes=[], reads=[x])
 
 
 def test_removed_op_kind_is_refused(dev):

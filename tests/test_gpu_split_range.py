@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import fence
 from tests.util import from_dev, round_up, to_dev
 from tests.test_gpu_ops import _dev_vec
 
@@ -85,7 +86,7 @@ def test_pointwise_split_vs_fp32_mfma(dev, shape, kind):
         op.wgt = keep[0].data_ptr()
         op.out, op.out_ld = out.data_ptr(), round_up(cout, 4)
         op.se_reduced = {'split': 0, 'ksplit': rt.PWF_KSPLIT, 'fp32': rt.PWF_F32_MFMA}[form]
-        rt.run_op(op, b)
+        fence.run_op(op, b, writes=[out], reads=devs + keep)
         torch.cuda.synchronize()
         errs[form] = err_vs_fp64(from_dev(out, cout), ref)
     check_pair(errs['split'], errs['fp32'], 'pointwise %s %s' % (shape, kind))
@@ -118,7 +119,7 @@ def test_mbr_split_vs_fp32_mfma(dev, case, kind):
         ref = t @ wp.astype(np.float64) * sp + hp
         if residual:
             ref = ref + x64
-        rt.run_op(op, b)
+        fence.run_op(op, b, writes=[out], reads=keep[:-1] + [xd])
         torch.cuda.synchronize()
         errs[form] = err_vs_fp64(from_dev(out), ref)
     check_pair(errs['split'], errs['fp32'], 'mbr %s %s' % (case, kind))
@@ -160,7 +161,7 @@ def test_head_forms_under_adversarial_ranges(dev, kind):
             op.src[i] = rt.make_src(t, c=c, xform=xf)
         op.wgt, op.scale, op.shift = [k_.data_ptr() for k_ in keep]
         op.out, op.out_ld = e.data_ptr(), f
-        rt.run_op(op, b)
+        fence.run_op(op, b, writes=[e], reads=devs + keep)
         dwk = np.zeros((9, f), np.float32)
         dwk[:] = L['dk'].reshape(9, f)
         k2 = [_dev_vec(dwk, dev), _dev_vec(L['ds'], dev), _dev_vec(L['dh'], dev)]
@@ -170,7 +171,7 @@ def test_head_forms_under_adversarial_ranges(dev, kind):
         op2.src[0] = rt.make_src(e, c=f)
         op2.wgt, op2.scale, op2.shift = [k_.data_ptr() for k_ in k2]
         op2.out, op2.out_ld = y.data_ptr(), f
-        rt.run_op(op2, b)
+        fence.run_op(op2, b, writes=[y], reads=[e] + k2)
         torch.cuda.synchronize()
         check_pair(err_vs_fp64(got, ref), err_vs_fp64(from_dev(y), ref), 'head %s %s' % (form, kind))
 

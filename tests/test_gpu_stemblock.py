@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from oracle import nn
+from tests import fence
 from tests.util import assert_close, assert_rounded_once, from_dev, from_dev16, round_up
 
 pytestmark = pytest.mark.gpu
@@ -29,6 +30,16 @@ CASES = [((64, 64), 24, 16, 'relu6'), ((416, 416), 24, 16, 'relu6'), ((32, 96), 
 @pytest.mark.parametrize('hw,c1,cout,act', CASES)
 def test_stemblock(dev, hw, c1, cout, act, dt):
     """dt: element type of the OUTPUT map (the image is float32 in every plan)."""
+    _stemblock(dev, hw, c1, cout, act, dt)
+
+
+@pytest.mark.parametrize('dt', ['f32', 'bf16', 'f16'])
+def test_stemblock_wide_rows(dev, dt):
+    """out_ld two vectors wider than the padded width (odd map, ragged tiles): the elements past it keep their bytes in every row."""
+    _stemblock(dev, *CASES[4], dt, wide=True)
+
+
+def _stemblock(dev, hw, c1, cout, act, dt, wide=False):
     from yoloret_amd import runtime as rt
     rng = np.random.default_rng(zlib.crc32(str((hw, c1, cout)).encode()))
     b = 2
@@ -58,6 +69,9 @@ def test_stemblock(dev, hw, c1, cout, act, dt):
     xd = torch.from_numpy(x).to(dev)
     if dt != 'f32':
         ldo = round_up(cout, 8)
+    cols = ldo
+    if wide:
+        ldo += 2 * rt.VEC[rt.dtype_id(dt)]
     out = torch.full((b, ref.shape[1], ref.shape[2], ldo), float('nan'), dtype=rt.TORCH_DTYPE[rt.dtype_id(dt)], device=dev)
     op = rt.new_op(rt.OP_STEMBLOCK, act)
     op.dtype = op.out_dtype = rt.dtype_id(dt)
@@ -65,7 +79,7 @@ def test_stemblock(dev, hw, c1, cout, act, dt):
     op.src[0] = rt.make_src(xd, c=3, ld=3)
     op.wgt, op.wgt2, op.b1, op.b2 = [k.data_ptr() for k in keep]
     op.out, op.out_ld = out.data_ptr(), ldo
-    rt.run_op(op, b)
+    fence.run_op(op, b, writes=[out], reads=[xd] + keep, cols=cols)
     torch.cuda.synchronize()
     if dt == 'f32':
         assert_close(from_dev(out, cout), ref, 3e-5, 'stemblock')
@@ -120,7 +134,7 @@ def test_stem_plus_depthwise(dev, hw, c1, act, with_sums, dt):
     op.out, op.out_ld = out.data_ptr(), ldo
     if with_sums:
         op.gate, op.gate_ld = part.data_ptr(), ldo
-    rt.run_op(op, b)
+    fence.run_op(op, b, writes=[out] + ([part] if with_sums else []), reads=[xd] + keep)
     torch.cuda.synchronize()
     got = from_dev(out, c1) if dt == 'f32' else from_dev16(out, dt, c1)
     if dt == 'f32':
@@ -191,7 +205,7 @@ def test_stemblock_matrix_pipe(dev, hw, c1, cout, act, dt, u8):
     op.src[0] = rt.make_src(xd, c=3, ld=3)
     op.wgt, op.scale, op.shift, op.wgt2, op.b1, op.b2 = [k.data_ptr() for k in keep]
     op.out, op.out_ld = out.data_ptr(), ldo
-    rt.run_op(op, b)
+    fence.run_op(op, b, writes=[out], reads=[xd] + keep)
     torch.cuda.synchronize()
     got = from_dev16(out, dt, cout)
     err = np.abs(got.astype(np.float64) - ref) / np.maximum(1.0, np.abs(ref))

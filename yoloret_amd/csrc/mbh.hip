@@ -645,6 +645,9 @@ static int launch_mbh_t(const yr_op& op_in, int batch, hipStream_t s) {
         // no forced tile: it is the default where it is built (YOLORET_MBXR=0: the LDS-tiled form below, for A/B runs)
         if (!legacy && yr_mbh_prefers_chained(op) && yr_mbxr_takes(op)) return yr_launch_mbxr(op, batch, fth == YR_MBH_TILE_CHAINED ? ftw : 0, s);
         YR_REQUIRE(fth != YR_MBH_TILE_CHAINED, "mbx: the register-chained form (tile 255) is not built for this op");
+        // the LDS-tiled kernel masks its channel quads by ld_out: in a wider row it would also write the zero quads of the last
+        // 32-channel chunk behind round_up(cout, 8)
+        YR_REQUIRE(op.out_ld == yr_round_up(op.cout, 8), "mbx: the LDS-tiled form needs out_ld == round_up(cout, 8) (%d, not %d)", yr_round_up(op.cout, 8), op.out_ld);
     }
     const int cp = !full ? 0 : op.cout <= 32 ? 1 : (op.cout <= 64 ? 2 : 4);
     if (fth && ftw) { a.th = fth; a.tw = ftw; }
