@@ -19,8 +19,17 @@ constexpr int pws_min_blocks(int pt, int ct) {
     return tiles >= 16 ? 1 : (tiles >= 8 || (pt == 4 && ct == 1)) ? 2 : tiles >= 4 ? 3 : 4;   // (256 x 16: eight fetch passes in two register sets)
 }
 
-template <int PT, int CT, int WM, int WN, bool SIMPLE>
+// taps of a 4 x 4-pooled source's window in flight at once (PwRow::issue): all sixteen where a thread fetches two pixel rows per
+// chunk and the tile shape's register budget (pws_min_blocks) has room for them, else a 4-pixel run at a time
+#ifndef PWS_POOL_TAPS
+#define PWS_POOL_TAPS(pt, ct) ((pt) == 1 && (ct) >= 4 ? 16 : 4)
+#endif
+
+// POOLED (gathering form only): a source is read through a 2 x 2 or 4 x 4 maximum.  An instantiation of its own: the window taps
+// in flight take registers that the other ops of the same tile shape then do not pay for with a wave per SIMD.
+template <int PT, int CT, int WM, int WN, bool SIMPLE, bool POOLED = false>
 __global__ __launch_bounds__(256, pws_min_blocks(PT, CT)) void pws_kernel(PwArgs a) {
+    static_assert(!(SIMPLE && POOLED), "a single identity source is not pooled");
     constexpr bool DW = false;
     constexpr int BM = 16 * PT * WM;
     constexpr int BN = 16 * CT * WN;
@@ -74,7 +83,7 @@ __global__ __launch_bounds__(256, pws_min_blocks(PT, CT)) void pws_kernel(PwArgs
     for (int c = 0; c < CT; ++c)
 #pragma unroll
         for (int p = 0; p < PT; ++p) { acc[c][p] = (f32x4){0.f, 0.f, 0.f, 0.f}; ac1[c][p] = acc[c][p]; }
-    pws_k_loop<256, PT, CT, WM, WN, MODE, A_PASSES, B_PASSES>(a, row, brow, gated, lds, acc, ac1);
+    pws_k_loop<256, PT, CT, WM, WN, MODE, A_PASSES, B_PASSES, (POOLED ? 1 : 2), PWS_POOL_TAPS(PT, CT)>(a, row, brow, gated, lds, acc, ac1);
 
     // ---- epilogue: (pre-BN addend,) BN scale/shift, activation, (residual,) (2x2 max,) store: 4 consecutive couts
     // per lane.  Branches are uniform or guard stores only; every load is unconditional (pw_load_quad): a load under
@@ -104,7 +113,10 @@ static int launch_split_cfg(const PwArgs& a, hipStream_t s) {
                               snprintf(nm[1], sizeof(nm[1]), "pws_kernel<%d,%d,%d,%d,1>", PT, CT, WM, WN);
     (void)nm_len;
     yr_note_kernel(nm[simple ? 1 : 0]);
+    bool pooled = false;
+    for (int i = 0; i < a.S.n; ++i) pooled |= a.S.s[i].xform == YR_X_MAXPOOL2 || a.S.s[i].xform == YR_X_MAXPOOL4;
     if (simple) hipLaunchKernelGGL((pws_kernel<PT, CT, WM, WN, true>), grid, dim3(256), 0, s, a);
+    else if (pooled) hipLaunchKernelGGL((pws_kernel<PT, CT, WM, WN, false, true>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((pws_kernel<PT, CT, WM, WN, false>), grid, dim3(256), 0, s, a);
     YR_LAUNCH_CHECK();
     return YR_OK;

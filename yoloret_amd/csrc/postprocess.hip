@@ -8,6 +8,8 @@
 // are bit-identical to the C oracle (oracle/csrc/yr_oracle.c) on identical logits.
 #include "yr_common.h"
 #include <cstdlib>
+#include <type_traits>
+#include <utility>
 
 // ------------------------------------------------------------------ letterbox inverse terms
 struct Letterbox {
@@ -515,10 +517,13 @@ __global__ __launch_bounds__(T) void nms_lazy_kernel(NmsLazyArgs L) {
 // Band-wise lazy greedy NMS: the first launch of yr_nms.  Greedy NMS pops candidates in descending (score, then
 // ascending index) order and tests each only against the boxes selected so far, so only the top of the order ever
 // matters - typically a few more entries than max_boxes.  One workgroup of T lanes per (image, class):
-//   1. every lane reads its <= SR scores ONCE into registers; candidates (score > thr) go into a 2048-bin histogram
-//      of the scores (linear in [thr, 1], monotone in the score) in LDS;
+//   1. every lane reads its <= SR scores ONCE and keeps, per score, its bin in a 2048-bin histogram of the scores (linear in
+//      [thr, 1], monotone in the score) - 16 bits, two per register, a sentinel for "not a candidate" (score <= thr): SR / 2
+//      registers.  (SR floats did not stay in registers: 196 bytes of private memory per lane, 63 MB written per 1280 problems.)
+//      The candidates' bins are counted into the histogram in LDS;
 //   2. a BAND is the widest run of bins below the previous band that holds <= 64 (then 128, ... T) candidates (found
-//      from a block-wide scan of the histogram).  Its candidates are compacted from the registers (one per lane), every lane fetches
+//      from a block-wide scan of the histogram).  Its candidates are found from the bins in the registers and compacted (about one
+//      per lane: only these scores are read again, from L2), every lane fetches
 //      its box and computes the rank of its entry among the band's by (score desc, index asc) - T broadcast reads,
 //      no sort, no barrier - and scatters (box, index) to that rank;
 //   3. wave 0 walks the ranked band: entry r is selected unless its IoU with an already selected box exceeds the
@@ -529,6 +534,16 @@ __global__ __launch_bounds__(T) void nms_lazy_kernel(NmsLazyArgs L) {
 // the second pass) built and insertion-sorted a list of up to 5200 candidates and found every pick by a block-wide
 // arg-max with three barriers: ~100 us per problem, latency-bound; this one is ~10 us.  A problem whose next bin alone
 // holds more than a band's capacity (a mass of equal scores) is flagged (count = -1) for the second pass.
+template <class F, int... I>
+__device__ __forceinline__ void nms_unroll_impl(F& f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N-1>): the register array's indices are constants for the front end
+template <int N, class F>
+__device__ __forceinline__ void nms_unroll(F f) {
+    nms_unroll_impl(f, std::make_integer_sequence<int, N>{});
+}
+
 template <int T, int SR>
 #ifndef NMS_BAND_WPE
 #define NMS_BAND_WPE 5
@@ -555,21 +570,29 @@ __global__ __launch_bounds__(T, (T <= 256 ? NMS_BAND_WPE : 4)) void nms_band_ker
     const float scale = (float)NB / (1.0f - thr);
     auto bin_of = [&](float v) { const int q = (int)((v - thr) * scale); return q < 0 ? 0 : (q > NB - 1 ? NB - 1 : q); };
 
-    float sreg[SR];
-#pragma unroll
-    for (int u = 0; u < SR; ++u) {
-        const int i = u * T + tid;
-        const float v = sc[i < a.N ? i : a.N - 1];   // (clamped, unconditional: all SR loads in flight at once - written
-        sreg[u] = i < a.N ? v : thr;                 //  as a branch per load they ran one HBM round trip after the other)
-                                                     // thr itself is not a candidate
-    }
+    // per score its BIN, not the float: two 16-bit bins per register (SR / 2 registers; SR floats did not fit beside the unrolled
+    // bodies' temporaries and lived in private memory).  NOBIN: not a candidate.  The float itself is needed only by the <= T
+    // members of a band and is read again from sc[] when they are compacted.
+    static_assert(SR % 2 == 0 && SR <= 64, "two bins per register; one mask bit per score slot");
+    constexpr unsigned NOBIN = 0xffffu;
+    unsigned sbin[SR / 2];
+    nms_unroll<SR / 2>([&](auto U) __attribute__((always_inline)) {
+        constexpr int u = decltype(U)::value;
+        const int i0 = (2 * u) * T + tid, i1 = (2 * u + 1) * T + tid;
+        const float v0 = sc[i0 < a.N ? i0 : a.N - 1];   // (clamped, unconditional: all SR loads in flight at once - written
+        const float v1 = sc[i1 < a.N ? i1 : a.N - 1];   //  as a branch per load they ran one HBM round trip after the other)
+        const unsigned q0 = (i0 < a.N && v0 > thr) ? (unsigned)bin_of(v0) : NOBIN;   // thr itself is not a candidate
+        const unsigned q1 = (i1 < a.N && v1 > thr) ? (unsigned)bin_of(v1) : NOBIN;
+        sbin[u] = q0 | (q1 << 16);
+    });
     for (int i = tid; i < NB; i += T) hist[i] = 0u;
     __syncthreads();
-#pragma unroll
-    for (int u = 0; u < SR; ++u) {
-        if (sreg[u] > thr) atomicAdd(&hist[bin_of(sreg[u])], 1u);
-        if ((u & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // (keeps the unrolled bodies from piling up their temporaries)
-    }
+    nms_unroll<SR / 2>([&](auto U) __attribute__((always_inline)) {
+        constexpr int u = decltype(U)::value;
+        const unsigned q0 = sbin[u] & 0xffffu, q1 = sbin[u] >> 16;
+        if (q0 != NOBIN) atomicAdd(&hist[q0], 1u);
+        if (q1 != NOBIN) atomicAdd(&hist[q1], 1u);
+    });
     __syncthreads();
     // inclusive scan over the lanes of the per-lane bin sums (descending bins)
     int mine = 0;
@@ -614,16 +637,13 @@ __global__ __launch_bounds__(T, (T <= 256 ? NMS_BAND_WPE : 4)) void nms_band_ker
             return;
         }
         {   // compact the band from the registers: per-lane count, wave scan, ONE LDS atomic per wave, then the writes
-            static_assert(SR <= 64, "one mask bit per score register");
-            unsigned long long km = 0ull;
-#pragma unroll
-            for (int u = 0; u < SR; ++u) {
-                const float v = sreg[u];
-                bool keep = v > thr;
-                if (keep) { const int q = bin_of(v); keep = q >= lo && q < hi; }
-                km |= (unsigned long long)(keep ? 1 : 0) << u;
-                if ((u & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-            }
+            unsigned long long km = 0ull;    // bit s: score slot s (box s * T + tid) lies in the band
+            nms_unroll<SR / 2>([&](auto U) __attribute__((always_inline)) {
+                constexpr int u = decltype(U)::value;
+                const int q0 = (int)(sbin[u] & 0xffffu), q1 = (int)(sbin[u] >> 16);   // (NOBIN >= NB >= hi: never in a band)
+                km |= (unsigned long long)((q0 >= lo && q0 < hi) ? 1 : 0) << (2 * u);
+                km |= (unsigned long long)((q1 >= lo && q1 < hi) ? 1 : 0) << (2 * u + 1);
+            });
             const int mycnt = __popcll(km);
             int incl2 = mycnt;
 #pragma unroll
@@ -635,9 +655,11 @@ __global__ __launch_bounds__(T, (T <= 256 ? NMS_BAND_WPE : 4)) void nms_band_ker
             if (lane == 63 && incl2 > 0) wbase = atomicAdd(&cnt, incl2);
             wbase = __shfl(wbase, 63);
             int pos = wbase + incl2 - mycnt;
-#pragma unroll
-            for (int u = 0; u < SR; ++u)
-                if ((km >> u) & 1ull) { ks[pos] = sreg[u]; ki[pos] = u * T + tid; ++pos; }
+            while (km) {                     // slots ascending, as before; the members' scores come from sc[] again (<= T per band)
+                const int i = __builtin_ctzll(km) * T + tid;
+                km &= km - 1ull;
+                ks[pos] = sc[i]; ki[pos] = i; ++pos;
+            }
         }
         __syncthreads();
         const int n = cnt;                   // 1 <= n <= T

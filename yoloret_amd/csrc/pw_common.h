@@ -204,7 +204,8 @@ struct PwRow {
     // s_waitcnt insertion must assume the path that issued none and emits vmcnt(0), which serialises every
     // prefetch behind the newest load; only the extra taps of pooled sources stay conditional here.
     // POOLS = false promises that no source is pooled (the caller checked): the code is then straight-line.
-    template <bool POOLS = true>
+    // TAPS: how many taps of a 4 x 4 window are in flight at once (1: one after the other)
+    template <bool POOLS = true, int TAPS = 1>
     __device__ __forceinline__ void issue(const PwArgs& a, int kraw, int kp, float4& v, float4& gt, int& cv) const {
         const int k = kraw < kp ? kraw : kp - 4;
         int cvalid;
@@ -250,10 +251,30 @@ struct PwRow {
                 const float4 v2 = pw_ldg(q, ((size_t)sw * sld) >> 2);
                 const float4 v3 = pw_ldg(q, (((size_t)sw + 1) * sld) >> 2);
                 v = yr_max4(yr_max4(v, v1), yr_max4(v2, v3));
-            } else if (xf == YR_X_MAXPOOL4) {
-                for (int dy = 0; dy < 4; ++dy)
-                    for (int dx = 0; dx < 4; ++dx)
-                        v = yr_max4(v, pw_ldg(q, (((size_t)dy * sw + dx) * sld) >> 2));
+            } else if (xf == YR_X_MAXPOOL4 && (TAPS == 1 || kraw < kp)) {   // (TAPS > 1: a quad beyond kp - the k tail, a dead chunk - is zeroed through cv, its window is not fetched)
+                // TAPS of the window's sixteen taps are issued before their first maximum - 16: ONE round trip and the window's four
+                // 4-pixel runs asked for together; 4: a run per round trip - where the kernel has the registers for them (TAPS x 4).
+                // The maxima are taken in the order they always were - from tap (0,0), dy-major, dx-minor -, so signed zeros come out
+                // as before; the addresses are the same sixteen.
+                if constexpr (TAPS > 1) {
+                    static_assert(16 % TAPS == 0, "whole groups of taps");
+                    pw_unroll<16 / TAPS>([&](auto G) __attribute__((always_inline)) {
+                        constexpr int g = decltype(G)::value;
+                        float4 t[TAPS];
+                        pw_unroll<TAPS>([&](auto I) __attribute__((always_inline)) {
+                            constexpr int i = g * TAPS + decltype(I)::value;
+                            t[i - g * TAPS] = pw_ldg(q, (((size_t)(i >> 2) * sw + (i & 3)) * sld) >> 2);
+                        });
+                        pw_unroll<TAPS>([&](auto I) __attribute__((always_inline)) {
+                            constexpr int i = decltype(I)::value;
+                            v = yr_max4(v, t[i]);
+                        });
+                    });
+                } else {
+                    for (int dy = 0; dy < 4; ++dy)
+                        for (int dx = 0; dx < 4; ++dx)
+                            v = yr_max4(v, pw_ldg(q, (((size_t)dy * sw + dx) * sld) >> 2));
+                }
             }
         }
         cv = (valid && kraw < kp) ? cvalid : 0;

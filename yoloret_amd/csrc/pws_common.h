@@ -34,7 +34,9 @@ __device__ __forceinline__ f32x4 pws_mfma(pws_u4 a, pws_u4 b, f32x4 c) {
 // The whole k loop of one workgroup tile.  NTH threads = WM x WN waves, each PT x CT MFMA tiles; row[] / brow[]: the activation
 // rows and weight rows this thread fetches (pass p: tile row lr + p * (NTH / 8)); lds: 2 * (BM + BN) * PWS_LD halves.
 // acc / ac1: h h' | h m' + m h' (the caller joins them with 2^-11).  Ends with a barrier: the LDS may be reused at once.
-template <int NTH, int PT, int CT, int WM, int WN, int MODE, int A_PASSES, int B_PASSES>
+// POOL_SEL: 0 = the loop is built with and without support for pooled sources and picks at run time; 1 / 2 = the caller knows that a
+// source is pooled / that none is (pws_kernel: an instantiation each, so that neither pays for the other's registers).  TAPS: PwRow::issue.
+template <int NTH, int PT, int CT, int WM, int WN, int MODE, int A_PASSES, int B_PASSES, int POOL_SEL = 0, int TAPS = 1>
 __device__ __forceinline__ void pws_k_loop(const PwArgs& a, PwRow<MODE> (&row)[A_PASSES], const float* (&brow)[B_PASSES], const bool gated,
                                            _Float16* lds, f32x4 (&acc)[CT][PT], f32x4 (&ac1)[CT][PT]) {
     constexpr int RPP = NTH / PWS_KQ;     // rows loaded per pass of the NTH threads
@@ -67,7 +69,7 @@ __device__ __forceinline__ void pws_k_loop(const PwArgs& a, PwRow<MODE> (&row)[A
             const int k = kraw < kp ? kraw : kp - 4;
             pw_unroll<A_PASSES>([&](auto P) __attribute__((always_inline)) {
                 constexpr int p = decltype(P)::value;
-                row[p].template issue<POOLS>(a, kraw, kp, R.ra[p][0], R.rg[p], R.cv[p]);
+                row[p].template issue<POOLS, TAPS>(a, kraw, kp, R.ra[p][0], R.rg[p], R.cv[p]);
             });
             pw_unroll<B_PASSES>([&](auto P) __attribute__((always_inline)) {
                 constexpr int p = decltype(P)::value;
@@ -137,12 +139,16 @@ __device__ __forceinline__ void pws_k_loop(const PwArgs& a, PwRow<MODE> (&row)[A
             for (int k0 = 0; k0 < kp; k0 += PWS_BK) step(k0, R0, true);
         }
     };
-    bool pooled = false;
-    if (MODE == 0) {
+    if constexpr (POOL_SEL == 1) {
+        k_loop(std::true_type{});
+    } else if constexpr (POOL_SEL == 2 || MODE != 0) {
+        k_loop(std::false_type{});
+    } else {
+        bool pooled = false;
 #pragma unroll
         for (int i = 0; i < YR_MAX_SRC; ++i)
             pooled |= a.S.s[i].xform == YR_X_MAXPOOL2 || a.S.s[i].xform == YR_X_MAXPOOL4;
+        if (pooled) k_loop(std::true_type{});
+        else k_loop(std::false_type{});
     }
-    if (pooled) k_loop(std::true_type{});
-    else k_loop(std::false_type{});
 }
