@@ -529,6 +529,28 @@ int yr_yolo_loss(const float* feats, const float* y_true, int batch, int gh, int
                  float ignore_thresh, void* workspace, size_t workspace_bytes,
                  float* out5 /*device*/, void* stream);
 
+/* ---- VOC matching of detections to ground truth: the greedy loop of MAPCallback.calculate_aps (code/yolo3/map.py:157-215)
+ * on the device, per image; added under ABI 9 (additive: no struct or existing entry changed).
+ *   det [B,rows,6], det_count [B]   exactly what yr_pack_detections writes; only the first det_count[b] rows of image b
+ *                                   are read, in any order (rows of a class need not be contiguous or sorted)
+ *   gt [B,max_gt,5] float32         (xmin, ymin, xmax, ymax, label): the label file's order; the first gt_count[b] [B]
+ *                                   rows of image b are read.  max_gt may be 0, gt then null
+ *   flags [B,rows] int32            1 true positive, 0 false positive; -1 for rows at or beyond det_count[b] and for rows
+ *                                   whose class is outside [0, num_classes)
+ *   npos [B,num_classes] int32      valid ground-truth rows of image b with label == class (labels outside the range or
+ *                                   with a fractional part count nowhere)
+ * Rule, per (image, class): detections in score order (float32 values, descending; ties by lower row index); the best box
+ * is the ground-truth row of that class with the largest IoU (VOC +1 convention, float64, ties to the lowest index), chosen
+ * before the claim check; true positive iff IoU > iou_thr (strict) and the box is unclaimed, which claims it.  Since a
+ * detection only competes inside its image and class, these are the verdicts of the reference's pass over the data set.
+ * Scores and coordinates must be finite, and max >= min on both axes of every box.  One launch on `stream`, no workspace,
+ * no host synchronisation; the same call gives the same bytes. */
+#define YR_VOC_MAX_ROWS 4096   /* rows per image (C * max_boxes; the reference's largest is 80 * 20) */
+#define YR_VOC_MAX_GT   512    /* padded ground-truth rows per image */
+int yr_voc_match(const int32_t* det, const int32_t* det_count, int batch, int rows, int num_classes,
+                 const float* gt, const int32_t* gt_count, int max_gt, double iou_thr,
+                 int32_t* flags, int32_t* npos, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

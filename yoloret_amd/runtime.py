@@ -106,7 +106,7 @@ class YrBuf(ctypes.Structure):
 ABI_VERSION = 9   # == YR_ABI_VERSION of include/yoloret_hip.h
 EXPORTS = ['yr_last_error', 'yr_abi_version', 'yr_abi_sizeof', 'yr_create', 'yr_create_from_blob', 'yr_plan_io_dims', 'yr_destroy', 'yr_load_weights', 'yr_workspace_bytes',
            'yr_forward', 'yr_forward_profile', 'yr_forward_ranges', 'yr_autotune', 'yr_get_tuning', 'yr_set_tuning', 'yr_plan_num_launches', 'yr_op_run', 'yr_head_regions', 'yr_head_walk_rows', 'yr_head_stream_rows', 'yr_pwt_chunks', 'yr_decode', 'yr_decode_zoom', 'yr_yolo_head', 'yr_correct_boxes',
-           'yr_nms', 'yr_pack_detections', 'yr_letterbox', 'yr_letterbox_batch', 'yr_yolo_loss_workspace_bytes', 'yr_yolo_loss']
+           'yr_nms', 'yr_pack_detections', 'yr_letterbox', 'yr_letterbox_batch', 'yr_yolo_loss_workspace_bytes', 'yr_yolo_loss', 'yr_voc_match']
 
 _lib = None
 
@@ -168,6 +168,8 @@ def lib():
         L.yr_yolo_loss.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                                                             ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t,
                                                                                             ctypes.c_void_p, ctypes.c_void_p]
+        L.yr_voc_match.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                                                            ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         if L.yr_abi_version() != ABI_VERSION:
             raise YoloretHipError('libyoloret_hip.so ABI version mismatch')
         L.yr_abi_sizeof.argtypes = [ctypes.c_int]
@@ -380,6 +382,45 @@ def yolo_loss(feats, y_true, anchors, input_hw, ignore_thresh=.5, workspace=None
                                  int(input_hw[0]), int(input_hw[1]), float(ignore_thresh), _ptr(ws), ws.numel(), _ptr(out),
                                  stream_ptr(dev)))
     return out
+
+
+VOC_MAX_ROWS, VOC_MAX_GT = 4096, 512     # YR_VOC_MAX_ROWS, YR_VOC_MAX_GT of include/yoloret_hip.h
+
+
+def _is_cuda_i32(t):
+    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
+
+
+def voc_match(det, det_count, gt, gt_count, num_classes, iou=.5):
+    """VOC matching of packed detections to ground truth, per image (the greedy loop of reference map.py:157-215 on the device).
+    det [B,rows,6] int32, det_count [B] int32: what pack_detections returns; gt [B,G,5] float32 rows (xmin, ymin, xmax, ymax,
+    label) of which the first gt_count[b] [B] int32 are valid (G may be 0) -> flags [B,rows] int32 (1 true positive, 0 false
+    positive, -1 no verdict: beyond det_count or class outside [0, num_classes)), npos [B,num_classes] int32.  Launches only."""
+    shapes = 'det %s, det_count %s, gt %s, gt_count %s' % tuple(tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
+                                                                for t in (det, det_count, gt, gt_count))
+    if not (_is_cuda_i32(det) and _is_cuda_i32(det_count) and _is_cuda_i32(gt_count)):
+        raise ValueError('voc_match: det, det_count and gt_count must be contiguous int32 CUDA tensors (%s)' % shapes)
+    if not (isinstance(gt, torch.Tensor) and gt.is_cuda and gt.dtype == torch.float32 and gt.is_contiguous()):
+        raise ValueError('voc_match: gt must be a contiguous float32 CUDA tensor (%s)' % shapes)
+    if det.dim() != 3 or det.shape[2] != 6 or det.shape[0] < 1 or not 1 <= det.shape[1] <= VOC_MAX_ROWS:
+        raise ValueError('voc_match: det must be [B,rows,6] with B >= 1 and 1 <= rows <= %d (%s)' % (VOC_MAX_ROWS, shapes))
+    b, rows = det.shape[0], det.shape[1]
+    if gt.dim() != 3 or gt.shape[0] != b or gt.shape[2] != 5 or gt.shape[1] > VOC_MAX_GT:
+        raise ValueError('voc_match: gt must be [B=%d,G,5] with G <= %d (%s)' % (b, VOC_MAX_GT, shapes))
+    if tuple(det_count.shape) != (b,) or tuple(gt_count.shape) != (b,):
+        raise ValueError('voc_match: det_count and gt_count must be [B=%d] (%s)' % (b, shapes))
+    if int(num_classes) < 1:
+        raise ValueError('voc_match: num_classes must be at least 1, not %d' % num_classes)
+    dev = det.device
+    if not (det_count.device == dev and gt.device == dev and gt_count.device == dev):
+        raise ValueError('voc_match: det on %s, det_count on %s, gt on %s, gt_count on %s: one device expected (%s)'
+                         % (dev, det_count.device, gt.device, gt_count.device, shapes))
+    flags = torch.empty((b, rows), dtype=torch.int32, device=dev)
+    npos = torch.empty((b, int(num_classes)), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().yr_voc_match(_ptr(det), _ptr(det_count), b, rows, int(num_classes), _ptr(gt) if gt.shape[1] else None,
+                                 _ptr(gt_count), gt.shape[1], float(iou), _ptr(flags), _ptr(npos), stream_ptr(dev)))
+    return flags, npos
 
 
 def correct_boxes(box_xy, box_wh, input_hw, image_hw):

@@ -81,10 +81,10 @@ class YoloModel:
         letterboxed = rt.letterbox(torch.from_numpy(decoded).to(self.device), self.input_shapes)
         return decoded, letterboxed
 
-    def call(self, input, zoom_in=False, layer_num=0):
-        """yolo.py:117-165.  ``input``: [image_bytes] (or a list of several) -> (boxes int32 [K,4] as
-        (ymin,xmin,ymax,xmax) in original-image pixels, scores float32 [K], classes int32 [K]) on the GPU;
-        a list of such triples when more than one image is given."""
+    def call_packed(self, input, zoom_in=False):
+        """The detection path up to the packed records, which stay on the GPU: ``input`` as for ``call`` -> (det [B,C*20,6] int32
+        words (ymin, xmin, ymax, xmax, score as float32 bits, class), det_count [B] int32), the layout of yr_pack_detections.
+        What ``call`` unpacks, and what ``runtime.voc_match`` / ``yolo3.map.DeviceEvaluator`` consume without a copy to the host."""
         if isinstance(input, (bytes, bytearray)):
             input = [input]
         b = len(input)
@@ -106,6 +106,14 @@ class YoloModel:
                                         self.nms, zoom_outputs=self.model(xz))
         else:
             det, cnt = self._pipe(x, image_hw)
+        return det, cnt
+
+    def call(self, input, zoom_in=False, layer_num=0):
+        """yolo.py:117-165.  ``input``: [image_bytes] (or a list of several) -> (boxes int32 [K,4] as
+        (ymin,xmin,ymax,xmax) in original-image pixels, scores float32 [K], classes int32 [K]) on the GPU;
+        a list of such triples when more than one image is given."""
+        det, cnt = self.call_packed(input, zoom_in)
+        b = det.shape[0]
         res = unpack_detections(det, cnt)
         if self.with_classes:
             res = [(bx, sc, [self.classes[int(c)] for c in cl.tolist()]) for bx, sc, cl in res]

@@ -91,14 +91,100 @@ def evaluate_detections(pred_res, true_res, num_classes, iou=0.5):
     return aps
 
 
+VOC_MAX_GT = 512      # YR_VOC_MAX_GT of include/yoloret_hip.h: ground-truth rows per image the device matcher takes
+
+
+def pack_ground_truth(boxes, device):
+    """List of [n,5] label arrays (xmin, ymin, xmax, ymax, label), one per image -> (gt [B,G,5] float32, gt_count [B] int32) on
+    `device`, G = the largest n of the batch (at least 1); rows beyond an image's count are zero."""
+    import torch
+    boxes = [np.asarray(bb, np.float32).reshape(-1, 5) for bb in boxes]
+    if not boxes:
+        raise ValueError('pack_ground_truth: no image')
+    counts = [bb.shape[0] for bb in boxes]
+    if max(counts) > VOC_MAX_GT:
+        raise ValueError('pack_ground_truth: image %d has %d ground-truth boxes, at most %d are supported'
+                         % (int(np.argmax(counts)), max(counts), VOC_MAX_GT))
+    gt = np.zeros((len(boxes), max(1, max(counts)), 5), np.float32)
+    for i, bb in enumerate(boxes):
+        gt[i, :bb.shape[0]] = bb
+    return torch.from_numpy(gt).to(device), torch.from_numpy(np.asarray(counts, np.int32)).to(device)
+
+
+def aps_from_flags(scores, classes, flags, npos_per_class, num_classes):
+    """Per-class AP from per-detection verdicts: `scores`, `classes`, `flags` (1 true positive, 0 false positive) are 1-D over the
+    valid detections in (image, row) order, `npos_per_class[c]` the number of ground-truth boxes of class c in the data set.
+    The `rec` / `prec` / `voc_ap` expressions of `evaluate_detections`; equal to it with ==, given the flags of its matching rule."""
+    scores = np.asarray(scores, np.float64).reshape(-1)
+    classes = np.asarray(classes).reshape(-1)
+    flags = np.asarray(flags).reshape(-1)
+    aps = {}
+    for cls in range(num_classes):
+        sel = classes == cls
+        if not sel.any():
+            aps[cls] = 0
+            continue
+        order = np.argsort(-scores[sel], kind='stable')
+        hit = flags[sel][order] == 1
+        tp = np.cumsum(hit.astype(np.float64))
+        fp = np.cumsum((~hit).astype(np.float64))
+        rec = tp / np.maximum(float(npos_per_class[cls]), np.finfo(np.float64).eps)
+        prec = tp / np.maximum(tp + fp, np.finfo(np.float64).eps)
+        aps[cls] = voc_ap(rec, prec)
+    return aps
+
+
+class DeviceEvaluator:
+    """Accumulates batches of packed detections matched on the GPU; `result()` makes the one copy to the host.
+    Images count in the order added, so the APs equal `evaluate_detections` over the same images in that order."""
+
+    def __init__(self, num_classes, iou=.5):
+        self.num_classes = int(num_classes)
+        self.iou = iou
+        self._kept = []
+
+    def add(self, det, det_count, gt_boxes):
+        """det [B,rows,6] int32, det_count [B] int32 on the GPU (YoloModel.call_packed); gt_boxes: B label arrays [n,5]."""
+        from .. import runtime as rt
+        if len(gt_boxes) != det.shape[0]:
+            raise ValueError('DeviceEvaluator.add: %d label arrays for %d images' % (len(gt_boxes), det.shape[0]))
+        gt, gt_count = pack_ground_truth(gt_boxes, det.device)
+        flags, npos = rt.voc_match(det, det_count, gt, gt_count, self.num_classes, self.iou)
+        # the score and class columns are copied out: the caller may reuse `det`
+        self._kept.append((det[:, :, 4].contiguous(), det[:, :, 5].contiguous(), flags, npos))
+
+    def result(self):
+        import torch
+        if not self._kept:
+            return {c: 0 for c in range(self.num_classes)}
+        dev = self._kept[0][0].device
+        parts = [t.to(dev).reshape(-1) for kept in self._kept for t in kept]
+        host = torch.cat(parts).cpu().numpy()          # the one copy (and synchronisation)
+        scores, classes, flags, at = [], [], [], 0
+        npos = np.zeros(self.num_classes, np.int64)
+        for kept in self._kept:
+            cut = []
+            for t in kept:
+                cut.append(host[at:at + t.numel()])
+                at += t.numel()
+            sc, cl, fl, np_ = cut
+            valid = fl >= 0                            # a verdict: inside det_count, class in range; already in (image, row) order
+            scores.append(sc[valid].view(np.float32))
+            classes.append(cl[valid])
+            flags.append(fl[valid])
+            npos += np_.reshape(-1, self.num_classes).sum(axis=0)
+        return aps_from_flags(np.concatenate(scores), np.concatenate(classes), np.concatenate(flags), npos, self.num_classes)
+
+
 class MAPCallback:
     """Same construction and use as the reference callback (map.py:223-253): `MAPCallback(glob_path, input_shape,
     class_names, iou=.5, batch_size=1)`, `set_model(m)` with `m([encoded image bytes]) -> (boxes (top, left,
     bottom, right), scores, classes)` (yoloret_amd.yolo.YoloModel), then `calculate_aps()` or `on_train_end(logs)`.
     `glob_path` matches text label files (see parse_text); image paths are taken as written, or relative to
-    `root` if given."""
+    `root` if given.  `on_device=True`: the images go through `model.call_packed` in batches of `batch_size` (a shorter last
+    batch) and the matching runs on the GPU (DeviceEvaluator); one copy to the host at the end."""
 
-    def __init__(self, glob_path, input_shape, class_names, iou=.5, batch_size=1, root=None):
+    def __init__(self, glob_path, input_shape, class_names, iou=.5, batch_size=1, root=None, on_device=False):
         self.input_shape = input_shape
         self.class_names = class_names
         self.num_classes = len(class_names)
@@ -106,6 +192,7 @@ class MAPCallback:
         self.iou = iou
         self.batch_size = batch_size
         self.root = root
+        self.on_device = on_device
         self.model = None
         self.seconds_per_image = None
 
@@ -131,6 +218,8 @@ class MAPCallback:
     def calculate_aps(self):
         if self.model is None:
             raise RuntimeError('MAPCallback: set_model() first')
+        if self.on_device:
+            return self._calculate_aps_on_device()
         true_res, pred_res = {}, []
         start = timer()
         idx = 0
@@ -145,6 +234,32 @@ class MAPCallback:
             idx += 1
         self.seconds_per_image = (timer() - start) / max(idx, 1)
         return evaluate_detections(pred_res, true_res, self.num_classes, self.iou)
+
+    def _read(self, path):
+        with open(path if self.root is None else os.path.join(self.root, path), 'rb') as fh:
+            return fh.read()
+
+    def _calculate_aps_on_device(self):
+        if not callable(getattr(self.model, 'call_packed', None)):
+            raise TypeError('MAPCallback(on_device=True) needs a model with call_packed(images) -> (det, det_count) '
+                            '(yoloret_amd.yolo.YoloModel); %s has none' % type(self.model).__name__)
+        batch = max(int(self.batch_size), 1)
+        ev = DeviceEvaluator(self.num_classes, self.iou)
+        start = timer()
+        images, labels, count = [], [], 0
+        for path, bbox in self._records():
+            images.append(self._read(path))
+            labels.append(bbox)
+            if len(images) == batch:
+                ev.add(*self.model.call_packed(images), labels)
+                count += len(images)
+                images, labels = [], []
+        if images:
+            ev.add(*self.model.call_packed(images), labels)
+            count += len(images)
+        aps = ev.result()
+        self.seconds_per_image = (timer() - start) / max(count, 1)
+        return aps
 
     def on_train_end(self, logs=None):
         logs = {} if logs is None else logs
