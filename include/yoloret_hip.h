@@ -551,6 +551,39 @@ int yr_voc_match(const int32_t* det, const int32_t* det_count, int batch, int ro
                  const float* gt, const int32_t* gt_count, int max_gt, double iou_thr,
                  int32_t* flags, int32_t* npos, void* stream);
 
+/* ---- preprocess_true_boxes (code/yolo3/utils.py:298-376) for a whole batch on the device: ground-truth boxes -> the y_true
+ * tensors yr_yolo_loss reads; added under ABI 9 (additive: no struct or existing entry changed).
+ *   true_boxes [B,max_boxes,5] float32 rows (x_min, y_min, x_max, y_max, class) in pixels of the network input, padded with
+ *                                   zero rows: the host function's argument for one image, stacked over the batch
+ *   anchors    host, 9 x (w,h) float32: ALL anchors (:339), not those of one scale
+ *   y1..y3     output l < num_scales is dense float32 [B, in_h / s, in_w / s, 3, 5+C] with s = (32, 16, 8)[l] and the anchors
+ *              ([6,7,8], [3,4,5], [0,1,2])[3 - num_scales + l] (:317-318: with fewer than 3 scales the SMALL anchors meet
+ *              stride 32, as in the reference); the others are not touched and may be null.  Every element is written:
+ *              nothing needs zeroing first
+ *   skipped    [B] int32, may be null: rows of image b that were not written, see below
+ * Contract: the bytes equal the host function's, image by image, for every input on which it neither raises nor writes outside
+ * its grids.  That fixes the arithmetic: centre = floor((min + max) / 2) and size = max - min in float32 (:321-322); the four
+ * relative values are float64 quotients rounded once to float32 (:323-324); a row is valid when its float32 width is > 0 (:342);
+ * the best anchor is the first maximum over the nine anchors of the float32 IoU of the two centred boxes in the operation order of
+ * do_giou_calculate(anchor_box, bbox, mode='iou') with divide_no_nan (:349-354; parity is claimed for float32 anchors); the r-th
+ * VALID row supplies the anchor while row r of the UNFILTERED rows supplies the coordinates, the class and the cell (:356-368);
+ * the cell is floor(relative centre * grid) with the product in float64 (:359-362); entry[0:4] = the relative values,
+ * entry[4] = 1, entry[5 + int(class)] = 1 with int() truncating toward zero (:364-368); the last row in index order that lands
+ * on a (scale, cell, slot) leaves its box there and the class bits of all of them accumulate.
+ * Rows the host function does not write safely (it raises, or a negative index wraps) write nothing and are counted in
+ * skipped[b]: a row with a non-finite value among its five is removed before anything else, so that the remaining rows are
+ * encoded exactly as if it had not been in the list; a row whose truncated class is outside [0, C) or whose cell is outside the
+ * grid is dropped when its turn to be written comes.  (A row that is never a supplier of coordinates - beyond the number of
+ * valid rows, or paired with an anchor of a scale that num_scales leaves out - is not looked at and not counted.)
+ * Two launches on `stream` (zero-fill, then one workgroup per image), no workspace, no host synchronisation, no atomics: the
+ * same call gives the same bytes.  Outputs need 4-byte alignment only. */
+#define YR_ENC_MAX_BOXES 256   /* rows per image (one lane each) */
+int yr_encode_labels(const float* true_boxes /*device [B,T,5]*/, int batch, int max_boxes /*T*/,
+                     int in_h, int in_w, const float* anchors_host /*9 x (w,h)*/,
+                     int num_classes, int num_scales,
+                     float* y1, float* y2, float* y3 /*device; only the first num_scales are used, the others may be null*/,
+                     int32_t* skipped /*device [B], may be null*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

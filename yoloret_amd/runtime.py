@@ -106,7 +106,7 @@ class YrBuf(ctypes.Structure):
 ABI_VERSION = 9   # == YR_ABI_VERSION of include/yoloret_hip.h
 EXPORTS = ['yr_last_error', 'yr_abi_version', 'yr_abi_sizeof', 'yr_create', 'yr_create_from_blob', 'yr_plan_io_dims', 'yr_destroy', 'yr_load_weights', 'yr_workspace_bytes',
            'yr_forward', 'yr_forward_profile', 'yr_forward_ranges', 'yr_autotune', 'yr_get_tuning', 'yr_set_tuning', 'yr_plan_num_launches', 'yr_op_run', 'yr_head_regions', 'yr_head_walk_rows', 'yr_head_stream_rows', 'yr_pwt_chunks', 'yr_decode', 'yr_decode_zoom', 'yr_yolo_head', 'yr_correct_boxes',
-           'yr_nms', 'yr_pack_detections', 'yr_letterbox', 'yr_letterbox_batch', 'yr_yolo_loss_workspace_bytes', 'yr_yolo_loss', 'yr_voc_match']
+           'yr_nms', 'yr_pack_detections', 'yr_letterbox', 'yr_letterbox_batch', 'yr_yolo_loss_workspace_bytes', 'yr_yolo_loss', 'yr_voc_match', 'yr_encode_labels']
 
 _lib = None
 
@@ -170,6 +170,7 @@ def lib():
                                                                                             ctypes.c_void_p, ctypes.c_void_p]
         L.yr_voc_match.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                                                                             ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.yr_encode_labels.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5
         if L.yr_abi_version() != ABI_VERSION:
             raise YoloretHipError('libyoloret_hip.so ABI version mismatch')
         L.yr_abi_sizeof.argtypes = [ctypes.c_int]
@@ -421,6 +422,74 @@ def voc_match(det, det_count, gt, gt_count, num_classes, iou=.5):
         check(lib().yr_voc_match(_ptr(det), _ptr(det_count), b, rows, int(num_classes), _ptr(gt) if gt.shape[1] else None,
                                  _ptr(gt_count), gt.shape[1], float(iou), _ptr(flags), _ptr(npos), stream_ptr(dev)))
     return flags, npos
+
+
+ENC_MAX_BOXES = 256     # YR_ENC_MAX_BOXES of include/yoloret_hip.h
+_GRID_STEPS = (32, 16, 8)
+
+
+def label_shapes(batch, input_hw, num_classes, num_scales):
+    """The shapes [B,gh,gw,3,5+C] of the y_true tensors of `num_scales` scales (utils.py:327-336)."""
+    return [(int(batch), int(input_hw[0]) // _GRID_STEPS[l], int(input_hw[1]) // _GRID_STEPS[l], 3, 5 + int(num_classes))
+            for l in range(num_scales)]
+
+
+def label_args(true_boxes, input_hw, anchors, num_classes, num_scales):
+    """The argument checks of encode_labels that need no device (ValueError) -> (B, T, in_h, in_w, float32 anchors [9,2], shapes)."""
+    if not isinstance(true_boxes, torch.Tensor) or true_boxes.dtype != torch.float32:
+        raise ValueError('encode_labels: true_boxes must be a float32 tensor, not %s'
+                         % (true_boxes.dtype if isinstance(true_boxes, torch.Tensor) else type(true_boxes).__name__))
+    if true_boxes.dim() != 3 or true_boxes.shape[2] != 5 or true_boxes.shape[0] < 1:
+        raise ValueError('encode_labels: true_boxes has shape %s, expected [B,T,5] with B >= 1' % (tuple(true_boxes.shape),))
+    b, t = int(true_boxes.shape[0]), int(true_boxes.shape[1])
+    if not 1 <= t <= ENC_MAX_BOXES:
+        raise ValueError('encode_labels: T = %d rows per image, 1..%d expected' % (t, ENC_MAX_BOXES))
+    if num_scales not in (1, 2, 3):
+        raise ValueError('encode_labels: num_scales must be 1, 2 or 3, not %r' % (num_scales,))
+    in_h, in_w = int(input_hw[0]), int(input_hw[1])
+    if in_h <= 0 or in_w <= 0 or in_h % 32 or in_w % 32:
+        raise ValueError('encode_labels: input shape %dx%d, positive multiples of 32 expected' % (in_h, in_w))
+    if int(num_classes) < 0:
+        raise ValueError('encode_labels: num_classes must not be negative (%d)' % num_classes)
+    anchors = np.ascontiguousarray(np.asarray(anchors, np.float32).reshape(-1, 2))
+    if anchors.shape[0] != 9:
+        raise ValueError('encode_labels: %d anchors, all 9 expected' % anchors.shape[0])
+    shapes = label_shapes(b, (in_h, in_w), num_classes, num_scales)
+    for shp in shapes:
+        if int(np.prod(shp, dtype=np.int64)) > 1 << 31:
+            raise ValueError('encode_labels: a label tensor %s has more than 2^31 elements' % (shp,))
+    return b, t, in_h, in_w, anchors, shapes
+
+
+def encode_labels(true_boxes, input_hw, anchors, num_classes, num_scales, out=None, skipped=None):
+    """preprocess_true_boxes (utils.py:298-376) for a whole batch on the device.  true_boxes: float32 CUDA tensor [B,T,5] of rows
+    (x_min, y_min, x_max, y_max, class) in pixels of the network input, zero rows last, T <= 256; anchors: all 9 (w,h) anchors
+    -> the tuple of `num_scales` float32 tensors [B,gh,gw,3,5+C] on that device, byte for byte what the host function returns
+    image by image (contract and quirks: include/yoloret_hip.h).  They are fresh tensors unless `out` (a sequence of num_scales
+    contiguous float32 tensors of those shapes) is given; every element is written, nothing needs zeroing.  `skipped`: an int32
+    [B] tensor that receives the number of rows per image that could not be written: rows with a non-finite value (removed from
+    the list before anything else) plus rows whose class or cell is out of range (they keep their place in the list, only their
+    write is dropped).  Launches only, on the current stream of that device."""
+    b, t, in_h, in_w, anchors, shapes = label_args(true_boxes, input_hw, anchors, num_classes, num_scales)
+    if not (true_boxes.is_cuda and true_boxes.is_contiguous()):
+        raise ValueError('encode_labels: true_boxes must be a contiguous CUDA tensor (it is on %s)' % true_boxes.device)
+    dev = true_boxes.device
+    if out is None:
+        out = [torch.empty(shp, dtype=torch.float32, device=dev) for shp in shapes]
+    else:
+        out = list(out)
+        if len(out) != num_scales:
+            raise ValueError('encode_labels: %d out tensors for %d scales' % (len(out), num_scales))
+        for o, shp in zip(out, shapes):
+            if not (isinstance(o, torch.Tensor) and o.dtype == torch.float32 and o.is_contiguous() and o.device == dev and tuple(o.shape) == shp):
+                raise ValueError('encode_labels: out tensors must be contiguous float32 %s on %s' % (shapes, dev))
+    if skipped is not None and not (_is_cuda_i32(skipped) and skipped.device == dev and tuple(skipped.shape) == (b,)):
+        raise ValueError('encode_labels: skipped must be a contiguous int32 [B=%d] tensor on %s' % (b, dev))
+    yp = [_ptr(out[l]) if l < num_scales else None for l in range(3)]
+    with torch.cuda.device(dev):
+        check(lib().yr_encode_labels(_ptr(true_boxes), b, t, in_h, in_w, anchors.ctypes.data_as(ctypes.c_void_p), int(num_classes),
+                                     int(num_scales), yp[0], yp[1], yp[2], _ptr(skipped), stream_ptr(dev)))
+    return tuple(out)
 
 
 def correct_boxes(box_xy, box_wh, input_hw, image_hw):

@@ -339,3 +339,20 @@ def yolo_loss(yolo_outputs, y_trues, anchors, num_scales, ignore_thresh=.5):
         rows.append(layer.last_terms)
     terms = torch.stack(rows)
     return terms[:, 0].sum(), terms
+
+
+def yolo_loss_from_boxes(yolo_outputs, true_boxes, anchors, num_classes, num_scales, ignore_thresh=.5):
+    """``yolo_loss`` from ground-truth boxes instead of encoded labels: true_boxes [B,T,5] rows (x_min, y_min, x_max, y_max,
+    class) in pixels of the network input (a NumPy array or a float32 tensor on the logits' device), encoded on the logits'
+    device and current stream by the kernels behind ``yr_encode_labels`` - the label tensors never exist on the host.  The
+    input shape is derived from the grid of the first output, as YoloLoss does (:628) -> (total, terms) of ``yolo_loss``."""
+    from .utils import preprocess_true_boxes_device
+    if len(yolo_outputs) < num_scales:
+        raise ValueError('yolo_loss_from_boxes: %d logit tensors for %d scales' % (len(yolo_outputs), num_scales))
+    y0 = yolo_outputs[0]
+    if not (isinstance(y0, torch.Tensor) and y0.is_cuda and y0.dim() in (4, 5)):
+        raise ValueError('yolo_outputs must be CUDA tensors (the logits of yolov3_body)')
+    input_hw = (y0.shape[1] * 32, y0.shape[2] * 32)
+    with torch.cuda.device(y0.device):
+        y_trues = preprocess_true_boxes_device(true_boxes, input_hw, anchors, num_classes, num_scales, device=y0.device)
+    return yolo_loss(yolo_outputs, [y_trues] if num_scales == 1 else list(y_trues), anchors, num_scales, ignore_thresh)

@@ -114,3 +114,29 @@ def preprocess_true_boxes(true_boxes, input_shape, anchors, num_classes, num_sca
         entry[4] = 1.
         entry[5 + int(true_boxes[t, 4])] = 1.
     return y_true[0] if num_scales == 1 else tuple(y_true)
+
+
+def preprocess_true_boxes_device(true_boxes, input_shape, anchors, num_classes, num_scales, device=None):
+    """The batched twin of ``preprocess_true_boxes`` on the device (the HIP kernels behind ``yr_encode_labels``).
+
+    true_boxes [B,T,5]: the host function's rows for B images, T <= 256, as a NumPy array (copied to ``device``, default the
+    current CUDA device: a few KB) or a float32 CUDA tensor (``device`` is then its own).  Returns float32 device tensors
+    [B,gh,gw,3,5+num_classes], one per scale (a single tensor for num_scales == 1, else a tuple): byte for byte the host
+    function's arrays stacked over the batch.  Rows it could not write are not written: a row with a non-finite value is
+    removed from the list first (the others are encoded as if it were absent); a row with a class or cell out of range keeps its
+    place in the list - and so its part in the reference's pairing of anchors and rows - and only its own write is dropped.
+    ``runtime.encode_labels(..., skipped=)`` counts both kinds per image."""
+    import torch
+    from .. import runtime as rt
+    if not isinstance(true_boxes, torch.Tensor):
+        true_boxes = np.asarray(true_boxes) if isinstance(true_boxes, np.ndarray) else np.asarray(true_boxes, np.float32)
+        if true_boxes.dtype != np.float32:
+            raise ValueError('preprocess_true_boxes_device: a %s array, float32 rows expected' % true_boxes.dtype)
+        host = torch.from_numpy(np.ascontiguousarray(true_boxes))
+        rt.label_args(host, input_shape, anchors, num_classes, num_scales)     # (raises before anything is copied)
+        true_boxes = host.to(torch.device('cuda', torch.cuda.current_device()) if device is None else device)
+    elif device is not None and (torch.device(device).type != true_boxes.device.type
+                                 or torch.device(device).index not in (None, true_boxes.device.index)):
+        raise ValueError('preprocess_true_boxes_device: true_boxes is on %s, device=%s' % (true_boxes.device, device))
+    y_true = rt.encode_labels(true_boxes, input_shape, anchors, num_classes, num_scales)
+    return y_true[0] if num_scales == 1 else y_true
