@@ -4,10 +4,12 @@
 // and walks down the rows -
 //   * the conv of one strip row on v_mfma_f32_16x16x32_f16 in the SPLIT form (float32 operands as two float16 planes, three MFMAs
 //     per product), the weight fragments of its tiles STATIONARY in registers (cut by the plan: compiler.head_pack, BN scale folded
-//     in), the pixel operand straight from global memory in operand layout, one row ahead;
+//     in); the pixel operand: one chunk - straight from global memory in operand layout, one row ahead; two chunks and more - the
+//     SHARED ROW (round 8): the four waves of a workgroup multiply the same pixels, so chunk c of a strip row is fetched (two rows
+//     ahead) and cut ONCE, by wave c % 4, and handed to all four through a double-buffered LDS row, one barrier per row;
 //   * the MFMA result registers ARE the depthwise conv's input: horizontal taps by DPP row shifts, vertical taps = the last three
 //     rows of the walk kept in registers; BN shift as first addend, Swish (hardware exp2 / rcp), one 16-byte store per lane and tile;
-//   * no LDS but the tap table, no barrier inside the walk: the F-wide conv output never exists outside the register file.
+//   * no LDS but the tap table and the shared row: the F-wide conv output never exists outside the register file.
 // Round 5 measured why this form and not a GEMM tile: the LDS-tiled head kernels (headblock.hip) spend their time in per-workgroup
 // latency chains (prologue, one DMA round trip per 32-channel chunk, LDS hand-over to the depthwise phase) at two workgroups per
 // CU - 82-124 us per 26 x 26 / 52 x 52 head where the unfused chain took 90-112; a walking wave has ONE prologue per ~13 rows and
@@ -17,8 +19,8 @@
 // wave adds up what it stores, per channel; a workgroup's four waves (same image, strip, segment - four tile groups) write their
 // slices of the (strip, segment) row and arrive together; the workgroup that completes an image runs the FC pair (se_tail.h).
 // Built for NKE <= 4 chunks of 32 channels (the weights must stay in registers, two cout tiles per wave): the 52 x 52 heads; the
-// 26 x 26 ones (6-7 chunks: one tile per wave, 250 registers, the pixel operand cut 16 times - measured slower), 13 x 13 (K = 216 /
-// 331, F = 512) and pooled sources stay on headblock.hip.
+// 26 x 26 ones (6-7 chunks: one tile per wave; with the shared row 135-152 registers and 47 / 52 us, was 201-236 and 73 / 81 -
+// still behind headstream.hip's 43 / 47) go to headstream.hip, 13 x 13 (K = 216 / 331, F = 512) and pooled sources stay on headblock.hip.
 #include "mbr_common.h"
 #include "se_tail.h"
 
@@ -45,9 +47,12 @@ __device__ __forceinline__ float hw_swish(float v) { return v * __builtin_amdgcn
 
 template <int NKE, int NT, bool PRE, bool GATED>
 #ifndef HW_OCC
-#define HW_OCC 2
+#define HW_OCC 2          // waves per SIMD of the one-chunk kernels (the whole row in registers)
 #endif
-__global__ __launch_bounds__(256, HW_OCC) void hwalk_kernel(HwArgs a) {
+#ifndef HW_OCC_SHARED
+#define HW_OCC_SHARED 3   // ... of the kernels that share the row through LDS (a wave keeps only its own chunks in flight); four
+#endif                    //     chunks with the addend stay at two: at three they spill 76 bytes per lane
+__global__ __launch_bounds__(256, NKE >= 2 && !(PRE && NKE == 4) ? HW_OCC_SHARED : HW_OCC) void hwalk_kernel(HwArgs a) {
     typedef unsigned u4 __attribute__((ext_vector_type(4)));
     extern __shared__ __attribute__((aligned(16))) float tab[];
     __shared__ unsigned se_flag;
@@ -108,83 +113,133 @@ __global__ __launch_bounds__(256, HW_OCC) void hwalk_kernel(HwArgs a) {
             }
         }
     }
-    // ---- descriptors: one per source (whole batch: offsets are 32-bit, the launcher checks the sizes), the addend, the output image
-    const mbr_rsrc rs0 = mbr_make_rsrc(a.src[0], 0x7effffffu);
-    const mbr_rsrc rs1 = mbr_make_rsrc(a.nsrc > 1 ? a.src[1] : a.src[0], 0x7effffffu);
-    const mbr_rsrc rs2 = mbr_make_rsrc(a.nsrc > 2 ? a.src[2] : a.src[0], 0x7effffffu);
+    // ---- descriptors: the addend, the output image (the sources': one per fetched chunk, below)
     const mbr_rsrc prs = mbr_make_rsrc(PRE ? a.pre + (size_t)b * (a.H >> 1) * (a.W >> 1) * a.pre_ld : a.src[0], PRE ? (unsigned)((a.H >> 1) * (a.W >> 1) * a.pre_ld) * 4u : 0u);
     const mbr_rsrc osrc = mbr_make_rsrc(a.out + (size_t)b * a.H * a.W * a.ld_out, (unsigned)(a.H * a.W * a.ld_out) * 4u);
-    // per chunk: byte offset of this lane's 8 channels in its pixel (row offset added per row), or dead; the row pitch of its source
-    unsigned xsoff[NKE], xsoff2[NKE], xpitch[NKE];
-    int vcc[NKE];
+    // The chunks this wave FETCHES.  One chunk (NKE == 1): that chunk, and the wave cuts it for itself (the direct path).  More:
+    // the four waves of the workgroup multiply the SAME pixels (same image, strip, segment) with their own tiles, so a chunk of
+    // a strip row is fetched and cut ONCE - by wave c % 4 - and handed to all four through LDS: slot i of wave w is chunk w + 4 i.
+    // Per slot: byte offset of this lane's 8 channels in its pixel (row offset added per row), or dead; the row pitch of its source.
+    constexpr bool SHARED = NKE >= 2;
+    constexpr int NOWN = (NKE + 3) / 4;
+    mbr_rsrc rso[NOWN];
+    unsigned xsoff[NOWN], xsoff2[NOWN], xpitch[NOWN];
+    int vcc[NOWN];
+    bool own[NOWN];
 #pragma unroll
-    for (int c = 0; c < NKE; ++c) {
-        const int s = a.csrc[c], kl = a.ckl[c] + 8 * mg;
+    for (int i = 0; i < NOWN; ++i) {
+        const int c = SHARED ? wave + 4 * i : 0;
+        own[i] = 4 * i + 3 < NKE || c < NKE;       // uniform (a full slot: known at compile time)
+        const int cc = own[i] ? c : 0;
+        const int s = SHARED ? a.csrc[cc] : 0;     // (chunk 0 is the first source's)
+        const int kl = a.ckl[cc] + 8 * mg;
         const int cs = s == 0 ? a.cs[0] : s == 1 ? a.cs[1] : a.cs[2], ld = s == 0 ? a.ld[0] : s == 1 ? a.ld[1] : a.ld[2];
         const int cq = (cs + 3) & ~3;
         const unsigned base = (unsigned)((b * a.H * a.W + xc) * ld + kl) * 4u;
-        xsoff[c] = kl < cq ? base : MBR_DEAD;
-        xsoff2[c] = kl + 4 < cq ? base + 16u : MBR_DEAD;
-        xpitch[c] = (unsigned)(a.W * ld) * 4u;
-        vcc[c] = cs - a.ckl[c];                 // valid channels of the chunk (>= 32: all)
+        rso[i] = mbr_make_rsrc(s == 0 ? a.src[0] : s == 1 ? a.src[1] : a.src[2], 0x7effffffu);   // (whole batch: offsets are 32-bit, the launcher checks the sizes)
+        xsoff[i] = own[i] && kl < cq ? base : MBR_DEAD;
+        xsoff2[i] = own[i] && kl + 4 < cq ? base + 16u : MBR_DEAD;
+        xpitch[i] = (unsigned)(a.W * ld) * 4u;
+        vcc[i] = cs - a.ckl[cc];                // valid channels of the chunk (>= 32: all)
     }
     const unsigned pcol = PRE ? (unsigned)((xc >> 1) * a.pre_ld + 4 * mg) * 4u : 0u;
 
-    struct XRow { v4f m[2 * NKE]; v4f p[PRE ? NT : 1]; };
+    struct XRow { v4f m[2 * NOWN]; };
+    struct PRow { v4f p[PRE ? NT : 1]; };
     XRow xa, xb;
+    PRow pa, pb;
     auto load_row = [&](XRow& x, int r) __attribute__((always_inline)) {
         const int rc = min(max(r, 0), a.H - 1);
 #pragma unroll
-        for (int c = 0; c < NKE; ++c) {
-            const unsigned so = (unsigned)rc * xpitch[c];
-            const int s = c == 0 ? 0 : a.csrc[c];     // (chunk 0 is the first source's: a compile-time fact the one-chunk kernels need -
-            if (s == 0) {                              //  left with a run-time choice among descriptors they kept them in scratch memory)
-                x.m[2 * c] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rs0, xsoff[c], so, 0));
-                x.m[2 * c + 1] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rs0, xsoff2[c], so, 0));
-            } else if (s == 1) {
-                x.m[2 * c] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rs1, xsoff[c], so, 0));
-                x.m[2 * c + 1] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rs1, xsoff2[c], so, 0));
-            } else {
-                x.m[2 * c] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rs2, xsoff[c], so, 0));
-                x.m[2 * c + 1] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rs2, xsoff2[c], so, 0));
-            }
+        for (int i = 0; i < NOWN; ++i) {
+            const unsigned so = (unsigned)rc * xpitch[i];
+            x.m[2 * i] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rso[i], xsoff[i], so, 0));
+            x.m[2 * i + 1] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rso[i], xsoff2[i], so, 0));
         }
+    };
+    auto load_pre = [&](PRow& x, int r) __attribute__((always_inline)) {
         if constexpr (PRE) {
+            const int rc = min(max(r, 0), a.H - 1);
             const unsigned so = (unsigned)((rc >> 1) * (a.W >> 1) * a.pre_ld) * 4u;
 #pragma unroll
             for (int j = 0; j < NT; ++j)
                 x.p[j] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(prs, t0 + j < a.T ? pcol + 64u * (t0 + j) : MBR_DEAD, so, 0));
         }
     };
+    // the float16 planes of slot i of a fetched row (a source's last chunk: the lanes of a partial quad may hold anything - pad channels)
+    auto cut = [&](const XRow& x, const int i, mbs_u4& xh, mbs_u4& xm) __attribute__((always_inline)) {
+        float v[8] = {x.m[2 * i][0], x.m[2 * i][1], x.m[2 * i][2], x.m[2 * i][3], x.m[2 * i + 1][0], x.m[2 * i + 1][1], x.m[2 * i + 1][2], x.m[2 * i + 1][3]};
+        if (vcc[i] < 32) {   // uniform
+#pragma unroll
+            for (int q = 0; q < 8; ++q) v[q] = 8 * mg + q < vcc[i] ? v[q] : 0.f;
+        }
+        mbs_split8(v, xh, xm);
+    };
+    // The shared row: [2 buffers][NKE chunks][2 planes][64 lanes] x 16 bytes behind the tap table, a lane's 16 bytes = its MFMA B
+    // operand.  In step k a wave fetches its slots of row k + 2, cuts those of row k + 1 (fetched a step ago) into buffer (k + 1) & 1
+    // and multiplies row k out of buffer k & 1; ONE barrier per row: the buffer written in step k was last read in step k - 1.
+    // Only the LDS traffic is waited for (lgkmcnt(0)) - the row in flight and the output stores stay in flight across the barrier.
+    mbs_u4* const xl = reinterpret_cast<mbs_u4*>(tab + a.T * MBR_TAB) + lane;
+    auto park = [&](const XRow& x, const int buf) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < NOWN; ++i)
+            if (own[i]) {
+                mbs_u4 xh, xm;
+                cut(x, i, xh, xm);
+                mbs_u4* const w = xl + ((buf * NKE + wave + 4 * i) * 2) * 64;
+                w[0] = xh;
+                w[64] = xm;
+            }
+    };
+    auto handover = [&]() __attribute__((always_inline)) {
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_s_waitcnt(0xc07f);       // lgkmcnt(0): this wave's planes are written, its reads of the other buffer are done
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+    };
     const int rbeg = yo0 - 1, nout = yo1 - yo0;
-    load_row(xa, rbeg);
+    if constexpr (SHARED) {
+        load_row(xb, rbeg);
+        load_row(xa, rbeg + 1);
+        load_pre(pa, rbeg);
+        park(xb, 0);
+        handover();
+    } else {
+        load_row(xa, rbeg);
+        load_pre(pa, rbeg);
+    }
     v4f ea[NT], eb[NT], psum[NT];
 #pragma unroll
     for (int j = 0; j < NT; ++j) { ea[j] = (v4f){0.f, 0.f, 0.f, 0.f}; eb[j] = ea[j]; psum[j] = ea[j]; }
     const float actmax = a.act == YR_ACT_RELU6 ? 6.f : 3.0e38f;     // conv activation: ReLU6, or none (lower bound below)
     const float actmin = a.act == YR_ACT_RELU6 ? 0.f : -3.0e38f;
 
-    auto row = [&](auto emit_c, const int k, const int yo, const XRow& xc_, XRow& xn_) __attribute__((always_inline)) {
+    // step k of the walk.  Direct: xc_ holds row k, xn_ takes row k + 1.  Shared: xc_ holds row k + 1, xn_ takes row k + 2.
+    auto row = [&](auto emit_c, auto par_c, const int k, const int yo, const XRow& xc_, XRow& xn_, const PRow& pc_, PRow& pn_) __attribute__((always_inline)) {
         constexpr bool EMIT = decltype(emit_c)::value;
+        constexpr int PAR = decltype(par_c)::value;     // k & 1: the buffer of the shared row this step reads
         const int r = rbeg + k;
-        load_row(xn_, r + 1);
+        load_row(xn_, SHARED ? r + 2 : r + 1);
+        load_pre(pn_, r + 1);
+        if constexpr (SHARED) park(xc_, PAR ^ 1);
         const float live = (r >= 0 && r < a.H) ? hi : 0.f;
         v4f ec[NT], e1[NT];
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             ec[j] = se[j];
-            if constexpr (PRE) ec[j] = psc[j] * xc_.p[j] + ec[j];     // (acc + pre) * scale + shift, the scale folded into the weights
+            if constexpr (PRE) ec[j] = psc[j] * pc_.p[j] + ec[j];     // (acc + pre) * scale + shift, the scale folded into the weights
             e1[j] = (v4f){0.f, 0.f, 0.f, 0.f};
         }
 #pragma unroll
         for (int c = 0; c < NKE; ++c) {
-            float v[8] = {xc_.m[2 * c][0], xc_.m[2 * c][1], xc_.m[2 * c][2], xc_.m[2 * c][3], xc_.m[2 * c + 1][0], xc_.m[2 * c + 1][1], xc_.m[2 * c + 1][2], xc_.m[2 * c + 1][3]};
-            if (vcc[c] < 32) {   // uniform: a source's last chunk - the lanes of a partial quad may hold anything (pad channels)
-#pragma unroll
-                for (int i = 0; i < 8; ++i) v[i] = 8 * mg + i < vcc[c] ? v[i] : 0.f;
-            }
             mbs_u4 xh, xm;
-            mbs_split8(v, xh, xm);
+            if constexpr (SHARED) {
+                const mbs_u4* const rd = xl + ((PAR * NKE + c) * 2) * 64;
+                xh = rd[0];
+                xm = rd[64];
+            } else {
+                cut(xc_, c, xh, xm);
+            }
 #pragma unroll
             for (int j = 0; j < NT; ++j) ec[j] = mbs_mfma(weh[j][c], xh, ec[j]);
 #pragma unroll
@@ -222,17 +277,20 @@ __global__ __launch_bounds__(256, HW_OCC) void hwalk_kernel(HwArgs a) {
         }
 #pragma unroll
         for (int j = 0; j < NT; ++j) { ea[j] = eb[j]; eb[j] = ec[j]; }
+        if constexpr (SHARED) handover();
     };
     constexpr std::true_type Y{};
     constexpr std::false_type N{};
-    row(N, 0, 0, xa, xb);
-    row(N, 1, 0, xb, xa);
+    constexpr std::integral_constant<int, 0> E{};
+    constexpr std::integral_constant<int, 1> O{};
+    row(N, E, 0, 0, xa, xb, pa, pb);
+    row(N, O, 1, 0, xb, xa, pb, pa);
     int i = 0;
     for (; i + 1 < nout; i += 2) {
-        row(Y, i + 2, yo0 + i, xa, xb);
-        row(Y, i + 3, yo0 + i + 1, xb, xa);
+        row(Y, E, i + 2, yo0 + i, xa, xb, pa, pb);
+        row(Y, O, i + 3, yo0 + i + 1, xb, xa, pb, pa);
     }
-    if (i < nout) row(Y, i + 2, yo0 + i, xa, xb);
+    if (i < nout) row(Y, E, i + 2, yo0 + i, xa, xb, pa, pb);
     if (a.sums == nullptr) return;   // uniform
 
     // ---- squeeze-excite sums: the 14 output columns of the strip meet by a fixed butterfly over the 16 lanes of a DPP row; lane
@@ -263,7 +321,7 @@ static int launch_hwalk(HwArgs& a, int batch, hipStream_t s) {
     YR_REQUIRE(a.groups % 4 == 0, "head (walking form): %d tile groups are no multiple of the 4 waves of a workgroup", a.groups);
     a.nwaves = batch * a.strips * a.segs * a.groups;
     a.se.arrivals = (unsigned)(a.strips * a.segs * (a.groups / 4));
-    size_t lds = (size_t)a.T * MBR_TAB * 4;
+    size_t lds = (size_t)a.T * MBR_TAB * 4 + (NKE >= 2 ? (size_t)2 * NKE * 2 * 64 * 16 : 0);   // the tap table | the shared row, two buffers
     if (a.se.sums) lds = lds > yr_se_tail_floats(a.se.C, a.se.R, 256) * 4 ? lds : yr_se_tail_floats(a.se.C, a.se.R, 256) * 4;
     YR_REQUIRE(lds <= 64 * 1024, "head (walking form): %d channels exceed the LDS budget", a.T * 16);
     const bool pre = a.pre != nullptr, gated = a.gate != nullptr;
