@@ -379,7 +379,7 @@ typedef struct yr_handle yr_handle;
 
 const char* yr_last_error(void);
 int yr_abi_version(void);
-/* sizeof(yr_src) / sizeof(yr_op) / sizeof(yr_buf) for which = 0 / 1 / 2 (else 0): lets a binding that restates the
+/* sizeof(yr_src) / sizeof(yr_op) / sizeof(yr_buf) / sizeof(yr_ingest_geom) for which = 0 / 1 / 2 / 3 (else 0): lets a binding that restates the
  * structs (ctypes, cgo, JNA ...) verify its layout against the library's at load time. */
 int yr_abi_sizeof(int which);
 
@@ -583,6 +583,57 @@ int yr_encode_labels(const float* true_boxes /*device [B,T,5]*/, int batch, int 
                      int num_classes, int num_scales,
                      float* y1, float* y2, float* y3 /*device; only the first num_scales are used, the others may be null*/,
                      int32_t* skipped /*device [B], may be null*/, void* stream);
+
+/* ---- ragged batched ingest: B decoded uint8 images of different sizes -> the float32 [B,H,W,3] network input in one launch,
+ * and - for the validation data path - their ground-truth boxes mapped into that input in the same launch; added under ABI 9
+ * (additive: no struct or existing entry changed; yr_abi_sizeof(3) reports sizeof(yr_ingest_geom)).  Replaces, after the host's
+ * image decode and text parse, per image:
+ *   YR_INGEST_LETTERBOX  letterbox_image (code/yolo3/utils.py:67-83) behind code/yolo.py:105-112: the geometry and the bytes of
+ *                        yr_letterbox, for every consumer of mixed-size images (one copy and one launch instead of B of each);
+ *   YR_INGEST_VALIDATE   get_random_data(train=False, zoom_in=False) (code/yolo3/utils.py:239-295) as Dataset.parse_text calls it
+ *                        (code/yolo3/data.py:71-121).  This is NOT letterbox_image's arithmetic: the geometry is float32, the
+ *                        pad offset is int((h - nh) / 2) with the UNTRUNCATED nh, and the boxes are mapped with the untruncated
+ *                        nw, nh, dx, dy.  At 96x96 a 5x7 image sits at dy = 13 here and at dy = 14 there. */
+#define YR_INGEST_LETTERBOX 0   /* utils.py:67-83 - exactly the geometry yr_letterbox computes */
+#define YR_INGEST_VALIDATE  1   /* utils.py:239-252, get_random_data(train=False, zoom_in=False) */
+#define YR_INGEST_MAX_BOXES 256 /* input rows per image (one lane each) */
+typedef struct {                /* 64 bytes; yr_abi_sizeof(3) reports it */
+    int64_t src_off;            /* byte offset of image b in the packed source, a multiple of 16 */
+    int32_t ih, iw, nh, nw, dy, dx;   /* source size; size and offset of the resized window inside H x W */
+    float   nh_f, nw_f, dy_f, dx_f;   /* VALIDATE: the untruncated float32 values the boxes use; LETTERBOX: 0 */
+    int32_t reserved[4];        /* 0 */
+} yr_ingest_geom;
+/* The one place where the arithmetic of both rules lives (utils.py:76-79 | :152-155,239-242,247-250); pure host, no device touched.
+ *   dims_host [B][2] = (ih, iw) per image;  geom_host [B] receives the table;  packed_bytes (nullable) the size of the packed
+ *   source: the images [ih][iw][3] uint8 back to back, each offset rounded up to 16, the end rounded up to 16 as well
+ * LETTERBOX: the ratio min(W / iw, H / ih) in float64, nh / nw truncated, dy = (H - nh) / 2 and dx = (W - nw) / 2 floor-divided.
+ * VALIDATE: float32 in TF's order - m = min(w / iw, h / ih); nh_f = ih * m; nw_f = iw * m; dx_f = (w - nw_f) / 2;
+ * dy_f = (h - nh_f) / 2; the integer fields are the truncations of those four.
+ * YR_ERR_ARG, with the image's index in the message, where nh or nw truncates to 0 (tf.image.resize raises there too).
+ * A caller places the table next to the images in its staging buffer and uploads both with one copy. */
+int yr_ingest_geometry(int mode, int batch, const int32_t* dims_host /*[B][2] = ih, iw*/, int H, int W,
+                       yr_ingest_geom* geom_host /*[B]*/, int64_t* packed_bytes);
+/* The launch.  `mode` is the rule the table was computed with (the table lives on the device; the entry does not read it).
+ * Image part (utils.py:81-82 | :246-252,277) - every element of dst is written: inside the nh x nw window of image b at (dy, dx)
+ * u8 * (1/255), then the bilinear half-pixel resize in yr_letterbox's operation order with the scales (float)ih / (float)nh and
+ * (float)iw / (float)nw, then in VALIDATE mode clip_by_value(0, 1); zeros outside.  In LETTERBOX mode the bytes equal
+ * yr_letterbox's image by image.
+ * Box part (VALIDATE mode only; boxes_in non-null in LETTERBOX mode is YR_ERR_ARG; boxes_in null: images only, boxes_out and
+ * kept are not touched), all float32:
+ *   boxes_in [B,max_in,5]   rows (xmin, ymin, xmax, ymax, label) in pixels of the SOURCE image - the label file's order, what
+ *                           yr_voc_match reads; the first box_count[b] [B] rows of image b are read (clamped to 0..max_in);
+ *                           max_in <= YR_INGEST_MAX_BOXES
+ *   x' = x * nw_f / iw + dx_f, y' = y * nh_f / ih + dy_f, left to right (:253-256); each coordinate clipped to [0, W - 1] /
+ *   [0, H - 1] (:258-273); a row is kept iff xmax' - xmin' > 1 and ymax' - ymin' > 1, both strict (:289-291); the first
+ *   max_boxes kept rows, in input order (:292-293), go to the front of boxes_out[b] [B,max_boxes,5] as (xmin', ymin', xmax',
+ *   ymax', label) - yr_encode_labels's input -, the rest of boxes_out[b] is zero; kept[b] [B] (nullable) is their number.  The
+ *   label's bits are copied through.  Coordinates must be finite.
+ * One launch on `stream` (the box part is one extra workgroup per image of the same grid), no workspace, no atomics, no host
+ * synchronisation; the same call gives the same bytes.  src_u8, geom and dst need 16-byte alignment, B * H * W < 2^31. */
+int yr_ingest_batch(int mode, const unsigned char* src_u8 /*device, packed*/, const yr_ingest_geom* geom /*device [B]*/, int batch,
+                    float* dst /*[B,H,W,3]*/, int H, int W,
+                    const float* boxes_in /*[B,max_in,5] or null*/, const int32_t* box_count /*[B]*/, int max_in,
+                    float* boxes_out /*[B,max_boxes,5]*/, int32_t* kept /*[B], may be null*/, int max_boxes, void* stream);
 
 #ifdef __cplusplus
 }

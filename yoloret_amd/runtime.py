@@ -103,8 +103,19 @@ class YrBuf(ctypes.Structure):
                 ('external_slot', ctypes.c_int32), ('dtype', ctypes.c_int32)]
 
 
+class YrIngestGeom(ctypes.Structure):
+    """yr_ingest_geom: one image of a ragged batch - where it sits in the packed source and in the network input."""
+    _fields_ = [('src_off', ctypes.c_int64), ('ih', ctypes.c_int32), ('iw', ctypes.c_int32), ('nh', ctypes.c_int32), ('nw', ctypes.c_int32),
+                ('dy', ctypes.c_int32), ('dx', ctypes.c_int32), ('nh_f', ctypes.c_float), ('nw_f', ctypes.c_float), ('dy_f', ctypes.c_float),
+                ('dx_f', ctypes.c_float), ('reserved', ctypes.c_int32 * 4)]
+
+
+# the same layout for NumPy: a table is one structured array, its bytes are what the device reads
+INGEST_GEOM_DTYPE = np.dtype([('src_off', '<i8'), ('ih', '<i4'), ('iw', '<i4'), ('nh', '<i4'), ('nw', '<i4'), ('dy', '<i4'), ('dx', '<i4'),
+                              ('nh_f', '<f4'), ('nw_f', '<f4'), ('dy_f', '<f4'), ('dx_f', '<f4'), ('reserved', '<i4', (4,))])
+
 ABI_VERSION = 9   # == YR_ABI_VERSION of include/yoloret_hip.h
-EXPORTS = ['yr_last_error', 'yr_abi_version', 'yr_abi_sizeof', 'yr_create', 'yr_create_from_blob', 'yr_plan_io_dims', 'yr_destroy', 'yr_load_weights', 'yr_workspace_bytes',
+EXPORTS = ['yr_ingest_geometry', 'yr_ingest_batch','yr_last_error', 'yr_abi_version', 'yr_abi_sizeof', 'yr_create', 'yr_create_from_blob', 'yr_plan_io_dims', 'yr_destroy', 'yr_load_weights', 'yr_workspace_bytes',
            'yr_forward', 'yr_forward_profile', 'yr_forward_ranges', 'yr_autotune', 'yr_get_tuning', 'yr_set_tuning', 'yr_plan_num_launches', 'yr_op_run', 'yr_head_regions', 'yr_head_walk_rows', 'yr_head_stream_rows', 'yr_pwt_chunks', 'yr_decode', 'yr_decode_zoom', 'yr_yolo_head', 'yr_correct_boxes',
            'yr_nms', 'yr_pack_detections', 'yr_letterbox', 'yr_letterbox_batch', 'yr_yolo_loss_workspace_bytes', 'yr_yolo_loss', 'yr_voc_match', 'yr_encode_labels']
 
@@ -171,10 +182,15 @@ def lib():
         L.yr_voc_match.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                                                                             ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.yr_encode_labels.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5
+        L.yr_ingest_geometry.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        L.yr_ingest_batch.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
         if L.yr_abi_version() != ABI_VERSION:
             raise YoloretHipError('libyoloret_hip.so ABI version mismatch')
         L.yr_abi_sizeof.argtypes = [ctypes.c_int]
-        for which, st in enumerate((YrSrc, YrOp, YrBuf)):
+        if INGEST_GEOM_DTYPE.itemsize != ctypes.sizeof(YrIngestGeom):
+            raise YoloretHipError('INGEST_GEOM_DTYPE: %d bytes, YrIngestGeom %d' % (INGEST_GEOM_DTYPE.itemsize, ctypes.sizeof(YrIngestGeom)))
+        for which, st in enumerate((YrSrc, YrOp, YrBuf, YrIngestGeom)):
             if L.yr_abi_sizeof(which) != ctypes.sizeof(st):
                 raise YoloretHipError('struct %s: %d bytes here, %d in libyoloret_hip.so'
                                       % (st.__name__, ctypes.sizeof(st), L.yr_abi_sizeof(which)))
@@ -523,6 +539,124 @@ def letterbox(image_u8, input_hw, out=None):
         check(lib().yr_letterbox_batch(_ptr(image_u8), image_u8.shape[0] if batched else 1, image_u8.shape[-3],
                                        image_u8.shape[-2], _ptr(out), h, w, stream_ptr(image_u8.device)))
     return out
+
+
+# ----------------------------------------------------------------------------- ragged batched ingest
+INGEST_LETTERBOX, INGEST_VALIDATE, INGEST_MAX_BOXES = 0, 1, 256     # YR_INGEST_* of include/yoloret_hip.h
+
+
+class IngestTable:
+    """The geometry table of one ragged batch (yr_ingest_geometry): ``host`` is the structured array [B] (INGEST_GEOM_DTYPE: src_off,
+    ih, iw, nh, nw, dy, dx, nh_f, nw_f, dy_f, dx_f), ``mode`` the rule it was computed with, ``packed_bytes`` the size of the packed
+    source, ``device`` the uint8 tensor [B * 64] that holds its bytes on the GPU once it has been uploaded (RaggedStager.upload)."""
+
+    def __init__(self, host, mode, input_hw, packed_bytes):
+        self.host, self.mode, self.input_hw, self.packed_bytes = host, int(mode), (int(input_hw[0]), int(input_hw[1])), int(packed_bytes)
+        self.batch = int(host.shape[0])
+        self.device = None
+
+    def upload(self, device):
+        """The table alone, in a copy of its own (tests and tools; a pipeline uploads it with the images: RaggedStager)."""
+        self.device = torch.from_numpy(self.host.view(np.uint8).copy()).to(device)
+        return self
+
+
+def ingest_geometry(dims, input_hw, mode):
+    """dims: B x (ih, iw) -> IngestTable: per image the offset in the packed source (images back to back, each offset a multiple
+    of 16) and the letterbox window in the rule of ``mode`` - INGEST_LETTERBOX (utils.py:67-83, what ``letterbox`` computes) or
+    INGEST_VALIDATE (utils.py:239-252, the float32 geometry of the validation data path).  Host arithmetic inside the library; no
+    device is touched.  YoloretHipError naming the image where one collapses to zero size."""
+    dims = np.ascontiguousarray(np.asarray(dims, np.int64).reshape(-1, 2).astype(np.int32))
+    if dims.shape[0] == 0:
+        raise ValueError('ingest_geometry: no image')
+    host = np.zeros(dims.shape[0], INGEST_GEOM_DTYPE)
+    packed = ctypes.c_int64(0)
+    check(lib().yr_ingest_geometry(int(mode), dims.shape[0], dims.ctypes.data_as(ctypes.c_void_p), int(input_hw[0]), int(input_hw[1]),
+                                   host.ctypes.data_as(ctypes.c_void_p), ctypes.byref(packed)))
+    return IngestTable(host, mode, input_hw, packed.value)
+
+
+def ingest_batch(packed_u8, geom, input_hw, boxes=None, box_count=None, max_boxes=20, out=None):
+    """One launch for a ragged batch.  packed_u8: uint8 CUDA tensor holding the decoded images at the offsets of ``geom`` (an
+    uploaded IngestTable for ``input_hw``) -> float32 [B,H,W,3]: ``letterbox`` image by image in INGEST_LETTERBOX mode, the
+    validation pipeline's image (utils.py:239-252,277) in INGEST_VALIDATE mode.  With ``boxes`` (float32 CUDA [B,max_in,5] rows
+    (xmin, ymin, xmax, ymax, label) in source pixels, max_in <= 256) and ``box_count`` (int32 [B]), VALIDATE mode only:
+    -> (images, boxes_out [B,max_boxes,5] mapped, clipped, filtered and cut as utils.py:253-293, kept [B] int32)."""
+    if not (isinstance(packed_u8, torch.Tensor) and packed_u8.is_cuda and packed_u8.dtype == torch.uint8 and packed_u8.is_contiguous()):
+        raise ValueError('ingest_batch: the packed source must be a contiguous uint8 CUDA tensor')
+    if not isinstance(geom, IngestTable) or geom.device is None:
+        raise ValueError('ingest_batch: geom must be an uploaded IngestTable (ingest_geometry + RaggedStager.upload / IngestTable.upload)')
+    dev = packed_u8.device
+    h, w = int(input_hw[0]), int(input_hw[1])
+    b = geom.batch
+    if (h, w) != geom.input_hw:
+        raise ValueError('ingest_batch: the table was computed for %dx%d, not %dx%d' % (geom.input_hw + (h, w)))
+    if geom.device.device != dev or geom.device.dtype != torch.uint8 or geom.device.numel() != b * INGEST_GEOM_DTYPE.itemsize:
+        raise ValueError('ingest_batch: the table\'s device copy must be %d bytes on %s' % (b * INGEST_GEOM_DTYPE.itemsize, dev))
+    if packed_u8.numel() < geom.packed_bytes - 15:
+        raise ValueError('ingest_batch: the packed source holds %d bytes, the table addresses %d' % (packed_u8.numel(), geom.packed_bytes))
+    shape = (b, h, w, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise ValueError('out must be a contiguous float32 tensor %s on the source\'s device' % (shape,))
+    boxes_out = kept = None
+    max_in = 0
+    if boxes is not None:
+        if geom.mode != INGEST_VALIDATE:
+            raise ValueError('ingest_batch: boxes are mapped in INGEST_VALIDATE mode only')
+        if not (isinstance(boxes, torch.Tensor) and boxes.dtype == torch.float32 and boxes.is_contiguous() and boxes.device == dev
+                and boxes.dim() == 3 and boxes.shape[0] == b and boxes.shape[2] == 5 and 1 <= boxes.shape[1] <= INGEST_MAX_BOXES):
+            raise ValueError('ingest_batch: boxes must be a contiguous float32 tensor [B=%d,max_in,5] on %s with 1 <= max_in <= %d'
+                             % (b, dev, INGEST_MAX_BOXES))
+        if not (_is_cuda_i32(box_count) and box_count.device == dev and tuple(box_count.shape) == (b,)):
+            raise ValueError('ingest_batch: box_count must be a contiguous int32 [B=%d] tensor on %s' % (b, dev))
+        if int(max_boxes) < 1:
+            raise ValueError('ingest_batch: max_boxes must be at least 1, not %d' % max_boxes)
+        max_in = int(boxes.shape[1])
+        boxes_out = torch.empty((b, int(max_boxes), 5), dtype=torch.float32, device=dev)
+        kept = torch.empty((b,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().yr_ingest_batch(geom.mode, _ptr(packed_u8), _ptr(geom.device), b, _ptr(out), h, w, _ptr(boxes), _ptr(box_count), max_in,
+                                    _ptr(boxes_out), _ptr(kept), int(max_boxes), stream_ptr(dev)))
+    return out if boxes is None else (out, boxes_out, kept)
+
+
+class RaggedStager:
+    """Host side of the ragged ingest: packs a list of decoded uint8 images [h,w,3] and their geometry table into ONE pinned host
+    buffer (reused, grown on demand) and uploads both with one non-blocking copy on the current stream.  An event recorded behind
+    the copy is waited for before the buffer is written again: without it the next batch's bytes could overtake a copy in flight."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self._host = None
+        self._event = None
+
+    def upload(self, images, input_hw, mode):
+        """-> (packed uint8 CUDA tensor, uploaded IngestTable): the arguments of ``ingest_batch``."""
+        images = [np.ascontiguousarray(im, np.uint8) for im in images]
+        for i, im in enumerate(images):
+            if im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError('RaggedStager: image %d has shape %s, [h,w,3] expected' % (i, im.shape))
+        table = ingest_geometry([im.shape[:2] for im in images], input_hw, mode)
+        tbytes = table.batch * INGEST_GEOM_DTYPE.itemsize
+        total = table.packed_bytes + tbytes
+        if self._event is not None:
+            self._event.synchronize()      # the previous copy has read the buffer
+            self._event = None
+        if self._host is None or self._host.numel() < total:
+            self._host = torch.empty(max(total, 2 * (self._host.numel() if self._host is not None else 0)), dtype=torch.uint8, pin_memory=True)
+        hv = self._host.numpy()
+        for im, off in zip(images, table.host['src_off']):
+            hv[off:off + im.size] = im.reshape(-1)
+        hv[table.packed_bytes:total] = table.host.view(np.uint8)
+        with torch.cuda.device(self.device):
+            dev = torch.empty(total, dtype=torch.uint8, device=self.device)
+            dev.copy_(self._host[:total], non_blocking=True)
+            self._event = torch.cuda.Event()
+            self._event.record(torch.cuda.current_stream(self.device))
+        table.device = dev[table.packed_bytes:total]
+        return dev[:table.packed_bytes], table
 
 
 def image_hw_tensor(image_shape, batch, device):

@@ -63,6 +63,7 @@ class YoloModel:
                                   iou_threshold=self.nms, name='yolo')
         self._pipe = DetectionPipeline(self.model, self.anchors, self.num_classes, self.num_scales, max_boxes=20,
                                        score_threshold=self.score, iou_threshold=self.nms)
+        self._stager = None
 
     def _load_weights(self, model_path):
         if isinstance(model_path, dict):
@@ -88,12 +89,17 @@ class YoloModel:
         if isinstance(input, (bytes, bytearray)):
             input = [input]
         b = len(input)
-        x = torch.empty((b, *self.input_shapes, 3), dtype=torch.float32, device=self.device)
-        shapes = []
-        for i, img in enumerate(input):
-            decoded = _decode_to_u8(img) if isinstance(img, (bytes, bytearray)) else np.ascontiguousarray(img, np.uint8)
-            rt.letterbox(torch.from_numpy(decoded).to(self.device), self.input_shapes, out=x[i])
-            shapes.append(decoded.shape[:2])
+        decoded = [_decode_to_u8(img) if isinstance(img, (bytes, bytearray)) else np.ascontiguousarray(img, np.uint8) for img in input]
+        shapes = [d.shape[:2] for d in decoded]
+        if zoom_in:
+            x = torch.empty((b, *self.input_shapes, 3), dtype=torch.float32, device=self.device)
+            for i, d in enumerate(decoded):
+                rt.letterbox(torch.from_numpy(d).to(self.device), self.input_shapes, out=x[i])
+        else:
+            # the ragged batch in one pinned copy and one launch (yr_ingest_batch, LETTERBOX rule): the bytes of the loop above
+            if self._stager is None:
+                self._stager = rt.RaggedStager(self.device)
+            x = rt.ingest_batch(*self._stager.upload(decoded, self.input_shapes, rt.INGEST_LETTERBOX), self.input_shapes)
         image_hw = rt.image_hw_tensor(np.asarray(shapes, np.int32), b, self.device)
         if zoom_in:
             # yolo.py:154-159: a second pass over the central crop of every image, merged inside the decode

@@ -1,0 +1,131 @@
+"""The validation data path - mirror of reference code/yolo3/data.py for ``mode=VALIDATE`` / ``TEST`` (both ``train=False``):
+label file -> batches of (letterboxed images, y_true) on the GPU.
+
+``Dataset(...)`` has the reference's constructor (:151-167) plus ``device`` and ``root``; ``build()`` (:172-200) returns
+``(iterable, num)`` and raises its errors.  Per batch only the JPEG / PNG decode (PIL) and the text parse stay on the host:
+
+    map.parse_text -> PIL decode -> runtime.RaggedStager (one pinned buffer, one copy)
+                   -> runtime.ingest_batch(INGEST_VALIDATE): get_random_data(train=False) for images AND boxes (utils.py:239-295)
+                   -> runtime.encode_labels: preprocess_true_boxes (utils.py:298-376)
+
+Differences that are deliberate:
+  * iteration is deterministic - files sorted, lines in order, batches of ``batch_size`` with a shorter last one.  The reference's
+    ``interleave(cycle_length=AUTOTUNE)`` leaves the order open, and the loss depends on which images share a batch (the labelled
+    boxes are gathered over the whole batch, model.py:643);
+  * ``mode=TRAIN`` (augmentation, shuffling) and ``zoom_in=True`` (the experimental branch of utils.py:243-245,279-283) are not
+    built: ``build()`` raises NotImplementedError.  TFRecord files need TensorFlow's proto parser (as in map.py).
+"""
+import glob
+import os
+
+import numpy as np
+
+from .enums import DATASET_MODE
+from .map import parse_text
+
+MAX_BOXES = 20      # get_random_data's max_boxes (utils.py:142)
+
+
+def decode_image(path):
+    """tf.io.decode_image(tf.io.read_file(path), channels=3) on the host (data.py:73-75) -> uint8 [h,w,3]; the /255 of
+    dtype=float32 happens in the ingest kernel."""
+    from PIL import Image
+    with Image.open(path) as img:
+        return np.array(img.convert('RGB'), dtype=np.uint8)
+
+
+class _Batches:
+    """The iterable ``Dataset.build`` returns: every pass reads the label files again and yields (images, y_true)."""
+
+    def __init__(self, dataset, files):
+        self.dataset, self.files = dataset, files
+
+    def __iter__(self):
+        for records in self.dataset.record_batches(self.files):
+            yield self.dataset.load_batch(records)
+
+
+class Dataset(object):
+    def __init__(self, glob_path, batch_size, anchors=None, num_classes=None, input_shape=None, num_scales=None,
+                 mode=DATASET_MODE.TRAIN, zoom_in=False, device=None, root=None):
+        self.glob_path = glob_path
+        self.batch_size = batch_size
+        self.input_shape = input_shape
+        self.anchors = anchors
+        self.num_classes = num_classes
+        self.num_scales = num_scales
+        self.mode = mode
+        self.zoom_in = zoom_in
+        self.device = device
+        self.root = root
+        self.last_boxes = None      # (boxes_out [b,20,5], kept [b]) of the last batch, on the device
+        self._stager = None
+
+    def _get_num_from_name(self, name):
+        return int(name.split('/')[-1].split('.')[0].split('_')[-1])
+
+    def build(self, split=None):
+        if self.glob_path is None:
+            return None, 0
+        files = sorted(glob.glob(self.glob_path))
+        if len(files) == 0:
+            raise ValueError('No file found')
+        try:
+            num = sum(self._get_num_from_name(f) for f in files)
+        except Exception:
+            raise ValueError('Please format file name like <name>_<number>.<extension>')
+        if any(f.endswith(('.tfrecord', '.tfrecords')) for f in files):
+            raise NotImplementedError('TFRecord label files need TensorFlow; use the text format')
+        if self.mode == DATASET_MODE.TRAIN:
+            raise NotImplementedError('Dataset(mode=TRAIN): augmentation and training are not built; use DATASET_MODE.VALIDATE or TEST')
+        if self.mode not in (DATASET_MODE.VALIDATE, DATASET_MODE.TEST):
+            raise ValueError('Dataset: mode must be a DATASET_MODE, not %r' % (self.mode,))
+        if self.zoom_in:
+            raise NotImplementedError('Dataset(zoom_in=True): the zoom-in branch of get_random_data is not built')
+        txts = [f for f in files if f.endswith('.txt')]
+        if not txts:
+            raise ValueError('No .txt label file among %d matching files' % len(files))
+        return _Batches(self, txts), num
+
+    # ------------------------------------------------------------------------- host side
+    def records(self, files):
+        """(image path, float32 [n,5] rows (xmin, ymin, xmax, ymax, label)) per non-empty line, files and lines in order."""
+        for f in files:
+            with open(f) as fh:
+                for line in fh:
+                    if line.strip():
+                        yield parse_text(line)
+
+    def record_batches(self, files):
+        """Lists of ``batch_size`` records, the last one shorter."""
+        size = max(int(self.batch_size), 1)
+        batch = []
+        for rec in self.records(files):
+            batch.append(rec)
+            if len(batch) == size:
+                yield batch
+                batch = []
+        if batch:
+            yield batch
+
+    # ------------------------------------------------------------------------- device side
+    def load_batch(self, records):
+        """One batch of records -> (images [b,H,W,3] float32, y_true tuple of num_scales tensors [b,gh,gw,3,5+C]) on the device."""
+        import torch
+        from .. import runtime as rt
+        dev = torch.device(self.device if self.device is not None else 'cuda:0')
+        if self._stager is None or self._stager.device != dev:
+            self._stager = rt.RaggedStager(dev)
+        images = [decode_image(path if self.root is None else os.path.join(self.root, path)) for path, _ in records]
+        counts = np.asarray([bb.shape[0] for _, bb in records], np.int32)
+        if counts.max() > rt.INGEST_MAX_BOXES:
+            raise ValueError('Dataset: %s has %d boxes, at most %d are supported' % (records[int(counts.argmax())][0], counts.max(), rt.INGEST_MAX_BOXES))
+        boxes = np.zeros((len(records), max(1, int(counts.max())), 5), np.float32)
+        for i, (_, bb) in enumerate(records):
+            boxes[i, :bb.shape[0]] = bb
+        packed, table = self._stager.upload(images, self.input_shape, rt.INGEST_VALIDATE)
+        x, boxes_out, kept = rt.ingest_batch(packed, table, self.input_shape, boxes=torch.from_numpy(boxes).to(dev),
+                                             box_count=torch.from_numpy(counts).to(dev), max_boxes=MAX_BOXES)
+        self.last_boxes = (boxes_out, kept)
+        y_true = rt.encode_labels(boxes_out, self.input_shape, self.anchors, self.num_classes, self.num_scales)
+        return x, tuple(y_true)

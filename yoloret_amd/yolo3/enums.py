@@ -1,4 +1,4 @@
-"""Backbone names (reference code/yolo3/enums.py:25-28) and box-loss kinds (:32-34)."""
+"""Backbone names (reference code/yolo3/enums.py:25-28), box-loss kinds (:32-34) and data set modes (:38-41)."""
 from enum import Enum, unique
 
 
@@ -13,3 +13,10 @@ class BACKBONE(Enum):
 class BOX_LOSS(Enum):
     MSE = 0
     GIOU = 1
+
+
+@unique
+class DATASET_MODE(Enum):
+    TRAIN = 0
+    VALIDATE = 1
+    TEST = 2
