@@ -529,6 +529,28 @@ int yr_yolo_loss(const float* feats, const float* y_true, int batch, int gh, int
                  float ignore_thresh, void* workspace, size_t workspace_bytes,
                  float* out5 /*device*/, void* stream);
 
+/* ---- the gradient of that loss with respect to its logits: what differentiating the scalar of YoloLoss.call (model.py:607-671,
+ * GIOU branch; through yolo_head(calc_loss=True) :344-369 and do_giou_calculate, utils.py:9-53) gives at `feats`, as _train_step
+ * does (code/yolo3/train.py:18-46); added under ABI 9 (additive: no struct or existing entry changed).  Arguments, workspace
+ * (yr_yolo_loss_workspace_bytes) and checks as yr_yolo_loss, and out5 receives exactly the bits yr_yolo_loss writes, in the same
+ * three launches.
+ *   upstream_dev  device, one float32: the cotangent of the scalar loss, read by the kernel; null stands for 1.  It multiplies each
+ *                 finished float32 element as the last operation (a power of two scales the result exactly)
+ *   dfeats        device float32 [B,gh,gw,A,5+C] = upstream * d loss / d feats with m = B.  EVERY element is written, zeros
+ *                 included: nothing needs zeroing first.  4-byte alignment suffices
+ * Rules (TensorFlow's autodiff; unpinned by the reference like the forward, see csrc/loss.hip): ignore_mask is a constant and
+ * best_iou contributes nothing; channel 4: (om + (1 - om) * ignore) * (sigmoid(x4) - om) / m; channels 5..: om * (sigmoid(x_c) -
+ * t_c) / m; channels 0-3: -om / m * d giou / d(pred box) chained through the corners and the decode, the true box a constant;
+ * Maximum / Minimum send the gradient to their first operand on a tie (the prediction; maximum(zero, v) passes it only where
+ * v > 0), divide_no_nan passes none where the denominator is 0.  Box and class channels are exactly 0 where the object flag is 0.
+ * Float32 arithmetic; no atomics beyond the forward's list counter: the same call gives the same bytes.  This is the gradient at
+ * the logits only: no backward through the network. */
+int yr_yolo_loss_grad(const float* feats, const float* y_true, int batch, int gh, int gw, int num_anchors,
+                      int num_classes, const float* anchors_host /*A x (w,h)*/, int in_h, int in_w,
+                      float ignore_thresh, void* workspace, size_t workspace_bytes,
+                      const float* upstream_dev /*device, may be null = 1*/, float* out5 /*device*/,
+                      float* dfeats /*device*/, void* stream);
+
 /* ---- VOC matching of detections to ground truth: the greedy loop of MAPCallback.calculate_aps (code/yolo3/map.py:157-215)
  * on the device, per image; added under ABI 9 (additive: no struct or existing entry changed).
  *   det [B,rows,6], det_count [B]   exactly what yr_pack_detections writes; only the first det_count[b] rows of image b

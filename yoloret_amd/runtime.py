@@ -117,7 +117,7 @@ INGEST_GEOM_DTYPE = np.dtype([('src_off', '<i8'), ('ih', '<i4'), ('iw', '<i4'), 
 ABI_VERSION = 9   # == YR_ABI_VERSION of include/yoloret_hip.h
 EXPORTS = ['yr_ingest_geometry', 'yr_ingest_batch','yr_last_error', 'yr_abi_version', 'yr_abi_sizeof', 'yr_create', 'yr_create_from_blob', 'yr_plan_io_dims', 'yr_destroy', 'yr_load_weights', 'yr_workspace_bytes',
            'yr_forward', 'yr_forward_profile', 'yr_forward_ranges', 'yr_autotune', 'yr_get_tuning', 'yr_set_tuning', 'yr_plan_num_launches', 'yr_op_run', 'yr_head_regions', 'yr_head_walk_rows', 'yr_head_stream_rows', 'yr_pwt_chunks', 'yr_decode', 'yr_decode_zoom', 'yr_yolo_head', 'yr_correct_boxes',
-           'yr_nms', 'yr_pack_detections', 'yr_letterbox', 'yr_letterbox_batch', 'yr_yolo_loss_workspace_bytes', 'yr_yolo_loss', 'yr_voc_match', 'yr_encode_labels']
+           'yr_nms', 'yr_pack_detections', 'yr_letterbox', 'yr_letterbox_batch', 'yr_yolo_loss_workspace_bytes', 'yr_yolo_loss', 'yr_yolo_loss_grad', 'yr_voc_match', 'yr_encode_labels']
 
 _lib = None
 
@@ -179,6 +179,10 @@ def lib():
         L.yr_yolo_loss.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                                                             ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t,
                                                                                             ctypes.c_void_p, ctypes.c_void_p]
+        L.yr_yolo_loss_grad.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                                                                 ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t,
+                                                                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                                                                 ctypes.c_void_p]
         L.yr_voc_match.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                                                                             ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.yr_encode_labels.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5
@@ -370,35 +374,64 @@ def yolo_loss_workspace_bytes(batch, gh, gw, num_anchors):
     return int(lib().yr_yolo_loss_workspace_bytes(int(batch), int(gh), int(gw), int(num_anchors)))
 
 
+def _yolo_loss_args(name, feats, y_true, anchors, workspace):
+    """The validation yolo_loss and yolo_loss_grad share -> (b, gh, gw, a, ch, anchors, device, workspace, its size)."""
+    _require_cuda_f32(feats, 'feats')
+    _require_cuda_f32(y_true, 'y_true')
+    if feats.dim() != 5 or feats.shape[-1] < 5 or feats.numel() == 0:
+        raise ValueError('%s: feats has shape %s, expected [B,gh,gw,A,5+C]' % (name, tuple(feats.shape)))
+    if y_true.shape != feats.shape or y_true.device != feats.device:
+        raise ValueError('%s: y_true %s on %s, expected the logits\' %s on %s'
+                         % (name, tuple(y_true.shape), y_true.device, tuple(feats.shape), feats.device))
+    b, gh, gw, a, ch = feats.shape
+    anchors = np.ascontiguousarray(np.asarray(anchors, np.float32).reshape(-1, 2))
+    if anchors.shape[0] != a:
+        raise ValueError('%s: %d anchors for %d anchor slots' % (name, anchors.shape[0], a))
+    if not 1 <= a <= 8:
+        raise ValueError('%s: 1..8 anchor slots per cell, not %d' % (name, a))
+    dev = feats.device
+    need = yolo_loss_workspace_bytes(b, gh, gw, a)
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev) if workspace is None else workspace
+    if not (isinstance(ws, torch.Tensor) and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.device == dev and ws.numel() >= need):
+        raise ValueError('%s: workspace must be a contiguous uint8 tensor of at least %d bytes on %s' % (name, need, dev))
+    return b, gh, gw, a, ch, anchors, dev, ws
+
+
 def yolo_loss(feats, y_true, anchors, input_hw, ignore_thresh=.5, workspace=None):
     """YoloLoss.call, GIOU branch (model.py:607-671) for one scale.  feats, y_true [B,gh,gw,A,5+C] float32 on one device,
     anchors: the A (w,h) anchors of this scale -> float32 [5] on that device: loss, giou_loss, confidence_loss, class_loss,
     ignore_sum.  Launches only; nothing is copied to the host.  workspace: a uint8 tensor of at least
     yolo_loss_workspace_bytes(B, gh, gw, A) bytes on that device to work in (its contents do not matter); default: a fresh one."""
-    _require_cuda_f32(feats, 'feats')
-    _require_cuda_f32(y_true, 'y_true')
-    if feats.dim() != 5 or feats.shape[-1] < 5 or feats.numel() == 0:
-        raise ValueError('yolo_loss: feats has shape %s, expected [B,gh,gw,A,5+C]' % (tuple(feats.shape),))
-    if y_true.shape != feats.shape or y_true.device != feats.device:
-        raise ValueError('yolo_loss: y_true %s on %s, expected the logits\' %s on %s'
-                         % (tuple(y_true.shape), y_true.device, tuple(feats.shape), feats.device))
-    b, gh, gw, a, ch = feats.shape
-    anchors = np.ascontiguousarray(np.asarray(anchors, np.float32).reshape(-1, 2))
-    if anchors.shape[0] != a:
-        raise ValueError('yolo_loss: %d anchors for %d anchor slots' % (anchors.shape[0], a))
-    if not 1 <= a <= 8:
-        raise ValueError('yolo_loss: 1..8 anchor slots per cell, not %d' % a)
-    dev = feats.device
+    b, gh, gw, a, ch, anchors, dev, ws = _yolo_loss_args('yolo_loss', feats, y_true, anchors, workspace)
     out = torch.empty((5,), dtype=torch.float32, device=dev)
-    need = yolo_loss_workspace_bytes(b, gh, gw, a)
-    ws = torch.empty((need,), dtype=torch.uint8, device=dev) if workspace is None else workspace
-    if not (isinstance(ws, torch.Tensor) and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.device == dev and ws.numel() >= need):
-        raise ValueError('yolo_loss: workspace must be a contiguous uint8 tensor of at least %d bytes on %s' % (need, dev))
     with torch.cuda.device(dev):
         check(lib().yr_yolo_loss(_ptr(feats), _ptr(y_true), b, gh, gw, a, ch - 5, anchors.ctypes.data_as(ctypes.c_void_p),
                                  int(input_hw[0]), int(input_hw[1]), float(ignore_thresh), _ptr(ws), ws.numel(), _ptr(out),
                                  stream_ptr(dev)))
     return out
+
+
+def yolo_loss_grad(feats, y_true, anchors, input_hw, ignore_thresh=.5, upstream=None, workspace=None, out=None):
+    """The loss of ``yolo_loss`` and its gradient with respect to ``feats`` in one call (yr_yolo_loss_grad; the rules are in
+    csrc/loss.hip) -> (terms float32 [5]: the bits ``yolo_loss`` returns, dfeats float32 of feats' shape = upstream * d loss / d feats).
+    upstream: a float32 tensor of one element on the logits' device, the cotangent of the scalar loss (default: 1); it is read on
+    the device.  out: a contiguous float32 tensor of feats' shape on that device to receive dfeats (every element is written);
+    default: a fresh one.  Launches only."""
+    b, gh, gw, a, ch, anchors, dev, ws = _yolo_loss_args('yolo_loss_grad', feats, y_true, anchors, workspace)
+    if upstream is not None and not (isinstance(upstream, torch.Tensor) and upstream.dtype == torch.float32 and upstream.numel() == 1
+                                     and upstream.device == dev):
+        raise ValueError('yolo_loss_grad: upstream must be a float32 tensor of one element on %s' % dev)
+    if out is None:
+        out = torch.empty_like(feats)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == dev and out.shape == feats.shape
+              and out.is_contiguous()):
+        raise ValueError('yolo_loss_grad: out must be a contiguous float32 tensor of shape %s on %s' % (tuple(feats.shape), dev))
+    terms = torch.empty((5,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().yr_yolo_loss_grad(_ptr(feats), _ptr(y_true), b, gh, gw, a, ch - 5, anchors.ctypes.data_as(ctypes.c_void_p),
+                                      int(input_hw[0]), int(input_hw[1]), float(ignore_thresh), _ptr(ws), ws.numel(), _ptr(upstream),
+                                      _ptr(terms), _ptr(out), stream_ptr(dev)))
+    return terms, out
 
 
 VOC_MAX_ROWS, VOC_MAX_GT = 4096, 512     # YR_VOC_MAX_ROWS, YR_VOC_MAX_GT of include/yoloret_hip.h

@@ -11,7 +11,8 @@ Graph builders (record a ``yoloret_amd.layers`` graph, lowered by ``yoloret_amd.
   rfcr_module :146-168, yolov3_body :170-342.
 Post-processing (launch HIP kernels): yolo_head :344-371, yolo_correct_boxes :374-399,
   yolo_boxes_and_scores :402-428, yolo_eval :431-491, YoloEval :494-526.
-Loss forward (validation loss from device logits; no gradients): YoloLoss :585-691 (GIOU branch), yolo_loss.
+Loss (validation loss from device logits, and its gradient with respect to those logits; no backward through the
+network): YoloLoss :585-691 (GIOU branch), yolo_loss, yolo_loss_and_grad.
 
 Batch semantics: the reference folds the batch axis into the box list before NMS
 (:425-427) and pins inference to batch 1 (yolo.py:84).  Here a batch means "the
@@ -278,15 +279,41 @@ class YoloEval:
                 'score_threshold': self.score_threshold, 'iou_threshold': self.iou_threshold}
 
 
-# ----------------------------------------------------------------------------- loss forward
+# ----------------------------------------------------------------------------- loss: forward, and the gradient w.r.t. the logits
+class _YoloLossFunction(torch.autograd.Function):
+    """``YoloLoss.call`` for logits that require a gradient.  forward is the call of ``yr_yolo_loss`` that ``call`` makes anyway;
+    backward RECOMPUTES: nothing but the two inputs is saved, and one call of ``yr_yolo_loss_grad`` with ``grad_output`` as
+    its ``upstream`` (read on the device) yields the logits' gradient - no torch arithmetic on either side."""
+
+    @staticmethod
+    def forward(ctx, yolo_output, y_true, layer, input_hw):
+        terms = rt.yolo_loss(yolo_output, y_true, layer.anchor, input_hw, layer.ignore_thresh)
+        ctx.save_for_backward(yolo_output, y_true)
+        ctx.anchor, ctx.input_hw, ctx.ignore_thresh = layer.anchor, input_hw, layer.ignore_thresh
+        layer.last_terms = terms
+        return terms[0]
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        yolo_output, y_true = ctx.saved_tensors
+        upstream = grad_output.to(torch.float32).contiguous()      # (a 0-d float32 tensor on the logits' device already)
+        _, dfeats = rt.yolo_loss_grad(yolo_output, y_true, ctx.anchor, ctx.input_hw, ctx.ignore_thresh, upstream=upstream)
+        return dfeats, None, None, None
+
+
 class YoloLoss:
-    """The loss of one output scale (model.py:585-691), forward only: the GIoU / confidence / class sums of the GIOU
-    branch (:623-671) from the logits on the device, in one call of the HIP kernels behind ``yr_yolo_loss``.
+    """The loss of one output scale (model.py:585-691): the GIoU / confidence / class sums of the GIOU branch (:623-671)
+    from the logits on the device, in one call of the HIP kernels behind ``yr_yolo_loss``, and the gradient of that scalar
+    with respect to the logits (``yr_yolo_loss_grad``); there is no backward through the network.
 
     ``call(y_true, yolo_output)``: both [B,gh,gw,A,5+C] float32 CUDA tensors (``y_true`` as ``preprocess_true_boxes``
     writes it; a NumPy array is copied to the logits' device) -> the 0-d float32 device tensor ``loss``.
     ``last_terms`` keeps the device tensor [5] = (loss, giou_loss, confidence_loss, class_loss, ignore_sum) of the last
     call.  As in the reference, the labelled boxes a prediction is compared with are those of the whole batch (:643).
+    When ``yolo_output.requires_grad``, the same value comes back attached to a ``torch.autograd.Function`` whose backward
+    calls ``yr_yolo_loss_grad`` with the incoming gradient as ``upstream``: ``loss.backward()`` fills the logits' ``.grad``.
+    ``gradient(y_true, yolo_output, upstream=None)`` -> d loss / d yolo_output (times ``upstream``: a number, or a float32
+    tensor of one element on the logits' device) in the shape that was passed; it sets ``last_terms`` and never prints.
     ``print_loss`` prints the reference's line "<idx>: giou conf class ignore_sum" (:671); reading the four numbers
     SYNCHRONISES with the device, so pass ``print_loss=False`` where the loss is evaluated inside a pipeline.
     ``box_loss=BOX_LOSS.MSE`` raises NotImplementedError: the reference's MSE branch reads names that do not exist
@@ -305,7 +332,8 @@ class YoloLoss:
         self.anchor = np.asarray(anchors, np.float32).reshape(-1, 2)[anchor_masks[idx]]
         self.last_terms = None
 
-    def call(self, y_true, yolo_output):
+    def _inputs(self, y_true, yolo_output):
+        """-> (y_true, yolo_output) as [B,gh,gw,A,5+C], input_hw"""
         if not isinstance(yolo_output, torch.Tensor):
             raise ValueError('yolo_output must be a CUDA tensor (the logits of yolov3_body)')
         if not isinstance(y_true, torch.Tensor):
@@ -317,21 +345,44 @@ class YoloLoss:
         if y_true.dim() == 4 and y_true.numel() == yolo_output.numel():
             y_true = y_true.reshape(yolo_output.shape)
         input_hw = (yolo_output.shape[1] * self.grid_step, yolo_output.shape[2] * self.grid_step)   # :628
-        terms = rt.yolo_loss(yolo_output.contiguous(), y_true.contiguous(), self.anchor, input_hw, self.ignore_thresh)
-        self.last_terms = terms
+        return y_true, yolo_output, input_hw
+
+    def call(self, y_true, yolo_output):
+        y_true, yolo_output, input_hw = self._inputs(y_true, yolo_output)
+        if yolo_output.requires_grad and torch.is_grad_enabled():
+            loss = _YoloLossFunction.apply(yolo_output.contiguous(), y_true.detach().contiguous(), self, input_hw)   # (sets last_terms)
+            terms = self.last_terms
+        else:
+            terms = rt.yolo_loss(yolo_output.contiguous(), y_true.contiguous(), self.anchor, input_hw, self.ignore_thresh)
+            self.last_terms = terms
+            loss = terms[0]
         if self.print_loss:
             t = terms.tolist()   # (synchronises)
             print('%d: %s %s %s %s' % ((self.idx,) + tuple(str(np.float32(v)) for v in t[1:])))
-        return terms[0]
+        return loss
 
     __call__ = call
+
+    def gradient(self, y_true, yolo_output, upstream=None):
+        shape = tuple(yolo_output.shape) if isinstance(yolo_output, torch.Tensor) else None
+        y_true, yolo_output, input_hw = self._inputs(y_true, yolo_output)
+        if upstream is not None and not isinstance(upstream, torch.Tensor):
+            upstream = torch.full((1,), float(upstream), dtype=torch.float32, device=yolo_output.device)
+        terms, dfeats = rt.yolo_loss_grad(yolo_output.detach().contiguous(), y_true.detach().contiguous(), self.anchor, input_hw,
+                                          self.ignore_thresh, upstream=upstream)
+        self.last_terms = terms
+        return dfeats.reshape(shape)
+
+
+def _check_scales(name, yolo_outputs, y_trues, num_scales):
+    if len(yolo_outputs) < num_scales or len(y_trues) < num_scales:
+        raise ValueError('%s: %d logit tensors and %d label tensors for %d scales' % (name, len(yolo_outputs), len(y_trues), num_scales))
 
 
 def yolo_loss(yolo_outputs, y_trues, anchors, num_scales, ignore_thresh=.5):
     """The sum the reference forms over its list of per-scale losses: -> (total 0-d float32 device tensor,
     terms [num_scales,5] device tensor, one row of (loss, giou, conf, class, ignore_sum) per scale)."""
-    if len(yolo_outputs) < num_scales or len(y_trues) < num_scales:
-        raise ValueError('yolo_loss: %d logit tensors and %d label tensors for %d scales' % (len(yolo_outputs), len(y_trues), num_scales))
+    _check_scales('yolo_loss', yolo_outputs, y_trues, num_scales)
     rows = []
     for idx in range(num_scales):
         layer = YoloLoss(idx, anchors, num_scales, ignore_thresh, BOX_LOSS.GIOU, print_loss=False)
@@ -341,18 +392,44 @@ def yolo_loss(yolo_outputs, y_trues, anchors, num_scales, ignore_thresh=.5):
     return terms[:, 0].sum(), terms
 
 
-def yolo_loss_from_boxes(yolo_outputs, true_boxes, anchors, num_classes, num_scales, ignore_thresh=.5):
-    """``yolo_loss`` from ground-truth boxes instead of encoded labels: true_boxes [B,T,5] rows (x_min, y_min, x_max, y_max,
-    class) in pixels of the network input (a NumPy array or a float32 tensor on the logits' device), encoded on the logits'
-    device and current stream by the kernels behind ``yr_encode_labels`` - the label tensors never exist on the host.  The
-    input shape is derived from the grid of the first output, as YoloLoss does (:628) -> (total, terms) of ``yolo_loss``."""
+def yolo_loss_and_grad(yolo_outputs, y_trues, anchors, num_scales, ignore_thresh=.5):
+    """``yolo_loss`` and the gradient of its total (the sum over the scales, train.py:18-46) with respect to every logit
+    tensor, one call of ``yr_yolo_loss_grad`` per scale -> (total, terms, grads): total and terms as ``yolo_loss`` returns
+    them (the same bits), grads[i] float32 of the shape of yolo_outputs[i]."""
+    _check_scales('yolo_loss_and_grad', yolo_outputs, y_trues, num_scales)
+    rows, grads = [], []
+    for idx in range(num_scales):
+        layer = YoloLoss(idx, anchors, num_scales, ignore_thresh, BOX_LOSS.GIOU, print_loss=False)
+        grads.append(layer.gradient(y_trues[idx], yolo_outputs[idx]))
+        rows.append(layer.last_terms)
+    terms = torch.stack(rows)
+    return terms[:, 0].sum(), terms, grads
+
+
+def _labels_from_boxes(name, yolo_outputs, true_boxes, anchors, num_classes, num_scales):
     from .utils import preprocess_true_boxes_device
     if len(yolo_outputs) < num_scales:
-        raise ValueError('yolo_loss_from_boxes: %d logit tensors for %d scales' % (len(yolo_outputs), num_scales))
+        raise ValueError('%s: %d logit tensors for %d scales' % (name, len(yolo_outputs), num_scales))
     y0 = yolo_outputs[0]
     if not (isinstance(y0, torch.Tensor) and y0.is_cuda and y0.dim() in (4, 5)):
         raise ValueError('yolo_outputs must be CUDA tensors (the logits of yolov3_body)')
     input_hw = (y0.shape[1] * 32, y0.shape[2] * 32)
     with torch.cuda.device(y0.device):
         y_trues = preprocess_true_boxes_device(true_boxes, input_hw, anchors, num_classes, num_scales, device=y0.device)
-    return yolo_loss(yolo_outputs, [y_trues] if num_scales == 1 else list(y_trues), anchors, num_scales, ignore_thresh)
+    return [y_trues] if num_scales == 1 else list(y_trues)
+
+
+def yolo_loss_from_boxes(yolo_outputs, true_boxes, anchors, num_classes, num_scales, ignore_thresh=.5):
+    """``yolo_loss`` from ground-truth boxes instead of encoded labels: true_boxes [B,T,5] rows (x_min, y_min, x_max, y_max,
+    class) in pixels of the network input (a NumPy array or a float32 tensor on the logits' device), encoded on the logits'
+    device and current stream by the kernels behind ``yr_encode_labels`` - the label tensors never exist on the host.  The
+    input shape is derived from the grid of the first output, as YoloLoss does (:628) -> (total, terms) of ``yolo_loss``."""
+    y_trues = _labels_from_boxes('yolo_loss_from_boxes', yolo_outputs, true_boxes, anchors, num_classes, num_scales)
+    return yolo_loss(yolo_outputs, y_trues, anchors, num_scales, ignore_thresh)
+
+
+def yolo_loss_and_grad_from_boxes(yolo_outputs, true_boxes, anchors, num_classes, num_scales, ignore_thresh=.5):
+    """``yolo_loss_and_grad`` with the labels encoded from ground-truth boxes on the device, as ``yolo_loss_from_boxes``
+    does -> (total, terms, grads)."""
+    y_trues = _labels_from_boxes('yolo_loss_and_grad_from_boxes', yolo_outputs, true_boxes, anchors, num_classes, num_scales)
+    return yolo_loss_and_grad(yolo_outputs, y_trues, anchors, num_scales, ignore_thresh)
