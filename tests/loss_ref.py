@@ -110,25 +110,30 @@ def terms(res):
     return np.array([res['loss'], res['giou'], res['conf'], res['cls'], res['ignore_sum']], np.float64)
 
 
-def random_case(seed, batch, input_hw, num_classes, anchors, scales=(0, 1, 2), boxes_per_image=4):
+def random_case(seed, batch, input_hw, num_classes, anchors, scales=(0, 1, 2), boxes_per_image=4, slot_anchors=None):
     """The parity recipe: RandomState(seed).randn logits; per image and scale `boxes_per_image` labelled boxes at random
-    cells and slots, size = the slot's anchor x U(0.6, 1.6) per side, centre uniform inside the cell, one class bit.
-    -> {scale: (logits, y_true)} float32 [B,gh,gw,3,5+C]."""
+    cells and slots, size = the slot's anchor x U(0.6, 1.6) per side, centre uniform inside the cell, one class bit (none
+    with num_classes == 0).  -> {scale: (logits, y_true)} float32 [B,gh,gw,A,5+C].
+    A = 3 and the slots' anchors are scale_anchors(anchors, s), unless ``slot_anchors`` ([A,2], any A) names them: then every
+    scale of ``scales`` (which only sets the grid step) works with those A anchors and ``anchors`` is not read.  The defaults
+    draw what they always drew: the cases of the existing tests keep their bytes."""
     rs = np.random.RandomState(seed)
     case = {}
     for s in scales:
         gh, gw = input_hw[0] // GRID_STEPS[s], input_hw[1] // GRID_STEPS[s]
-        an = scale_anchors(anchors, s)
-        logits = rs.randn(batch, gh, gw, 3, 5 + num_classes).astype(np.float32)
+        an = scale_anchors(anchors, s) if slot_anchors is None else np.asarray(slot_anchors, np.float32).reshape(-1, 2)
+        na = an.shape[0]
+        logits = rs.randn(batch, gh, gw, na, 5 + num_classes).astype(np.float32)
         y_true = np.zeros_like(logits)
         for b in range(batch):
             for _ in range(boxes_per_image):
-                j, i, k = rs.randint(gh), rs.randint(gw), rs.randint(3)
+                j, i, k = rs.randint(gh), rs.randint(gw), rs.randint(na)
                 w, h = an[k] * rs.uniform(0.6, 1.6, 2)
                 cx, cy = (i + rs.uniform()) / gw, (j + rs.uniform()) / gh
                 y_true[b, j, i, k] = 0
                 y_true[b, j, i, k, :5] = (cx, cy, w / input_hw[1], h / input_hw[0], 1)
-                y_true[b, j, i, k, 5 + rs.randint(num_classes)] = 1
+                if num_classes:
+                    y_true[b, j, i, k, 5 + rs.randint(num_classes)] = 1
         case[s] = (logits, y_true)
     return case
 

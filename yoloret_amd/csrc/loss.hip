@@ -24,7 +24,12 @@
 // The gradient (yr_yolo_loss_grad): dfeats = upstream * d loss / d feats, [B,gh,gw,A,5+C] float32, m = B, in the same three launches
 // (loss_main_kernel<true>), so out5 holds the bits yr_yolo_loss writes.  The rules are what TensorFlow's autodiff gives for
 // model.py:607-671; like the rest of the oracle they are UNPINNED BY THE REFERENCE (no TensorFlow where this is tested) and pinned
-// by hand-derived answers and finite differences of the float64 restatement (tests/lossgrad_ref.py, tests/test_lossgrad_host.py):
+// by hand-derived answers and finite differences of the float64 restatement (tests/lossgrad_ref.py, tests/test_lossgrad_host.py).
+// Pinned on the device (tests/test_gpu_lossgrad_edges.py, against that restatement with every Maximum / Minimum as a select, which
+// makes it valid AT ties): the tie rules below at all 13 x 13 interval relations of a label to its prediction and at zero-size
+// labels; the strict threshold at an IoU of exactly 0.5; box lists of one chunk exactly, one box more, two and three chunks; rows
+// of 5 to 305 floats (C = 0 .. 300: LOSS_T / row == 0 and LOSS_T % row == 0 included); A from 1 to 8; totals below and equal to
+// LOSS_T; object flags other than 1.  Outside the contract: non-finite inputs, and logits beyond yr_expf's clamp (last rule).
 //   * ignore_mask (:649) is the result of a comparison: a constant.  best_iou (:644-648) contributes nothing.
 //   * channel 4:    ((om + (1 - om) * ignore) * (sigmoid(x4) - om)) / m          [d sce(z, x) / dx = sigmoid(x) - z; :653-657, :663]
 //   * channels 5..: (om * (sigmoid(x_c) - t_c)) / m, exactly 0 where om == 0     [:658-662]
