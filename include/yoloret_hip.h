@@ -379,7 +379,7 @@ typedef struct yr_handle yr_handle;
 
 const char* yr_last_error(void);
 int yr_abi_version(void);
-/* sizeof(yr_src) / sizeof(yr_op) / sizeof(yr_buf) / sizeof(yr_ingest_geom) for which = 0 / 1 / 2 / 3 (else 0): lets a binding that restates the
+/* sizeof(yr_src) / sizeof(yr_op) / sizeof(yr_buf) / sizeof(yr_ingest_geom) / sizeof(yr_augment_geom) for which = 0 / 1 / 2 / 3 / 4 (else 0): lets a binding that restates the
  * structs (ctypes, cgo, JNA ...) verify its layout against the library's at load time. */
 int yr_abi_sizeof(int which);
 
@@ -656,6 +656,66 @@ int yr_ingest_batch(int mode, const unsigned char* src_u8 /*device, packed*/, co
                     float* dst /*[B,H,W,3]*/, int H, int W,
                     const float* boxes_in /*[B,max_in,5] or null*/, const int32_t* box_count /*[B]*/, int max_in,
                     float* boxes_out /*[B,max_boxes,5]*/, int32_t* kept /*[B], may be null*/, int max_boxes, void* stream);
+
+/* ---- training data transform: get_random_data(train=True) (code/yolo3/utils.py:170-237, then :258-293) for a ragged batch of
+ * decoded uint8 images -> the float32 [B,H,W,3] network input and the mapped boxes; added under ABI 9 (additive: no struct or
+ * existing entry changed; yr_abi_sizeof(4) reports sizeof(yr_augment_geom)).  Per image, in the reference's order: random
+ * aspect and scale, resize (bilinear, half-pixel centres, no antialias), crop and / or pad to H x W, flip, random_hue,
+ * random_saturation, adjust_gamma, random_contrast, clip_by_value(0, 1); the boxes follow the geometry and the flip.
+ * NOT built: random_jpeg_quality (:228-230, ON by default in the reference: a libjpeg encode and decode of the augmented float
+ * image), random_brightness (val), noise, blur, zoom_in (all off by default).
+ * TensorFlow is not available to this project: adjust_hue and adjust_saturation follow TF 2.x's fused CPU kernels as restated
+ * from memory in tests/augment_ref.py, which is the definition the kernels are tested against. */
+#define YR_AUG_HUE      1       /* stage mask: random_hue        (the reference's `hue > 0`) */
+#define YR_AUG_SAT      2       /*             random_saturation (`sat > 0`) */
+#define YR_AUG_GAMMA    4       /*             adjust_gamma      (`min_gamma < max_gamma`) */
+#define YR_AUG_CONTRAST 8       /*             random_contrast   (`cont > 0`) */
+#define YR_AUG_NOFLIP   16      /*             set: `flip=False`, the flip draw is ignored */
+#define YR_AUG_ALL      31
+typedef struct {                /* 96 bytes; yr_abi_sizeof(4) reports it */
+    int64_t src_off;            /* byte offset of image b in the packed source, a multiple of 16 (yr_ingest_geometry's packing) */
+    int32_t ih, iw;             /* source size */
+    int32_t rh, rw;             /* the size the source is resized to: int(nh), int(nw) */
+    int32_t cy, cx;             /* crop offset inside the resized image */
+    int32_t wh, ww;             /* the visible window: min(H, rh) x min(W, rw) after a crop, rh x rw without */
+    int32_t py, px;             /* where the window sits in the H x W canvas (before the flip) */
+    int32_t flip;               /* 1: the canvas is mirrored, out[y][x] = canvas[y][W - 1 - x] */
+    int32_t clamped;            /* 1: max(ratio, 1) took the 1 (information only) */
+    int32_t reserved[2];        /* 0 */
+    float   nh_f, nw_f, dy_f, dx_f;   /* the untruncated float32 values the boxes use */
+    float   hue6, sat, gamma, cont;   /* delta * 6, saturation factor, gamma, contrast factor; the identity (0, 1, 1, 1) for a stage that is off */
+} yr_augment_geom;
+/* The one place where the arithmetic of utils.py:171-181 and of the ten draws lives; pure host, no device touched, all float32,
+ * uniform(lo, hi) = lo + u * (hi - lo) with the bounds rounded to float32 once from the double expression (1 - jitter, ...):
+ *   draws_host [B][10] = j1, j2, scale, dx, dy, flip, hue, sat, gamma, contrast, each u in [0, 1)
+ *   new_ar = (W / H) * (U(j1; 1 - jitter, 1 + jitter) / U(j2; same));  scale = U(min_scale, max_scale)
+ *   ratio = max(new_ar < 1 ? scale * new_ar : scale / new_ar, 1)
+ *   (nw, nh) = new_ar < 1 ? (ratio * H, scale * H) : (scale * W, ratio * W);  dx = U(0, W - nw);  dy = U(0, H - nh)
+ *   nw > W or nh > H: crop at (int(max(-dy, 0)), int(max(-dx, 0))) to min(H, int(nh)) x min(W, int(nw)); always: pad at
+ *   (int(max(dy, 0)), int(max(dx, 0)));  flip iff the flip draw < 0.5 and YR_AUG_NOFLIP is clear
+ *   hue6 = U(-hue, hue) * 6;  sat = U(1 - sat, 1 + sat);  gamma = U(min_gamma, max_gamma);  cont = U(1 - cont, 1 + cont)
+ * dims_host and packed_bytes as in yr_ingest_geometry.  YR_ERR_ARG, with the image's index in the message, where a resized side
+ * truncates to 0 or where a precondition of crop_to_bounding_box / pad_to_bounding_box fails (TensorFlow raises there too; no
+ * draw in [0, 1) is known to get there), and for parameters outside jitter in [0, 1), hue in [0, .5], sat and cont in [0, 1]. */
+int yr_augment_geometry(int batch, const int32_t* dims_host /*[B][2] = ih, iw*/, int H, int W, const float* draws_host /*[B][10]*/,
+                        int stages, double jitter /*.3*/, double min_scale /*.25*/, double max_scale /*2*/, double hue /*.5*/,
+                        double sat /*.5*/, double min_gamma /*.8*/, double max_gamma /*2*/, double cont /*.1*/,
+                        yr_augment_geom* geom_host /*[B]*/, int64_t* packed_bytes);
+/* Bytes of the workspace of the launch below: one slot of three float32 channel sums per image workgroup. */
+size_t yr_augment_workspace_bytes(int batch, int H, int W);
+/* The launches.  `stages` is the mask the table was computed with.  Every element of dst [B,H,W,3] is written; with boxes_in
+ * (the arguments and the rules of yr_ingest_batch's box part, plus (xmin, xmax) -> (W - xmax, W - xmin) on a flipped image) every
+ * element of boxes_out and kept; boxes_in null: images only.  Contrast uses the mean of each channel over the whole H x W canvas,
+ * padding included, after gamma: launch 1 stores every pixel through gamma and one slot of channel sums per workgroup, launch 2
+ * adds an image's slots in a fixed order, applies contrast and the clip in place and maps the boxes in one extra workgroup per
+ * image.  Without YR_AUG_CONTRAST launch 1 clips, launch 2 carries only the boxes and the workspace may be null.  No atomics; the
+ * same call gives the same bytes.  H * W must be a multiple of 4; src_u8, geom, dst and workspace need 16-byte alignment;
+ * B * H * W < 2^31.  Pixel values before gamma are non-negative by construction, so pow sees no negative base. */
+int yr_augment_batch(const unsigned char* src_u8 /*device, packed*/, const yr_augment_geom* geom /*device [B]*/, int batch, int stages,
+                     float* dst /*[B,H,W,3]*/, int H, int W,
+                     const float* boxes_in /*[B,max_in,5] or null*/, const int32_t* box_count /*[B]*/, int max_in,
+                     float* boxes_out /*[B,max_boxes,5]*/, int32_t* kept /*[B], may be null*/, int max_boxes,
+                     void* workspace /*device*/, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -21,6 +21,7 @@
 //   * box workgroups (VALIDATE mode with boxes only): one per image behind the image workgroups, lane = input row.  The order-
 //     preserving compaction is a ballot per wave and a prefix over the four waves, as in labels.hip.
 #include "yr_common.h"
+#include "datapath_common.h"
 
 #define ING_T YR_INGEST_MAX_BOXES   // lanes of a workgroup = input rows per image
 
@@ -54,70 +55,24 @@ __device__ __forceinline__ IngGeo ing_geo(const IngArgs& a, unsigned b) {
     return o;
 }
 
-// one pixel of the network input: letterbox_kernel's body (preprocess.hip), then VALIDATE's clip (utils.py:277)
+// one pixel of the network input: the window, the resize (datapath_common.h), then VALIDATE's clip (utils.py:277)
 __device__ __forceinline__ void ing_pixel(const IngGeo& g, int y, int x, bool clip, float* o) {
     const int ry = y - g.dy, rx = x - g.dx;
     if (ry < 0 || ry >= g.nh || rx < 0 || rx >= g.nw) { o[0] = o[1] = o[2] = 0.0f; return; }
-    const float inv255 = 1.0f / 255.0f;
-    const float fy = ((float)ry + 0.5f) * g.sy - 0.5f, fx = ((float)rx + 0.5f) * g.sx - 0.5f;
-    const float fly = floorf(fy), flx = floorf(fx);
-    const int y0 = max((int)fly, 0), y1 = min((int)ceilf(fy), g.ih - 1);
-    const int x0 = max((int)flx, 0), x1 = min((int)ceilf(fx), g.iw - 1);
-    const float ly = fy - fly, lx = fx - flx;
-    const unsigned char* p00 = g.src + ((size_t)y0 * g.iw + x0) * 3;
-    const unsigned char* p01 = g.src + ((size_t)y0 * g.iw + x1) * 3;
-    const unsigned char* p10 = g.src + ((size_t)y1 * g.iw + x0) * 3;
-    const unsigned char* p11 = g.src + ((size_t)y1 * g.iw + x1) * 3;
+    yr_resize_pixel(g.src, g.ih, g.iw, g.sy, g.sx, ry, rx, o);
+    if (clip) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float tl = (float)p00[c] * inv255, tr = (float)p01[c] * inv255;
-        const float bl = (float)p10[c] * inv255, br = (float)p11[c] * inv255;
-        const float top = tl + (tr - tl) * lx;
-        const float bot = bl + (br - bl) * lx;
-        float v = top + (bot - top) * ly;
-        if (clip) v = fmaxf(fminf(v, 1.0f), 0.0f);
-        o[c] = v;
+        for (int c = 0; c < 3; ++c) o[c] = fmaxf(fminf(o[c], 1.0f), 0.0f);
     }
 }
 
+// the box workgroup of image b: datapath_common.h (shared with augment.hip), without the flip
 __device__ __forceinline__ void ing_boxes(const IngArgs& a, unsigned b) {
-    __shared__ int wkept[ING_T / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const yr_ingest_geom* g = a.geom + b;
-    const float iwf = (float)g->iw, ihf = (float)g->ih;
-    const float nwf = g->nw_f, nhf = g->nh_f, dxf = g->dx_f, dyf = g->dy_f;
-    int n = a.box_count[b];
-    n = n < 0 ? 0 : (n > a.max_in ? a.max_in : n);
-    float x0 = 0.0f, y0 = 0.0f, x1 = 0.0f, y1 = 0.0f, label = 0.0f;
-    bool keep = false;
-    if (tid < n) {
-        const float* t = a.boxes_in + ((size_t)b * a.max_in + tid) * 5;
-        const float xmax = (float)(a.W - 1), ymax = (float)(a.H - 1);
-        // :253-256 left to right, then :258-273 (clip_by_value: the minimum first)
-        x0 = fmaxf(fminf(t[0] * nwf / iwf + dxf, xmax), 0.0f);
-        y0 = fmaxf(fminf(t[1] * nhf / ihf + dyf, ymax), 0.0f);
-        x1 = fmaxf(fminf(t[2] * nwf / iwf + dxf, xmax), 0.0f);
-        y1 = fmaxf(fminf(t[3] * nhf / ihf + dyf, ymax), 0.0f);
-        label = t[4];
-        keep = x1 - x0 > 1.0f && y1 - y0 > 1.0f;     // :289-291
-    }
-    const unsigned long long m = __ballot(keep);
-    if (lane == 0) wkept[wave] = __popcll(m);
-    __syncthreads();
-    int rank = __popcll(m & ((1ull << lane) - 1ull)), total = 0;
-#pragma unroll
-    for (int k = 0; k < ING_T / 64; ++k) {
-        if (k < wave) rank += wkept[k];
-        total += wkept[k];
-    }
-    const int nk = total < a.max_boxes ? total : a.max_boxes;     // :292-293
-    float* out = a.boxes_out + (size_t)b * a.max_boxes * 5;
-    if (keep && rank < nk) {
-        float* e = out + (size_t)rank * 5;
-        e[0] = x0; e[1] = y0; e[2] = x1; e[3] = y1; e[4] = label;
-    }
-    for (int e = nk * 5 + tid; e < a.max_boxes * 5; e += ING_T) out[e] = 0.0f;
-    if (tid == 0 && a.kept != nullptr) a.kept[b] = nk;
+    YrBoxMap m;
+    m.boxes_in = a.boxes_in; m.box_count = a.box_count; m.max_in = a.max_in; m.boxes_out = a.boxes_out; m.kept = a.kept;
+    m.max_boxes = a.max_boxes; m.H = a.H; m.W = a.W;
+    yr_map_boxes(m, b, (float)g->ih, (float)g->iw, g->nh_f, g->nw_f, g->dy_f, g->dx_f, false);
 }
 
 __global__ __launch_bounds__(ING_T) void ingest_kernel(IngArgs a) {

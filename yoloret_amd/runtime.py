@@ -114,8 +114,24 @@ class YrIngestGeom(ctypes.Structure):
 INGEST_GEOM_DTYPE = np.dtype([('src_off', '<i8'), ('ih', '<i4'), ('iw', '<i4'), ('nh', '<i4'), ('nw', '<i4'), ('dy', '<i4'), ('dx', '<i4'),
                               ('nh_f', '<f4'), ('nw_f', '<f4'), ('dy_f', '<f4'), ('dx_f', '<f4'), ('reserved', '<i4', (4,))])
 
+
+class YrAugmentGeom(ctypes.Structure):
+    """yr_augment_geom: one image of a ragged batch under get_random_data(train=True) - resize size, crop, window, pad, flip, the
+    untruncated floats of the boxes and the four colour scalars."""
+    _fields_ = [('src_off', ctypes.c_int64), ('ih', ctypes.c_int32), ('iw', ctypes.c_int32), ('rh', ctypes.c_int32), ('rw', ctypes.c_int32),
+                ('cy', ctypes.c_int32), ('cx', ctypes.c_int32), ('wh', ctypes.c_int32), ('ww', ctypes.c_int32), ('py', ctypes.c_int32),
+                ('px', ctypes.c_int32), ('flip', ctypes.c_int32), ('clamped', ctypes.c_int32), ('reserved', ctypes.c_int32 * 2),
+                ('nh_f', ctypes.c_float), ('nw_f', ctypes.c_float), ('dy_f', ctypes.c_float), ('dx_f', ctypes.c_float),
+                ('hue6', ctypes.c_float), ('sat', ctypes.c_float), ('gamma', ctypes.c_float), ('cont', ctypes.c_float)]
+
+
+AUGMENT_GEOM_DTYPE = np.dtype([('src_off', '<i8'), ('ih', '<i4'), ('iw', '<i4'), ('rh', '<i4'), ('rw', '<i4'), ('cy', '<i4'), ('cx', '<i4'),
+                               ('wh', '<i4'), ('ww', '<i4'), ('py', '<i4'), ('px', '<i4'), ('flip', '<i4'), ('clamped', '<i4'),
+                               ('reserved', '<i4', (2,)), ('nh_f', '<f4'), ('nw_f', '<f4'), ('dy_f', '<f4'), ('dx_f', '<f4'),
+                               ('hue6', '<f4'), ('sat', '<f4'), ('gamma', '<f4'), ('cont', '<f4')])
+
 ABI_VERSION = 9   # == YR_ABI_VERSION of include/yoloret_hip.h
-EXPORTS = ['yr_ingest_geometry', 'yr_ingest_batch','yr_last_error', 'yr_abi_version', 'yr_abi_sizeof', 'yr_create', 'yr_create_from_blob', 'yr_plan_io_dims', 'yr_destroy', 'yr_load_weights', 'yr_workspace_bytes',
+EXPORTS = ['yr_augment_geometry', 'yr_augment_workspace_bytes', 'yr_augment_batch', 'yr_ingest_geometry', 'yr_ingest_batch', 'yr_last_error', 'yr_abi_version', 'yr_abi_sizeof', 'yr_create', 'yr_create_from_blob', 'yr_plan_io_dims', 'yr_destroy', 'yr_load_weights', 'yr_workspace_bytes',
            'yr_forward', 'yr_forward_profile', 'yr_forward_ranges', 'yr_autotune', 'yr_get_tuning', 'yr_set_tuning', 'yr_plan_num_launches', 'yr_op_run', 'yr_head_regions', 'yr_head_walk_rows', 'yr_head_stream_rows', 'yr_pwt_chunks', 'yr_decode', 'yr_decode_zoom', 'yr_yolo_head', 'yr_correct_boxes',
            'yr_nms', 'yr_pack_detections', 'yr_letterbox', 'yr_letterbox_batch', 'yr_yolo_loss_workspace_bytes', 'yr_yolo_loss', 'yr_yolo_loss_grad', 'yr_voc_match', 'yr_encode_labels']
 
@@ -189,12 +205,21 @@ def lib():
         L.yr_ingest_geometry.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         L.yr_ingest_batch.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        L.yr_augment_geometry.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + \
+            [ctypes.c_double] * 8 + [ctypes.c_void_p, ctypes.c_void_p]
+        L.yr_augment_workspace_bytes.restype = ctypes.c_size_t
+        L.yr_augment_workspace_bytes.argtypes = [ctypes.c_int] * 3
+        L.yr_augment_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                       ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         if L.yr_abi_version() != ABI_VERSION:
             raise YoloretHipError('libyoloret_hip.so ABI version mismatch')
         L.yr_abi_sizeof.argtypes = [ctypes.c_int]
         if INGEST_GEOM_DTYPE.itemsize != ctypes.sizeof(YrIngestGeom):
             raise YoloretHipError('INGEST_GEOM_DTYPE: %d bytes, YrIngestGeom %d' % (INGEST_GEOM_DTYPE.itemsize, ctypes.sizeof(YrIngestGeom)))
-        for which, st in enumerate((YrSrc, YrOp, YrBuf, YrIngestGeom)):
+        if AUGMENT_GEOM_DTYPE.itemsize != ctypes.sizeof(YrAugmentGeom):
+            raise YoloretHipError('AUGMENT_GEOM_DTYPE: %d bytes, YrAugmentGeom %d' % (AUGMENT_GEOM_DTYPE.itemsize, ctypes.sizeof(YrAugmentGeom)))
+        for which, st in enumerate((YrSrc, YrOp, YrBuf, YrIngestGeom, YrAugmentGeom)):
             if L.yr_abi_sizeof(which) != ctypes.sizeof(st):
                 raise YoloretHipError('struct %s: %d bytes here, %d in libyoloret_hip.so'
                                       % (st.__name__, ctypes.sizeof(st), L.yr_abi_sizeof(which)))
@@ -671,8 +696,15 @@ class RaggedStager:
         for i, im in enumerate(images):
             if im.ndim != 3 or im.shape[2] != 3:
                 raise ValueError('RaggedStager: image %d has shape %s, [h,w,3] expected' % (i, im.shape))
-        table = ingest_geometry([im.shape[:2] for im in images], input_hw, mode)
-        tbytes = table.batch * INGEST_GEOM_DTYPE.itemsize
+        return self.upload_table(images, ingest_geometry([im.shape[:2] for im in images], input_hw, mode))
+
+    def upload_table(self, images, table):
+        """The same for a table the caller made (an IngestTable or an AugmentTable of these images, in this order)
+        -> (packed uint8 CUDA tensor, the table, uploaded)."""
+        images = [np.ascontiguousarray(im, np.uint8) for im in images]
+        if table.batch != len(images) or any(tuple(im.shape) != (int(g['ih']), int(g['iw']), 3) for im, g in zip(images, table.host)):
+            raise ValueError('RaggedStager: the table was not computed for these %d images' % len(images))
+        tbytes = table.host.nbytes
         total = table.packed_bytes + tbytes
         if self._event is not None:
             self._event.synchronize()      # the previous copy has read the buffer
@@ -690,6 +722,117 @@ class RaggedStager:
             self._event.record(torch.cuda.current_stream(self.device))
         table.device = dev[table.packed_bytes:total]
         return dev[:table.packed_bytes], table
+
+
+# ----------------------------------------------------------------------------- training data transform
+AUG_HUE, AUG_SAT, AUG_GAMMA, AUG_CONTRAST, AUG_NOFLIP, AUG_ALL = 1, 2, 4, 8, 16, 31     # YR_AUG_* of include/yoloret_hip.h
+AUGMENT_DEFAULTS = dict(jitter=.3, min_scale=.25, max_scale=2., hue=.5, sat=.5, min_gamma=.8, max_gamma=2., cont=.1)   # utils.py:130-140
+AUGMENT_DRAWS = ('j1', 'j2', 'scale', 'dx', 'dy', 'flip', 'hue', 'sat', 'gamma', 'contrast')     # the order of one image's ten draws
+
+
+class AugmentTable:
+    """The table of one ragged batch under get_random_data(train=True) (yr_augment_geometry): ``host`` is the structured array
+    [B] (AUGMENT_GEOM_DTYPE), ``stages`` the mask it was computed with, ``packed_bytes`` the size of the packed source, ``device``
+    the uint8 tensor [B * 96] with its bytes on the GPU once uploaded (RaggedStager.upload_table)."""
+
+    def __init__(self, host, stages, input_hw, packed_bytes):
+        self.host, self.stages, self.input_hw, self.packed_bytes = host, int(stages), (int(input_hw[0]), int(input_hw[1])), int(packed_bytes)
+        self.batch = int(host.shape[0])
+        self.device = None
+
+    def upload(self, device):
+        """The table alone, in a copy of its own (tests and tools; a pipeline uploads it with the images: RaggedStager)."""
+        self.device = torch.from_numpy(self.host.view(np.uint8).copy()).to(device)
+        return self
+
+
+def augment_stages(flip=True, hue=.5, sat=.5, min_gamma=.8, max_gamma=2., cont=.1):
+    """The stage mask of the reference's own conditions (utils.py:212,218,220,224,226)."""
+    return ((0 if flip else AUG_NOFLIP) | (AUG_HUE if hue > 0 else 0) | (AUG_SAT if sat > 0 else 0)
+            | (AUG_GAMMA if min_gamma < max_gamma else 0) | (AUG_CONTRAST if cont > 0 else 0))
+
+
+def augment_geometry(dims, input_hw, draws, stages=None, flip=True, **params):
+    """dims: B x (ih, iw); draws: B x 10 uniforms in [0, 1) in the order AUGMENT_DRAWS -> AugmentTable: utils.py:171-181 and the
+    colour draws of :218-227 in float32, inside the library (host arithmetic, no device touched).  ``params``: jitter, min_scale,
+    max_scale, hue, sat, min_gamma, max_gamma, cont (AUGMENT_DEFAULTS).  ``stages``: the mask of AUG_* bits; None derives it from
+    the parameters and ``flip`` as the reference does.  YoloretHipError naming the image where a resized side truncates to 0 or a
+    crop / pad precondition of TensorFlow's fails."""
+    unknown = set(params) - set(AUGMENT_DEFAULTS)
+    if unknown:
+        raise TypeError('augment_geometry: unknown parameters %s' % sorted(unknown))
+    p = dict(AUGMENT_DEFAULTS, **params)
+    if stages is None:
+        stages = augment_stages(flip, p['hue'], p['sat'], p['min_gamma'], p['max_gamma'], p['cont'])
+    dims = np.ascontiguousarray(np.asarray(dims, np.int64).reshape(-1, 2).astype(np.int32))
+    if dims.shape[0] == 0:
+        raise ValueError('augment_geometry: no image')
+    draws = np.ascontiguousarray(np.asarray(draws, np.float32))
+    if draws.shape != (dims.shape[0], 10):
+        raise ValueError('augment_geometry: draws must be [B=%d,10], not %s' % (dims.shape[0], draws.shape))
+    host = np.zeros(dims.shape[0], AUGMENT_GEOM_DTYPE)
+    packed = ctypes.c_int64(0)
+    check(lib().yr_augment_geometry(dims.shape[0], dims.ctypes.data_as(ctypes.c_void_p), int(input_hw[0]), int(input_hw[1]),
+                                    draws.ctypes.data_as(ctypes.c_void_p), int(stages), *[float(p[k]) for k in
+                                    ('jitter', 'min_scale', 'max_scale', 'hue', 'sat', 'min_gamma', 'max_gamma', 'cont')],
+                                    host.ctypes.data_as(ctypes.c_void_p), ctypes.byref(packed)))
+    return AugmentTable(host, stages, input_hw, packed.value)
+
+
+def augment_workspace_bytes(batch, input_hw):
+    return int(lib().yr_augment_workspace_bytes(int(batch), int(input_hw[0]), int(input_hw[1])))
+
+
+def augment_batch(packed_u8, table, input_hw, boxes=None, box_count=None, max_boxes=20, out=None, workspace=None):
+    """get_random_data(train=True) for a ragged batch, two launches.  packed_u8: uint8 CUDA tensor holding the decoded images at
+    the offsets of ``table`` (an uploaded AugmentTable for ``input_hw``) -> float32 [B,H,W,3].  With ``boxes`` (float32 CUDA
+    [B,max_in,5] rows (xmin, ymin, xmax, ymax, label) in source pixels, max_in <= 256) and ``box_count`` (int32 [B]):
+    -> (images, boxes_out [B,max_boxes,5], kept [B] int32) as utils.py:208-217,258-293.  random_jpeg_quality, which the reference
+    applies by default, is not built.  ``workspace``: a uint8 CUDA tensor of augment_workspace_bytes, made here when None."""
+    if not (isinstance(packed_u8, torch.Tensor) and packed_u8.is_cuda and packed_u8.dtype == torch.uint8 and packed_u8.is_contiguous()):
+        raise ValueError('augment_batch: the packed source must be a contiguous uint8 CUDA tensor')
+    if not isinstance(table, AugmentTable) or table.device is None:
+        raise ValueError('augment_batch: table must be an uploaded AugmentTable (augment_geometry + RaggedStager.upload_table / AugmentTable.upload)')
+    dev = packed_u8.device
+    h, w = int(input_hw[0]), int(input_hw[1])
+    b = table.batch
+    if (h, w) != table.input_hw:
+        raise ValueError('augment_batch: the table was computed for %dx%d, not %dx%d' % (table.input_hw + (h, w)))
+    if h * w % 4:
+        raise ValueError('augment_batch: H * W must be a multiple of 4, not %dx%d' % (h, w))
+    if table.device.device != dev or table.device.dtype != torch.uint8 or table.device.numel() != b * AUGMENT_GEOM_DTYPE.itemsize:
+        raise ValueError('augment_batch: the table\'s device copy must be %d bytes on %s' % (b * AUGMENT_GEOM_DTYPE.itemsize, dev))
+    if packed_u8.numel() < table.packed_bytes - 15:
+        raise ValueError('augment_batch: the packed source holds %d bytes, the table addresses %d' % (packed_u8.numel(), table.packed_bytes))
+    shape = (b, h, w, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise ValueError('out must be a contiguous float32 tensor %s on the source\'s device' % (shape,))
+    need = augment_workspace_bytes(b, (h, w))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not (isinstance(workspace, torch.Tensor) and workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous()
+              and workspace.numel() >= need):
+        raise ValueError('augment_batch: workspace must be a contiguous uint8 tensor of at least %d bytes on %s' % (need, dev))
+    boxes_out = kept = None
+    max_in = 0
+    if boxes is not None:
+        if not (isinstance(boxes, torch.Tensor) and boxes.dtype == torch.float32 and boxes.is_contiguous() and boxes.device == dev
+                and boxes.dim() == 3 and boxes.shape[0] == b and boxes.shape[2] == 5 and 1 <= boxes.shape[1] <= INGEST_MAX_BOXES):
+            raise ValueError('augment_batch: boxes must be a contiguous float32 tensor [B=%d,max_in,5] on %s with 1 <= max_in <= %d'
+                             % (b, dev, INGEST_MAX_BOXES))
+        if not (_is_cuda_i32(box_count) and box_count.device == dev and tuple(box_count.shape) == (b,)):
+            raise ValueError('augment_batch: box_count must be a contiguous int32 [B=%d] tensor on %s' % (b, dev))
+        if int(max_boxes) < 1:
+            raise ValueError('augment_batch: max_boxes must be at least 1, not %d' % max_boxes)
+        max_in = int(boxes.shape[1])
+        boxes_out = torch.empty((b, int(max_boxes), 5), dtype=torch.float32, device=dev)
+        kept = torch.empty((b,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().yr_augment_batch(_ptr(packed_u8), _ptr(table.device), b, table.stages, _ptr(out), h, w, _ptr(boxes), _ptr(box_count), max_in,
+                                     _ptr(boxes_out), _ptr(kept), int(max_boxes), _ptr(workspace), workspace.numel(), stream_ptr(dev)))
+    return out if boxes is None else (out, boxes_out, kept)
 
 
 def image_hw_tensor(image_shape, batch, device):

@@ -1,5 +1,6 @@
-"""The validation data path - mirror of reference code/yolo3/data.py for ``mode=VALIDATE`` / ``TEST`` (both ``train=False``):
-label file -> batches of (letterboxed images, y_true) on the GPU.
+"""The data paths - mirror of reference code/yolo3/data.py: label file -> batches of (images, y_true) on the GPU.
+``Dataset`` is the validation path, ``mode=VALIDATE`` / ``TEST`` (both ``train=False``: one fixed letterbox per image);
+``AugmentedDataset`` is the training path (``train=True``: shuffled records, get_random_data's augmentation).
 
 ``Dataset(...)`` has the reference's constructor (:151-167) plus ``device`` and ``root``; ``build()`` (:172-200) returns
 ``(iterable, num)`` and raises its errors.  Per batch only the JPEG / PNG decode (PIL) and the text parse stay on the host:
@@ -12,8 +13,9 @@ Differences that are deliberate:
   * iteration is deterministic - files sorted, lines in order, batches of ``batch_size`` with a shorter last one.  The reference's
     ``interleave(cycle_length=AUTOTUNE)`` leaves the order open, and the loss depends on which images share a batch (the labelled
     boxes are gathered over the whole batch, model.py:643);
-  * ``mode=TRAIN`` (augmentation, shuffling) and ``zoom_in=True`` (the experimental branch of utils.py:243-245,279-283) are not
-    built: ``build()`` raises NotImplementedError.  TFRecord files need TensorFlow's proto parser (as in map.py).
+  * ``Dataset(mode=TRAIN)`` still raises NotImplementedError: the training path is a class of its own, ``AugmentedDataset``, with
+    its seed and the augmentation's parameters in the constructor.  ``zoom_in=True`` (the experimental branch of
+    utils.py:243-245,279-283) is not built.  TFRecord files need TensorFlow's proto parser (as in map.py).
 """
 import glob
 import os
@@ -64,9 +66,8 @@ class Dataset(object):
     def _get_num_from_name(self, name):
         return int(name.split('/')[-1].split('.')[0].split('_')[-1])
 
-    def build(self, split=None):
-        if self.glob_path is None:
-            return None, 0
+    def _label_files(self):
+        """-> (the files ``glob_path`` matches, the number of records their names promise): data.py:172-183."""
         files = sorted(glob.glob(self.glob_path))
         if len(files) == 0:
             raise ValueError('No file found')
@@ -76,16 +77,26 @@ class Dataset(object):
             raise ValueError('Please format file name like <name>_<number>.<extension>')
         if any(f.endswith(('.tfrecord', '.tfrecords')) for f in files):
             raise NotImplementedError('TFRecord label files need TensorFlow; use the text format')
+        return files, num
+
+    @staticmethod
+    def _text_files(files):
+        txts = [f for f in files if f.endswith('.txt')]
+        if not txts:
+            raise ValueError('No .txt label file among %d matching files' % len(files))
+        return txts
+
+    def build(self, split=None):
+        if self.glob_path is None:
+            return None, 0
+        files, num = self._label_files()
         if self.mode == DATASET_MODE.TRAIN:
-            raise NotImplementedError('Dataset(mode=TRAIN): augmentation and training are not built; use DATASET_MODE.VALIDATE or TEST')
+            raise NotImplementedError('Dataset(mode=TRAIN): the TRAIN data path is yolo3.data.AugmentedDataset; Dataset takes DATASET_MODE.VALIDATE or TEST')
         if self.mode not in (DATASET_MODE.VALIDATE, DATASET_MODE.TEST):
             raise ValueError('Dataset: mode must be a DATASET_MODE, not %r' % (self.mode,))
         if self.zoom_in:
             raise NotImplementedError('Dataset(zoom_in=True): the zoom-in branch of get_random_data is not built')
-        txts = [f for f in files if f.endswith('.txt')]
-        if not txts:
-            raise ValueError('No .txt label file among %d matching files' % len(files))
-        return _Batches(self, txts), num
+        return _Batches(self, self._text_files(files)), num
 
     # ------------------------------------------------------------------------- host side
     def records(self, files):
@@ -108,6 +119,18 @@ class Dataset(object):
         if batch:
             yield batch
 
+    def decode_batch(self, records):
+        """What stays on the host per batch: -> (decoded uint8 images, float32 [b,max_in,5] rows padded with zeros, int32 [b] counts)."""
+        from .. import runtime as rt
+        images = [decode_image(path if self.root is None else os.path.join(self.root, path)) for path, _ in records]
+        counts = np.asarray([bb.shape[0] for _, bb in records], np.int32)
+        if counts.max() > rt.INGEST_MAX_BOXES:
+            raise ValueError('Dataset: %s has %d boxes, at most %d are supported' % (records[int(counts.argmax())][0], counts.max(), rt.INGEST_MAX_BOXES))
+        boxes = np.zeros((len(records), max(1, int(counts.max())), 5), np.float32)
+        for i, (_, bb) in enumerate(records):
+            boxes[i, :bb.shape[0]] = bb
+        return images, boxes, counts
+
     # ------------------------------------------------------------------------- device side
     def load_batch(self, records):
         """One batch of records -> (images [b,H,W,3] float32, y_true tuple of num_scales tensors [b,gh,gw,3,5+C]) on the device."""
@@ -116,16 +139,77 @@ class Dataset(object):
         dev = torch.device(self.device if self.device is not None else 'cuda:0')
         if self._stager is None or self._stager.device != dev:
             self._stager = rt.RaggedStager(dev)
-        images = [decode_image(path if self.root is None else os.path.join(self.root, path)) for path, _ in records]
-        counts = np.asarray([bb.shape[0] for _, bb in records], np.int32)
-        if counts.max() > rt.INGEST_MAX_BOXES:
-            raise ValueError('Dataset: %s has %d boxes, at most %d are supported' % (records[int(counts.argmax())][0], counts.max(), rt.INGEST_MAX_BOXES))
-        boxes = np.zeros((len(records), max(1, int(counts.max())), 5), np.float32)
-        for i, (_, bb) in enumerate(records):
-            boxes[i, :bb.shape[0]] = bb
+        images, boxes, counts = self.decode_batch(records)
         packed, table = self._stager.upload(images, self.input_shape, rt.INGEST_VALIDATE)
         x, boxes_out, kept = rt.ingest_batch(packed, table, self.input_shape, boxes=torch.from_numpy(boxes).to(dev),
                                              box_count=torch.from_numpy(counts).to(dev), max_boxes=MAX_BOXES)
         self.last_boxes = (boxes_out, kept)
+        y_true = rt.encode_labels(boxes_out, self.input_shape, self.anchors, self.num_classes, self.num_scales)
+        return x, tuple(y_true)
+
+
+class _AugmentedBatches:
+    """The iterable ``AugmentedDataset.build`` returns: every pass shuffles the records and draws new augmentations."""
+
+    def __init__(self, dataset, files, rng):
+        self.dataset, self.files, self.rng = dataset, files, rng
+
+    def __iter__(self):
+        for records, draws in self.dataset.epoch_plan(self.files, self.rng):
+            yield self.dataset.load_batch(records, draws)
+
+
+class AugmentedDataset(Dataset):
+    """The training data path: ``Dataset(mode=TRAIN)`` of the reference (data.py:172-200 with ``shuffle(train_num)``, parse_text
+    calling ``get_random_data(train=True)``).  Per pass the records are permuted and ten uniforms per image are drawn, both from one
+    ``np.random.Generator`` seeded with ``seed`` in ``build()``: the same seed yields the same batches, byte for byte, and every
+    further pass of one iterable a new order and new draws.  Per batch the host decodes (PIL) and stages once; the device does the
+    rest: ``runtime.augment_batch`` (utils.py:170-227, 258-293), then ``runtime.encode_labels``.
+
+    The augmentation's keyword arguments are ``yolo3.utils.get_random_data_device``'s: jitter, min_scale, max_scale, min_gamma,
+    max_gamma, flip, hue, sat, cont are honoured; val, noise, blur, zoom_in raise NotImplementedError when switched on; the
+    jpeg-quality bounds are accepted and ignored - ``random_jpeg_quality``, on by default in the reference, is not built."""
+
+    def __init__(self, glob_path, batch_size, anchors=None, num_classes=None, input_shape=None, num_scales=None, seed=0, device=None,
+                 root=None, min_scale=0.25, max_scale=2, jitter=0.3, min_gamma=0.8, max_gamma=2, blur=False, flip=True, hue=.5, sat=.5,
+                 val=0., cont=.1, noise=0, min_jpeg_quality=80, max_jpeg_quality=100, zoom_in=False):
+        from .utils import _augment_params
+        super().__init__(glob_path, batch_size, anchors, num_classes, input_shape, num_scales, mode=DATASET_MODE.TRAIN, zoom_in=zoom_in,
+                         device=device, root=root)
+        self.seed = seed
+        self.flip = flip
+        self.params = _augment_params(min_scale, max_scale, jitter, min_gamma, max_gamma, blur, hue, sat, val, cont, noise, zoom_in)
+        self.last_draws = None      # float32 [b,10] of the last batch
+
+    def build(self, split=None):
+        if self.glob_path is None:
+            return None, 0
+        files, num = self._label_files()
+        return _AugmentedBatches(self, self._text_files(files), np.random.default_rng(self.seed)), num
+
+    def epoch_plan(self, files, rng):
+        """One pass, host only: [(records, draws float32 [b,10])] - the records permuted (the reference's shuffle over the whole
+        set), cut into batches of ``batch_size`` with a shorter last one, each batch with its images' ten draws."""
+        records = list(self.records(files))
+        order = rng.permutation(len(records))
+        size = max(int(self.batch_size), 1)
+        plan = []
+        for at in range(0, len(order), size):
+            batch = [records[i] for i in order[at:at + size]]
+            plan.append((batch, rng.random((len(batch), 10), dtype=np.float32)))
+        return plan
+
+    def load_batch(self, records, draws):
+        """One batch of records and its draws -> (images [b,H,W,3] float32, y_true tuple) on the device."""
+        import torch
+        from .. import runtime as rt
+        from .utils import get_random_data_device
+        dev = torch.device(self.device if self.device is not None else 'cuda:0')
+        if self._stager is None or self._stager.device != dev:
+            self._stager = rt.RaggedStager(dev)
+        images, boxes, counts = self.decode_batch(records)
+        x, boxes_out, kept = get_random_data_device(images, boxes, counts, self.input_shape, draws=draws, flip=self.flip, max_boxes=MAX_BOXES,
+                                                    device=dev, stager=self._stager, **self.params)
+        self.last_boxes, self.last_draws = (boxes_out, kept), draws
         y_true = rt.encode_labels(boxes_out, self.input_shape, self.anchors, self.num_classes, self.num_scales)
         return x, tuple(y_true)

@@ -1,6 +1,7 @@
 """The validation epoch of reference code/yolo3/train.py, forward only: ``_val_step`` (:48-52, the model's logits ->
 ``_compute_total_loss`` :11-16, the sum of the per-scale YoloLoss values) inside ``_distributed_epoch(dataset, False)`` (:55-75,
-the mean over the batches).  Training (``_train_step``, ``fit``) is not built."""
+the mean over the batches).  Training (``_train_step``, ``fit``) is not built; both tensors ``_train_step`` consumes are: ``yolo3.data.AugmentedDataset``
+yields the augmented ``images`` and ``y_true`` on the device, and ``runtime.yolo_loss_grad`` (``yr_yolo_loss_grad``) is the loss's gradient at the logits."""
 import torch
 
 from .model import yolo_loss

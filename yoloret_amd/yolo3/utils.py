@@ -140,3 +140,50 @@ def preprocess_true_boxes_device(true_boxes, input_shape, anchors, num_classes, 
         raise ValueError('preprocess_true_boxes_device: true_boxes is on %s, device=%s' % (true_boxes.device, device))
     y_true = rt.encode_labels(true_boxes, input_shape, anchors, num_classes, num_scales)
     return y_true[0] if num_scales == 1 else y_true
+
+
+def _augment_params(min_scale, max_scale, jitter, min_gamma, max_gamma, blur, hue, sat, val, cont, noise, zoom_in):
+    """The reference's keyword arguments -> the parameters of ``runtime.augment_geometry``; raises for the steps that are not built."""
+    if val > 0:
+        raise NotImplementedError('get_random_data_device(val=%r): random_brightness is not built' % (val,))
+    if noise > 0:
+        raise NotImplementedError('get_random_data_device(noise=%r): the additive noise is not built' % (noise,))
+    if blur:
+        raise NotImplementedError('get_random_data_device(blur=True): random_blur is not built')
+    if zoom_in:
+        raise NotImplementedError('get_random_data_device(zoom_in=True): the zoom-in branch is not built')
+    return dict(jitter=jitter, min_scale=min_scale, max_scale=max_scale, hue=hue, sat=sat, min_gamma=min_gamma, max_gamma=max_gamma, cont=cont)
+
+
+def get_random_data_device(images, boxes, counts, input_shape, draws=None, seed=None, min_scale=0.25, max_scale=2, jitter=0.3,
+                           min_gamma=0.8, max_gamma=2, blur=False, flip=True, hue=.5, sat=.5, val=0., cont=.1, noise=0, max_boxes=20,
+                           min_jpeg_quality=80, max_jpeg_quality=100, zoom_in=False, device=None, stager=None):
+    """The batch-level mirror of ``get_random_data(train=True)`` (utils.py:120-237, then :258-293) on the device: the HIP kernels
+    behind ``yr_augment_batch``.
+
+    images: a list of B decoded uint8 arrays [h,w,3] of any sizes; boxes: float32 [B,max_in,5] rows (xmin, ymin, xmax, ymax, label)
+    in source pixels (NumPy or a CUDA tensor); counts: int32 [B], the rows of each image that are boxes.  ``draws``: float32 [B,10]
+    uniforms in [0, 1), per image in the reference's order j1, j2, scale, dx, dy, flip, hue, sat, gamma, contrast; None draws them
+    from ``np.random.default_rng(seed)``.  Returns (images float32 [B,H,W,3], boxes_out [B,max_boxes,5], kept int32 [B]) on the device.
+
+    ``jitter``, ``min_scale``, ``max_scale``, ``min_gamma``, ``max_gamma``, ``flip``, ``hue``, ``sat`` and ``cont`` are honoured, each
+    step switched off by the reference's own condition.  ``val``, ``noise``, ``blur`` and ``zoom_in`` raise NotImplementedError when
+    switched on.  ``min_jpeg_quality`` / ``max_jpeg_quality`` are accepted and IGNORED: ``random_jpeg_quality`` (:228-230), which the
+    reference applies by default, is a libjpeg encode and decode of the augmented float image and is not built - this one default-on
+    step is missing from the result.  The draws are NumPy's, not TensorFlow's generator: the distribution is the reference's, the
+    stream is not."""
+    import torch
+    from .. import runtime as rt
+    params = _augment_params(min_scale, max_scale, jitter, min_gamma, max_gamma, blur, hue, sat, val, cont, noise, zoom_in)
+    b = len(images)
+    if draws is None:
+        draws = np.random.default_rng(seed).random((b, 10), dtype=np.float32)
+    dev = torch.device(device if device is not None else (boxes.device if isinstance(boxes, torch.Tensor) else 'cuda:0'))
+    table = rt.augment_geometry([np.shape(im)[:2] for im in images], input_shape, draws, flip=flip, **params)
+    stager = rt.RaggedStager(dev) if stager is None else stager
+    packed, table = stager.upload_table(images, table)
+    if not isinstance(boxes, torch.Tensor):
+        boxes = torch.from_numpy(np.array(boxes, dtype=np.float32)).to(dev)
+    if not isinstance(counts, torch.Tensor):
+        counts = torch.from_numpy(np.array(counts, dtype=np.int32)).to(dev)
+    return rt.augment_batch(packed, table, input_shape, boxes=boxes, box_count=counts, max_boxes=max_boxes)
