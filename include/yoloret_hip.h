@@ -662,8 +662,8 @@ int yr_ingest_batch(int mode, const unsigned char* src_u8 /*device, packed*/, co
  * existing entry changed; yr_abi_sizeof(4) reports sizeof(yr_augment_geom)).  Per image, in the reference's order: random
  * aspect and scale, resize (bilinear, half-pixel centres, no antialias), crop and / or pad to H x W, flip, random_hue,
  * random_saturation, adjust_gamma, random_contrast, clip_by_value(0, 1); the boxes follow the geometry and the flip.
- * NOT built: random_jpeg_quality (:228-230, ON by default in the reference: a libjpeg encode and decode of the augmented float
- * image), random_brightness (val), noise, blur, zoom_in (all off by default).
+ * random_jpeg_quality (:228-230, ON by default in the reference) is a stage of its own behind these launches: yr_jpeg_roundtrip_batch
+ * below.  NOT built: random_brightness (val), noise, blur, zoom_in (all off by default).
  * TensorFlow is not available to this project: adjust_hue and adjust_saturation follow TF 2.x's fused CPU kernels as restated
  * from memory in tests/augment_ref.py, which is the definition the kernels are tested against. */
 #define YR_AUG_HUE      1       /* stage mask: random_hue        (the reference's `hue > 0`) */
@@ -716,6 +716,25 @@ int yr_augment_batch(const unsigned char* src_u8 /*device, packed*/, const yr_au
                      const float* boxes_in /*[B,max_in,5] or null*/, const int32_t* box_count /*[B]*/, int max_in,
                      float* boxes_out /*[B,max_boxes,5]*/, int32_t* kept /*[B], may be null*/, int max_boxes,
                      void* workspace /*device*/, size_t workspace_bytes, void* stream);
+
+/* ---- tf.image.random_jpeg_quality (code/yolo3/utils.py:228-230: convert_image_dtype to uint8, adjust_jpeg_quality, back to float32),
+ * the last image step of get_random_data(train=True), for a batch of float32 canvases IN PLACE, one quality per image; added under
+ * ABI 9 (additive: no struct or existing entry changed).  Entropy coding is lossless, so the encode and decode are integer arithmetic
+ * without a bitstream: float -> uint8 (trunc(min(max(x * 255.5f, 0), 255))), RGB -> YCbCr, 2x2 chroma mean, forward DCT (jfdctint.c),
+ * quantise with the Annex K tables scaled to the quality | dequantise, inverse DCT (jidctint.c), triangle-filter chroma upsampling,
+ * YCbCr -> RGB, uint8 -> float (u * (1 / 255)f): 4:2:0, the "islow" DCT and fancy upsampling, libjpeg's and TensorFlow's defaults.
+ * tests/jpeg_ref.py restates every step and is pinned byte for byte against Pillow on libjpeg-turbo; the kernels equal it bit for bit.
+ * H and W must be multiples of 16 (whole MCUs; the network input is a multiple of 32): libjpeg's edge replication and dummy blocks
+ * are not built.  The quality is drawn by the caller (TensorFlow: an int32 uniform over [min_jpeg_quality, max_jpeg_quality)). */
+/* Bytes of the workspace of the launches below: the decoded Y plane and the two quarter-size chroma planes, uint8. */
+size_t yr_jpeg_workspace_bytes(int batch, int H, int W);
+/* Two launches: launch 1 reads the images and writes the decoded planes of every MCU to the workspace, launch 2 upsamples the
+ * chroma, converts and overwrites every element of images.  quality [B] is read on the device and clamped there to 1..100 (libjpeg
+ * reads 0 as 1).  No atomics, no host synchronisation; the same call gives the same bytes whatever the workspace held.  YR_ERR_ARG,
+ * nothing written: H or W not a multiple of 16, a null pointer, B * H * W >= 2^31, batch > 65535, a workspace smaller than
+ * yr_jpeg_workspace_bytes, images or workspace not 16-byte aligned. */
+int yr_jpeg_roundtrip_batch(float* images /*device [B,H,W,3], in place*/, const int32_t* quality /*device [B]*/, int batch, int H, int W,
+                            void* workspace /*device*/, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

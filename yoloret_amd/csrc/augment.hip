@@ -7,7 +7,7 @@
 //             :212-217  flip of the whole padded canvas;
 //             :218-227  random_hue, random_saturation, adjust_gamma, random_contrast with the table's scalars;  :277 the clip.
 //   boxes     :208-217, then :258-293 - datapath_common.h, the workgroup ingest.hip runs, with the flip.
-// Not built: random_jpeg_quality (:228-230, a libjpeg round trip of the float image), val, noise, blur, zoom_in.
+// random_jpeg_quality (:228-230) is a stage of its own behind these launches: jpeg.hip.  Not built: val, noise, blur, zoom_in.
 //
 // TensorFlow's adjust_hue / adjust_saturation kernels are restated here as tests/augment_ref.py restates them (that NumPy text is
 // the definition under test): every operation one float32 operation in the same order, the build keeps -ffp-contract=off.

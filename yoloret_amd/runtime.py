@@ -131,7 +131,7 @@ AUGMENT_GEOM_DTYPE = np.dtype([('src_off', '<i8'), ('ih', '<i4'), ('iw', '<i4'),
                                ('hue6', '<f4'), ('sat', '<f4'), ('gamma', '<f4'), ('cont', '<f4')])
 
 ABI_VERSION = 9   # == YR_ABI_VERSION of include/yoloret_hip.h
-EXPORTS = ['yr_augment_geometry', 'yr_augment_workspace_bytes', 'yr_augment_batch', 'yr_ingest_geometry', 'yr_ingest_batch', 'yr_last_error', 'yr_abi_version', 'yr_abi_sizeof', 'yr_create', 'yr_create_from_blob', 'yr_plan_io_dims', 'yr_destroy', 'yr_load_weights', 'yr_workspace_bytes',
+EXPORTS = ['yr_jpeg_workspace_bytes', 'yr_jpeg_roundtrip_batch', 'yr_augment_geometry', 'yr_augment_workspace_bytes', 'yr_augment_batch', 'yr_ingest_geometry', 'yr_ingest_batch', 'yr_last_error', 'yr_abi_version', 'yr_abi_sizeof', 'yr_create', 'yr_create_from_blob', 'yr_plan_io_dims', 'yr_destroy', 'yr_load_weights', 'yr_workspace_bytes',
            'yr_forward', 'yr_forward_profile', 'yr_forward_ranges', 'yr_autotune', 'yr_get_tuning', 'yr_set_tuning', 'yr_plan_num_launches', 'yr_op_run', 'yr_head_regions', 'yr_head_walk_rows', 'yr_head_stream_rows', 'yr_pwt_chunks', 'yr_decode', 'yr_decode_zoom', 'yr_yolo_head', 'yr_correct_boxes',
            'yr_nms', 'yr_pack_detections', 'yr_letterbox', 'yr_letterbox_batch', 'yr_yolo_loss_workspace_bytes', 'yr_yolo_loss', 'yr_yolo_loss_grad', 'yr_voc_match', 'yr_encode_labels']
 
@@ -212,6 +212,10 @@ def lib():
         L.yr_augment_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        L.yr_jpeg_workspace_bytes.restype = ctypes.c_size_t
+        L.yr_jpeg_workspace_bytes.argtypes = [ctypes.c_int] * 3
+        L.yr_jpeg_roundtrip_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
+                                              ctypes.c_void_p]
         if L.yr_abi_version() != ABI_VERSION:
             raise YoloretHipError('libyoloret_hip.so ABI version mismatch')
         L.yr_abi_sizeof.argtypes = [ctypes.c_int]
@@ -788,7 +792,8 @@ def augment_batch(packed_u8, table, input_hw, boxes=None, box_count=None, max_bo
     the offsets of ``table`` (an uploaded AugmentTable for ``input_hw``) -> float32 [B,H,W,3].  With ``boxes`` (float32 CUDA
     [B,max_in,5] rows (xmin, ymin, xmax, ymax, label) in source pixels, max_in <= 256) and ``box_count`` (int32 [B]):
     -> (images, boxes_out [B,max_boxes,5], kept [B] int32) as utils.py:208-217,258-293.  random_jpeg_quality, which the reference
-    applies by default, is not built.  ``workspace``: a uint8 CUDA tensor of augment_workspace_bytes, made here when None."""
+    applies by default, is the stage behind this one: ``jpeg_roundtrip_batch``.  ``workspace``: a uint8 CUDA tensor of
+    augment_workspace_bytes, made here when None."""
     if not (isinstance(packed_u8, torch.Tensor) and packed_u8.is_cuda and packed_u8.dtype == torch.uint8 and packed_u8.is_contiguous()):
         raise ValueError('augment_batch: the packed source must be a contiguous uint8 CUDA tensor')
     if not isinstance(table, AugmentTable) or table.device is None:
@@ -833,6 +838,40 @@ def augment_batch(packed_u8, table, input_hw, boxes=None, box_count=None, max_bo
         check(lib().yr_augment_batch(_ptr(packed_u8), _ptr(table.device), b, table.stages, _ptr(out), h, w, _ptr(boxes), _ptr(box_count), max_in,
                                      _ptr(boxes_out), _ptr(kept), int(max_boxes), _ptr(workspace), workspace.numel(), stream_ptr(dev)))
     return out if boxes is None else (out, boxes_out, kept)
+
+
+def jpeg_workspace_bytes(batch, input_hw):
+    return int(lib().yr_jpeg_workspace_bytes(int(batch), int(input_hw[0]), int(input_hw[1])))
+
+
+def jpeg_roundtrip_batch(images, quality, workspace=None):
+    """tf.image.adjust_jpeg_quality for a batch IN PLACE, two launches (yr_jpeg_roundtrip_batch): images float32 CUDA [B,H,W,3] with
+    H and W multiples of 16, quality int32 [B] (a CUDA tensor, or an array that is copied to the device; values outside 1..100 are
+    clamped on the device) -> ``images``, every element the float32 image's JPEG encode at that quality (4:2:0) and decode, bit
+    for bit libjpeg's arithmetic.  ``workspace``: a uint8 CUDA tensor of jpeg_workspace_bytes, made here when None."""
+    _require_cuda_f32(images, 'jpeg_roundtrip_batch: images')
+    if images.dim() != 4 or images.shape[3] != 3 or images.shape[0] < 1:
+        raise ValueError('jpeg_roundtrip_batch: images must be [B,H,W,3], not %s' % (tuple(images.shape),))
+    dev = images.device
+    b, h, w = (int(n) for n in images.shape[:3])
+    if h % 16 or w % 16 or h == 0 or w == 0:
+        raise ValueError('jpeg_roundtrip_batch: H and W must be multiples of 16 (whole MCUs), not %dx%d' % (h, w))
+    if not isinstance(quality, torch.Tensor):
+        quality = np.asarray(quality)
+        if quality.dtype.kind not in 'iu':
+            raise ValueError('jpeg_roundtrip_batch: quality must hold integers, not %s' % quality.dtype)
+        quality = torch.from_numpy(np.ascontiguousarray(quality.astype(np.int32))).to(dev)
+    if not (_is_cuda_i32(quality) and quality.device == dev and tuple(quality.shape) == (b,)):
+        raise ValueError('jpeg_roundtrip_batch: quality must be a contiguous int32 [B=%d] tensor on %s' % (b, dev))
+    need = jpeg_workspace_bytes(b, (h, w))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not (isinstance(workspace, torch.Tensor) and workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous()
+              and workspace.numel() >= need):
+        raise ValueError('jpeg_roundtrip_batch: workspace must be a contiguous uint8 tensor of at least %d bytes on %s' % (need, dev))
+    with torch.cuda.device(dev):
+        check(lib().yr_jpeg_roundtrip_batch(_ptr(images), _ptr(quality), b, h, w, _ptr(workspace), workspace.numel(), stream_ptr(dev)))
+    return images
 
 
 def image_hw_tensor(image_shape, batch, device):

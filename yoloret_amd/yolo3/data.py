@@ -9,6 +9,9 @@
                    -> runtime.ingest_batch(INGEST_VALIDATE): get_random_data(train=False) for images AND boxes (utils.py:239-295)
                    -> runtime.encode_labels: preprocess_true_boxes (utils.py:298-376)
 
+``AugmentedDataset`` runs runtime.augment_batch in place of ingest_batch and, with ``apply_jpeg=True``, runtime.jpeg_roundtrip_batch
+(random_jpeg_quality, utils.py:228-230) behind it.
+
 Differences that are deliberate:
   * iteration is deterministic - files sorted, lines in order, batches of ``batch_size`` with a shorter last one.  The reference's
     ``interleave(cycle_length=AUTOTUNE)`` leaves the order open, and the loss depends on which images share a batch (the labelled
@@ -151,12 +154,13 @@ class Dataset(object):
 class _AugmentedBatches:
     """The iterable ``AugmentedDataset.build`` returns: every pass shuffles the records and draws new augmentations."""
 
-    def __init__(self, dataset, files, rng):
-        self.dataset, self.files, self.rng = dataset, files, rng
+    def __init__(self, dataset, files, rng, jpeg_rng=None):
+        self.dataset, self.files, self.rng, self.jpeg_rng = dataset, files, rng, jpeg_rng
 
     def __iter__(self):
         for records, draws in self.dataset.epoch_plan(self.files, self.rng):
-            yield self.dataset.load_batch(records, draws)
+            jpeg_draws = self.jpeg_rng.random(len(records), dtype=np.float32) if self.dataset.jpeg else None
+            yield self.dataset.load_batch(records, draws, jpeg_draws)
 
 
 class AugmentedDataset(Dataset):
@@ -164,28 +168,40 @@ class AugmentedDataset(Dataset):
     calling ``get_random_data(train=True)``).  Per pass the records are permuted and ten uniforms per image are drawn, both from one
     ``np.random.Generator`` seeded with ``seed`` in ``build()``: the same seed yields the same batches, byte for byte, and every
     further pass of one iterable a new order and new draws.  Per batch the host decodes (PIL) and stages once; the device does the
-    rest: ``runtime.augment_batch`` (utils.py:170-227, 258-293), then ``runtime.encode_labels``.
+    rest: ``runtime.augment_batch`` (utils.py:170-227, 258-293), ``runtime.jpeg_roundtrip_batch`` (:228-230) when switched on, then
+    ``runtime.encode_labels``.
 
     The augmentation's keyword arguments are ``yolo3.utils.get_random_data_device``'s: jitter, min_scale, max_scale, min_gamma,
-    max_gamma, flip, hue, sat, cont are honoured; val, noise, blur, zoom_in raise NotImplementedError when switched on; the
-    jpeg-quality bounds are accepted and ignored - ``random_jpeg_quality``, on by default in the reference, is not built."""
+    max_gamma, flip, hue, sat, cont are honoured; val, noise, blur, zoom_in raise NotImplementedError when switched on.
+
+    ``apply_jpeg=True`` is the reference's default behaviour: ``random_jpeg_quality`` with the bounds ``min_jpeg_quality`` /
+    ``max_jpeg_quality`` (80 / 100) as the last image step, run iff min < max.  The default here is False - the bytes of every batch
+    stay what they were before the step was built, and the bounds are accepted and unused.  The qualities come from a second
+    generator, ``np.random.default_rng((seed, 1))`` made in ``build()``, one float32 uniform per image in batch order: records, the
+    ten draws, boxes and y_true of a seed do not depend on the switch.  ``last_quality`` holds the last batch's qualities."""
 
     def __init__(self, glob_path, batch_size, anchors=None, num_classes=None, input_shape=None, num_scales=None, seed=0, device=None,
                  root=None, min_scale=0.25, max_scale=2, jitter=0.3, min_gamma=0.8, max_gamma=2, blur=False, flip=True, hue=.5, sat=.5,
-                 val=0., cont=.1, noise=0, min_jpeg_quality=80, max_jpeg_quality=100, zoom_in=False):
-        from .utils import _augment_params
+                 val=0., cont=.1, noise=0, min_jpeg_quality=80, max_jpeg_quality=100, zoom_in=False, apply_jpeg=False):
+        from .utils import _augment_params, _check_jpeg_bounds
         super().__init__(glob_path, batch_size, anchors, num_classes, input_shape, num_scales, mode=DATASET_MODE.TRAIN, zoom_in=zoom_in,
                          device=device, root=root)
         self.seed = seed
         self.flip = flip
         self.params = _augment_params(min_scale, max_scale, jitter, min_gamma, max_gamma, blur, hue, sat, val, cont, noise, zoom_in)
         self.last_draws = None      # float32 [b,10] of the last batch
+        self.jpeg = bool(apply_jpeg) and min_jpeg_quality < max_jpeg_quality      # utils.py:228
+        self.jpeg_bounds = (min_jpeg_quality, max_jpeg_quality)
+        if self.jpeg:
+            _check_jpeg_bounds(min_jpeg_quality, max_jpeg_quality)
+        self.last_quality = None    # int32 [b] of the last batch (apply_jpeg=True)
 
     def build(self, split=None):
         if self.glob_path is None:
             return None, 0
         files, num = self._label_files()
-        return _AugmentedBatches(self, self._text_files(files), np.random.default_rng(self.seed)), num
+        return _AugmentedBatches(self, self._text_files(files), np.random.default_rng(self.seed),
+                                 np.random.default_rng((self.seed, 1) if self.seed is not None else None)), num
 
     def epoch_plan(self, files, rng):
         """One pass, host only: [(records, draws float32 [b,10])] - the records permuted (the reference's shuffle over the whole
@@ -199,11 +215,14 @@ class AugmentedDataset(Dataset):
             plan.append((batch, rng.random((len(batch), 10), dtype=np.float32)))
         return plan
 
-    def load_batch(self, records, draws):
-        """One batch of records and its draws -> (images [b,H,W,3] float32, y_true tuple) on the device."""
+    def load_batch(self, records, draws, jpeg_draws=None):
+        """One batch of records and its draws (``jpeg_draws``: float32 [b], needed with apply_jpeg=True) -> (images [b,H,W,3] float32,
+        y_true tuple) on the device."""
         import torch
         from .. import runtime as rt
-        from .utils import get_random_data_device
+        from .utils import get_random_data_device, random_jpeg_quality_device
+        if self.jpeg and jpeg_draws is None:
+            raise ValueError('AugmentedDataset.load_batch: apply_jpeg=True needs the batch\'s jpeg_draws')
         dev = torch.device(self.device if self.device is not None else 'cuda:0')
         if self._stager is None or self._stager.device != dev:
             self._stager = rt.RaggedStager(dev)
@@ -211,5 +230,7 @@ class AugmentedDataset(Dataset):
         x, boxes_out, kept = get_random_data_device(images, boxes, counts, self.input_shape, draws=draws, flip=self.flip, max_boxes=MAX_BOXES,
                                                     device=dev, stager=self._stager, **self.params)
         self.last_boxes, self.last_draws = (boxes_out, kept), draws
+        if self.jpeg:
+            _, self.last_quality = random_jpeg_quality_device(x, self.jpeg_bounds[0], self.jpeg_bounds[1], draws=jpeg_draws)
         y_true = rt.encode_labels(boxes_out, self.input_shape, self.anchors, self.num_classes, self.num_scales)
         return x, tuple(y_true)

@@ -155,11 +155,45 @@ def _augment_params(min_scale, max_scale, jitter, min_gamma, max_gamma, blur, hu
     return dict(jitter=jitter, min_scale=min_scale, max_scale=max_scale, hue=hue, sat=sat, min_gamma=min_gamma, max_gamma=max_gamma, cont=cont)
 
 
+def _check_jpeg_bounds(min_jpeg_quality, max_jpeg_quality):
+    """tf.image.random_jpeg_quality's own argument check."""
+    if min_jpeg_quality < 0 or max_jpeg_quality < 0 or min_jpeg_quality > 100 or max_jpeg_quality > 100:
+        raise ValueError('jpeg encoding range must be between 0 and 100.')
+    if min_jpeg_quality >= max_jpeg_quality:
+        raise ValueError('`min_jpeg_quality` must be less than `max_jpeg_quality`.')
+
+
+def draw_jpeg_quality(u, min_jpeg_quality, max_jpeg_quality):
+    """One image's quality from a uniform ``u`` in [0, 1) (float32): TensorFlow draws an int32 uniformly in [min, max); here, in
+    double, min + int(u * (max - min)), kept below max; libjpeg reads quality 0 as 1."""
+    lo, hi = int(min_jpeg_quality), int(max_jpeg_quality)
+    return max(min(lo + int(float(np.float32(u)) * (hi - lo)), hi - 1), 1)
+
+
+def random_jpeg_quality_device(images, min_jpeg_quality, max_jpeg_quality, draws=None, seed=None):
+    """``tf.image.random_jpeg_quality`` (utils.py:228-230) for a batch on the device, IN PLACE: images float32 CUDA [B,H,W,3] with H
+    and W multiples of 16, each encoded as a JPEG (4:2:0) at a quality drawn uniformly from [min_jpeg_quality, max_jpeg_quality) and
+    decoded again - the HIP kernels behind ``yr_jpeg_roundtrip_batch``, bit for bit libjpeg's integer arithmetic, no bitstream.
+    ``draws``: float32 [B] uniforms in [0, 1), one per image; None draws them from ``np.random.default_rng(seed)``.  ValueError
+    unless 0 <= min_jpeg_quality < max_jpeg_quality <= 100, as TensorFlow raises.  Returns (images, quality int32 [B] as drawn)."""
+    from .. import runtime as rt
+    _check_jpeg_bounds(min_jpeg_quality, max_jpeg_quality)
+    b = int(images.shape[0])
+    if draws is None:
+        draws = np.random.default_rng(seed).random(b, dtype=np.float32)
+    draws = np.asarray(draws, np.float32).reshape(-1)
+    if draws.shape[0] != b:
+        raise ValueError('random_jpeg_quality_device: %d draws for %d images' % (draws.shape[0], b))
+    quality = np.array([draw_jpeg_quality(u, min_jpeg_quality, max_jpeg_quality) for u in draws], np.int32)
+    return rt.jpeg_roundtrip_batch(images, quality), quality
+
+
 def get_random_data_device(images, boxes, counts, input_shape, draws=None, seed=None, min_scale=0.25, max_scale=2, jitter=0.3,
                            min_gamma=0.8, max_gamma=2, blur=False, flip=True, hue=.5, sat=.5, val=0., cont=.1, noise=0, max_boxes=20,
-                           min_jpeg_quality=80, max_jpeg_quality=100, zoom_in=False, device=None, stager=None):
+                           min_jpeg_quality=80, max_jpeg_quality=100, zoom_in=False, device=None, stager=None, apply_jpeg=False,
+                           jpeg_draws=None):
     """The batch-level mirror of ``get_random_data(train=True)`` (utils.py:120-237, then :258-293) on the device: the HIP kernels
-    behind ``yr_augment_batch``.
+    behind ``yr_augment_batch`` and, with ``apply_jpeg=True``, ``yr_jpeg_roundtrip_batch``.
 
     images: a list of B decoded uint8 arrays [h,w,3] of any sizes; boxes: float32 [B,max_in,5] rows (xmin, ymin, xmax, ymax, label)
     in source pixels (NumPy or a CUDA tensor); counts: int32 [B], the rows of each image that are boxes.  ``draws``: float32 [B,10]
@@ -168,16 +202,29 @@ def get_random_data_device(images, boxes, counts, input_shape, draws=None, seed=
 
     ``jitter``, ``min_scale``, ``max_scale``, ``min_gamma``, ``max_gamma``, ``flip``, ``hue``, ``sat`` and ``cont`` are honoured, each
     step switched off by the reference's own condition.  ``val``, ``noise``, ``blur`` and ``zoom_in`` raise NotImplementedError when
-    switched on.  ``min_jpeg_quality`` / ``max_jpeg_quality`` are accepted and IGNORED: ``random_jpeg_quality`` (:228-230), which the
-    reference applies by default, is a libjpeg encode and decode of the augmented float image and is not built - this one default-on
-    step is missing from the result.  The draws are NumPy's, not TensorFlow's generator: the distribution is the reference's, the
-    stream is not."""
+    switched on.
+
+    ``apply_jpeg``: ``random_jpeg_quality`` (:228-230), the last image step, which the reference applies by default with the bounds
+    80 / 100.  ``apply_jpeg=True`` IS THE REFERENCE'S DEFAULT BEHAVIOUR; the default here is False, which keeps the bytes this
+    function returned before the step was built, and then ``min_jpeg_quality`` / ``max_jpeg_quality`` are accepted and unused.  With
+    ``apply_jpeg=True`` the step runs iff ``min_jpeg_quality < max_jpeg_quality`` (the reference's condition; bounds outside 0..100
+    raise ValueError as TensorFlow does) and needs both sides of ``input_shape`` to be multiples of 16.  ``jpeg_draws``: float32 [B]
+    uniforms in [0, 1), one per image; None draws them from a second generator, ``np.random.default_rng((seed, 1))``, so the ten
+    draws above do not depend on this switch.  The draws are NumPy's, not TensorFlow's generator: the distribution is the
+    reference's, the stream is not."""
     import torch
     from .. import runtime as rt
     params = _augment_params(min_scale, max_scale, jitter, min_gamma, max_gamma, blur, hue, sat, val, cont, noise, zoom_in)
+    jpeg = bool(apply_jpeg) and min_jpeg_quality < max_jpeg_quality
+    if jpeg:
+        _check_jpeg_bounds(min_jpeg_quality, max_jpeg_quality)
+        if int(input_shape[0]) % 16 or int(input_shape[1]) % 16:
+            raise ValueError('get_random_data_device(apply_jpeg=True): input_shape must be multiples of 16, not %s' % (tuple(input_shape),))
     b = len(images)
     if draws is None:
         draws = np.random.default_rng(seed).random((b, 10), dtype=np.float32)
+    if jpeg and jpeg_draws is None:
+        jpeg_draws = np.random.default_rng((seed, 1) if seed is not None else None).random(b, dtype=np.float32)
     dev = torch.device(device if device is not None else (boxes.device if isinstance(boxes, torch.Tensor) else 'cuda:0'))
     table = rt.augment_geometry([np.shape(im)[:2] for im in images], input_shape, draws, flip=flip, **params)
     stager = rt.RaggedStager(dev) if stager is None else stager
@@ -186,4 +233,7 @@ def get_random_data_device(images, boxes, counts, input_shape, draws=None, seed=
         boxes = torch.from_numpy(np.array(boxes, dtype=np.float32)).to(dev)
     if not isinstance(counts, torch.Tensor):
         counts = torch.from_numpy(np.array(counts, dtype=np.int32)).to(dev)
-    return rt.augment_batch(packed, table, input_shape, boxes=boxes, box_count=counts, max_boxes=max_boxes)
+    x, boxes_out, kept = rt.augment_batch(packed, table, input_shape, boxes=boxes, box_count=counts, max_boxes=max_boxes)
+    if jpeg:
+        random_jpeg_quality_device(x, min_jpeg_quality, max_jpeg_quality, draws=jpeg_draws)
+    return x, boxes_out, kept
