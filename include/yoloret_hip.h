@@ -736,6 +736,37 @@ size_t yr_jpeg_workspace_bytes(int batch, int H, int W);
 int yr_jpeg_roundtrip_batch(float* images /*device [B,H,W,3], in place*/, const int32_t* quality /*device [B]*/, int batch, int H, int W,
                             void* workspace /*device*/, size_t workspace_bytes, void* stream);
 
+/* ---- training the output convolutions (the three *_y 1x1 convs, code/yolo3/model.py:111): what _train_step (code/yolo3/train.py:18-46)
+ * does for them between the features and optimizer.apply_gradients when the body is frozen (code/train.py:150-171, "Train with frozen
+ * layers first"); added under ABI 9 (additive: no struct or existing entry changed).  csrc/headtrain.hip has the kernels' forms.
+ * Rows are float32, row-major over pixels, P = B * H * W: x [P][x_ld] with cin channels taken, dy / y [P][ld] with cout taken.
+ * Weights are Wt[cout][kp], kp = round_up(cin, 4): the layout of YR_OP_POINTWISE, pad columns 0.  Every pointer needs 4-byte
+ * alignment only (a dense row of 75 floats).  Operands and accumulation are float32 on the float32 matrix pipe.  1 <= cin, cout
+ * <= 256, 1 <= pixels < 2^40, ld >= the channels taken; YR_ERR_ARG, nothing written, otherwise (also: a null pointer, byte offsets
+ * beyond 2^63, a workspace that is short or not 16-byte aligned). */
+/* the layer's forward (model.py:111, a bias-free 1x1 Conv2D): y[p][co] = sum_k x[p][k] * wt[co][k].  Every y[p][0..cout) is written
+ * and nothing else; pad columns of wt are not read.  One launch. */
+int yr_linear_forward(const float* x, int x_ld, const float* wt /*[cout][kp]*/, long long pixels, int cin, int cout,
+                      float* y, int y_ld, void* stream);
+/* d loss / d Wt, what tape.gradient (yolo3/train.py:39) gives for the layer's kernel: dwt[co][ci] = sum_p dy[p][co] * x[p][ci].
+ * Two launches, no float atomics: stage 1 gives every workgroup a contiguous range of yr_linear_wgrad_chunk(pixels, cin, cout)
+ * pixels - a function of its three arguments only, never of the device - and writes one partial [cout][kp] slab per range to the
+ * workspace; stage 2 adds the slabs in index order and writes EVERY element of dwt, pad columns as +0.  Nothing needs zeroing
+ * first, the workspace contents before the call do not matter, and the same call gives the same bytes.  Pad columns of the rows
+ * (elements at and beyond cin / cout) are never read.  The two size entries return 0 for sizes the call refuses. */
+int    yr_linear_wgrad_chunk(long long pixels, int cin, int cout);
+size_t yr_linear_wgrad_workspace_bytes(long long pixels, int cin, int cout);
+int    yr_linear_wgrad(const float* x, int x_ld, const float* dy, int dy_ld, long long pixels, int cin, int cout,
+                       void* workspace /*device*/, size_t workspace_bytes, float* dwt /*[cout][kp]*/, void* stream);
+/* Keras Adam's dense update (code/train.py:158 Adam(lr[0], epsilon=1e-8) behind optimizer.apply_gradients, yolo3/train.py:40), in place, one
+ * launch for n elements, float32 operations in this order with nothing contracted:
+ *   m = beta1 * m + (1 - beta1) * g;   v = beta2 * v + (1 - beta2) * (g * g);   w = w - alpha * m / (sqrt(v) + eps)
+ * 1 - beta1 and 1 - beta2 are formed once in float32; alpha = float32(lr * sqrt(1 - beta2^t) / (1 - beta1^t)) is the caller's, from
+ * float64.  TF 2.x OptimizerV2 Adam without amsgrad, restated (no TensorFlow where this is tested: tests/headtrain_ref.py is the
+ * definition).  g is only read.  1 <= n <= 2^39. */
+int yr_adam_step(float* w, float* m, float* v, const float* g, long long n,
+                 float alpha, float beta1, float beta2, float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

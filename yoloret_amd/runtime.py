@@ -133,7 +133,8 @@ AUGMENT_GEOM_DTYPE = np.dtype([('src_off', '<i8'), ('ih', '<i4'), ('iw', '<i4'),
 ABI_VERSION = 9   # == YR_ABI_VERSION of include/yoloret_hip.h
 EXPORTS = ['yr_jpeg_workspace_bytes', 'yr_jpeg_roundtrip_batch', 'yr_augment_geometry', 'yr_augment_workspace_bytes', 'yr_augment_batch', 'yr_ingest_geometry', 'yr_ingest_batch', 'yr_last_error', 'yr_abi_version', 'yr_abi_sizeof', 'yr_create', 'yr_create_from_blob', 'yr_plan_io_dims', 'yr_destroy', 'yr_load_weights', 'yr_workspace_bytes',
            'yr_forward', 'yr_forward_profile', 'yr_forward_ranges', 'yr_autotune', 'yr_get_tuning', 'yr_set_tuning', 'yr_plan_num_launches', 'yr_op_run', 'yr_head_regions', 'yr_head_walk_rows', 'yr_head_stream_rows', 'yr_pwt_chunks', 'yr_decode', 'yr_decode_zoom', 'yr_yolo_head', 'yr_correct_boxes',
-           'yr_nms', 'yr_pack_detections', 'yr_letterbox', 'yr_letterbox_batch', 'yr_yolo_loss_workspace_bytes', 'yr_yolo_loss', 'yr_yolo_loss_grad', 'yr_voc_match', 'yr_encode_labels']
+           'yr_nms', 'yr_pack_detections', 'yr_letterbox', 'yr_letterbox_batch', 'yr_yolo_loss_workspace_bytes', 'yr_yolo_loss', 'yr_yolo_loss_grad', 'yr_voc_match', 'yr_encode_labels',
+           'yr_linear_forward', 'yr_linear_wgrad_chunk', 'yr_linear_wgrad_workspace_bytes', 'yr_linear_wgrad', 'yr_adam_step']
 
 _lib = None
 
@@ -216,6 +217,14 @@ def lib():
         L.yr_jpeg_workspace_bytes.argtypes = [ctypes.c_int] * 3
         L.yr_jpeg_roundtrip_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
                                               ctypes.c_void_p]
+        L.yr_linear_forward.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                        ctypes.c_int, ctypes.c_void_p]
+        L.yr_linear_wgrad_chunk.argtypes = [ctypes.c_longlong, ctypes.c_int, ctypes.c_int]
+        L.yr_linear_wgrad_workspace_bytes.restype = ctypes.c_size_t
+        L.yr_linear_wgrad_workspace_bytes.argtypes = [ctypes.c_longlong, ctypes.c_int, ctypes.c_int]
+        L.yr_linear_wgrad.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+        L.yr_adam_step.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_longlong] + [ctypes.c_float] * 4 + [ctypes.c_void_p]
         if L.yr_abi_version() != ABI_VERSION:
             raise YoloretHipError('libyoloret_hip.so ABI version mismatch')
         L.yr_abi_sizeof.argtypes = [ctypes.c_int]
@@ -461,6 +470,101 @@ def yolo_loss_grad(feats, y_true, anchors, input_hw, ignore_thresh=.5, upstream=
                                       int(input_hw[0]), int(input_hw[1]), float(ignore_thresh), _ptr(ws), ws.numel(), _ptr(upstream),
                                       _ptr(terms), _ptr(out), stream_ptr(dev)))
     return terms, out
+
+
+# ----------------------------------------------------------------------------- training the output convolutions (csrc/headtrain.hip)
+def _rows(t, name):
+    """A float32 CUDA tensor whose last axis holds the channels and whose leading axes are dense -> (pixels, channels)."""
+    _require_cuda_f32(t, name)
+    if t.dim() < 2 or t.numel() == 0:
+        raise ValueError('%s has shape %s, expected [..., channels]' % (name, tuple(t.shape)))
+    return t.numel() // t.shape[-1], t.shape[-1]
+
+
+def _linear_wt(wt, name, cin=None):
+    _require_cuda_f32(wt, name)
+    if wt.dim() != 2 or wt.shape[1] % 4 or not 1 <= wt.shape[0] <= 256 or (cin is not None and wt.shape[1] != (cin + 3) // 4 * 4):
+        raise ValueError('%s has shape %s, expected [cout, round_up(cin, 4)] with cout <= 256' % (name, tuple(wt.shape)))
+
+
+def linear_forward(x, wt, out=None):
+    """A bias-free 1x1 convolution on dense rows (yr_linear_forward): x [..., cin] float32, wt [cout, round_up(cin, 4)] (the layout of
+    YR_OP_POINTWISE, pad columns 0) -> y [..., cout] = x @ wt[:, :cin].T on the float32 matrix pipe.  out: a contiguous float32
+    tensor of that shape on x's device (every element is written); default: a fresh one.  One launch."""
+    pixels, cin = _rows(x, 'x')
+    if not 1 <= cin <= 256:
+        raise ValueError('linear_forward: 1..256 channels, not %d' % cin)
+    _linear_wt(wt, 'wt', cin)
+    if wt.device != x.device:
+        raise ValueError('linear_forward: wt on %s, x on %s' % (wt.device, x.device))
+    shape = tuple(x.shape[:-1]) + (wt.shape[0],)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == x.device and tuple(out.shape) == shape
+              and out.is_contiguous()):
+        raise ValueError('linear_forward: out must be a contiguous float32 tensor of shape %s on %s' % (shape, x.device))
+    with torch.cuda.device(x.device):
+        check(lib().yr_linear_forward(_ptr(x), cin, _ptr(wt), pixels, cin, wt.shape[0], _ptr(out), wt.shape[0], stream_ptr(x.device)))
+    return out
+
+
+def linear_wgrad_chunk(pixels, cin, cout):
+    """Pixels per workgroup of the gradient's first stage: a function of these three numbers only (0: sizes the call refuses)."""
+    return int(lib().yr_linear_wgrad_chunk(int(pixels), int(cin), int(cout)))
+
+
+def linear_wgrad_workspace_bytes(pixels, cin, cout):
+    return int(lib().yr_linear_wgrad_workspace_bytes(int(pixels), int(cin), int(cout)))
+
+
+def linear_wgrad(x, dy, out=None, workspace=None):
+    """The weight gradient of ``linear_forward`` (yr_linear_wgrad): x [..., cin], dy [..., cout] float32 with the same leading axes
+    -> dwt [cout, round_up(cin, 4)] = dy.T @ x, pad columns +0, float32 on the float32 matrix pipe; no atomics, the same call gives
+    the same bytes.  out: a contiguous float32 tensor of that shape on x's device (every element is written); workspace: a uint8
+    tensor of at least linear_wgrad_workspace_bytes(pixels, cin, cout) bytes there (its contents do not matter).  Defaults: fresh
+    ones.  Two launches."""
+    pixels, cin = _rows(x, 'x')
+    pdy, cout = _rows(dy, 'dy')
+    if pdy != pixels or dy.device != x.device:
+        raise ValueError('linear_wgrad: dy %s on %s for x %s on %s' % (tuple(dy.shape), dy.device, tuple(x.shape), x.device))
+    if not (1 <= cin <= 256 and 1 <= cout <= 256):
+        raise ValueError('linear_wgrad: 1..256 channels, not %d and %d' % (cin, cout))
+    dev = x.device
+    shape = (cout, (cin + 3) // 4 * 4)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == dev and tuple(out.shape) == shape
+              and out.is_contiguous()):
+        raise ValueError('linear_wgrad: out must be a contiguous float32 tensor of shape %s on %s' % (shape, dev))
+    need = linear_wgrad_workspace_bytes(pixels, cin, cout)
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev) if workspace is None else workspace
+    if not (isinstance(ws, torch.Tensor) and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.device == dev and ws.numel() >= need):
+        raise ValueError('linear_wgrad: workspace must be a contiguous uint8 tensor of at least %d bytes on %s' % (need, dev))
+    with torch.cuda.device(dev):
+        check(lib().yr_linear_wgrad(_ptr(x), cin, _ptr(dy), cout, pixels, cin, cout, _ptr(ws), ws.numel(), _ptr(out), stream_ptr(dev)))
+    return out
+
+
+def adam_alpha(learning_rate, step, beta1=.9, beta2=.999):
+    """Keras Adam's step size at the 1-based ``step``: float32(lr * sqrt(1 - beta2^t) / (1 - beta1^t)), formed in float64."""
+    return float(np.float32(float(learning_rate) * np.sqrt(1.0 - float(beta2) ** step) / (1.0 - float(beta1) ** step)))
+
+
+def adam_step(w, m, v, g, alpha, beta1=.9, beta2=.999, eps=1e-8):
+    """Keras Adam's dense update in place (yr_adam_step): m = beta1 m + (1 - beta1) g; v = beta2 v + (1 - beta2) g g;
+    w = w - alpha m / (sqrt(v) + eps), float32 in that order.  w, m, v, g: contiguous float32 tensors of one size on one device (g is
+    only read); alpha: ``adam_alpha(lr, t)``.  One launch."""
+    _require_cuda_f32(w, 'w')
+    for t, name in ((m, 'm'), (v, 'v'), (g, 'g')):
+        _require_cuda_f32(t, name)
+        if t.numel() != w.numel() or t.device != w.device:
+            raise ValueError('adam_step: %s has %d elements on %s, w %d on %s' % (name, t.numel(), t.device, w.numel(), w.device))
+    if w.numel() == 0:
+        raise ValueError('adam_step: no elements')
+    with torch.cuda.device(w.device):
+        check(lib().yr_adam_step(_ptr(w), _ptr(m), _ptr(v), _ptr(g), w.numel(), float(alpha), float(beta1), float(beta2), float(eps),
+                                 stream_ptr(w.device)))
+    return w
 
 
 VOC_MAX_ROWS, VOC_MAX_GT = 4096, 512     # YR_VOC_MAX_ROWS, YR_VOC_MAX_GT of include/yoloret_hip.h

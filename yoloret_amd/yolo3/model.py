@@ -167,6 +167,53 @@ def yolov3_body(inputs, model_name, num_anchors, **kwargs):
     return AdvLossModel(backbone.inputs, [y1, y2, y3])
 
 
+def output_convs(model):
+    """The graph nodes of the convolutions that produce ``model``'s logits, one per output: each output must be
+    ``Reshape5 <- 1x1 Conv2D`` with stride 1 and no bias (hence no BatchNorm and no activation between them) - the ``*_y`` convs
+    of make_last_layers_efficientnet_lite (model.py:111-114).  Found by walking the graph, not by name.  ValueError otherwise."""
+    convs = []
+    for i, out in enumerate(model.outputs):
+        node = out.node
+        if node is None or node.op != 'reshape5':
+            raise ValueError('output %d is not a Reshape5 of a convolution\'s logits' % i)
+        conv = node.inputs[0].node
+        if conv is None or conv.op != 'conv2d' or conv.attrs['k'] != 1 or conv.attrs['stride'] != 1 or conv.attrs['use_bias']:
+            raise ValueError('output %d is not produced by a bias-free 1x1 convolution (found %s)' % (i, 'the input' if conv is None else conv.op))
+        convs.append(conv)
+    return convs
+
+
+def yolov3_features(model):
+    """``Model`` on ``model``'s input whose outputs are the INPUTS of the convolutions that produce ``model``'s logits (``bu1_y``,
+    ``bu2_y``, ``bu3_y`` of ``yolov3_body``): dense float32 [B,G,G,cin] per scale.  It is the body a frozen-layers training stage
+    (reference code/train.py:150-171) runs in inference mode; its ``param_shapes`` are ``model``'s without the output
+    convolutions' kernels, so ``features.set_weights(model.get_weights())`` shares the body weights.  Float32 plans only."""
+    if model.dtype != 0:
+        raise NotImplementedError('yolov3_features: float32 plans only (the model was built under the %s policy)' % rt.DTYPE_NAME[model.dtype])
+    feats = [_own_producer(conv.inputs[0]) for conv in output_convs(model)]
+    return Model(model.inputs, feats, dtype='float32')
+
+
+def _own_producer(t):
+    """A tensor equal to ``t`` that nothing else consumes.  A plan writes a model output densely (a channel stride of 75), which no
+    op of the plan can read back (sources need a stride that is a multiple of 4) - and the features of ``bu3`` and ``bu2`` also feed
+    the bottom-up path.  So the 1x1 convolution that produces a feature (with its BatchNorm and activation, if any) is recorded a
+    second time under the SAME layer names, hence the same parameters: the copy feeds the output, the original the rest of the
+    graph (the throughput plan runs both as one two-output convolution; an original that nothing else consumes is dead and is
+    dropped).  A feature with another kind of producer is returned as it is."""
+    chain, x = [], t
+    while x.node is not None and x.node.op in ('batchnorm', 'act'):
+        chain.append(x.node)
+        x = x.node.inputs[0]
+    n = x.node
+    if n is None or n.op != 'conv2d' or n.attrs['k'] != 1 or n.attrs['stride'] != 1:
+        return t
+    x = L.Node('conv2d', list(n.inputs), n.output.shape, n.attrs, n.params, n.name).output
+    for n in reversed(chain):
+        x = L.Node(n.op, [x], n.output.shape, n.attrs, n.params, n.name).output
+    return x
+
+
 # ----------------------------------------------------------------------------- post-processing
 def _hw(shape):
     if isinstance(shape, torch.Tensor):

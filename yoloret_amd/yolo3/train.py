@@ -1,10 +1,26 @@
-"""The validation epoch of reference code/yolo3/train.py, forward only: ``_val_step`` (:48-52, the model's logits ->
-``_compute_total_loss`` :11-16, the sum of the per-scale YoloLoss values) inside ``_distributed_epoch(dataset, False)`` (:55-75,
-the mean over the batches).  Training (``_train_step``, ``fit``) is not built; both tensors ``_train_step`` consumes are: ``yolo3.data.AugmentedDataset``
-yields the augmented ``images`` and ``y_true`` on the device, and ``runtime.yolo_loss_grad`` (``yr_yolo_loss_grad``) is the loss's gradient at the logits."""
+"""Reference code/yolo3/train.py on the device.
+
+Validation, forward only: ``_val_step`` (:48-52, the model's logits -> ``_compute_total_loss`` :11-16, the sum of the per-scale
+YoloLoss values) inside ``_distributed_epoch(dataset, False)`` (:55-75, the mean over the batches) is ``validation_loss``.
+
+Training of the output convolutions: ``OutputLayerTrainer`` is ``_train_step`` (:18-46) and ``fit`` (:81-128) for the stage reference
+code/train.py:150-171 calls "Train with frozen layers first, to get a stable loss" - ``Adam(lr[0], epsilon=1e-8)`` under
+``cos_lr_freeze`` - with everything frozen but the three ``*_y`` 1x1 convolutions that produce the logits.  The reference's
+``ModelFactory.build`` (code/yolo3/utils.py:392) still carries the lines for that freeze ("freeze all but 2 output layers"), commented
+out, so its stage 1 as shipped trains every layer: the frozen-body stage is BUILD-DEFINED, like the oracle.  The body runs as a
+feature model in inference mode (what a frozen Keras layer does), the trained layer's forward, its weight gradient and the Adam
+update are the kernels of csrc/headtrain.hip, the loss and its gradient at the logits those of csrc/loss.hip.  ``yolo3.data.AugmentedDataset``
+yields the augmented ``images`` and ``y_true`` on the device.
+
+Not built: the gradient with respect to the layer's input and anything behind it (no parameter of the body has a gradient),
+BatchNorm in training mode, ``use_ema``, ``use_adv`` and the gradient reduction over several devices."""
+import math
+
+import numpy as np
 import torch
 
-from .model import yolo_loss
+from .. import runtime as rt
+from .model import output_convs, yolo_loss, yolo_loss_and_grad, yolo_loss_and_grad_from_boxes, yolov3_features
 
 
 def validation_loss(model, dataset, anchors, num_scales, ignore_thresh=.5):
@@ -27,3 +43,151 @@ def validation_loss(model, dataset, anchors, num_scales, ignore_thresh=.5):
     mean = total / torch.full((), float(len(rows)), dtype=total.dtype, device=total.device)      # (a true division, not a reciprocal multiply)
     host = torch.cat([mean.reshape(1)] + [t.reshape(-1) for t in rows]).cpu().numpy()      # the one copy (and synchronisation)
     return float(host[0]), host[1:].reshape(len(rows), num_scales, 5).copy()
+
+
+def cosine_decay(learning_rate, epoch, epochs):
+    """``tf.keras.experimental.CosineDecay(learning_rate, epochs)(epoch)`` (code/train.py:95-97, alpha = 0)."""
+    return learning_rate * 0.5 * (1.0 + math.cos(math.pi * min(epoch, epochs) / epochs))
+
+
+class OutputLayerTrainer:
+    """Trains the convolutions that produce ``model``'s logits with Keras Adam, the body frozen.
+
+    ``model``: ``yolov3_body``'s float32 ``Model`` with its weights set.  The feature model (``yolov3_features``) is built once and
+    given the same body weights.  The ``num_scales`` matrices Wt[cout][round_up(cin, 4)] live in ONE contiguous device tensor
+    (``weights`` are views into it), and so do the moments ``m``, ``v`` and the gradient ``grads``: one ``adam_step`` launch covers
+    all scales.  They start from the model's ``*_y/kernel`` (Keras layout [1,1,cin,cout]) and are created on the device of the
+    first batch.  ``commit()`` writes them back into ``model``."""
+
+    def __init__(self, model, anchors, num_classes, num_scales, learning_rate=1e-3, beta_1=.9, beta_2=.999, epsilon=1e-8, ignore_thresh=.5):
+        self.model = model
+        self.anchors = np.asarray(anchors, np.float32).reshape(-1, 2)
+        self.num_classes, self.num_scales = int(num_classes), int(num_scales)
+        self.learning_rate = self.lr = float(learning_rate)
+        self.beta_1, self.beta_2, self.epsilon, self.ignore_thresh = float(beta_1), float(beta_2), float(epsilon), ignore_thresh
+        self.features = yolov3_features(model)          # (raises for a 16-bit plan or outputs that are not bias-free 1x1 convs)
+        weights = model.get_weights()
+        if weights is None:
+            raise ValueError('OutputLayerTrainer: the model has no weights (set_weights / load_weights)')
+        self.features.set_weights(weights)
+        convs = output_convs(model)[:self.num_scales]
+        if len(convs) < self.num_scales:
+            raise ValueError('OutputLayerTrainer: %d outputs for %d scales' % (len(convs), self.num_scales))
+        self.kernel_names = [c.name + '/kernel' for c in convs]
+        self.num_anchors = [o.node.attrs['num_anchors'] for o in model.outputs[:self.num_scales]]
+        self.dims = []          # (cin, cout, kp) per scale
+        for c, a in zip(convs, self.num_anchors):
+            cin, cout = c.inputs[0].shape[2], c.output.shape[2]
+            if cout != a * (5 + self.num_classes):
+                raise ValueError('OutputLayerTrainer: %s has %d filters, %d anchors x (5 + %d classes) expected' % (c.name, cout, a, self.num_classes))
+            if not (1 <= cin <= 256 and 1 <= cout <= 256):
+                raise ValueError('OutputLayerTrainer: %s is %d -> %d channels; 1..256 are built' % (c.name, cin, cout))
+            self.dims.append((cin, cout, (cin + 3) // 4 * 4))
+        self.step = 0           # Adam's t: optimizer.iterations
+        self.device = None
+        self._workspace = None
+
+    # ------------------------------------------------------------------ state
+    def _views(self, flat):
+        out, at = [], 0
+        for cin, cout, kp in self.dims:
+            out.append(flat[at:at + cout * kp].view(cout, kp))
+            at += cout * kp
+        return out
+
+    def _ensure(self, device):
+        if self.device is not None:
+            if device != self.device:
+                raise ValueError('OutputLayerTrainer: the state lives on %s, this batch on %s' % (self.device, device))
+            return
+        host = self.model.get_weights()
+        n = sum(cout * kp for _, cout, kp in self.dims)
+        flat = np.zeros((n,), np.float32)
+        at = 0
+        for name, (cin, cout, kp) in zip(self.kernel_names, self.dims):
+            wt = flat[at:at + cout * kp].reshape(cout, kp)
+            wt[:, :cin] = np.asarray(host[name], np.float32).reshape(cin, cout).T          # pad columns stay 0
+            at += cout * kp
+        self.device = device
+        self.w = torch.from_numpy(flat).to(device)
+        self.m, self.v, self.g = torch.zeros_like(self.w), torch.zeros_like(self.w), torch.zeros_like(self.w)
+        self.weights, self.grads = self._views(self.w), self._views(self.g)
+
+    # ------------------------------------------------------------------ one step
+    def logits(self, images, features=None):
+        """The trained layer's forward on the frozen body's features -> [B,G,G,A,5+C] per scale (fresh tensors)."""
+        self._ensure(images.device)
+        feats = self.features(images) if features is None else features
+        ys = []
+        for f, wt, a in zip(feats, self.weights, self.num_anchors):
+            y = rt.linear_forward(f, wt)
+            ys.append(y.view(tuple(y.shape[:3]) + (a, y.shape[3] // a)))
+        return ys
+
+    def _apply(self, feats, dys):
+        for f, dy, g, (cin, cout, kp) in zip(feats, dys, self.grads, self.dims):
+            need = rt.linear_wgrad_workspace_bytes(f.numel() // cin, cin, cout)
+            if self._workspace is None or self._workspace.numel() < need:
+                self._workspace = torch.empty((need,), dtype=torch.uint8, device=self.device)        # (calls on one stream are ordered: one workspace serves all scales)
+            rt.linear_wgrad(f, dy.reshape(tuple(f.shape[:3]) + (cout,)), out=g, workspace=self._workspace)
+        self.step += 1
+        rt.adam_step(self.w, self.m, self.v, self.g, rt.adam_alpha(self.lr, self.step, self.beta_1, self.beta_2), self.beta_1, self.beta_2, self.epsilon)
+
+    def train_step(self, images, y_true):
+        """``_train_step`` (:18-46) for the output convolutions: features -> logits -> loss and its gradient at the logits -> the
+        weight gradients -> one Adam update -> the total loss BEFORE the update, a 0-d float32 device tensor.  Launches only: no host
+        synchronisation.  ``y_true``: the label tensors of the scales (``preprocess_true_boxes``' rows) on the images' device."""
+        y_true = [y_true] if isinstance(y_true, torch.Tensor) else list(y_true)
+        feats = self.features(images)
+        ys = self.logits(images, feats)
+        total, self.last_terms, dys = yolo_loss_and_grad(ys, y_true, self.anchors, self.num_scales, self.ignore_thresh)
+        self._apply(feats, dys)
+        return total
+
+    def train_step_from_boxes(self, images, true_boxes):
+        """``train_step`` with the labels encoded on the device from ground-truth boxes [B,T,5] (``yolo_loss_and_grad_from_boxes``)."""
+        feats = self.features(images)
+        ys = self.logits(images, feats)
+        total, self.last_terms, dys = yolo_loss_and_grad_from_boxes(ys, true_boxes, self.anchors, self.num_classes, self.num_scales, self.ignore_thresh)
+        self._apply(feats, dys)
+        return total
+
+    # ------------------------------------------------------------------ the loop
+    def commit(self):
+        """Writes the trained kernels back into ``model`` (``set_weights``), so ``model(images)``, ``YoloModel``, ``MAPCallback`` and
+        ``save_weights`` see the trained layer.  One copy to the host (synchronises)."""
+        if self.device is None:
+            return
+        host = self.w.cpu().numpy()
+        weights = self.model.get_weights()
+        at = 0
+        for name, (cin, cout, kp) in zip(self.kernel_names, self.dims):
+            wt = host[at:at + cout * kp].reshape(cout, kp)
+            weights[name] = np.ascontiguousarray(wt[:, :cin].T).reshape(1, 1, cin, cout)
+            at += cout * kp
+        self.model.set_weights(weights)
+
+    def fit(self, epochs, train_dataset, val_dataset=None, use_ema=False, use_adv=False):
+        """``fit`` (:81-128) under ``cos_lr_freeze`` (code/train.py:95-97): epoch e runs at learning_rate * 0.5 * (1 + cos(pi e / epochs));
+        the train loss of an epoch is the float32 sum of its batches' losses in order divided by their number (:68-74), formed on the
+        device and read once per epoch; ``val_loss`` is ``validation_loss`` of the committed model.  Datasets: iterables of
+        (images, y_true) on one device -> (train_losses, val_losses), lists of np.float32 (val_losses empty without a val_dataset)."""
+        if use_ema or use_adv:
+            raise NotImplementedError('OutputLayerTrainer.fit: use_ema and use_adv are not built')
+        train_losses, val_losses = [], []
+        for epoch in range(epochs):
+            self.lr = cosine_decay(self.learning_rate, epoch, epochs)
+            total, n = None, 0
+            for images, y_true in train_dataset:
+                loss = self.train_step(images, y_true)
+                total = loss if total is None else total + loss
+                n += 1
+            if n == 0:
+                raise ValueError('OutputLayerTrainer.fit: the training data set is empty')
+            mean = total / torch.full((), float(n), dtype=total.dtype, device=total.device)
+            train_losses.append(np.float32(mean.item()))
+            if val_dataset is not None:
+                self.commit()
+                val_losses.append(np.float32(validation_loss(self.model, val_dataset, self.anchors, self.num_scales, self.ignore_thresh)[0]))
+        self.commit()
+        return train_losses, val_losses
