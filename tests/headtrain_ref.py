@@ -73,7 +73,8 @@ def cosine_lr(lr, epoch, epochs):
 
 
 def int_case(seed, pixels, cin, cout, x_ld=None, dy_ld=None):
-    """Integers in [-4, 4] as float32: every product and partial sum of up to 2^19 pixels is exact in float32.
+    """Integers in [-4, 4] as float32: every product is at most 16 in magnitude, so every partial sum over P pixels is an integer
+    of magnitude <= 16 P: exact in float32, in any order, for up to 2^20 pixels (16 P <= 2^24).
     -> (x [P, x_ld], dy [P, dy_ld]) with NaN in the pad columns."""
     rng = np.random.default_rng(seed)
     x_ld, dy_ld = x_ld or cin, dy_ld or cout

@@ -184,6 +184,61 @@ def test_chunk_and_workspace_are_functions_of_the_sizes_only():
         assert rt.linear_wgrad_chunk(*bad) == 0 and rt.linear_wgrad_workspace_bytes(*bad) == 0
 
 
+# ----------------------------------------------------------------------------- what tests/test_gpu_headtrain_forms.py reaches
+def test_form_cases_reach_every_instantiation():
+    """The claim of tests/test_gpu_headtrain_forms.py, from its own case lists and its restatement of ht_blocking: the unblocked
+    cases run all 25 ht_wgrad_partial_kernel<TCO, TCI> and all 5 ht_forward_kernel<NT>."""
+    from tests import test_gpu_headtrain_forms as forms
+    assert [forms.blocking(n) for n in forms.WIDTHS] == [(1, 1), (1, 2), (1, 3), (1, 4), (1, 5)]
+    assert all(n % 4 and forms.idle_tiles(n) == 0 for n in forms.WIDTHS)
+    assert len(forms.FORM_WGRAD) == 25
+    assert {forms.wgrad_form(cin, cout) for cin, cout in forms.FORM_WGRAD} == {(tco, tci) for tco in range(1, 6) for tci in range(1, 6)}
+    for cin in (29, 77):
+        assert {forms.forward_form(cout) for c, cout in forms.FORM_FORWARD if c == cin} == {1, 2, 3, 4, 5}
+    # the restatement against the source's own words
+    import os
+    from yoloret_amd import build
+    src = open(os.path.join(os.path.dirname(build.__file__), 'csrc', 'headtrain.hip')).read()
+    assert '#define HT_MAX_T %d ' % forms.MAX_T in src
+    assert '*blocks = (t + HT_MAX_T - 1) / HT_MAX_T;' in src and '*per = (t + *blocks - 1) / *blocks;' in src
+
+
+def test_ragged_cases_leave_whole_tiles_out_of_range():
+    from tests import test_gpu_headtrain_forms as forms
+    assert forms.RAGGED_BLOCKINGS == {97: (2, 4), 161: (3, 4), 193: (3, 5), 81: (2, 3), 209: (3, 5)}
+    for n, want in forms.RAGGED_BLOCKINGS.items():
+        assert forms.blocking(n) == want, n
+    assert forms.blocking(3) == (1, 1)
+    assert [forms.idle_tiles(n) for n in (97, 161, 193, 81, 209, 3)] == [1, 1, 2, 0, 1, 0]
+    used = {n for case in forms.RAGGED_WGRAD + forms.RAGGED_FORWARD for n in case}
+    assert used == set(forms.RAGGED_BLOCKINGS) | {3}
+    # a block with a whole tile beyond the channel count on the cin side, on the cout side, both at once, and in the forward
+    assert any(forms.idle_tiles(cin) and not forms.idle_tiles(cout) for cin, cout in forms.RAGGED_WGRAD)
+    assert any(forms.idle_tiles(cout) and not forms.idle_tiles(cin) for cin, cout in forms.RAGGED_WGRAD)
+    assert any(forms.idle_tiles(cin) and forms.idle_tiles(cout) for cin, cout in forms.RAGGED_WGRAD)
+    assert any(forms.idle_tiles(cout) == 2 for _, cout in forms.RAGGED_FORWARD)
+    # blocked shapes take the larger minimum chunk
+    from yoloret_amd import runtime as rt
+    assert all(rt.linear_wgrad_chunk(p, cin, cout) == 512 for cin, cout in forms.RAGGED_WGRAD for p in (1, 5, 513, 2048 * 512))
+
+
+def test_chunk_leaves_its_minimum_at_2048_chunks():
+    from tests import test_gpu_headtrain_forms as forms
+    from yoloret_amd import runtime as rt
+    assert (forms.BIG_PIXELS, forms.BIG_CIN, forms.BIG_COUT) == (524289, 5, 3)
+    assert rt.linear_wgrad_chunk(524289, 5, 3) == 272 == forms.BIG_CHUNK
+    assert rt.linear_wgrad_chunk(524288, 5, 3) == 256
+    assert -(-524289 // 272) == 1928 == forms.BIG_SLABS
+    assert rt.linear_wgrad_workspace_bytes(524289, 5, 3) == 1928 * 3 * 8 * 4
+    assert rt.linear_wgrad_workspace_bytes(524288, 5, 3) == 2048 * 3 * 8 * 4
+    for pixels, chunk in forms.BIG_EXACT:
+        assert rt.linear_wgrad_chunk(pixels, 5, 3) == chunk and 16 * pixels < 2 ** 24
+    # 272 pixels: 68 = 17 quartets per wave, an odd number: eight groups of HT_U = 2 and one single quartet in every wave
+    assert 272 % 16 == 0 and (272 // 4) % 4 == 0 and (272 // 4 // 4) % 2 == 1
+    # the blocked shapes leave their minimum at 2048 * 512 + 1
+    assert rt.linear_wgrad_chunk(2048 * 512, 255, 255) == 512 and rt.linear_wgrad_chunk(2048 * 512 + 1, 255, 255) == 528
+
+
 def test_kernels_use_no_scratch():
     from yoloret_amd import build
     rows = build.kernel_resources()['headtrain.hip']
