@@ -767,6 +767,48 @@ int    yr_linear_wgrad(const float* x, int x_ld, const float* dy, int dy_ld, lon
 int yr_adam_step(float* w, float* m, float* v, const float* g, long long n,
                  float alpha, float beta1, float beta2, float eps, void* stream);
 
+/* ---- backward operators of the layers behind the output convolutions (code/train.py:150-171 trains the neck and the heads: bias-free
+ * 1x1 convolutions, k x k depthwise convolutions, BatchNorm, ReLU6 / Swish); added under ABI 9 (additive).  csrc/convgrad.hip has the
+ * kernels' forms, tests/convgrad_ref.py is the definition (the reference's backward is TensorFlow's tape).  The conventions of the
+ * entries above hold: float32, rows row-major over pixels with a leading dimension in floats, 4-byte alignment, no float atomics,
+ * nothing read before the call wrote it, every named output element written and nothing else, the same call gives the same bytes.
+ * YR_ERR_ARG, nothing written, for sizes outside the contract, a null pointer, a short or misaligned workspace. */
+/* d loss / d x of yr_linear_forward: dx[p][ci] = sum_co dy[p][co] * wt[co][ci] on the float32 matrix pipe.  1 <= cin, cout <= 256,
+ * 1 <= pixels < 2^40.  Every dx[p][0..cin) is written, dx[p][cin..dx_ld) is not touched; pad columns of wt and of dy are not read.
+ * One launch. */
+int yr_linear_dgrad(const float* dy, int dy_ld, const float* wt /*[cout][kp]*/, long long pixels, int cin, int cout,
+                    float* dx, int dx_ld, void* stream);
+/* Depthwise convolution on plain maps [B][H][W][ld] (C <= ld channels taken), taps w[k * k][C] (the Keras kernel [k,k,C,1] reshaped),
+ * k in {3, 5}, stride in {1, 2}.  The padding is explicit: pad_top, pad_left in 0..k-1 and the output size (OH, OW), which must be
+ * floor((H + pad_top + pad_bottom - k) / stride) + 1 for some pad_bottom in 0..k-1 (columns alike).  Taps are taken in the order
+ * t = ty * k + tx, one fmaf each from +0; out-of-range taps contribute nothing.
+ *   forward  y[b][oy][ox][c] = sum_t x[b][oy s - pad_top + ty][ox s - pad_left + tx][c] * w[t][c].  One launch.
+ *   dgrad    dx[b][iy][ix][c] = sum over the taps with iy + pad_top - ty = oy s, ix + pad_left - tx = ox s inside the output of
+ *            dy[b][oy][ox][c] * w[t][c]: a gather, every dx element written once.  One launch.
+ *   wgrad    dw[t][c] = sum_{b,oy,ox} dy[b][oy][ox][c] * x[b][oy s - pad_top + ty][ox s - pad_left + tx][c].  Two launches: stage 1
+ *            writes one partial [k * k][C] slab per yr_depthwise_wgrad_chunk(B, OH, OW, C, k) rows of the B * OH output rows - a
+ *            function of its arguments only -, stage 2 adds the slabs in index order and writes every dw element.  The workspace
+ *            (16-byte aligned) holds the slabs; its contents before the call do not matter.  The two size entries return 0 for
+ *            sizes the call refuses. */
+int    yr_depthwise_forward(const float* x, int x_ld, const float* w /*[k*k][C]*/, int B, int H, int W, int C, int k, int stride,
+                            int pad_top, int pad_left, int OH, int OW, float* y, int y_ld, void* stream);
+int    yr_depthwise_dgrad(const float* dy, int dy_ld, const float* w /*[k*k][C]*/, int B, int H, int W, int C, int k, int stride,
+                          int pad_top, int pad_left, int OH, int OW, float* dx, int dx_ld, void* stream);
+int    yr_depthwise_wgrad_chunk(int B, int OH, int OW, int C, int k);
+size_t yr_depthwise_wgrad_workspace_bytes(int B, int OH, int OW, int C, int k);
+int    yr_depthwise_wgrad(const float* x, int x_ld, const float* dy, int dy_ld, int B, int H, int W, int C, int k, int stride,
+                          int pad_top, int pad_left, int OH, int OW, void* workspace /*device*/, size_t workspace_bytes,
+                          float* dw /*[k*k][C]*/, void* stream);
+/* Frozen BatchNorm (inference mode: per-channel scale and shift) + activation (act: YR_ACT_NONE, YR_ACT_RELU6 or YR_ACT_SWISH) on
+ * rows [pixels][ld].  forward: u = z * scale[c] + shift[c] (a float32 multiply, then a float32 add), a = act(u); u (may be null) also
+ * receives u, for the backward.  backward: dz = (da * act'(u)) * scale[c]; ReLU6: act' = 1 where 0 < u < 6, both strict
+ * (TensorFlow's Relu6Grad), dz = +0 elsewhere; Swish: act' = sg (1 + u (1 - sg)), sg the forward kernels' sigmoid; none: u is not
+ * read and may be null.  No gradient for scale or shift.  One launch each. */
+int yr_bn_act_forward(const float* z, int z_ld, const float* scale, const float* shift, long long pixels, int C, int act,
+                      float* a, int a_ld, float* u /*or null*/, int u_ld, void* stream);
+int yr_bn_act_backward(const float* da, int da_ld, const float* u /*null for YR_ACT_NONE*/, int u_ld, const float* scale,
+                       long long pixels, int C, int act, float* dz, int dz_ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

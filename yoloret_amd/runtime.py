@@ -134,7 +134,9 @@ ABI_VERSION = 9   # == YR_ABI_VERSION of include/yoloret_hip.h
 EXPORTS = ['yr_jpeg_workspace_bytes', 'yr_jpeg_roundtrip_batch', 'yr_augment_geometry', 'yr_augment_workspace_bytes', 'yr_augment_batch', 'yr_ingest_geometry', 'yr_ingest_batch', 'yr_last_error', 'yr_abi_version', 'yr_abi_sizeof', 'yr_create', 'yr_create_from_blob', 'yr_plan_io_dims', 'yr_destroy', 'yr_load_weights', 'yr_workspace_bytes',
            'yr_forward', 'yr_forward_profile', 'yr_forward_ranges', 'yr_autotune', 'yr_get_tuning', 'yr_set_tuning', 'yr_plan_num_launches', 'yr_op_run', 'yr_head_regions', 'yr_head_walk_rows', 'yr_head_stream_rows', 'yr_pwt_chunks', 'yr_decode', 'yr_decode_zoom', 'yr_yolo_head', 'yr_correct_boxes',
            'yr_nms', 'yr_pack_detections', 'yr_letterbox', 'yr_letterbox_batch', 'yr_yolo_loss_workspace_bytes', 'yr_yolo_loss', 'yr_yolo_loss_grad', 'yr_voc_match', 'yr_encode_labels',
-           'yr_linear_forward', 'yr_linear_wgrad_chunk', 'yr_linear_wgrad_workspace_bytes', 'yr_linear_wgrad', 'yr_adam_step']
+           'yr_linear_forward', 'yr_linear_wgrad_chunk', 'yr_linear_wgrad_workspace_bytes', 'yr_linear_wgrad', 'yr_adam_step',
+           'yr_linear_dgrad', 'yr_depthwise_forward', 'yr_depthwise_dgrad', 'yr_depthwise_wgrad_chunk', 'yr_depthwise_wgrad_workspace_bytes', 'yr_depthwise_wgrad',
+           'yr_bn_act_forward', 'yr_bn_act_backward']
 
 _lib = None
 
@@ -225,6 +227,19 @@ def lib():
         L.yr_linear_wgrad.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
         L.yr_adam_step.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_longlong] + [ctypes.c_float] * 4 + [ctypes.c_void_p]
+        L.yr_linear_dgrad.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                      ctypes.c_int, ctypes.c_void_p]
+        for entry in (L.yr_depthwise_forward, L.yr_depthwise_dgrad):
+            entry.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p] + [ctypes.c_int] * 10 + [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        L.yr_depthwise_wgrad_chunk.argtypes = [ctypes.c_int] * 5
+        L.yr_depthwise_wgrad_workspace_bytes.restype = ctypes.c_size_t
+        L.yr_depthwise_wgrad_workspace_bytes.argtypes = [ctypes.c_int] * 5
+        L.yr_depthwise_wgrad.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_int] * 10 + \
+            [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+        L.yr_bn_act_forward.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        L.yr_bn_act_backward.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
+                                         ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
         if L.yr_abi_version() != ABI_VERSION:
             raise YoloretHipError('libyoloret_hip.so ABI version mismatch')
         L.yr_abi_sizeof.argtypes = [ctypes.c_int]
@@ -565,6 +580,174 @@ def adam_step(w, m, v, g, alpha, beta1=.9, beta2=.999, eps=1e-8):
         check(lib().yr_adam_step(_ptr(w), _ptr(m), _ptr(v), _ptr(g), w.numel(), float(alpha), float(beta1), float(beta2), float(eps),
                                  stream_ptr(w.device)))
     return w
+
+
+# ----------------------------------------------------------------------------- backward operators (csrc/convgrad.hip)
+def _out_like(out, shape, dev, name):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    if not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == dev and tuple(out.shape) == tuple(shape)
+            and out.is_contiguous()):
+        raise ValueError('%s: out must be a contiguous float32 tensor of shape %s on %s' % (name, tuple(shape), dev))
+    return out
+
+
+def linear_dgrad(dy, wt, cin, out=None):
+    """The input gradient of ``linear_forward`` (yr_linear_dgrad): dy [..., cout] float32, wt [cout, round_up(cin, 4)] ->
+    dx [..., cin] = dy @ wt[:, :cin] on the float32 matrix pipe.  ``cin`` names the channels taken of wt's rows.  out: a contiguous
+    float32 tensor of that shape on dy's device (every element is written); default: a fresh one.  One launch."""
+    pixels, cout = _rows(dy, 'dy')
+    cin = int(cin)
+    if not (1 <= cin <= 256 and 1 <= cout <= 256):
+        raise ValueError('linear_dgrad: 1..256 channels, not %d and %d' % (cin, cout))
+    _linear_wt(wt, 'wt', cin)
+    if wt.device != dy.device or wt.shape[0] != cout:
+        raise ValueError('linear_dgrad: wt %s on %s for dy %s on %s' % (tuple(wt.shape), wt.device, tuple(dy.shape), dy.device))
+    out = _out_like(out, tuple(dy.shape[:-1]) + (cin,), dy.device, 'linear_dgrad')
+    with torch.cuda.device(dy.device):
+        check(lib().yr_linear_dgrad(_ptr(dy), cout, _ptr(wt), pixels, cin, cout, _ptr(out), cin, stream_ptr(dy.device)))
+    return out
+
+
+def depthwise_geometry(h, w, k, stride=1, padding='same'):
+    """-> (pad_top, pad_left, out_h, out_w) of a k x k depthwise convolution.  padding: 'same' (the Keras rule: out = ceil(n / stride),
+    total pad max((out - 1) stride + k - n, 0), the smaller half in front) or (top, left, bottom, right), e.g. MobileNetV2's
+    ZeroPadding2D(correct_pad) in front of its stride-2 'valid' convolutions."""
+    h, w, k, stride = int(h), int(w), int(k), int(stride)
+    if k not in (3, 5) or stride not in (1, 2) or h < 1 or w < 1:
+        raise ValueError('depthwise: k in {3, 5}, stride in {1, 2} and a non-empty map, not k %d, stride %d, %d x %d' % (k, stride, h, w))
+    if isinstance(padding, str):
+        if padding != 'same':
+            raise ValueError("depthwise: padding must be 'same' or (top, left, bottom, right), not %r" % (padding,))
+        oh, ow = -(-h // stride), -(-w // stride)
+        return max((oh - 1) * stride + k - h, 0) // 2, max((ow - 1) * stride + k - w, 0) // 2, oh, ow
+    pt, pl, pb, pr = (int(v) for v in padding)
+    if not all(0 <= v < k for v in (pt, pl, pb, pr)) or h + pt + pb < k or w + pl + pr < k:
+        raise ValueError('depthwise: pads %r outside 0..k-1, or the padded map is smaller than the kernel' % (padding,))
+    return pt, pl, (h + pt + pb - k) // stride + 1, (w + pl + pr - k) // stride + 1
+
+
+def _dw_map(t, name):
+    _require_cuda_f32(t, name)
+    if t.dim() != 4 or t.numel() == 0:
+        raise ValueError('%s has shape %s, expected [B, H, W, C]' % (name, tuple(t.shape)))
+    return tuple(t.shape)
+
+
+def _dw_taps(w, c, name):
+    _require_cuda_f32(w, name)
+    if w.dim() != 2 or w.shape[0] not in (9, 25) or w.shape[1] != c:
+        raise ValueError('%s has shape %s, expected [k * k, %d] with k in {3, 5}' % (name, tuple(w.shape), c))
+    return 3 if w.shape[0] == 9 else 5
+
+
+def depthwise_forward(x, w, stride=1, padding='same', out=None):
+    """A k x k depthwise convolution on a plain map (yr_depthwise_forward): x [B, H, W, C] float32, w [k * k, C] (the Keras kernel
+    [k, k, C, 1] reshaped) -> y [B, OH, OW, C]; stride and padding as ``depthwise_geometry`` reads them.  One launch."""
+    b, h, wd, c = _dw_map(x, 'x')
+    k = _dw_taps(w, c, 'w')
+    if w.device != x.device:
+        raise ValueError('depthwise_forward: w on %s, x on %s' % (w.device, x.device))
+    pt, pl, oh, ow = depthwise_geometry(h, wd, k, stride, padding)
+    out = _out_like(out, (b, oh, ow, c), x.device, 'depthwise_forward')
+    with torch.cuda.device(x.device):
+        check(lib().yr_depthwise_forward(_ptr(x), c, _ptr(w), b, h, wd, c, k, int(stride), pt, pl, oh, ow, _ptr(out), c, stream_ptr(x.device)))
+    return out
+
+
+def depthwise_dgrad(dy, w, input_hw, stride=1, padding='same', out=None):
+    """The input gradient of ``depthwise_forward`` (yr_depthwise_dgrad): dy [B, OH, OW, C], w [k * k, C], input_hw = (H, W) of the
+    forward's input -> dx [B, H, W, C], every element written once (a gather, taps in a fixed order).  One launch."""
+    b, oh, ow, c = _dw_map(dy, 'dy')
+    k = _dw_taps(w, c, 'w')
+    if w.device != dy.device:
+        raise ValueError('depthwise_dgrad: w on %s, dy on %s' % (w.device, dy.device))
+    h, wd = int(input_hw[0]), int(input_hw[1])
+    pt, pl, eh, ew = depthwise_geometry(h, wd, k, stride, padding)
+    if (eh, ew) != (oh, ow):
+        raise ValueError('depthwise_dgrad: dy is %d x %d, the forward of a %d x %d map gives %d x %d' % (oh, ow, h, wd, eh, ew))
+    out = _out_like(out, (b, h, wd, c), dy.device, 'depthwise_dgrad')
+    with torch.cuda.device(dy.device):
+        check(lib().yr_depthwise_dgrad(_ptr(dy), c, _ptr(w), b, h, wd, c, k, int(stride), pt, pl, oh, ow, _ptr(out), c, stream_ptr(dy.device)))
+    return out
+
+
+def depthwise_wgrad_chunk(b, oh, ow, c, k):
+    """Output rows (of the b * oh) per workgroup of the gradient's first stage: a function of these numbers only (0: refused sizes)."""
+    return int(lib().yr_depthwise_wgrad_chunk(int(b), int(oh), int(ow), int(c), int(k)))
+
+
+def depthwise_wgrad_workspace_bytes(b, oh, ow, c, k):
+    return int(lib().yr_depthwise_wgrad_workspace_bytes(int(b), int(oh), int(ow), int(c), int(k)))
+
+
+def depthwise_wgrad(x, dy, k, stride=1, padding='same', out=None, workspace=None):
+    """The weight gradient of ``depthwise_forward`` (yr_depthwise_wgrad): x [B, H, W, C], dy [B, OH, OW, C] -> dw [k * k, C]; two
+    stages, no atomics, the same call gives the same bytes.  workspace: a uint8 tensor of at least
+    depthwise_wgrad_workspace_bytes(B, OH, OW, C, k) bytes (its contents do not matter); default: a fresh one.  Two launches."""
+    b, h, wd, c = _dw_map(x, 'x')
+    pt, pl, oh, ow = depthwise_geometry(h, wd, k, stride, padding)
+    _require_cuda_f32(dy, 'dy')
+    if tuple(dy.shape) != (b, oh, ow, c) or dy.device != x.device:
+        raise ValueError('depthwise_wgrad: dy %s on %s, expected %s on %s' % (tuple(dy.shape), dy.device, (b, oh, ow, c), x.device))
+    dev = x.device
+    out = _out_like(out, (k * k, c), dev, 'depthwise_wgrad')
+    need = depthwise_wgrad_workspace_bytes(b, oh, ow, c, k)
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev) if workspace is None else workspace
+    if not (isinstance(ws, torch.Tensor) and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.device == dev and ws.numel() >= need):
+        raise ValueError('depthwise_wgrad: workspace must be a contiguous uint8 tensor of at least %d bytes on %s' % (need, dev))
+    with torch.cuda.device(dev):
+        check(lib().yr_depthwise_wgrad(_ptr(x), c, _ptr(dy), c, b, h, wd, c, int(k), int(stride), pt, pl, oh, ow, _ptr(ws), ws.numel(), _ptr(out),
+                                       stream_ptr(dev)))
+    return out
+
+
+BN_ACTS = {None: 0, 'none': 0, 'linear': 0, 'relu6': 1, 'swish': 2}      # YR_ACT_NONE, YR_ACT_RELU6, YR_ACT_SWISH
+
+
+def _bn_act_id(act):
+    key = act.lower() if isinstance(act, str) else act
+    if key not in BN_ACTS:
+        raise ValueError("bn_act: act must be None / 'none', 'relu6' or 'swish', not %r" % (act,))
+    return BN_ACTS[key]
+
+
+def _bn_vec(t, c, dev, name):
+    _require_cuda_f32(t, name)
+    if tuple(t.shape) != (c,) or t.device != dev:
+        raise ValueError('%s has shape %s on %s, expected (%d,) on %s' % (name, tuple(t.shape), t.device, c, dev))
+
+
+def bn_act_forward(z, scale, shift, act, out=None, keep_u=False):
+    """Frozen BatchNorm + activation (yr_bn_act_forward): z [..., C] float32, scale / shift [C] -> a = act(z * scale + shift), act in
+    {None, 'relu6', 'swish'}.  keep_u: also return u = z * scale + shift (what ``bn_act_backward`` needs) -> (a, u).  One launch."""
+    pixels, c = _rows(z, 'z')
+    _bn_vec(scale, c, z.device, 'scale')
+    _bn_vec(shift, c, z.device, 'shift')
+    out = _out_like(out, tuple(z.shape), z.device, 'bn_act_forward')
+    u = torch.empty_like(z) if keep_u else None
+    with torch.cuda.device(z.device):
+        check(lib().yr_bn_act_forward(_ptr(z), c, _ptr(scale), _ptr(shift), pixels, c, _bn_act_id(act), _ptr(out), c, _ptr(u), c, stream_ptr(z.device)))
+    return (out, u) if keep_u else out
+
+
+def bn_act_backward(da, u, scale, act, out=None):
+    """dz = da * act'(u) * scale (yr_bn_act_backward): da [..., C], u as ``bn_act_forward(keep_u=True)`` returned it (None for act
+    None, whose derivative does not read it), scale [C].  ReLU6' is 1 on 0 < u < 6 (both strict).  One launch."""
+    pixels, c = _rows(da, 'da')
+    a = _bn_act_id(act)
+    _bn_vec(scale, c, da.device, 'scale')
+    if u is None:
+        if a != 0:
+            raise ValueError('bn_act_backward: u is needed for %r' % (act,))
+    else:
+        _require_cuda_f32(u, 'u')
+        if tuple(u.shape) != tuple(da.shape) or u.device != da.device:
+            raise ValueError('bn_act_backward: u %s on %s for da %s on %s' % (tuple(u.shape), u.device, tuple(da.shape), da.device))
+    out = _out_like(out, tuple(da.shape), da.device, 'bn_act_backward')
+    with torch.cuda.device(da.device):
+        check(lib().yr_bn_act_backward(_ptr(da), c, _ptr(u), c, _ptr(scale), pixels, c, a, _ptr(out), c, stream_ptr(da.device)))
+    return out
 
 
 VOC_MAX_ROWS, VOC_MAX_GT = 4096, 512     # YR_VOC_MAX_ROWS, YR_VOC_MAX_GT of include/yoloret_hip.h
