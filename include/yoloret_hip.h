@@ -378,6 +378,9 @@ typedef struct {
 typedef struct yr_handle yr_handle;
 
 const char* yr_last_error(void);
+/* The name of the kernel instantiation the calling thread's last launch chose (spelled like the symbol, e.g. "dwp_kernel<bf16,3,0,1,4>";
+ * what yr_forward_profile reports per launch), "" before any launch.  A static string: valid for the life of the library. */
+const char* yr_last_kernel(void);
 int yr_abi_version(void);
 /* sizeof(yr_src) / sizeof(yr_op) / sizeof(yr_buf) / sizeof(yr_ingest_geom) / sizeof(yr_augment_geom) for which = 0 / 1 / 2 / 3 / 4 (else 0): lets a binding that restates the
  * structs (ctypes, cgo, JNA ...) verify its layout against the library's at load time. */

@@ -665,9 +665,11 @@ def test_depthwise_se_form(dev, dt, k, s, h, w, c, r):
 @pytest.mark.parametrize('dt', DTYPES)
 def test_depthwise_walk_is_batch_independent(dev, dt):
     """The walking 5x5 form (depthwise_walk.hip) cuts the rows of an image into segments by how many workgroups a LAUNCH has
-    (a batch of 2: one segment per row quantum; a batch of 400 on this map: whole images) - the stored map and the
-    squeeze-excite sums (one row per quantum whatever the segmentation) of an image must not depend on it.  Also an odd batch
-    (the second image slot of the last workgroup is empty) and the float64 reference on the large batch."""
+    - the stored map and the squeeze-excite sums (one row per quantum whatever the segmentation) of an image must not depend on
+    it.  Also an odd batch (the second image slot of the last workgroup is empty) and the float64 reference on the large batch.
+    (With 64 channels even the batches of 301 and 400 leave the launcher's cost model at one quantum per segment - 400 units against
+    768 resident workgroups, tests/depthwise_geo.py: dwq_segments - so what varies here is the number of workgroups; segments of
+    several quanta run in tests/test_gpu_depthwise_forms.py::test_dwq_segments_of_several_quanta.)"""
     rt = _rt()
     from yoloret_amd.compiler import dwl_geometry, DW_LDS, DW_WALK
     if not (DW_LDS and DW_WALK):
@@ -712,9 +714,12 @@ def test_depthwise_walk_is_batch_independent(dev, dt):
 
 @pytest.mark.gpu
 def test_depthwise_lds_form_geometry_mirror(dev):
-    """compiler.dwl_geometry must pick the tile the launcher picks (depthwise_lds.hip) for every map size: the SE partial-sum
-    buffer is sized from it and the launcher refuses a buffer of another height.  64 channels, one image, a grid of map
-    sizes (the stage maps of 320 ... 1280-pixel inputs and odd ones); the sums must equal those of the stored map."""
+    """compiler.dwl_geometry must give the rows of squeeze-excite sums the launcher writes for every map size: the SE partial-sum
+    buffer is sized from it and the launcher refuses a buffer of another height.  With k = 5 these launches go to the walking form
+    (dwq_kernel, depthwise_walk.hip: column blocks x row quanta) since it became the default for the 5 x 5 maps, and only with
+    YOLORET_DW_WALK=0 to the LDS-tiled dwp_kernel (depthwise_lds.hip: tiles) the test was written for; the 3 x 3 tiles of dwp_kernel
+    are covered class by class in tests/test_gpu_depthwise_forms.py.  64 channels, one image, a grid of map sizes (the stage maps
+    of 320 ... 1280-pixel inputs and odd ones); the sums must equal those of the stored map."""
     rt = _rt()
     from yoloret_amd.compiler import dwl_geometry, DW_LDS
     if not DW_LDS:

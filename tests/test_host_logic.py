@@ -4,6 +4,7 @@ exports every symbol include/yoloret_hip.h declares (no compute calls)."""
 import ctypes
 import os
 import re
+import threading
 
 import numpy as np
 import pytest
@@ -277,6 +278,14 @@ def test_c_abi_library_loads_and_exports_every_declared_symbol():
     assert declared == set(rt.EXPORTS)
     L.yr_abi_version.restype = ctypes.c_int
     assert L.yr_abi_version() == 9 == rt.ABI_VERSION
+    # the kernel name of the calling thread's last launch: a C string, empty before any launch (a new thread has launched nothing)
+    assert re.search(r'\bconst char\s*\*\s*yr_last_kernel\s*\(\s*void\s*\)', header)
+    L.yr_last_kernel.restype = ctypes.c_char_p
+    fresh = []
+    th = threading.Thread(target=lambda: fresh.append(L.yr_last_kernel()))
+    th.start()
+    th.join()
+    assert fresh == [b''] and rt.lib().yr_last_kernel.restype is ctypes.c_char_p
     # struct layouts agree with the header's (the library reports its own sizeof)
     for which, st in enumerate((rt.YrSrc, rt.YrOp, rt.YrBuf)):
         assert L.yr_abi_sizeof(which) == ctypes.sizeof(st), st.__name__

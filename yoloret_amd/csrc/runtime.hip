@@ -26,6 +26,7 @@ static thread_local const char* g_kernel = "";
 void yr_note_kernel(const char* name) { g_kernel = name; }
 
 extern "C" const char* yr_last_error(void) { return g_err; }
+extern "C" const char* yr_last_kernel(void) { return g_kernel; }
 extern "C" int yr_abi_version(void) { return YR_ABI_VERSION; }
 extern "C" int yr_abi_sizeof(int which) {
     return which == 0 ? (int)sizeof(yr_src) : which == 1 ? (int)sizeof(yr_op) : which == 2 ? (int)sizeof(yr_buf) : which == 3 ? (int)sizeof(yr_ingest_geom) : which == 4 ? (int)sizeof(yr_augment_geom) : 0;

@@ -131,7 +131,7 @@ AUGMENT_GEOM_DTYPE = np.dtype([('src_off', '<i8'), ('ih', '<i4'), ('iw', '<i4'),
                                ('hue6', '<f4'), ('sat', '<f4'), ('gamma', '<f4'), ('cont', '<f4')])
 
 ABI_VERSION = 9   # == YR_ABI_VERSION of include/yoloret_hip.h
-EXPORTS = ['yr_jpeg_workspace_bytes', 'yr_jpeg_roundtrip_batch', 'yr_augment_geometry', 'yr_augment_workspace_bytes', 'yr_augment_batch', 'yr_ingest_geometry', 'yr_ingest_batch', 'yr_last_error', 'yr_abi_version', 'yr_abi_sizeof', 'yr_create', 'yr_create_from_blob', 'yr_plan_io_dims', 'yr_destroy', 'yr_load_weights', 'yr_workspace_bytes',
+EXPORTS = ['yr_jpeg_workspace_bytes', 'yr_jpeg_roundtrip_batch', 'yr_augment_geometry', 'yr_augment_workspace_bytes', 'yr_augment_batch', 'yr_ingest_geometry', 'yr_ingest_batch', 'yr_last_error', 'yr_last_kernel', 'yr_abi_version', 'yr_abi_sizeof', 'yr_create', 'yr_create_from_blob', 'yr_plan_io_dims', 'yr_destroy', 'yr_load_weights', 'yr_workspace_bytes',
            'yr_forward', 'yr_forward_profile', 'yr_forward_ranges', 'yr_autotune', 'yr_get_tuning', 'yr_set_tuning', 'yr_plan_num_launches', 'yr_op_run', 'yr_head_regions', 'yr_head_walk_rows', 'yr_head_stream_rows', 'yr_pwt_chunks', 'yr_decode', 'yr_decode_zoom', 'yr_yolo_head', 'yr_correct_boxes',
            'yr_nms', 'yr_pack_detections', 'yr_letterbox', 'yr_letterbox_batch', 'yr_yolo_loss_workspace_bytes', 'yr_yolo_loss', 'yr_yolo_loss_grad', 'yr_voc_match', 'yr_encode_labels',
            'yr_linear_forward', 'yr_linear_wgrad_chunk', 'yr_linear_wgrad_workspace_bytes', 'yr_linear_wgrad', 'yr_adam_step',
@@ -155,6 +155,7 @@ def lib():
                 '(hipcc --offload-arch=gfx950); there is no CPU fallback.' % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
         L.yr_last_error.restype = ctypes.c_char_p
+        L.yr_last_kernel.restype = ctypes.c_char_p
         L.yr_abi_version.restype = ctypes.c_int
         L.yr_workspace_bytes.restype = ctypes.c_size_t
         L.yr_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
