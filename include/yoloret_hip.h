@@ -812,6 +812,41 @@ int yr_bn_act_forward(const float* z, int z_ld, const float* scale, const float*
 int yr_bn_act_backward(const float* da, int da_ld, const float* u /*null for YR_ACT_NONE*/, int u_ld, const float* scale,
                        long long pixels, int C, int act, float* dz, int dz_ld, void* stream);
 
+/* ---- BatchNorm (+ activation) in training mode (yolo3/model.py:24-105 puts a BatchNormalization, momentum 0.9, epsilon 1e-3, behind
+ * every convolution of the neck and the heads, and the training step calls the model with training=True); added under ABI 9 (additive).
+ * csrc/bntrain.hip has the kernels' forms, tests/bntrain_ref.py is the definition.  The conventions of the entries above hold: float32,
+ * rows [pixels][ld] with C <= ld channels taken (pad columns neither read nor written), 4-byte alignment, no float atomics, nothing read
+ * before the call wrote it, every named output element written and nothing else, the same call gives the same bytes.
+ * 1 <= pixels < 2^40, 1 <= C < 2^31 - 64, eps >= 0 and finite, 0 <= momentum <= 1, act one of YR_ACT_NONE, YR_ACT_RELU6, YR_ACT_SWISH; the
+ * workspace (device, 16-byte aligned, yr_bn_train_workspace_bytes(pixels, C) bytes: enough for either call) may hold anything before the
+ * call.  YR_ERR_ARG, nothing written, for anything else, a null pointer, a short or misaligned workspace, one moving pointer without the
+ * other.  Every operation is one IEEE float32 operation in this order, nothing contracted (N = pixels):
+ *   forward   mean[c] = (sum_p z[p][c]) / (float)N;  var[c] = (sum_p (z[p][c] - mean[c])^2) / (float)N - the squared deviations about the
+ *             finished mean, never E[z^2] - E[z]^2;  invstd[c] = 1.0f / sqrtf(var[c] + eps), both correctly rounded;
+ *             xhat = (z - mean[c]) * invstd[c];  u = xhat * gamma[c] + beta[c] (a multiply, then an add);  a = act(u) (the forward
+ *             kernels' activations).  The moving statistics, when given (both or neither), are updated in place as Keras' fused path
+ *             does, which stores the UNBIASED variance of the batch: d = 1.0f - momentum;  moving_mean -= (moving_mean - mean) * d;
+ *             moving_var -= (moving_var - var * bessel) * d,  bessel = (float)((double)N / (double)max(N - 1, 1)).  3 launches.
+ *   backward  u and xhat are recomputed from z, mean, invstd, gamma and beta by the forward's operations (the same bits); g = da * act'(u)
+ *             with the rules of yr_bn_act_backward (ReLU6: g = da where 0 < u < 6, both strict, +0 elsewhere; Swish: sg (1 + u (1 - sg)));
+ *             dbeta[c] = sum_p g;  dgamma[c] = sum_p (g * xhat) (a product, then the sum);
+ *             dz = ((g - dbeta[c] / (float)N) - xhat * (dgamma[c] / (float)N)) * (gamma[c] * invstd[c]).  dz may be null: it is not
+ *             computed, dgamma and dbeta are the same bits.  2 launches either way.
+ * Every per-channel sum has two stages: stage 1 gives each workgroup a contiguous range of yr_bn_train_chunk(pixels, C) pixels - a
+ * function of its arguments only - and writes one [C] slab per range; the slabs are added in index order (in the prologue of the next
+ * kernel).  The two size entries return 0 for sizes the calls refuse. */
+int    yr_bn_train_chunk(long long pixels, int C);
+size_t yr_bn_train_workspace_bytes(long long pixels, int C);
+int yr_bn_train_forward(const float* z, int z_ld, const float* gamma, const float* beta, long long pixels, int C,
+                        float eps, float momentum, int act,
+                        float* a, int a_ld, float* mean /*[C]*/, float* invstd /*[C]*/,
+                        float* moving_mean /*[C] in place, or null*/, float* moving_var /*[C] in place; both or neither*/,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int yr_bn_train_backward(const float* da, int da_ld, const float* z, int z_ld, const float* gamma, const float* beta,
+                         const float* mean, const float* invstd, long long pixels, int C, int act,
+                         float* dz /*or null: not computed*/, int dz_ld, float* dgamma /*[C]*/, float* dbeta /*[C]*/,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

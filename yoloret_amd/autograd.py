@@ -5,6 +5,9 @@ convolutions, depthwise convolutions and frozen BatchNorm + activation on top of
     linear1x1(x, wt)                        x [..., cin], wt [cout, round_up(cin, 4)] (pad columns 0) -> [..., cout]
     depthwise(x, w, stride=1, padding='same')   x [B, H, W, C], w [k * k, C] (the Keras kernel [k, k, C, 1] reshaped), k in {3, 5}
     frozen_bn_act(z, scale, shift, act)     act in {None, 'relu6', 'swish'}; scale and shift are frozen: they never get a gradient
+    batchnorm_act(z, gamma, beta, moving_mean, moving_var, momentum, eps, act)   BatchNorm in training mode (csrc/bntrain.hip): batch
+                                            statistics, gradients for z, gamma and beta, the moving statistics updated in place
+    fold_batchnorm(gamma, beta, moving_mean, moving_var, eps) -> (scale, shift) for frozen_bn_act: how a trained layer is evaluated
 
 Written the way ``_YoloLossFunction`` of yolo3/model.py is: forward and backward are calls of the C entries, only what backward needs
 is saved, a gradient is computed only for an input that requires one (the others are None and their kernel is not launched).  float32
@@ -89,6 +92,27 @@ class _FrozenBnAct(torch.autograd.Function):
         return dz, None, None, None
 
 
+class _BatchNormAct(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, gamma, beta, moving_mean, moving_var, momentum, eps, act):
+        pixels, c = z.numel() // z.shape[-1], z.shape[-1]
+        a, mean, invstd = rt.bn_train_forward(z, gamma, beta, eps, momentum, act, moving_mean, moving_var,
+                                              workspace=_workspace(z.device, rt.bn_train_workspace_bytes(pixels, c)))
+        ctx.act = act
+        ctx.save_for_backward(z, gamma, beta, mean, invstd)
+        return a
+
+    @staticmethod
+    def backward(ctx, da):
+        z, gamma, beta, mean, invstd = ctx.saved_tensors
+        if not any(ctx.needs_input_grad[:3]):
+            return (None,) * 8
+        pixels, c = z.numel() // z.shape[-1], z.shape[-1]
+        dz, dgamma, dbeta = rt.bn_train_backward(_f32(da), z, gamma, beta, mean, invstd, ctx.act, need_dz=ctx.needs_input_grad[0],
+                                                 workspace=_workspace(z.device, rt.bn_train_workspace_bytes(pixels, c)))
+        return (dz, dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None, None, None, None, None, None)
+
+
 def linear1x1(x, wt):
     """A bias-free 1x1 convolution, differentiable in x (``runtime.linear_dgrad``) and wt (``runtime.linear_wgrad``: pad columns +0)."""
     return _Linear1x1.apply(x.contiguous(), wt.contiguous())
@@ -103,5 +127,26 @@ def depthwise(x, w, stride=1, padding='same'):
 def frozen_bn_act(z, scale, shift, act=None):
     """Inference-mode BatchNorm (per-channel scale and shift) + activation, differentiable in z only."""
     if scale.requires_grad or shift.requires_grad:
-        raise ValueError('frozen_bn_act: scale and shift are frozen here (BatchNorm in training mode is not built)')
+        raise ValueError('frozen_bn_act: scale and shift are frozen here (BatchNorm in training mode is batchnorm_act)')
     return _FrozenBnAct.apply(z.contiguous(), scale, shift, act)
+
+
+def batchnorm_act(z, gamma, beta, moving_mean=None, moving_var=None, momentum=0.9, eps=1e-3, act=None):
+    """BatchNorm in training mode + activation (Keras' BatchNormalization called with training=True, then ``act``): z [..., C] is
+    normalised with the mean and the biased variance of the batch, differentiable in z, gamma and beta.  moving_mean / moving_var
+    (both or neither; they must not require a gradient) are updated IN PLACE during the forward:
+    moving -= (moving - batch value) * (1 - momentum), the variance the unbiased one, as Keras' fused path stores it."""
+    for t in (moving_mean, moving_var):
+        if t is not None and t.requires_grad:
+            raise ValueError('batchnorm_act: the moving statistics are updated in place and take no gradient')
+    return _BatchNormAct.apply(z.contiguous(), gamma, beta, moving_mean, moving_var, float(momentum), float(eps), act)
+
+
+def fold_batchnorm(gamma, beta, moving_mean, moving_var, eps=1e-3):
+    """-> (scale, shift), float32 tensors on gamma's device for ``frozen_bn_act``: the inference-mode form of a trained layer,
+    scale = gamma / sqrt(moving_var + eps), shift = beta - moving_mean * scale, computed on the host in float64 as the plan compiler
+    folds a BatchNormalization.  Copies the four vectors to the host: it SYNCHRONISES with the device."""
+    g, b, m, v = (t.detach().to('cpu', torch.float64) for t in (gamma, beta, moving_mean, moving_var))
+    scale = g / torch.sqrt(v + float(eps))
+    shift = b - m * scale
+    return scale.to(torch.float32).to(gamma.device), shift.to(torch.float32).to(gamma.device)

@@ -136,7 +136,8 @@ EXPORTS = ['yr_jpeg_workspace_bytes', 'yr_jpeg_roundtrip_batch', 'yr_augment_geo
            'yr_nms', 'yr_pack_detections', 'yr_letterbox', 'yr_letterbox_batch', 'yr_yolo_loss_workspace_bytes', 'yr_yolo_loss', 'yr_yolo_loss_grad', 'yr_voc_match', 'yr_encode_labels',
            'yr_linear_forward', 'yr_linear_wgrad_chunk', 'yr_linear_wgrad_workspace_bytes', 'yr_linear_wgrad', 'yr_adam_step',
            'yr_linear_dgrad', 'yr_depthwise_forward', 'yr_depthwise_dgrad', 'yr_depthwise_wgrad_chunk', 'yr_depthwise_wgrad_workspace_bytes', 'yr_depthwise_wgrad',
-           'yr_bn_act_forward', 'yr_bn_act_backward']
+           'yr_bn_act_forward', 'yr_bn_act_backward',
+           'yr_bn_train_chunk', 'yr_bn_train_workspace_bytes', 'yr_bn_train_forward', 'yr_bn_train_backward']
 
 _lib = None
 
@@ -241,6 +242,13 @@ def lib():
                                         ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
         L.yr_bn_act_backward.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
                                          ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        L.yr_bn_train_chunk.argtypes = [ctypes.c_longlong, ctypes.c_int]
+        L.yr_bn_train_workspace_bytes.restype = ctypes.c_size_t
+        L.yr_bn_train_workspace_bytes.argtypes = [ctypes.c_longlong, ctypes.c_int]
+        L.yr_bn_train_forward.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_float,
+                                          ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p]
+        L.yr_bn_train_backward.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4 + \
+            [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_size_t, ctypes.c_void_p]
         if L.yr_abi_version() != ABI_VERSION:
             raise YoloretHipError('libyoloret_hip.so ABI version mismatch')
         L.yr_abi_sizeof.argtypes = [ctypes.c_int]
@@ -751,7 +759,82 @@ def bn_act_backward(da, u, scale, act, out=None):
     return out
 
 
-VOC_MAX_ROWS, VOC_MAX_GT = 4096, 512     # YR_VOC_MAX_ROWS, YR_VOC_MAX_GT of include/yoloret_hip.h
+# ----------------------------------------------------------------------------- BatchNorm in training mode (csrc/bntrain.hip)
+def bn_train_chunk(pixels, c):
+    """Pixels per workgroup of the first stage of every per-channel sum: a function of these numbers only (0: refused sizes)."""
+    return int(lib().yr_bn_train_chunk(int(pixels), int(c)))
+
+
+def bn_train_workspace_bytes(pixels, c):
+    """Bytes of workspace that ``bn_train_forward`` and ``bn_train_backward`` need (the same for both; 0: refused sizes)."""
+    return int(lib().yr_bn_train_workspace_bytes(int(pixels), int(c)))
+
+
+def _bn_train_workspace(workspace, pixels, c, dev, name):
+    need = bn_train_workspace_bytes(pixels, c)
+    if need == 0:
+        raise ValueError('%s: %d pixels of %d channels are outside the contract' % (name, pixels, c))
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev) if workspace is None else workspace
+    if not (isinstance(ws, torch.Tensor) and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.device == dev and ws.numel() >= need):
+        raise ValueError('%s: workspace must be a contiguous uint8 tensor of at least %d bytes on %s' % (name, need, dev))
+    return ws
+
+
+def bn_train_forward(z, gamma, beta, eps=1e-3, momentum=0.9, act=None, moving_mean=None, moving_var=None, out=None, workspace=None):
+    """BatchNorm on the statistics of the batch + activation (yr_bn_train_forward): z [..., C] float32, gamma / beta [C] ->
+    (a, mean, invstd) with a = act((z - mean) * invstd * gamma + beta), mean and the biased variance taken over all leading axes,
+    invstd = 1 / sqrt(var + eps); act in {None, 'relu6', 'swish'}.  moving_mean / moving_var [C] (both or neither) are updated in place:
+    moving -= (moving - batch value) * (1 - momentum), the variance the unbiased one, as Keras stores it.  workspace: a uint8 tensor of
+    at least bn_train_workspace_bytes(pixels, C) bytes (its contents do not matter); default: a fresh one.  Three launches."""
+    pixels, c = _rows(z, 'z')
+    dev = z.device
+    _bn_vec(gamma, c, dev, 'gamma')
+    _bn_vec(beta, c, dev, 'beta')
+    if (moving_mean is None) != (moving_var is None):
+        raise ValueError('bn_train_forward: moving_mean and moving_var go together')
+    if moving_mean is not None:
+        _bn_vec(moving_mean, c, dev, 'moving_mean')
+        _bn_vec(moving_var, c, dev, 'moving_var')
+    eps, momentum = float(eps), float(momentum)
+    if not (0.0 <= eps < float('inf')) or not 0.0 <= momentum <= 1.0:
+        raise ValueError('bn_train_forward: eps must be finite and >= 0 and momentum in [0, 1], not %r and %r' % (eps, momentum))
+    a = _bn_act_id(act)
+    out = _out_like(out, tuple(z.shape), dev, 'bn_train_forward')
+    ws = _bn_train_workspace(workspace, pixels, c, dev, 'bn_train_forward')
+    mean = torch.empty((c,), dtype=torch.float32, device=dev)
+    invstd = torch.empty((c,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().yr_bn_train_forward(_ptr(z), c, _ptr(gamma), _ptr(beta), pixels, c, eps, momentum, a, _ptr(out), c, _ptr(mean), _ptr(invstd),
+                                        _ptr(moving_mean), _ptr(moving_var), _ptr(ws), ws.numel(), stream_ptr(dev)))
+    return out, mean, invstd
+
+
+def bn_train_backward(da, z, gamma, beta, mean, invstd, act, need_dz=True, out=None, workspace=None):
+    """The gradients of ``bn_train_forward`` (yr_bn_train_backward): da, z [..., C], gamma / beta / mean / invstd [C] (the last two as the
+    forward returned them) -> (dz or None, dgamma, dbeta).  need_dz=False skips the elementwise pass; dgamma and dbeta are the same bits.
+    Two launches."""
+    pixels, c = _rows(da, 'da')
+    dev = da.device
+    _require_cuda_f32(z, 'z')
+    if tuple(z.shape) != tuple(da.shape) or z.device != dev:
+        raise ValueError('bn_train_backward: z %s on %s for da %s on %s' % (tuple(z.shape), z.device, tuple(da.shape), dev))
+    for t, name in ((gamma, 'gamma'), (beta, 'beta'), (mean, 'mean'), (invstd, 'invstd')):
+        _bn_vec(t, c, dev, name)
+    a = _bn_act_id(act)
+    if need_dz:
+        out = _out_like(out, tuple(da.shape), dev, 'bn_train_backward')
+    elif out is not None:
+        raise ValueError('bn_train_backward: out given with need_dz=False')
+    ws = _bn_train_workspace(workspace, pixels, c, dev, 'bn_train_backward')
+    dgamma = torch.empty((c,), dtype=torch.float32, device=dev)
+    dbeta = torch.empty((c,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().yr_bn_train_backward(_ptr(da), c, _ptr(z), c, _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(invstd), pixels, c, a, _ptr(out), c,
+                                         _ptr(dgamma), _ptr(dbeta), _ptr(ws), ws.numel(), stream_ptr(dev)))
+    return out, dgamma, dbeta
+
+
+VOC_MAX_ROWS, VOC_MAX_GT = 4096, 512    # YR_VOC_MAX_ROWS, YR_VOC_MAX_GT of include/yoloret_hip.h
 
 
 def _is_cuda_i32(t):
