@@ -17,7 +17,10 @@ Two restatements:
 * float32 with NumPy, every operation in the order the header of the library gives, one rounding each.  Its per-channel sums run
   SEQUENTIALLY in pixel order from +0 (the last row of a float32 cumsum): the least accurate order a correct kernel could use, so its
   deviation from float64, E_ref, is an honest yardstick for any chunking (max |device - ref64| / max |ref64| <= 4 E_ref + 2^-24).  On
-  data whose sums are exact in any order it is what the device must return bit for bit."""
+  data whose sums are exact in any order it is what the device must return bit for bit.
+* the same float32 text with the sums in the DEVICE'S order (``ordered_sum``, the layout paragraph of bntrain.hip restated): what the
+  device must return bit for bit on arbitrary data.  ``forward32`` / ``backward32`` take the summation as an argument (``sums=``), so
+  nothing else is stated twice."""
 import numpy as np
 import torch
 
@@ -75,6 +78,33 @@ def seq_sum(x):
     return np.cumsum(np.concatenate([np.zeros((1, x.shape[1]), F32), x]), axis=0, dtype=F32)[-1]
 
 
+def ordered_sum(x, chunk, pp):
+    """[P, C] float32 -> [C] in the order of bntrain.hip's layout paragraph: slab j is the range [j chunk, min((j + 1) chunk, P)); pixel p
+    of it belongs to lane po = (p - j chunk) % pp; a lane adds its pixels in increasing p from +0; the lanes of a channel are added in the
+    order po = 0 .. pp - 1 from +0; the slabs in index order from +0.  Every addition is one float32 rounding (three ``seq_sum``s: a range
+    is padded with +0 rows to whole steps of pp pixels, which changes no bit - a sum that starts from +0 never is -0)."""
+    x = np.ascontiguousarray(x, F32)
+    p, c = x.shape
+    chunk, pp = int(chunk), int(pp)
+    assert p >= 1 and chunk >= 1 and pp >= 1
+    chunk = min(chunk, p)          # (one range either way)
+    slabs, steps = -(-p // chunk), -(-chunk // pp)
+    rows = np.zeros((slabs, steps * pp, c), F32)
+    full = p // chunk
+    rows[:full, :chunk] = x[:full * chunk].reshape(full, chunk, c)
+    if full < slabs:
+        rows[full, :p - full * chunk] = x[full * chunk:]
+    lanes = seq_sum(rows.reshape(slabs, steps, pp * c).transpose(1, 0, 2).reshape(steps, slabs * pp * c))           # [slabs * pp * c]
+    slab = seq_sum(lanes.reshape(slabs, pp, c).transpose(1, 0, 2).reshape(pp, slabs * c))                            # [slabs * c]
+    return seq_sum(slab.reshape(slabs, c))
+
+
+def device_order(c, chunk):
+    """-> the ``sums=`` of ``forward32`` / ``backward32`` for C = c channels and the chunk the library reports: pp = 1024 // min(C, 64)"""
+    pp = 1024 // min(int(c), 64)
+    return lambda x: ordered_sum(x, chunk, pp)
+
+
 def _sigmoid32(u):
     return F32(1) / (F32(1) + np.exp(-u, dtype=F32))
 
@@ -93,14 +123,15 @@ def _xhat_u32(z, mean, invstd, gamma, beta):
     return xhat, xhat * gamma[None, :] + beta[None, :]
 
 
-def forward32(z, gamma, beta, eps=1e-3, momentum=0.9, act=None, moving_mean=None, moving_var=None):
-    """-> {a, u, xhat, mean, var, invstd[, moving_mean, moving_var]} as float32 arrays (the moving statistics are returned, not changed)"""
+def forward32(z, gamma, beta, eps=1e-3, momentum=0.9, act=None, moving_mean=None, moving_var=None, sums=seq_sum):
+    """-> {a, u, xhat, mean, var, invstd[, moving_mean, moving_var]} as float32 arrays (the moving statistics are returned, not changed);
+    sums: the per-channel summation [P, C] -> [C] (``seq_sum``, or ``device_order(C, chunk)`` for the device's own order)"""
     z, gamma, beta = (np.ascontiguousarray(v, F32) for v in (z, gamma, beta))
     n = z.shape[0]
     fn = F32(n)
-    mean = seq_sum(z) / fn
+    mean = sums(z) / fn
     d = z - mean[None, :]
-    var = seq_sum(d * d) / fn
+    var = sums(d * d) / fn
     invstd = F32(1) / np.sqrt(var + F32(eps))
     xhat, u = _xhat_u32(z, mean, invstd, gamma, beta)
     out = {'a': _act32(u, act), 'u': u, 'xhat': xhat, 'mean': mean, 'var': var, 'invstd': invstd}
@@ -127,14 +158,14 @@ def act_grad32(da, u, act):
     return da
 
 
-def backward32(da, z, gamma, beta, mean, invstd, act=None):
-    """-> (dz, dgamma, dbeta) as float32 arrays; mean and invstd as the forward returned them"""
+def backward32(da, z, gamma, beta, mean, invstd, act=None, sums=seq_sum):
+    """-> (dz, dgamma, dbeta) as float32 arrays; mean and invstd as the forward returned them; sums as in ``forward32``"""
     da, z, gamma, beta, mean, invstd = (np.ascontiguousarray(v, F32) for v in (da, z, gamma, beta, mean, invstd))
     fn = F32(z.shape[0])
     xhat, u = _xhat_u32(z, mean, invstd, gamma, beta)
     g = act_grad32(da, u, act)
-    dbeta = seq_sum(g)
-    dgamma = seq_sum(g * xhat)
+    dbeta = sums(g)
+    dgamma = sums(g * xhat)
     mg, mgx = dbeta / fn, dgamma / fn
     dz = ((g - mg[None, :]) - xhat * mgx[None, :]) * (gamma * invstd)[None, :]
     assert dz.dtype == F32 and dgamma.dtype == F32 and dbeta.dtype == F32

@@ -219,3 +219,143 @@ def test_gpu_cases_reach_what_they_claim():
         z, gamma, beta, da = g.rounding_case(pixels, c)
         u = ref.forward64(z, gamma, beta, 1e-3)['u']
         assert min(np.abs(u).min(), np.abs(u - 6).min()) > 1e-6 and np.abs(u).max() < 87
+
+
+# ----------------------------------------------------------------------------- the device-order restatement
+def test_ordered_sum_by_hand():
+    """5 pixels, chunk 3, pp 2: slab 0 = pixels 0..2, lane 0 takes pixels 0 and 2, lane 1 pixel 1; slab 1 = pixels 3, 4, a lane each.
+    x = (2^24, 1, 1, 1, 1): lane 0 of slab 0 = 2^24 + 1 -> 2^24 (the tie goes to even), + lane 1's 1 -> 2^24 again; slab 1 = 1 + 1 = 2;
+    total 2^24 + 2.  The sequential sum stays at 2^24 (four times + 1, each lost), float64 gives 2^24 + 4.
+    x = (1, 2^24, 1, 1, -2^24) in channel 1: lane 0 = 1 + 1 = 2, lane 1 = 2^24; slab 0 = 2 + 2^24 = 2^24 + 2; slab 1 = 1 - 2^24;
+    1 - 2^24 is exact (2^24 - 1 fits), the total (2^24 + 2) + (1 - 2^24) = 3, as in float64.  In sequence: 1 + 2^24 -> 2^24, + 1 and + 1
+    lost, - 2^24: 0."""
+    big = 2.0 ** 24
+    x = np.array([[big, 1], [1, big], [1, 1], [1, 1], [1, -big]], F32)
+    got = ref.ordered_sum(x, 3, 2)
+    assert got.dtype == F32 and got[0] == big + 2 and got[1] == 3
+    seq = ref.seq_sum(x)
+    assert seq[0] == big and seq[1] == 0
+    assert float(x[:, 0].astype(np.float64).sum()) == big + 4 and float(x[:, 1].astype(np.float64).sum()) == 3
+    # one lane, one slab: the sequential sum; starts from +0
+    assert np.array_equal(ref.ordered_sum(x, 5, 1), seq) and np.array_equal(ref.ordered_sum(x, 9, 1), seq)
+    assert not np.signbit(ref.ordered_sum(np.full((5, 2), -0.0, F32), 3, 2)).any()
+    # chunk = 1: every slab one pixel, the slabs in index order: sequential again, whatever pp
+    assert np.array_equal(ref.ordered_sum(x, 1, 4), seq)
+
+
+def test_ordered_sum_equals_the_literal_loops():
+    """the vectorised form against the three loops as the header words them, one float32 addition at a time"""
+    def literal(x, chunk, pp):
+        p, c = x.shape
+        total = np.zeros(c, F32)
+        for j in range(-(-p // chunk)):
+            lo, hi = j * chunk, min((j + 1) * chunk, p)
+            lanes = np.zeros((pp, c), F32)
+            for q in range(lo, hi):
+                lanes[(q - lo) % pp] = lanes[(q - lo) % pp] + x[q]
+            slab = np.zeros(c, F32)
+            for po in range(pp):
+                slab = slab + lanes[po]
+            total = total + slab
+        return total
+    rng = np.random.default_rng(0)
+    for p, c, chunk, pp in ((1, 1, 5, 3), (17, 3, 5, 2), (100, 4, 7, 16), (1000, 5, 129, 16), (999, 2, 37, 341), (50, 3, 50, 4), (64, 2, 16, 16), (33, 1, 8, 1024)):
+        x = (50 + rng.standard_normal((p, c))).astype(F32)
+        assert np.array_equal(ref.ordered_sum(x, chunk, pp).view(np.uint32), literal(x, chunk, pp).view(np.uint32)), (p, c, chunk, pp)
+
+
+def test_ordered_sum_against_the_other_sums():
+    from tests import test_gpu_bntrain as g
+    rng = np.random.default_rng(3)
+    x = rng.standard_normal((1000, 7)).astype(F32)
+    for chunk in (1000, 1001, 5000):
+        assert np.array_equal(ref.ordered_sum(x, chunk, 1).view(np.uint32), ref.seq_sum(x).view(np.uint32))
+    # exact data: any order gives the float64 sum
+    z, m, _, _, _ = g.exact_forward_case(18437, 75)
+    for chunk, pp in ((128, 16), (129, 16), (2731, 341), (18437, 1)):
+        s = ref.ordered_sum(z, chunk, pp)
+        assert np.array_equal(s.astype(np.float64), z.astype(np.float64).sum(0)) and np.array_equal(s, m * F32(18437))
+    z, _, _, da = g.exact_backward_case(1030, 3)
+    assert np.array_equal(ref.ordered_sum(da, 100, 341).astype(np.float64), da.astype(np.float64).sum(0))
+    # arbitrary data at a workload size: other bits than the sequential sum, and closer to float64
+    from yoloret_amd import runtime as rt
+    pixels, c = 43264, 75
+    chunk = rt.bn_train_chunk(pixels, c)
+    assert chunk == 169
+    z = g.rounding_case(pixels, c)[0]
+    o, s, r64 = ref.device_order(c, chunk)(z), ref.seq_sum(z), z.astype(np.float64).sum(0)
+    assert np.array_equal(o.view(np.uint32), ref.ordered_sum(z, 169, 16).view(np.uint32))
+    assert (o.view(np.uint32) != s.view(np.uint32)).any()
+    e_o, e_s = ref.rel_err(o, r64), ref.rel_err(s, r64)
+    assert e_o < e_s, (e_o, e_s)
+    # the restatements with the ordered sums: the same text, another summation
+    gamma, beta, da = g.rounding_case(pixels, c)[1:]
+    fo, fs = ref.forward32(z, gamma, beta, sums=ref.device_order(c, chunk)), ref.forward32(z, gamma, beta)
+    assert np.array_equal(fo['mean'], o / F32(pixels)) and np.array_equal(fs['mean'], s / F32(pixels))
+    bo = ref.backward32(da, z, gamma, beta, fs['mean'], fs['invstd'], 'relu6', sums=ref.device_order(c, chunk))
+    bs = ref.backward32(da, z, gamma, beta, fs['mean'], fs['invstd'], 'relu6')
+    g32 = ref.act_grad32(da, fs['u'], 'relu6')
+    assert np.array_equal(bo[2], ref.ordered_sum(g32, chunk, 16)) and np.array_equal(bs[2], ref.seq_sum(g32))
+    assert ref.rel_err(bo[0], bs[0]) < 1e-4 and (bo[0].view(np.uint32) != bs[0].view(np.uint32)).any()
+
+
+# ----------------------------------------------------------------------------- what tests/test_gpu_bntrain_slabs.py reaches
+def _define(src, name):
+    return int(re.search(r'#define %s (\d+) ' % name, src).group(1))
+
+
+def test_gpu_slab_cases_reach_what_they_claim():
+    from tests import test_gpu_bntrain as g, test_gpu_bntrain_slabs as s
+    from yoloret_amd import runtime as rt
+    src = _source()
+    tile, most, min_elems, cb_max, threads = (_define(src, n) for n in ('BT_TILE', 'BT_MAX_CHUNKS', 'BT_MIN_ELEMS', 'BT_CB', 'BT_THREADS'))
+    assert (tile, most, min_elems, cb_max, threads) == (128, 256, 8192, 64, 1024)
+    # the table of the file, number for number
+    assert s.SLAB_ROWS == [(16385, 64, 128, 129), (18437, 75, 128, 145), (32768, 64, 128, 256), (32769, 130, 129, 255), (349569, 3, 2731, 129),
+                           (699137, 3, 2732, 256), (1048577, 1, 8192, 129)]
+    for pixels, c, chunk, slabs in s.SLAB_ROWS:
+        cb = min(c, cb_max)
+        minimum = -(-min_elems // cb)
+        for p in (pixels, s.next_even(pixels)):          # the exact backward runs at the next even P: the same chunk and slab count
+            assert rt.bn_train_chunk(p, c) == chunk == max(minimum, -(-p // most))
+            assert -(-p // chunk) == slabs and rt.bn_train_workspace_bytes(p, c) == 2 * slabs * c * 4
+        assert tile < slabs <= most, 'the second BT_TILE pass of bt_slab_sum'
+    rows = s.SLAB_ROWS
+    pp = [threads // min(c, cb_max) for _, c, _, _ in rows]
+    assert pp == [16, 16, 16, 16, 341, 341, 1024]
+    assert sum(slabs == most for _, _, _, slabs in rows) >= 2 and rows[2][3] == most and rows[2][2] == min_elems // cb_max      # both tiles full
+    assert rows[0][3] - tile == 1 and rows[0][0] - (rows[0][3] - 1) * rows[0][2] == 1          # one slab in the second tile; the last range one pixel
+    assert rows[1][3] - tile == 17 and rows[1][1] - cb_max == 11                               # a group of 16 and a tail; a second block of 11
+    p, c, chunk, slabs = rows[3]
+    assert chunk > min_elems // cb_max and chunk % pp[3] and p - (slabs - 1) * chunk == 3 and c - 2 * cb_max == 2
+    assert rows[2][0] + 1 == p, 'the first pixel count whose chunk is not the minimum'
+    assert any(chunk % q for (_, _, chunk, _), q in zip(rows, pp))
+    assert rows[4][1] < cb_max and 1024 % rows[4][1] and rows[4][2] == -(-min_elems // 3)      # the flat form with idle lanes, its minimum chunk
+    assert rows[5][2] == rows[4][2] + 1 and rows[5][0] == most * rows[4][2] + 1                # the first flat count above the minimum
+    assert rows[6][1] == 1 and rows[6][2] == min_elems
+    assert [r[:2] for r in s.SAME_BYTES_ROWS] == [(32769, 130), (699137, 3)]
+    # the exact data at these sizes: every partial sum below 2^24, the mean m exactly (the three largest rows and the widest)
+    for pixels, c, _, _ in (rows[3], rows[4], rows[5], rows[6]):
+        z, m, gamma, beta, moving = g.exact_forward_case(pixels, c)
+        z64 = z.astype(np.float64)
+        assert np.array_equal(z64.sum(0), m.astype(np.float64) * pixels) and np.abs(z64).sum(0).max() < 2 ** 24
+        assert ((z64 - m[None, :]) ** 2).sum(0).max() < 2 ** 24
+        assert np.array_equal(ref.forward32(z, gamma, beta)['mean'], m)
+    for pixels, c in ((32770, 130), (699138, 3)):
+        assert (pixels, c) in [(s.next_even(p), cc) for p, cc, _, _ in rows]
+        z, gamma, beta, da = g.exact_backward_case(pixels, c)
+        f = ref.forward32(z, gamma, beta, 0.0)
+        assert np.all(f['var'] == 4) and np.all(f['invstd'] == 0.5) and np.all(np.abs(f['xhat']) == 1)
+        for act in (None, 'relu6'):
+            grad = ref.act_grad32(da, f['u'], act).astype(np.float64)
+            assert np.abs(grad).sum(0).max() < 2 ** 24          # |g| <= 4, |g xhat| = |g|: every partial sum an integer below 2^24
+            dz, dgamma, dbeta = ref.backward32(da, z, gamma, beta, f['mean'], f['invstd'], act)
+            assert np.array_equal(dbeta.astype(np.float64), grad.sum(0)) and np.array_equal(dgamma.astype(np.float64), (grad * f['xhat']).sum(0))
+    # the ordered cases: the six rounding shapes, table rows 2, 4 and 6 (counted from 1), two workload-like shapes
+    assert s.ORDERED_SHAPES == g.ROUNDING_SHAPES + [(18437, 75), (32769, 130), (699137, 3), (43264, 75), (173056, 24)]
+    assert s.WORKLOAD_LIKE == [(64 * 26 * 26, 75), (64 * 52 * 52, 24)]
+    assert rt.bn_train_chunk(43264, 75) == 169 and -(-43264 // 169) == 256
+    assert rt.bn_train_chunk(173056, 24) == 676 and -(-173056 // 676) == 256 and threads // 24 == 42 and threads - 42 * 24 == 16 and 676 % 42
+    # the autograd case
+    b, h, w, c = s.AUTOGRAD_SHAPE
+    assert b * h * w == 16530 and c == 64 and rt.bn_train_chunk(16530, 64) == 128 and -(-16530 // 128) == 130 > tile

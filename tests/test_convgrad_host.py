@@ -208,3 +208,60 @@ def test_gpu_cases_reach_what_they_claim():
             u = z.astype(np.float64) * scale + shift
             assert (u == 0).any() and ((u == 6).any() or p * c == 1)
             assert np.array_equal(u, (z * scale + shift).astype(np.float64)), 'u is exact in float32'
+
+
+# ----------------------------------------------------------------------------- what tests/test_gpu_convgrad_forms.py reaches
+def test_gpu_form_cases_reach_what_they_claim():
+    import re
+    from tests import test_gpu_convgrad_forms as f
+    from yoloret_amd import build, runtime as rt
+    src = open(os.path.join(os.path.dirname(build.__file__), 'csrc', 'convgrad.hip')).read()
+    most, min_pixels, max_t = (int(re.search(r'#define %s (\d+)\s' % n, src).group(1)) for n in ('CG_DW_MAX_CHUNKS', 'CG_DW_MIN_PIXELS', 'CG_MAX_T'))
+    assert (most, min_pixels, max_t) == (1024, 128, 5)
+    # the depthwise table, number for number
+    assert f.DW_BIG == [((1, 1024, 128, 5, 3, 1, 'same'), 1, 1024), ((1, 1025, 128, 5, 3, 1, 'same'), 2, 513), ((5, 205, 128, 5, 5, 1, 'same'), 2, 513),
+                        ((3, 1366, 128, 5, 5, 2, 'mobilenet'), 3, 683), ((3, 1366, 128, 5, 3, 2, 'same'), 3, 683),
+                        ((1, 1025, 128, 67, 3, 1, 'same'), 2, 513)]
+    out = {}
+    for shape, chunk, chunks in f.DW_BIG:
+        b, h, w, c, k, stride, padding = shape
+        pads, (oh, ow) = ref.geometry(h, w, k, stride, padding)
+        rows = b * oh
+        minimum = -(-min_pixels // ow)
+        assert rt.depthwise_wgrad_chunk(b, oh, ow, c, k) == chunk == max(minimum, -(-rows // most))
+        assert -(-rows // chunk) == chunks <= most and rt.depthwise_wgrad_workspace_bytes(b, oh, ow, c, k) == chunks * k * k * c * 4
+        assert 16 * b * oh * ow < 2 ** 24, 'integers in [-4, 4]: every partial sum is exact'
+        assert b <= 65535 and h <= 65535 and oh <= 65535
+        out[shape] = (oh, ow, rows, minimum)
+    first, second, third, fourth, fifth, sixth = (s for s, _, _ in f.DW_BIG)
+    assert out[first][2:] == (most, 1) and f.DW_BIG[0][2] == most                    # the most chunks the minimum allows: the last size of that branch
+    assert out[second][2] == most + 1 and f.DW_BIG[1][1] > out[second][3]            # one row more: the `most` branch
+    assert out[second][2] - (f.DW_BIG[1][2] - 1) * f.DW_BIG[1][1] == 1               # the last chunk one row
+    assert all(chunk > out[s][3] for s, chunk, _ in f.DW_BIG[1:]), 'every shape but the first runs the `most` branch'
+    oh, chunk = out[third][0], f.DW_BIG[2][1]                                        # 205 rows an image, chunk 2: chunk 102 = rows 204 (image 0), 205 (image 1)
+    assert oh == 205 and 102 * chunk < oh < 103 * chunk
+    for s in (fourth, fifth):
+        oh, ow, rows, minimum = out[s]
+        assert (oh, ow, rows, minimum) == (683, 64, 2049, 2) and oh % 3 and any(j * 3 < oh < (j + 1) * 3 for j in range(683))
+    assert ref.geometry(1366, 128, 5, 2, 'mobilenet')[0] == ref.geometry(1366, 128, 5, 2, 'same')[0]          # even sizes: the same pads
+    assert {(s[4], s[5]) for s in out} == {(3, 1), (5, 1), (5, 2), (3, 2)}           # all four instantiations of the partial kernel
+    assert sixth[3] > 64 and sixth[3] % 64, 'two channel blocks, the second partial'
+    assert f.DW_SAME_BYTES == f.DW_BIG[1]
+    # the test's own tensors reach the largest |dw| the bound allows for: below 2^24
+    x, taps, dy, y64, dx64, dw64 = f._big_case(second)
+    assert np.abs(dw64).max() < 2 ** 24 and np.abs(y64).max() <= 16 * 9 and np.abs(dx64).max() <= 16 * 9
+    # yr_linear_dgrad: the blockings and their wholly empty tiles
+    assert f.DGRAD_CIN == [96, 97, 144, 161, 200] and f.DGRAD_COUT == [3, 75] and f.DGRAD_PIXELS == [69, 4161]
+    assert '(t + CG_MAX_T - 1) / CG_MAX_T, ti = (t + bi - 1) / bi;' in src
+    for cin in f.DGRAD_CIN:
+        blocks, per = _blocking(cin, max_t)
+        assert (blocks, per) == f.DGRAD_BLOCKINGS[cin]
+        assert blocks * per - (cin + 15) // 16 == f.DGRAD_EMPTY_TILES[cin]
+    assert [f.DGRAD_BLOCKINGS[c] for c in f.DGRAD_CIN] == [(2, 3), (2, 4), (2, 5), (3, 4), (3, 5)]
+    assert [f.DGRAD_EMPTY_TILES[c] for c in f.DGRAD_CIN] == [0, 1, 1, 1, 2]
+    assert [(c + 15) // 16 for c in f.DGRAD_CIN] == [6, 7, 9, 11, 13]
+    from tests import test_gpu_convgrad as g
+    assert all(_blocking(cin, max_t)[0] * _blocking(cin, max_t)[1] == (cin + 15) // 16 for cin, _ in g.DGRAD_SHAPES), 'the older cases fill their blocks'
+    assert any(c % 16 == 0 for c in f.DGRAD_CIN) and any(c % 16 == 1 for c in f.DGRAD_CIN) and any(c % 4 for c in f.DGRAD_CIN)
+    assert any(c <= 64 and c % 4 for c in f.DGRAD_COUT) and any(c > 64 for c in f.DGRAD_COUT)
+    assert any(p % 64 and p > 64 for p in f.DGRAD_PIXELS) and max(f.DGRAD_PIXELS) > 64 * 64
