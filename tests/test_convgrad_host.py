@@ -143,8 +143,12 @@ def test_new_entries_are_exported_under_abi_9():
 def test_kernels_use_no_scratch():
     from yoloret_amd import build
     rows = build.kernel_resources()['convgrad.hip']
-    assert len(rows) == 5 + 3 * 4 + 1 + 2          # cg_dgrad_kernel<1..5>, three depthwise kernels x (k, stride), the slab sum, two BatchNorm kernels
+    assert len(rows) == 5 + 3 * 4 + 2          # cg_dgrad_kernel<1..5>, three depthwise kernels x (k, stride), two BatchNorm kernels
     assert all(scratch == 0 for _, _, scratch, _, _ in rows)
+    # the slab sum is the library's one stage-2 kernel, in headtrain.hip (train_common.h): no copy of it here, and it does not spill either
+    assert not any('sum_kernel' in name for name, _, _, _, _ in rows)
+    shared = [r for r in build.kernel_resources()['headtrain.hip'] if 'tc_slab_sum_kernel' in r[0]]
+    assert len(shared) == 1 and shared[0][2] == 0
 
 
 def test_depthwise_chunk_is_a_function_of_the_sizes_only():
@@ -167,11 +171,21 @@ def _blocking(n, most=5):
     return blocks, (t + blocks - 1) // blocks
 
 
+def _common_blocking_rule(src):
+    """convgrad.hip takes its blocking from train_common.h, where the rule ``_blocking`` restates is written once -> TC_MAX_T."""
+    import re
+    from yoloret_amd import build
+    common = open(os.path.join(os.path.dirname(build.__file__), 'csrc', 'train_common.h')).read()
+    assert 'const int t = (n + 15) / 16;' in common and '*blocks = (t + TC_MAX_T - 1) / TC_MAX_T;' in common and '*per = (t + *blocks - 1) / *blocks;' in common
+    assert '#include "train_common.h"' in src and 'tc_blocking(cin, &bi, &ti);' in src and '_MAX_T - 1)' not in src
+    return int(re.search(r'#define TC_MAX_T (\d+)\s', common).group(1))
+
+
 def test_gpu_cases_reach_what_they_claim():
     from tests import test_gpu_convgrad as g
     from yoloret_amd import build, runtime as rt
     src = open(os.path.join(os.path.dirname(build.__file__), 'csrc', 'convgrad.hip')).read()
-    assert '#define CG_MAX_T 5 ' in src and '#define CG_KC 64 ' in src and '(t + CG_MAX_T - 1) / CG_MAX_T, ti = (t + bi - 1) / bi;' in src
+    assert _common_blocking_rule(src) == 5 and '#define CG_KC 64 ' in src
     assert '#define CG_DW_MIN_PIXELS 128 ' in src and '#define CG_DW_WAVES 8' in src
     # the lists that row f-9 of DESIGN.md names
     assert g.DGRAD_PIXELS == [1, 3, 15, 16, 17, 69]
@@ -216,7 +230,8 @@ def test_gpu_form_cases_reach_what_they_claim():
     from tests import test_gpu_convgrad_forms as f
     from yoloret_amd import build, runtime as rt
     src = open(os.path.join(os.path.dirname(build.__file__), 'csrc', 'convgrad.hip')).read()
-    most, min_pixels, max_t = (int(re.search(r'#define %s (\d+)\s' % n, src).group(1)) for n in ('CG_DW_MAX_CHUNKS', 'CG_DW_MIN_PIXELS', 'CG_MAX_T'))
+    most, min_pixels = (int(re.search(r'#define %s (\d+)\s' % n, src).group(1)) for n in ('CG_DW_MAX_CHUNKS', 'CG_DW_MIN_PIXELS'))
+    max_t = _common_blocking_rule(src)
     assert (most, min_pixels, max_t) == (1024, 128, 5)
     # the depthwise table, number for number
     assert f.DW_BIG == [((1, 1024, 128, 5, 3, 1, 'same'), 1, 1024), ((1, 1025, 128, 5, 3, 1, 'same'), 2, 513), ((5, 205, 128, 5, 5, 1, 'same'), 2, 513),
@@ -252,7 +267,6 @@ def test_gpu_form_cases_reach_what_they_claim():
     assert np.abs(dw64).max() < 2 ** 24 and np.abs(y64).max() <= 16 * 9 and np.abs(dx64).max() <= 16 * 9
     # yr_linear_dgrad: the blockings and their wholly empty tiles
     assert f.DGRAD_CIN == [96, 97, 144, 161, 200] and f.DGRAD_COUT == [3, 75] and f.DGRAD_PIXELS == [69, 4161]
-    assert '(t + CG_MAX_T - 1) / CG_MAX_T, ti = (t + bi - 1) / bi;' in src
     for cin in f.DGRAD_CIN:
         blocks, per = _blocking(cin, max_t)
         assert (blocks, per) == f.DGRAD_BLOCKINGS[cin]

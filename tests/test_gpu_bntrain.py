@@ -236,6 +236,26 @@ def test_backward_exact_at_the_chunk_edges(dev, c):
         _check_backward_exact(dev, pixels, c, n)
 
 
+def test_backward_relu6_passes_plus_zero_outside_the_open_interval(dev):
+    """3 pixels x 5 channels, xhat = -1, 0, +1 exactly (the backward takes mean and invstd as given): u at 0 and 6 under a positive and a
+    negative gamma, a channel wholly below 0 and one wholly above 6 (negative gamma).  g is +0 there, so the sums of those two channels
+    are +0 to the bit, and everything equals the definition bit for bit."""
+    z = np.array([[-2.0, 0.0, 2.0]], F32).T + np.array([1.0, -3.0, 0.0, 2.0, -1.0], F32)[None, :]
+    mean, invstd = np.array([1.0, -3.0, 0.0, 2.0, -1.0], F32), np.full(5, 0.5, F32)
+    gamma = np.array([3.0, -3.0, 1.0, -1.0, 0.5], F32)
+    beta = np.array([3.0, 3.0, -3.0, 8.0, 2.0], F32)
+    da = np.array([[1.0, -2.0, 3.0, -4.0, 2.0], [-1.0, 2.0, -3.0, 4.0, -2.0], [2.0, 3.0, -1.0, 1.0, -3.0]], F32)
+    xhat, u = ref._xhat_u32(z, mean, invstd, gamma, beta)
+    assert np.array_equal(u.T, np.array([[0, 3, 6], [6, 3, 0], [-4, -3, -2], [9, 8, 7], [1.5, 2, 2.5]], F32))
+    outside = ~((u > 0) & (u < 6))
+    assert np.all(_bits(ref.act_grad32(da, u, 'relu6'))[outside] == 0), 'the definition itself: +0 outside'
+    want = ref.backward32(da, z, gamma, beta, mean, invstd, 'relu6')
+    dz, dgamma, dbeta = dev_backward(dev, da, z, gamma, beta, mean, invstd, 5, 'relu6', 5)
+    assert np.all(_bits(dbeta)[2:4] == 0) and np.all(_bits(dgamma)[2:4] == 0)
+    for name, got, w in (('dz', dz, want[0]), ('dgamma', dgamma, want[1]), ('dbeta', dbeta, want[2])):
+        assert np.array_equal(_bits(got), _bits(w)), name
+
+
 def one_hot_da(pixels, c, where, rng):
     """da that is nonzero at one pixel per channel: each per-channel sum has one nonzero term, exact whatever xhat is"""
     da = np.zeros((pixels, c), F32)

@@ -354,6 +354,25 @@ def test_bn_act_exact_dyadic(dev, act):
         assert np.array_equal(_bits(got.cpu().numpy()), _bits(da * scale[None, :]))
 
 
+def test_bn_act_relu6_gives_plus_zero_outside_the_open_interval(dev):
+    """dz is +0 (bit pattern 0x00000000) wherever u is not inside (0, 6): at 0, at 6, below and above, under a negative scale too.
+    (A kernel that formed g = da * act'(u) first and multiplied by the scale afterwards would write 0 * -2 = -0 there.)"""
+    u = np.array([[0.0, 6.0, -1.0, 7.0, 3.0],
+                  [6.0, 0.0, 7.0, -1.0, 0.0],
+                  [-2.5, 8.0, 0.0, 6.0, 6.0]], np.float32)
+    scale = np.array([1.0, -2.0, 0.5, 3.0, 1.5], np.float32)          # channel 1: u = 6, 0 and 8 under a negative scale
+    da = np.array([[1.0, -2.0, 3.0, -4.0, 2.0],
+                   [-1.0, 2.0, -3.0, 4.0, -2.0],
+                   [2.0, 3.0, -1.0, 1.0, -3.0]], np.float32)
+    outside = ~((u > 0) & (u < 6))
+    assert outside.sum() == 14 and not outside[0, 4]
+    want = ref.bn_act_backward(da, u, scale, 'relu6')
+    assert np.all(_bits(want)[outside] == 0) and want[0, 4] == 3.0, 'the definition itself: +0 outside'
+    dz = dev_bn_backward(dev, da, u, scale, 5, 'relu6', 5)
+    assert np.all(_bits(dz)[outside] == 0), 'bits %s' % [hex(b) for b in _bits(dz)[outside]]
+    assert np.array_equal(_bits(dz), _bits(want))
+
+
 def test_bn_act_swish_rounding(dev):
     """Standard-normal z (x 3), P = 65, C = 75.  Measured on an MI355X (device, E_ref, bar): a 8.120e-08, 8.120e-08, 3.844e-07;
     dz 2.640e-07, 2.640e-07, 1.116e-06."""

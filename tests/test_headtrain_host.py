@@ -198,9 +198,13 @@ def test_form_cases_reach_every_instantiation():
     # the restatement against the source's own words
     import os
     from yoloret_amd import build
-    src = open(os.path.join(os.path.dirname(build.__file__), 'csrc', 'headtrain.hip')).read()
-    assert '#define HT_MAX_T %d ' % forms.MAX_T in src
-    assert '*blocks = (t + HT_MAX_T - 1) / HT_MAX_T;' in src and '*per = (t + *blocks - 1) / *blocks;' in src
+    csrc = os.path.join(os.path.dirname(build.__file__), 'csrc')
+    common = open(os.path.join(csrc, 'train_common.h')).read()       # the rule is stated there, once, for headtrain.hip and convgrad.hip
+    assert '#define TC_MAX_T %d ' % forms.MAX_T in common
+    assert '*blocks = (t + TC_MAX_T - 1) / TC_MAX_T;' in common and '*per = (t + *blocks - 1) / *blocks;' in common
+    src = open(os.path.join(csrc, 'headtrain.hip')).read()
+    assert '#include "train_common.h"' in src and 'tc_blocking(cout, &bo, &to);' in src and 'tc_blocking(cin, &bi, &ti);' in src
+    assert 'HT_MAX_T' not in src and '+ 15) / 16' not in src, 'no second statement of the rule'
 
 
 def test_ragged_cases_leave_whole_tiles_out_of_range():

@@ -3,11 +3,8 @@
 // of the batch, the moving-average update, and the gradients for the input, gamma and beta.  yoloret_amd/autograd.py wires the two
 // entries into torch.autograd; tests/bntrain_ref.py is the definition (TensorFlow's fused kernel and its gradient, restated).
 //
-// Conventions (those of headtrain.hip and convgrad.hip): float32 only, wave64.  Rows are [pixels][ld] row-major, the channel the fastest
-// index, C <= ld channels taken, and only 4-byte aligned, so every global access is a dword.  No float atomics, nothing is read before
-// this call wrote it, every output element the contract names is written and nothing else (pad columns [C, ld) are neither read nor
-// written), and every chunk size is a function of the sizes only: the same call gives the same bytes.  The file is compiled with
-// -ffp-contract=off and holds no fused multiply-add: every operation below is one IEEE float32 operation, in the order written.
+// The conventions are those of train_common.h.  This file holds no fused multiply-add: every operation below is one IEEE float32
+// operation, in the order written.
 //
 // Arithmetic (N = pixels):
 //   mean = (sum_p z) / (float)N;  var = (sum_p (z - mean)^2) / (float)N, the deviations about the finished mean (a second read of z; never
@@ -30,8 +27,7 @@
 //             [var, invstd from the slabs] a = act(...), chunk 0 writes invstd and the moving statistics.
 //   backward  2 launches: sums of g and g * xhat -> slabs;  [dbeta, dgamma from the slabs] dz, chunk 0 writes dgamma and dbeta.
 //             With dz == null the second launch only adds the slabs.
-#include "yr_common.h"
-#include <limits.h>
+#include "train_common.h"
 #include <math.h>
 
 #define BT_THREADS 1024         // lanes per workgroup: 16 waves, so that the at most 256 ranges of a map still fill the machine
@@ -46,16 +42,11 @@ struct bt_geo {
     float fn;      // (float)pixels
 };
 
-static inline bool bt_rows_fit(long long pixels, int ld) { return pixels <= (LLONG_MAX / 4) / ld; }
-static inline bool bt_act_ok(int act) { return act == YR_ACT_NONE || act == YR_ACT_RELU6 || act == YR_ACT_SWISH; }
 static inline bool bt_sizes_ok(long long pixels, int C) { return pixels >= 1 && pixels < (1ll << 40) && C >= 1 && C <= INT_MAX - BT_CB; }
 
 static inline long long bt_chunk(long long pixels, int C) {
     const int cb = C < BT_CB ? C : BT_CB;
-    long long c = (BT_MIN_ELEMS + cb - 1) / cb;
-    const long long slabs = pixels < (1ll << 38) ? BT_MAX_CHUNKS : 1024;
-    const long long most = (pixels + slabs - 1) / slabs;
-    return c < most ? most : c;
+    return tc_chunk(pixels, (BT_MIN_ELEMS + cb - 1) / cb, pixels < (1ll << 38) ? BT_MAX_CHUNKS : 1024);
 }
 
 static inline bt_geo bt_make_geo(long long pixels, int C) {
@@ -163,14 +154,8 @@ __device__ __forceinline__ float bt_invstd(float var, float eps) { return 1.0f /
 
 // g = da * act'(u)
 __device__ __forceinline__ float bt_act_grad(float da, float u, int act) {
-    if (act == YR_ACT_RELU6) return (u > 0.0f && u < 6.0f) ? da : 0.0f;
-    if (act == YR_ACT_SWISH) {
-        const float sg = yr_sigmoid(u);
-        const float t1 = 1.0f - sg;
-        const float t2 = u * t1;
-        const float t3 = 1.0f + t2;
-        return da * (sg * t3);
-    }
+    if (act == YR_ACT_RELU6) return tc_relu6_open(u) ? da : 0.0f;
+    if (act == YR_ACT_SWISH) return da * tc_swish_grad(u);
     return da;
 }
 
@@ -335,11 +320,8 @@ __global__ __launch_bounds__(BT_THREADS) void bt_bwd_finish_kernel(bt_geo g, con
 // ---------------------------------------------------------------- entries
 static int bt_check_common(const char* who, long long pixels, int C, int act, void* workspace, size_t workspace_bytes) {
     YR_REQUIRE(bt_sizes_ok(pixels, C), "%s: pixels must be 1..2^40-1 and C positive (pixels %lld, C %d)", who, pixels, C);
-    YR_REQUIRE(bt_act_ok(act), "%s: act %d is not none, ReLU6 or Swish", who, act);
-    const size_t need = yr_bn_train_workspace_bytes(pixels, C);
-    YR_REQUIRE(workspace && need && workspace_bytes >= need, "%s: workspace null or of %zu bytes, %zu needed", who, workspace_bytes, need);
-    YR_REQUIRE(((uintptr_t)workspace) % 16 == 0, "%s: workspace not 16-byte aligned", who);
-    return YR_OK;
+    YR_REQUIRE(tc_act_ok(act), "%s: act %d is not none, ReLU6 or Swish", who, act);
+    return tc_workspace_check(who, workspace, workspace_bytes, yr_bn_train_workspace_bytes(pixels, C));
 }
 
 extern "C" int yr_bn_train_forward(const float* z, int z_ld, const float* gamma, const float* beta, long long pixels, int C, float eps, float momentum,
@@ -352,7 +334,7 @@ extern "C" int yr_bn_train_forward(const float* z, int z_ld, const float* gamma,
     YR_REQUIRE(eps >= 0.0f && eps < INFINITY, "bn_train_forward: eps must be finite and not negative (%g)", (double)eps);
     YR_REQUIRE(momentum >= 0.0f && momentum <= 1.0f, "bn_train_forward: momentum must lie in [0, 1] (%g)", (double)momentum);
     YR_REQUIRE(z_ld >= C && a_ld >= C, "bn_train_forward: a leading dimension below C = %d", C);
-    YR_REQUIRE(bt_rows_fit(pixels, z_ld) && bt_rows_fit(pixels, a_ld), "bn_train_forward: byte offsets beyond 2^63");
+    YR_REQUIRE(tc_rows_fit(pixels, z_ld) && tc_rows_fit(pixels, a_ld), "bn_train_forward: byte offsets beyond 2^63");
     YR_REQUIRE(((uintptr_t)z | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)a | (uintptr_t)mean | (uintptr_t)invstd | (uintptr_t)moving_mean |
                 (uintptr_t)moving_var) % 4 == 0, "bn_train_forward: pointer not 4-byte aligned");
     const bt_geo g = bt_make_geo(pixels, C);
@@ -378,7 +360,7 @@ extern "C" int yr_bn_train_backward(const float* da, int da_ld, const float* z, 
     const int rc = bt_check_common("bn_train_backward", pixels, C, act, workspace, workspace_bytes);
     if (rc != YR_OK) return rc;
     YR_REQUIRE(da_ld >= C && z_ld >= C && (!dz || dz_ld >= C), "bn_train_backward: a leading dimension below C = %d", C);
-    YR_REQUIRE(bt_rows_fit(pixels, da_ld) && bt_rows_fit(pixels, z_ld) && (!dz || bt_rows_fit(pixels, dz_ld)), "bn_train_backward: byte offsets beyond 2^63");
+    YR_REQUIRE(tc_rows_fit(pixels, da_ld) && tc_rows_fit(pixels, z_ld) && (!dz || tc_rows_fit(pixels, dz_ld)), "bn_train_backward: byte offsets beyond 2^63");
     YR_REQUIRE(((uintptr_t)da | (uintptr_t)z | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)mean | (uintptr_t)invstd | (uintptr_t)dz |
                 (uintptr_t)dgamma | (uintptr_t)dbeta) % 4 == 0, "bn_train_backward: pointer not 4-byte aligned");
     const bt_geo g = bt_make_geo(pixels, C);

@@ -3,14 +3,11 @@
 // gradients, and the frozen BatchNorm + activation with its input gradient.  yoloret_amd/autograd.py wires them into torch.autograd;
 // tests/convgrad_ref.py is the definition (the reference has no backward code of its own: TensorFlow's tape provides it).
 //
-// Conventions (those of headtrain.hip): float32 only, wave64.  Rows are row-major over pixels with a leading dimension in floats and
-// are only 4-byte aligned, so every global access is a dword.  No float atomics, nothing is read before this call wrote it, every
-// output element the contract names is written and nothing else, and every chunk size is a function of the sizes only: the same
-// call gives the same bytes.  The file is compiled with -ffp-contract=off; every fused multiply-add below is an explicit fmaf / MFMA.
+// The conventions are those of train_common.h.
 //
 // yr_linear_dgrad: dx[p][ci] = sum_co dy[p][co] * wt[co][ci], wt = Wt[cout][kp] as yr_linear_forward reads it (pad columns not read).
-//   v_mfma_f32_16x16x4_f32 (float32 operands and accumulation, for the reason headtrain.hip gives).  A workgroup of 4 waves owns 64
-//   pixels and up to 5 tiles of 16 input channels; each wave 16 pixels.  Wt is the B operand in its natural layout: lane l holds
+//   On the float32 matrix pipe.  A workgroup of 4 waves owns 64 pixels and up to TC_MAX_T = 5 tiles of 16 input channels (tc_blocking);
+//   each wave 16 pixels.  Wt is the B operand in its natural layout: lane l holds
 //   wt[4 s + (l >> 4)][ci0 + (l & 15)], 64 contiguous bytes per sixteen lanes.  The A operand dy[p0 + (l & 15)][4 s + (l >> 4)] would be
 //   a 16-byte gather per row straight from memory (the weakness of yr_linear_forward), so dy passes through LDS: per 64 output
 //   channels a wave reads its 16 rows with 64 lanes along the row (256 contiguous bytes an instruction) into rows of 68 floats
@@ -32,27 +29,21 @@
 //   wgrad    dw[t][c] = sum_{b, oy, ox} dy[b][oy][ox][c] * x[b][oy s - pt + ty][ox s - pl + tx][c] over in-range positions, two stages
 //            like yr_linear_wgrad: stage 1, workgroup (chunk j, 64 channels): lane = channel, wave w of 8 takes the pixels w, w + 8, ... of
 //            the chunk's output rows [j * chunk, (j + 1) * chunk) of the B * OH rows, k * k accumulators in registers; the waves' sums
-//            are added in LDS in wave order and one [k * k][C] slab is written.  Stage 2 adds the slabs in index order and writes every
-//            dw element.  chunk = yr_depthwise_wgrad_chunk(B, OH, OW, C, k) rows.
+//            are added in LDS in wave order and one [k * k][C] slab is written.  Stage 2 (yr_launch_slab_sum) adds the slabs in index
+//            order and writes every dw element.  chunk = yr_depthwise_wgrad_chunk(B, OH, OW, C, k) rows.
 //
 // yr_bn_act_forward: u = z * scale[c] + shift[c] (a float32 multiply, then a float32 add), a = act(u) with act in {none, ReLU6, Swish}
 // (yr_apply_act of yr_common.h); u is stored as well when asked for.  yr_bn_act_backward: dz = (da * act'(u)) * scale[c];
-// ReLU6: act' = 1 where 0 < u < 6, both strict (TensorFlow's Relu6Grad), dz = +0 elsewhere; Swish: act' = sg * (1 + u * (1 - sg)),
-// sg = yr_sigmoid(u).  scale and shift are frozen: no gradient for them.
-#include "yr_common.h"
-#include <limits.h>
+// act' as train_common.h states it; ReLU6: dz = +0 outside the open interval, whatever the scale.  scale and shift are frozen: no
+// gradient for them.
+#include "train_common.h"
 
-typedef float cg_f4 __attribute__((ext_vector_type(4)));
-
-#define CG_MAX_T 5            // 16-channel tiles per workgroup of the 1x1 input gradient (as HT_MAX_T)
 #define CG_KC 64              // output channels per LDS pass
 #define CG_LDS_LD 68          // floats per LDS row: 64 + 4, conflict-free for the A reads
 #define CG_DW_NX 4             // output columns per lane of the stride-1 depthwise forward and input gradient
 #define CG_DW_WAVES 8
 #define CG_DW_MIN_PIXELS 128  // output pixels per workgroup of the depthwise weight gradient, at least
 #define CG_DW_MAX_CHUNKS 1024
-
-static inline bool cg_rows_fit(long long pixels, int ld) { return pixels <= (LLONG_MAX / 4) / ld; }
 
 // ---------------------------------------------------------------- 1x1: the input gradient
 template <int NT>
@@ -66,9 +57,9 @@ __global__ __launch_bounds__(256) void cg_dgrad_kernel(const float* __restrict__
     bool cok[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) cok[t] = ci0 + 16 * t + l15 < cin;
-    cg_f4 acc[NT];
+    tc_f4 acc[NT];
 #pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = (cg_f4){0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < NT; ++t) acc[t] = (tc_f4){0.f, 0.f, 0.f, 0.f};
     float* mine = tile[wave];
     for (int c0 = 0; c0 < cout; c0 += CG_KC) {
         if (c0) __syncthreads();      // the previous pass has been read
@@ -107,12 +98,13 @@ extern "C" int yr_linear_dgrad(const float* dy, int dy_ld, const float* wt, long
     YR_REQUIRE(pixels >= 1 && pixels < (1ll << 40) && cin >= 1 && cin <= 256 && cout >= 1 && cout <= 256,
                "linear_dgrad: pixels must be 1..2^40-1 and cin, cout 1..256 (pixels %lld, cin %d, cout %d)", pixels, cin, cout);
     YR_REQUIRE(dy_ld >= cout && dx_ld >= cin, "linear_dgrad: dy_ld %d < cout %d or dx_ld %d < cin %d", dy_ld, cout, dx_ld, cin);
-    YR_REQUIRE(cg_rows_fit(pixels, dy_ld) && cg_rows_fit(pixels, dx_ld), "linear_dgrad: byte offsets beyond 2^63");
+    YR_REQUIRE(tc_rows_fit(pixels, dy_ld) && tc_rows_fit(pixels, dx_ld), "linear_dgrad: byte offsets beyond 2^63");
     YR_REQUIRE(((uintptr_t)dy | (uintptr_t)wt | (uintptr_t)dx) % 4 == 0, "linear_dgrad: dy, wt or dx not 4-byte aligned");
     const long long blocks = (pixels + 63) / 64;
     YR_REQUIRE(blocks <= INT_MAX, "linear_dgrad: more than 2^37 pixels");
     const int kp = yr_round_up(cin, 4);
-    const int t = (cin + 15) / 16, bi = (t + CG_MAX_T - 1) / CG_MAX_T, ti = (t + bi - 1) / bi;
+    int bi, ti;
+    tc_blocking(cin, &bi, &ti);
     const dim3 grid((unsigned)blocks, bi);
     hipStream_t s = (hipStream_t)stream;
 #define CG_CASE(T) \
@@ -278,11 +270,7 @@ __global__ __launch_bounds__(256) void cg_dw_dgrad_x4_kernel(const float* __rest
 
 // output rows (of the B * OH) per workgroup of stage 1
 static inline int cg_dw_chunk(int B, int OH, int OW) {
-    const long long rows = (long long)B * OH;
-    long long c = (CG_DW_MIN_PIXELS + OW - 1) / OW;
-    const long long most = (rows + CG_DW_MAX_CHUNKS - 1) / CG_DW_MAX_CHUNKS;
-    if (c < most) c = most;
-    return (int)c;
+    return (int)tc_chunk((long long)B * OH, (CG_DW_MIN_PIXELS + OW - 1) / OW, CG_DW_MAX_CHUNKS);
 }
 
 static inline bool cg_dw_sizes_ok(int B, int OH, int OW, int C, int k) {
@@ -350,15 +338,6 @@ __global__ __launch_bounds__(64 * CG_DW_WAVES) void cg_dw_wgrad_partial_kernel(c
     }
 }
 
-__global__ __launch_bounds__(256) void cg_dw_wgrad_sum_kernel(const float* __restrict__ slabs, int nchunks, int n, float* __restrict__ dw) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= n) return;
-    const float* s = slabs + e;
-    float v = s[0];
-    for (int j = 1; j < nchunks; ++j) v += s[(size_t)j * n];
-    dw[e] = v;
-}
-
 #define CG_DW_DISPATCH(KERNEL, grid, block, ...)                                                                  \
     do {                                                                                                          \
         if (k == 3 && stride == 1) hipLaunchKernelGGL((KERNEL<3, 1>), grid, block, 0, s, __VA_ARGS__);             \
@@ -415,9 +394,8 @@ extern "C" int yr_depthwise_wgrad(const float* x, int x_ld, const float* dy, int
     YR_REQUIRE(((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dw) % 4 == 0, "depthwise_wgrad: x, dy or dw not 4-byte aligned");
     const int rc = cg_dw_check("depthwise_wgrad", B, H, W, C, k, stride, pad_top, pad_left, OH, OW, x_ld, dy_ld);
     if (rc != YR_OK) return rc;
-    const size_t need = yr_depthwise_wgrad_workspace_bytes(B, OH, OW, C, k);
-    YR_REQUIRE(need && workspace_bytes >= need, "depthwise_wgrad: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-    YR_REQUIRE(((uintptr_t)workspace) % 16 == 0, "depthwise_wgrad: workspace not 16-byte aligned");
+    const int wrc = tc_workspace_check("depthwise_wgrad", workspace, workspace_bytes, yr_depthwise_wgrad_workspace_bytes(B, OH, OW, C, k));
+    if (wrc != YR_OK) return wrc;
     const int chunk = cg_dw_chunk(B, OH, OW);
     const int nchunks = (int)(((long long)B * OH + chunk - 1) / chunk);
     const cg_dw d = {B, H, W, C, OH, OW, pad_top, pad_left, x_ld, dy_ld};
@@ -425,15 +403,10 @@ extern "C" int yr_depthwise_wgrad(const float* x, int x_ld, const float* dy, int
     hipStream_t s = (hipStream_t)stream;
     CG_DW_DISPATCH(cg_dw_wgrad_partial_kernel, dim3(nchunks, (C + 63) / 64), dim3(64 * CG_DW_WAVES), x, dy, slabs, d, chunk);
     YR_LAUNCH_CHECK();
-    const int n = k * k * C;
-    hipLaunchKernelGGL(cg_dw_wgrad_sum_kernel, dim3((n + 255) / 256), dim3(256), 0, s, slabs, nchunks, n, dw);
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+    return yr_launch_slab_sum(slabs, nchunks, k * k, C, C, dw, s);
 }
 
 // ---------------------------------------------------------------- frozen BatchNorm + activation
-static inline bool cg_act_ok(int act) { return act == YR_ACT_NONE || act == YR_ACT_RELU6 || act == YR_ACT_SWISH; }
-
 __global__ __launch_bounds__(256) void cg_bn_act_forward_kernel(const float* __restrict__ z, long long z_ld, const float* __restrict__ scale,
                                                                const float* __restrict__ shift, long long n, int C, int act, float* __restrict__ a,
                                                                long long a_ld, float* __restrict__ u, long long u_ld) {
@@ -460,16 +433,8 @@ __global__ __launch_bounds__(256) void cg_bn_act_backward_kernel(const float* __
         r = g * sc;
     } else {
         const float uv = u[p * u_ld + c];
-        if (act == YR_ACT_RELU6) {
-            r = (uv > 0.0f && uv < 6.0f) ? g * sc : 0.0f;
-        } else {
-            const float sg = yr_sigmoid(uv);
-            const float t1 = 1.0f - sg;
-            const float t2 = uv * t1;
-            const float t3 = 1.0f + t2;
-            const float dv = sg * t3;
-            r = (g * dv) * sc;
-        }
+        if (act == YR_ACT_RELU6) r = tc_relu6_open(uv) ? g * sc : 0.0f;      // (the select around the product: +0 outside, whatever sc)
+        else r = (g * tc_swish_grad(uv)) * sc;
     }
     dz[p * dz_ld + c] = r;
 }
@@ -477,10 +442,10 @@ __global__ __launch_bounds__(256) void cg_bn_act_backward_kernel(const float* __
 extern "C" int yr_bn_act_forward(const float* z, int z_ld, const float* scale, const float* shift, long long pixels, int C, int act, float* a,
                                  int a_ld, float* u, int u_ld, void* stream) {
     YR_REQUIRE(z && scale && shift && a, "bn_act_forward: null pointer");
-    YR_REQUIRE(cg_act_ok(act), "bn_act_forward: act %d is not none, ReLU6 or Swish", act);
+    YR_REQUIRE(tc_act_ok(act), "bn_act_forward: act %d is not none, ReLU6 or Swish", act);
     YR_REQUIRE(pixels >= 1 && pixels < (1ll << 40) && C >= 1, "bn_act_forward: pixels must be 1..2^40-1 and C positive (pixels %lld, C %d)", pixels, C);
     YR_REQUIRE(z_ld >= C && a_ld >= C && (!u || u_ld >= C), "bn_act_forward: a leading dimension below C = %d", C);
-    YR_REQUIRE(cg_rows_fit(pixels, z_ld) && cg_rows_fit(pixels, a_ld) && (!u || cg_rows_fit(pixels, u_ld)), "bn_act_forward: byte offsets beyond 2^63");
+    YR_REQUIRE(tc_rows_fit(pixels, z_ld) && tc_rows_fit(pixels, a_ld) && (!u || tc_rows_fit(pixels, u_ld)), "bn_act_forward: byte offsets beyond 2^63");
     YR_REQUIRE(((uintptr_t)z | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)a | (uintptr_t)u) % 4 == 0, "bn_act_forward: pointer not 4-byte aligned");
     const long long n = pixels * C;
     YR_REQUIRE((n + 255) / 256 <= INT_MAX, "bn_act_forward: more than 2^39 elements");
@@ -493,10 +458,10 @@ extern "C" int yr_bn_act_forward(const float* z, int z_ld, const float* scale, c
 extern "C" int yr_bn_act_backward(const float* da, int da_ld, const float* u, int u_ld, const float* scale, long long pixels, int C, int act,
                                   float* dz, int dz_ld, void* stream) {
     YR_REQUIRE(da && scale && dz && (u || act == YR_ACT_NONE), "bn_act_backward: null pointer");
-    YR_REQUIRE(cg_act_ok(act), "bn_act_backward: act %d is not none, ReLU6 or Swish", act);
+    YR_REQUIRE(tc_act_ok(act), "bn_act_backward: act %d is not none, ReLU6 or Swish", act);
     YR_REQUIRE(pixels >= 1 && pixels < (1ll << 40) && C >= 1, "bn_act_backward: pixels must be 1..2^40-1 and C positive (pixels %lld, C %d)", pixels, C);
     YR_REQUIRE(da_ld >= C && dz_ld >= C && (!u || u_ld >= C), "bn_act_backward: a leading dimension below C = %d", C);
-    YR_REQUIRE(cg_rows_fit(pixels, da_ld) && cg_rows_fit(pixels, dz_ld) && (!u || cg_rows_fit(pixels, u_ld)), "bn_act_backward: byte offsets beyond 2^63");
+    YR_REQUIRE(tc_rows_fit(pixels, da_ld) && tc_rows_fit(pixels, dz_ld) && (!u || tc_rows_fit(pixels, u_ld)), "bn_act_backward: byte offsets beyond 2^63");
     YR_REQUIRE(((uintptr_t)da | (uintptr_t)u | (uintptr_t)scale | (uintptr_t)dz) % 4 == 0, "bn_act_backward: pointer not 4-byte aligned");
     const long long n = pixels * C;
     YR_REQUIRE((n + 255) / 256 <= INT_MAX, "bn_act_backward: more than 2^39 elements");

@@ -3,11 +3,10 @@
 // does for these layers between the features and optimizer.apply_gradients, with the body frozen (code/train.py:150-171, "Train with
 // frozen layers first"; ModelFactory.build carries the freeze commented out, so the frozen-body stage is build-defined).
 //
-// Rows are float32, row-major over pixels: x [P][x_ld] (cin taken), dy / y [P][ld] (cout taken), P = B * H * W.  Weights are
-// Wt[cout][kp], kp = round_up(cin, 4), the layout YR_OP_POINTWISE documents.  Rows are only 4-byte aligned (a dense 75-float
-// row), so every global access is a dword.  All products run on the float32 matrix pipe (v_mfma_f32_16x16x4_f32: float32
-// operands, float32 accumulation; the float16-plane split of the forward kernels is not used: a gradient summed over 10^5 pixels
-// should not inherit a 2^-22 operand cut).
+// The conventions are those of train_common.h.  Rows: x [P][x_ld] (cin taken), dy / y [P][ld] (cout taken), P = B * H * W.  Weights
+// are Wt[cout][kp], kp = round_up(cin, 4), the layout YR_OP_POINTWISE documents.  All products run on the float32 matrix pipe
+// (the float16-plane split of the forward kernels is not used: a gradient summed over 10^5 pixels should not inherit a 2^-22
+// operand cut).
 //
 // yr_linear_wgrad: dWt[co][ci] = sum_p dy[p][co] * x[p][ci].  Both operands load in their natural layout: for a quartet of pixels
 // p0..p0+3, lane l holds A = dy[p0 + (l >> 4)][co0 + (l & 15)] and B = x[p0 + (l >> 4)][ci0 + (l & 15)] (A[i][k] with i the output
@@ -18,10 +17,9 @@
 //            tiles of 16 x 16.  Its 4 waves take chunk / 4 consecutive pixels each, keep all tiles in registers (5 x 5 tiles = 100
 //            VGPRs: x and dy are read once at 75 x 75), then add their tiles in LDS in wave order and write one partial
 //            [cout][kp] slab to the workspace.  cin or cout above 80: the tiles are blocked over the grid (operands re-read).
-//   stage 2  ht_wgrad_sum_kernel: one lane per element of dWt adds the slabs in index order and writes EVERY element, pad columns
-//            as +0.
-// chunk depends on (pixels, cin, cout) only - never on the device, the CU count or a tuner -, there are no float atomics and
-// nothing in the workspace is read before this call wrote it: the same call gives the same bytes.
+//   stage 2  yr_launch_slab_sum (tc_slab_sum_kernel, below; the depthwise weight gradient of convgrad.hip ends in it too): one lane
+//            per element of dWt adds the slabs in index order and writes EVERY element, pad columns as +0.
+// chunk depends on (pixels, cin, cout) only.
 //
 // yr_linear_forward: y[p][co] = sum_k x[p][k] * wt[co][k].  One wave per 16 pixels and up to 5 tiles of 16 output channels; lane l
 // holds A = x[p0 + (l & 15)][4 s + (l >> 4)] and B = wt[co0 + (l & 15)][4 s + (l >> 4)] in step s.  Every y[p][0..cout) is written
@@ -31,34 +29,23 @@
 //   m = b1 * m + (1 - b1) * g;  v = b2 * v + (1 - b2) * (g * g);  w = w - alpha * m / (sqrt(v) + eps)
 // 1 - b1 and 1 - b2 are formed once in float32 (on the host, the same IEEE subtraction); sqrt and the division are the
 // correctly rounded ones.  TF 2.x OptimizerV2 Adam without amsgrad, restated; tests/headtrain_ref.py is the definition.
-#include "yr_common.h"
-#include <limits.h>
+#include "train_common.h"
 
 #define HT_WAVES 4          // waves per workgroup of the gradient's stage 1
 #define HT_U 2              // quartets of pixels a wave loads at a time
-#define HT_MAX_T 5          // 16 x 16 tiles per wave and side: 5 x 5 accumulators = 100 VGPRs
 #define HT_MIN_CHUNK 256
 #define HT_MAX_CHUNKS 2048
-
-typedef float ht_f4 __attribute__((ext_vector_type(4)));
 
 static inline bool ht_sizes_ok(long long pixels, int cin, int cout) {
     return pixels >= 1 && pixels < (1ll << 40) && cin >= 1 && cin <= 256 && cout >= 1 && cout <= 256;
 }
 
 // pixels per workgroup of stage 1: a multiple of 4 * HT_WAVES, so every wave starts on a quartet
+// (the minimum is itself such a multiple, so rounding after the clamp is rounding before it)
 static inline int ht_chunk(long long pixels, int cin, int cout) {
-    long long c = (pixels + HT_MAX_CHUNKS - 1) / HT_MAX_CHUNKS;
-    c = (c + 4 * HT_WAVES - 1) / (4 * HT_WAVES) * (4 * HT_WAVES);
-    const long long lo = (cin > 16 * HT_MAX_T || cout > 16 * HT_MAX_T) ? 2 * HT_MIN_CHUNK : HT_MIN_CHUNK;   // blocked tiles: larger slabs
-    return (int)(c < lo ? lo : c);
-}
-
-// tiles of 16 -> (blocks, tiles per block <= HT_MAX_T)
-static inline void ht_blocking(int n, int* blocks, int* per) {
-    const int t = (n + 15) / 16;
-    *blocks = (t + HT_MAX_T - 1) / HT_MAX_T;
-    *per = (t + *blocks - 1) / *blocks;
+    const long long lo = (cin > 16 * TC_MAX_T || cout > 16 * TC_MAX_T) ? 2 * HT_MIN_CHUNK : HT_MIN_CHUNK;   // blocked tiles: larger slabs
+    const long long c = tc_chunk(pixels, lo, HT_MAX_CHUNKS);
+    return (int)((c + 4 * HT_WAVES - 1) / (4 * HT_WAVES) * (4 * HT_WAVES));
 }
 
 extern "C" int yr_linear_wgrad_chunk(long long pixels, int cin, int cout) {
@@ -93,11 +80,11 @@ __global__ __launch_bounds__(64 * HT_WAVES, 3) void ht_wgrad_partial_kernel(cons
     for (int t = 0; t < TCI; ++t) bok[t] = ci0 + 16 * t + l15 < cin;
     long long aoff = (p + g) * dy_ld + co0 + l15, boff = (p + g) * x_ld + ci0 + l15;      // element offsets of this lane's pixel row
 
-    ht_f4 acc[TCO][TCI];
+    tc_f4 acc[TCO][TCI];
 #pragma unroll
     for (int i = 0; i < TCO; ++i)
 #pragma unroll
-        for (int j = 0; j < TCI; ++j) acc[i][j] = (ht_f4){0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < TCI; ++j) acc[i][j] = (tc_f4){0.f, 0.f, 0.f, 0.f};
 
     float a[HT_U][TCO], b[HT_U][TCI];
     auto load = [&](float* av, float* bv, bool rowok, int q) {      // quartet q behind the current one
@@ -172,17 +159,25 @@ __global__ __launch_bounds__(64 * HT_WAVES, 3) void ht_wgrad_partial_kernel(cons
     }
 }
 
-__global__ __launch_bounds__(256) void ht_wgrad_sum_kernel(const float* __restrict__ slabs, int nchunks, int cin, int cout, int kp,
-                                                          float* __restrict__ dwt) {
-    const int n = cout * kp;
+// stage 2 of every two-stage sum of the training files (train_common.h): one lane per element.  (n is formed here, from the two
+// factors: the compiler then gives the 32 loads of a round independent addresses; with n as an argument it chains them.)
+__global__ __launch_bounds__(256) void tc_slab_sum_kernel(const float* __restrict__ slabs, int nchunks, int row_valid, int rows, int row_len,
+                                                         float* __restrict__ out) {
+    const int n = rows * row_len;
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= n) return;
-    if (e % kp >= cin) { dwt[e] = 0.0f; return; }
+    if (e % row_len >= row_valid) { out[e] = 0.0f; return; }
     const float* s = slabs + e;
     float v = s[0];
 #pragma unroll 32
     for (int c = 1; c < nchunks; ++c) v += s[(size_t)c * n];
-    dwt[e] = v;
+    out[e] = v;
+}
+
+int yr_launch_slab_sum(const float* slabs, int nchunks, int rows, int row_len, int row_valid, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(tc_slab_sum_kernel, dim3((rows * row_len + 255) / 256), dim3(256), 0, s, slabs, nchunks, row_valid, rows, row_len, out);
+    YR_LAUNCH_CHECK();
+    return YR_OK;
 }
 
 template <int TCO>
@@ -197,23 +192,20 @@ static void ht_wgrad_launch_ci(int tci, dim3 grid, hipStream_t s, const float* x
 #undef HT_CASE
 }
 
-static inline bool ht_rows_fit(long long pixels, int ld) { return pixels <= (LLONG_MAX / 4) / ld; }
-
 extern "C" int yr_linear_wgrad(const float* x, int x_ld, const float* dy, int dy_ld, long long pixels, int cin, int cout,
                                void* workspace, size_t workspace_bytes, float* dwt, void* stream) {
     YR_REQUIRE(x && dy && workspace && dwt, "linear_wgrad: null pointer");
     YR_REQUIRE(ht_sizes_ok(pixels, cin, cout), "linear_wgrad: pixels must be 1..2^40-1 and cin, cout 1..256 (pixels %lld, cin %d, cout %d)", pixels, cin, cout);
     YR_REQUIRE(x_ld >= cin && dy_ld >= cout, "linear_wgrad: x_ld %d < cin %d or dy_ld %d < cout %d", x_ld, cin, dy_ld, cout);
-    YR_REQUIRE(ht_rows_fit(pixels, x_ld) && ht_rows_fit(pixels, dy_ld), "linear_wgrad: byte offsets beyond 2^63");
+    YR_REQUIRE(tc_rows_fit(pixels, x_ld) && tc_rows_fit(pixels, dy_ld), "linear_wgrad: byte offsets beyond 2^63");
     YR_REQUIRE(((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dwt) % 4 == 0, "linear_wgrad: x, dy or dwt not 4-byte aligned");
-    const size_t need = yr_linear_wgrad_workspace_bytes(pixels, cin, cout);
-    YR_REQUIRE(workspace_bytes >= need, "linear_wgrad: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-    YR_REQUIRE(((uintptr_t)workspace) % 16 == 0, "linear_wgrad: workspace not 16-byte aligned");
+    const int rc = tc_workspace_check("linear_wgrad", workspace, workspace_bytes, yr_linear_wgrad_workspace_bytes(pixels, cin, cout));
+    if (rc != YR_OK) return rc;
     const int kp = yr_round_up(cin, 4), chunk = ht_chunk(pixels, cin, cout);
     const int nchunks = (int)((pixels + chunk - 1) / chunk);
     int bo, to, bi, ti;
-    ht_blocking(cout, &bo, &to);
-    ht_blocking(cin, &bi, &ti);
+    tc_blocking(cout, &bo, &to);
+    tc_blocking(cin, &bi, &ti);
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(nchunks, bo, bi);
     float* slabs = (float*)workspace;
@@ -225,9 +217,7 @@ extern "C" int yr_linear_wgrad(const float* x, int x_ld, const float* dy, int dy
         default: ht_wgrad_launch_ci<5>(ti, grid, s, x, x_ld, dy, dy_ld, pixels, cin, cout, kp, chunk, slabs); break;
     }
     YR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ht_wgrad_sum_kernel, dim3((cout * kp + 255) / 256), dim3(256), 0, s, slabs, nchunks, cin, cout, kp, dwt);
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+    return yr_launch_slab_sum(slabs, nchunks, cout, kp, cin, dwt, s);
 }
 
 // ---------------------------------------------------------------- the layer's forward
@@ -245,9 +235,9 @@ __global__ __launch_bounds__(256) void ht_forward_kernel(const float* __restrict
 #pragma unroll
     for (int t = 0; t < NT; ++t) cok[t] = co0 + 16 * t + l15 < cout;
     const int woff = (co0 + l15) * kp;
-    ht_f4 acc[NT];
+    tc_f4 acc[NT];
 #pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = (ht_f4){0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < NT; ++t) acc[t] = (tc_f4){0.f, 0.f, 0.f, 0.f};
     for (int k = g; k < kp; k += 4) {      // kp is a multiple of 4: the same number of steps in every lane
         const bool kok = k < cin;
         const float a = (pok && kok) ? x[xoff + k] : 0.f;
@@ -273,13 +263,13 @@ extern "C" int yr_linear_forward(const float* x, int x_ld, const float* wt, long
     YR_REQUIRE(x && wt && y, "linear_forward: null pointer");
     YR_REQUIRE(ht_sizes_ok(pixels, cin, cout), "linear_forward: pixels must be 1..2^40-1 and cin, cout 1..256 (pixels %lld, cin %d, cout %d)", pixels, cin, cout);
     YR_REQUIRE(x_ld >= cin && y_ld >= cout, "linear_forward: x_ld %d < cin %d or y_ld %d < cout %d", x_ld, cin, y_ld, cout);
-    YR_REQUIRE(ht_rows_fit(pixels, x_ld) && ht_rows_fit(pixels, y_ld), "linear_forward: byte offsets beyond 2^63");
+    YR_REQUIRE(tc_rows_fit(pixels, x_ld) && tc_rows_fit(pixels, y_ld), "linear_forward: byte offsets beyond 2^63");
     YR_REQUIRE(((uintptr_t)x | (uintptr_t)wt | (uintptr_t)y) % 4 == 0, "linear_forward: x, wt or y not 4-byte aligned");
     const long long blocks = (pixels + 63) / 64;
     YR_REQUIRE(blocks <= INT_MAX, "linear_forward: more than 2^37 pixels");
     const int kp = yr_round_up(cin, 4);
     int bo, to;
-    ht_blocking(cout, &bo, &to);
+    tc_blocking(cout, &bo, &to);
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)blocks, bo);
 #define HT_CASE(T) \

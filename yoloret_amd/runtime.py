@@ -349,37 +349,28 @@ def decode(ys, anchors, num_classes, image_hw, input_hw, num_scales=3, zoom_ys=N
 
 
 def _decode(ys, anchors, num_classes, image_hw, input_hw, num_scales, zoom_ys):
-    if zoom_ys is not None:
+    """anchors: the contiguous float32 [3 * A, 2] array ``decode`` made."""
+    zoom = zoom_ys is not None
+    if zoom:
         for i, (y, z) in enumerate(zip(ys[:num_scales], zoom_ys[:num_scales])):
             _require_cuda_f32(z, 'zoom y%d' % (i + 1))
             if z.shape != y.shape:
                 raise ValueError('zoom y%d has shape %s, expected %s' % (i + 1, tuple(z.shape), tuple(y.shape)))
-        b = ys[0].shape[0]
-        anchors = np.ascontiguousarray(np.asarray(anchors, np.float32).reshape(-1, 2))
-        a = anchors.shape[0] // 3
-        in_h, in_w = int(input_hw[0]), int(input_hw[1])
-        n = 2 * num_boxes(in_h, in_w, a, num_scales)
-        dev = ys[0].device
-        boxes = torch.empty((b, n, 4), dtype=torch.float32, device=dev)
-        scores = torch.empty((b, num_classes, n), dtype=torch.float32, device=dev)
-        yp = [_ptr(ys[i]) if i < num_scales else None for i in range(3)]
-        zp = [_ptr(zoom_ys[i]) if i < num_scales else None for i in range(3)]
-        check(lib().yr_decode_zoom(yp[0], yp[1], yp[2], zp[0], zp[1], zp[2], ZOOM_MUL, ZOOM_ADD, b, in_h, in_w, a,
-                                   num_classes, num_scales, anchors.ctypes.data_as(ctypes.c_void_p), _ptr(image_hw),
-                                   _ptr(boxes), _ptr(scores), stream_ptr(dev)))
-        return boxes, scores
     b = ys[0].shape[0]
-    anchors = np.ascontiguousarray(np.asarray(anchors, np.float32).reshape(-1, 2))
     a = anchors.shape[0] // 3
     in_h, in_w = int(input_hw[0]), int(input_hw[1])
-    n = num_boxes(in_h, in_w, a, num_scales)
+    n = (2 if zoom else 1) * num_boxes(in_h, in_w, a, num_scales)
     dev = ys[0].device
     boxes = torch.empty((b, n, 4), dtype=torch.float32, device=dev)
     scores = torch.empty((b, num_classes, n), dtype=torch.float32, device=dev)
     yp = [_ptr(ys[i]) if i < num_scales else None for i in range(3)]
-    check(lib().yr_decode(yp[0], yp[1], yp[2], b, in_h, in_w, a, num_classes, num_scales,
-                          anchors.ctypes.data_as(ctypes.c_void_p), _ptr(image_hw), _ptr(boxes), _ptr(scores),
-                          stream_ptr(dev)))
+    tail = (b, in_h, in_w, a, num_classes, num_scales, anchors.ctypes.data_as(ctypes.c_void_p), _ptr(image_hw), _ptr(boxes), _ptr(scores),
+            stream_ptr(dev))
+    if zoom:
+        zp = [_ptr(zoom_ys[i]) if i < num_scales else None for i in range(3)]
+        check(lib().yr_decode_zoom(*yp, *zp, ZOOM_MUL, ZOOM_ADD, *tail))
+    else:
+        check(lib().yr_decode(*yp, *tail))
     return boxes, scores
 
 
@@ -432,6 +423,26 @@ def yolo_head(feats, anchors, input_hw, with_scores=False):
     return (xy, wh, conf, probs, scores) if with_scores else (xy, wh, conf, probs)
 
 
+def _out_like(out, shape, dev, name):
+    """A fresh float32 tensor of ``shape`` on ``dev``, or the caller's, which must be exactly that and contiguous."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    if not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == dev and tuple(out.shape) == tuple(shape)
+            and out.is_contiguous()):
+        raise ValueError('%s: out must be a contiguous float32 tensor of shape %s on %s' % (name, tuple(shape), dev))
+    return out
+
+
+def _workspace_arg(workspace, need, dev, name):
+    """A fresh uint8 tensor of ``need`` bytes on ``dev``, or the caller's, which must be contiguous and hold at least that many."""
+    if workspace is None:
+        return torch.empty((need,), dtype=torch.uint8, device=dev)
+    if not (isinstance(workspace, torch.Tensor) and workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == dev
+            and workspace.numel() >= need):
+        raise ValueError('%s: workspace must be a contiguous uint8 tensor of at least %d bytes on %s' % (name, need, dev))
+    return workspace
+
+
 def yolo_loss_workspace_bytes(batch, gh, gw, num_anchors):
     return int(lib().yr_yolo_loss_workspace_bytes(int(batch), int(gh), int(gw), int(num_anchors)))
 
@@ -452,11 +463,7 @@ def _yolo_loss_args(name, feats, y_true, anchors, workspace):
     if not 1 <= a <= 8:
         raise ValueError('%s: 1..8 anchor slots per cell, not %d' % (name, a))
     dev = feats.device
-    need = yolo_loss_workspace_bytes(b, gh, gw, a)
-    ws = torch.empty((need,), dtype=torch.uint8, device=dev) if workspace is None else workspace
-    if not (isinstance(ws, torch.Tensor) and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.device == dev and ws.numel() >= need):
-        raise ValueError('%s: workspace must be a contiguous uint8 tensor of at least %d bytes on %s' % (name, need, dev))
-    return b, gh, gw, a, ch, anchors, dev, ws
+    return b, gh, gw, a, ch, anchors, dev, _workspace_arg(workspace, yolo_loss_workspace_bytes(b, gh, gw, a), dev, name)
 
 
 def yolo_loss(feats, y_true, anchors, input_hw, ignore_thresh=.5, workspace=None):
@@ -483,11 +490,7 @@ def yolo_loss_grad(feats, y_true, anchors, input_hw, ignore_thresh=.5, upstream=
     if upstream is not None and not (isinstance(upstream, torch.Tensor) and upstream.dtype == torch.float32 and upstream.numel() == 1
                                      and upstream.device == dev):
         raise ValueError('yolo_loss_grad: upstream must be a float32 tensor of one element on %s' % dev)
-    if out is None:
-        out = torch.empty_like(feats)
-    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == dev and out.shape == feats.shape
-              and out.is_contiguous()):
-        raise ValueError('yolo_loss_grad: out must be a contiguous float32 tensor of shape %s on %s' % (tuple(feats.shape), dev))
+    out = _out_like(out, feats.shape, dev, 'yolo_loss_grad')
     terms = torch.empty((5,), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         check(lib().yr_yolo_loss_grad(_ptr(feats), _ptr(y_true), b, gh, gw, a, ch - 5, anchors.ctypes.data_as(ctypes.c_void_p),
@@ -521,12 +524,7 @@ def linear_forward(x, wt, out=None):
     _linear_wt(wt, 'wt', cin)
     if wt.device != x.device:
         raise ValueError('linear_forward: wt on %s, x on %s' % (wt.device, x.device))
-    shape = tuple(x.shape[:-1]) + (wt.shape[0],)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == x.device and tuple(out.shape) == shape
-              and out.is_contiguous()):
-        raise ValueError('linear_forward: out must be a contiguous float32 tensor of shape %s on %s' % (shape, x.device))
+    out = _out_like(out, tuple(x.shape[:-1]) + (wt.shape[0],), x.device, 'linear_forward')
     with torch.cuda.device(x.device):
         check(lib().yr_linear_forward(_ptr(x), cin, _ptr(wt), pixels, cin, wt.shape[0], _ptr(out), wt.shape[0], stream_ptr(x.device)))
     return out
@@ -554,16 +552,8 @@ def linear_wgrad(x, dy, out=None, workspace=None):
     if not (1 <= cin <= 256 and 1 <= cout <= 256):
         raise ValueError('linear_wgrad: 1..256 channels, not %d and %d' % (cin, cout))
     dev = x.device
-    shape = (cout, (cin + 3) // 4 * 4)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=dev)
-    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == dev and tuple(out.shape) == shape
-              and out.is_contiguous()):
-        raise ValueError('linear_wgrad: out must be a contiguous float32 tensor of shape %s on %s' % (shape, dev))
-    need = linear_wgrad_workspace_bytes(pixels, cin, cout)
-    ws = torch.empty((need,), dtype=torch.uint8, device=dev) if workspace is None else workspace
-    if not (isinstance(ws, torch.Tensor) and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.device == dev and ws.numel() >= need):
-        raise ValueError('linear_wgrad: workspace must be a contiguous uint8 tensor of at least %d bytes on %s' % (need, dev))
+    out = _out_like(out, (cout, (cin + 3) // 4 * 4), dev, 'linear_wgrad')
+    ws = _workspace_arg(workspace, linear_wgrad_workspace_bytes(pixels, cin, cout), dev, 'linear_wgrad')
     with torch.cuda.device(dev):
         check(lib().yr_linear_wgrad(_ptr(x), cin, _ptr(dy), cout, pixels, cin, cout, _ptr(ws), ws.numel(), _ptr(out), stream_ptr(dev)))
     return out
@@ -592,15 +582,6 @@ def adam_step(w, m, v, g, alpha, beta1=.9, beta2=.999, eps=1e-8):
 
 
 # ----------------------------------------------------------------------------- backward operators (csrc/convgrad.hip)
-def _out_like(out, shape, dev, name):
-    if out is None:
-        return torch.empty(shape, dtype=torch.float32, device=dev)
-    if not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == dev and tuple(out.shape) == tuple(shape)
-            and out.is_contiguous()):
-        raise ValueError('%s: out must be a contiguous float32 tensor of shape %s on %s' % (name, tuple(shape), dev))
-    return out
-
-
 def linear_dgrad(dy, wt, cin, out=None):
     """The input gradient of ``linear_forward`` (yr_linear_dgrad): dy [..., cout] float32, wt [cout, round_up(cin, 4)] ->
     dx [..., cin] = dy @ wt[:, :cin] on the float32 matrix pipe.  ``cin`` names the channels taken of wt's rows.  out: a contiguous
@@ -701,10 +682,7 @@ def depthwise_wgrad(x, dy, k, stride=1, padding='same', out=None, workspace=None
         raise ValueError('depthwise_wgrad: dy %s on %s, expected %s on %s' % (tuple(dy.shape), dy.device, (b, oh, ow, c), x.device))
     dev = x.device
     out = _out_like(out, (k * k, c), dev, 'depthwise_wgrad')
-    need = depthwise_wgrad_workspace_bytes(b, oh, ow, c, k)
-    ws = torch.empty((need,), dtype=torch.uint8, device=dev) if workspace is None else workspace
-    if not (isinstance(ws, torch.Tensor) and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.device == dev and ws.numel() >= need):
-        raise ValueError('depthwise_wgrad: workspace must be a contiguous uint8 tensor of at least %d bytes on %s' % (need, dev))
+    ws = _workspace_arg(workspace, depthwise_wgrad_workspace_bytes(b, oh, ow, c, k), dev, 'depthwise_wgrad')
     with torch.cuda.device(dev):
         check(lib().yr_depthwise_wgrad(_ptr(x), c, _ptr(dy), c, b, h, wd, c, int(k), int(stride), pt, pl, oh, ow, _ptr(ws), ws.numel(), _ptr(out),
                                        stream_ptr(dev)))
@@ -774,10 +752,7 @@ def _bn_train_workspace(workspace, pixels, c, dev, name):
     need = bn_train_workspace_bytes(pixels, c)
     if need == 0:
         raise ValueError('%s: %d pixels of %d channels are outside the contract' % (name, pixels, c))
-    ws = torch.empty((need,), dtype=torch.uint8, device=dev) if workspace is None else workspace
-    if not (isinstance(ws, torch.Tensor) and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.device == dev and ws.numel() >= need):
-        raise ValueError('%s: workspace must be a contiguous uint8 tensor of at least %d bytes on %s' % (name, need, dev))
-    return ws
+    return _workspace_arg(workspace, need, dev, name)
 
 
 def bn_train_forward(z, gamma, beta, eps=1e-3, momentum=0.9, act=None, moving_mean=None, moving_var=None, out=None, workspace=None):
@@ -963,11 +938,7 @@ def letterbox(image_u8, input_hw, out=None):
         raise ValueError('image must be a contiguous uint8 CUDA tensor [h,w,3] or [B,h,w,3]')
     h, w = int(input_hw[0]), int(input_hw[1])
     batched = image_u8.dim() == 4
-    shape = ((image_u8.shape[0],) if batched else ()) + (h, w, 3)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=image_u8.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != image_u8.device:
-        raise ValueError('out must be a contiguous float32 tensor %s on the image\'s device' % (shape,))
+    out = _out_like(out, ((image_u8.shape[0],) if batched else ()) + (h, w, 3), image_u8.device, 'letterbox')
     with torch.cuda.device(image_u8.device):
         check(lib().yr_letterbox_batch(_ptr(image_u8), image_u8.shape[0] if batched else 1, image_u8.shape[-3],
                                        image_u8.shape[-2], _ptr(out), h, w, stream_ptr(image_u8.device)))
@@ -978,13 +949,12 @@ def letterbox(image_u8, input_hw, out=None):
 INGEST_LETTERBOX, INGEST_VALIDATE, INGEST_MAX_BOXES = 0, 1, 256     # YR_INGEST_* of include/yoloret_hip.h
 
 
-class IngestTable:
-    """The geometry table of one ragged batch (yr_ingest_geometry): ``host`` is the structured array [B] (INGEST_GEOM_DTYPE: src_off,
-    ih, iw, nh, nw, dy, dx, nh_f, nw_f, dy_f, dx_f), ``mode`` the rule it was computed with, ``packed_bytes`` the size of the packed
-    source, ``device`` the uint8 tensor [B * 64] that holds its bytes on the GPU once it has been uploaded (RaggedStager.upload)."""
+class _RaggedTable:
+    """The table of one ragged batch: ``host`` is the structured array [B] (DTYPE), ``packed_bytes`` the size of the packed source,
+    ``device`` the uint8 tensor [B * DTYPE.itemsize] that holds its bytes on the GPU once it has been uploaded."""
 
-    def __init__(self, host, mode, input_hw, packed_bytes):
-        self.host, self.mode, self.input_hw, self.packed_bytes = host, int(mode), (int(input_hw[0]), int(input_hw[1])), int(packed_bytes)
+    def __init__(self, host, input_hw, packed_bytes):
+        self.host, self.input_hw, self.packed_bytes = host, (int(input_hw[0]), int(input_hw[1])), int(packed_bytes)
         self.batch = int(host.shape[0])
         self.device = None
 
@@ -992,6 +962,48 @@ class IngestTable:
         """The table alone, in a copy of its own (tests and tools; a pipeline uploads it with the images: RaggedStager)."""
         self.device = torch.from_numpy(self.host.view(np.uint8).copy()).to(device)
         return self
+
+
+class IngestTable(_RaggedTable):
+    """The geometry table of yr_ingest_geometry (INGEST_GEOM_DTYPE: src_off, ih, iw, nh, nw, dy, dx, nh_f, nw_f, dy_f, dx_f; 64 bytes an
+    image); ``mode``: the rule it was computed with.  Uploaded by RaggedStager.upload."""
+    DTYPE, MADE_BY = INGEST_GEOM_DTYPE, 'ingest_geometry + RaggedStager.upload / IngestTable.upload'
+
+    def __init__(self, host, mode, input_hw, packed_bytes):
+        super().__init__(host, input_hw, packed_bytes)
+        self.mode = int(mode)
+
+
+def _ragged_args(name, packed_u8, table, cls, input_hw):
+    """The checks of a packed source and its uploaded table of class ``cls`` -> (device, H, W, B)."""
+    if not (isinstance(packed_u8, torch.Tensor) and packed_u8.is_cuda and packed_u8.dtype == torch.uint8 and packed_u8.is_contiguous()):
+        raise ValueError('%s: the packed source must be a contiguous uint8 CUDA tensor' % name)
+    if not isinstance(table, cls) or table.device is None:
+        raise ValueError('%s: the table must be an uploaded %s (%s)' % (name, cls.__name__, cls.MADE_BY))
+    dev = packed_u8.device
+    h, w = int(input_hw[0]), int(input_hw[1])
+    b = table.batch
+    if (h, w) != table.input_hw:
+        raise ValueError('%s: the table was computed for %dx%d, not %dx%d' % ((name,) + table.input_hw + (h, w)))
+    if table.device.device != dev or table.device.dtype != torch.uint8 or table.device.numel() != b * cls.DTYPE.itemsize:
+        raise ValueError('%s: the table\'s device copy must be %d bytes on %s' % (name, b * cls.DTYPE.itemsize, dev))
+    if packed_u8.numel() < table.packed_bytes - 15:
+        raise ValueError('%s: the packed source holds %d bytes, the table addresses %d' % (name, packed_u8.numel(), table.packed_bytes))
+    return dev, h, w, b
+
+
+def _ragged_boxes(name, boxes, box_count, max_boxes, b, dev):
+    """The checks of the box list of a ragged batch -> (max_in, boxes_out [B,max_boxes,5], kept [B]), fresh tensors."""
+    if not (isinstance(boxes, torch.Tensor) and boxes.dtype == torch.float32 and boxes.is_contiguous() and boxes.device == dev
+            and boxes.dim() == 3 and boxes.shape[0] == b and boxes.shape[2] == 5 and 1 <= boxes.shape[1] <= INGEST_MAX_BOXES):
+        raise ValueError('%s: boxes must be a contiguous float32 tensor [B=%d,max_in,5] on %s with 1 <= max_in <= %d'
+                         % (name, b, dev, INGEST_MAX_BOXES))
+    if not (_is_cuda_i32(box_count) and box_count.device == dev and tuple(box_count.shape) == (b,)):
+        raise ValueError('%s: box_count must be a contiguous int32 [B=%d] tensor on %s' % (name, b, dev))
+    if int(max_boxes) < 1:
+        raise ValueError('%s: max_boxes must be at least 1, not %d' % (name, max_boxes))
+    return (int(boxes.shape[1]), torch.empty((b, int(max_boxes), 5), dtype=torch.float32, device=dev),
+            torch.empty((b,), dtype=torch.int32, device=dev))
 
 
 def ingest_geometry(dims, input_hw, mode):
@@ -1015,40 +1027,13 @@ def ingest_batch(packed_u8, geom, input_hw, boxes=None, box_count=None, max_boxe
     validation pipeline's image (utils.py:239-252,277) in INGEST_VALIDATE mode.  With ``boxes`` (float32 CUDA [B,max_in,5] rows
     (xmin, ymin, xmax, ymax, label) in source pixels, max_in <= 256) and ``box_count`` (int32 [B]), VALIDATE mode only:
     -> (images, boxes_out [B,max_boxes,5] mapped, clipped, filtered and cut as utils.py:253-293, kept [B] int32)."""
-    if not (isinstance(packed_u8, torch.Tensor) and packed_u8.is_cuda and packed_u8.dtype == torch.uint8 and packed_u8.is_contiguous()):
-        raise ValueError('ingest_batch: the packed source must be a contiguous uint8 CUDA tensor')
-    if not isinstance(geom, IngestTable) or geom.device is None:
-        raise ValueError('ingest_batch: geom must be an uploaded IngestTable (ingest_geometry + RaggedStager.upload / IngestTable.upload)')
-    dev = packed_u8.device
-    h, w = int(input_hw[0]), int(input_hw[1])
-    b = geom.batch
-    if (h, w) != geom.input_hw:
-        raise ValueError('ingest_batch: the table was computed for %dx%d, not %dx%d' % (geom.input_hw + (h, w)))
-    if geom.device.device != dev or geom.device.dtype != torch.uint8 or geom.device.numel() != b * INGEST_GEOM_DTYPE.itemsize:
-        raise ValueError('ingest_batch: the table\'s device copy must be %d bytes on %s' % (b * INGEST_GEOM_DTYPE.itemsize, dev))
-    if packed_u8.numel() < geom.packed_bytes - 15:
-        raise ValueError('ingest_batch: the packed source holds %d bytes, the table addresses %d' % (packed_u8.numel(), geom.packed_bytes))
-    shape = (b, h, w, 3)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=dev)
-    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
-        raise ValueError('out must be a contiguous float32 tensor %s on the source\'s device' % (shape,))
-    boxes_out = kept = None
-    max_in = 0
+    dev, h, w, b = _ragged_args('ingest_batch', packed_u8, geom, IngestTable, input_hw)
+    out = _out_like(out, (b, h, w, 3), dev, 'ingest_batch')
+    max_in, boxes_out, kept = 0, None, None
     if boxes is not None:
         if geom.mode != INGEST_VALIDATE:
             raise ValueError('ingest_batch: boxes are mapped in INGEST_VALIDATE mode only')
-        if not (isinstance(boxes, torch.Tensor) and boxes.dtype == torch.float32 and boxes.is_contiguous() and boxes.device == dev
-                and boxes.dim() == 3 and boxes.shape[0] == b and boxes.shape[2] == 5 and 1 <= boxes.shape[1] <= INGEST_MAX_BOXES):
-            raise ValueError('ingest_batch: boxes must be a contiguous float32 tensor [B=%d,max_in,5] on %s with 1 <= max_in <= %d'
-                             % (b, dev, INGEST_MAX_BOXES))
-        if not (_is_cuda_i32(box_count) and box_count.device == dev and tuple(box_count.shape) == (b,)):
-            raise ValueError('ingest_batch: box_count must be a contiguous int32 [B=%d] tensor on %s' % (b, dev))
-        if int(max_boxes) < 1:
-            raise ValueError('ingest_batch: max_boxes must be at least 1, not %d' % max_boxes)
-        max_in = int(boxes.shape[1])
-        boxes_out = torch.empty((b, int(max_boxes), 5), dtype=torch.float32, device=dev)
-        kept = torch.empty((b,), dtype=torch.int32, device=dev)
+        max_in, boxes_out, kept = _ragged_boxes('ingest_batch', boxes, box_count, max_boxes, b, dev)
     with torch.cuda.device(dev):
         check(lib().yr_ingest_batch(geom.mode, _ptr(packed_u8), _ptr(geom.device), b, _ptr(out), h, w, _ptr(boxes), _ptr(box_count), max_in,
                                     _ptr(boxes_out), _ptr(kept), int(max_boxes), stream_ptr(dev)))
@@ -1105,20 +1090,14 @@ AUGMENT_DEFAULTS = dict(jitter=.3, min_scale=.25, max_scale=2., hue=.5, sat=.5, 
 AUGMENT_DRAWS = ('j1', 'j2', 'scale', 'dx', 'dy', 'flip', 'hue', 'sat', 'gamma', 'contrast')     # the order of one image's ten draws
 
 
-class AugmentTable:
-    """The table of one ragged batch under get_random_data(train=True) (yr_augment_geometry): ``host`` is the structured array
-    [B] (AUGMENT_GEOM_DTYPE), ``stages`` the mask it was computed with, ``packed_bytes`` the size of the packed source, ``device``
-    the uint8 tensor [B * 96] with its bytes on the GPU once uploaded (RaggedStager.upload_table)."""
+class AugmentTable(_RaggedTable):
+    """The table of one ragged batch under get_random_data(train=True) (yr_augment_geometry; AUGMENT_GEOM_DTYPE, 96 bytes an image);
+    ``stages``: the mask it was computed with.  Uploaded by RaggedStager.upload_table."""
+    DTYPE, MADE_BY = AUGMENT_GEOM_DTYPE, 'augment_geometry + RaggedStager.upload_table / AugmentTable.upload'
 
     def __init__(self, host, stages, input_hw, packed_bytes):
-        self.host, self.stages, self.input_hw, self.packed_bytes = host, int(stages), (int(input_hw[0]), int(input_hw[1])), int(packed_bytes)
-        self.batch = int(host.shape[0])
-        self.device = None
-
-    def upload(self, device):
-        """The table alone, in a copy of its own (tests and tools; a pipeline uploads it with the images: RaggedStager)."""
-        self.device = torch.from_numpy(self.host.view(np.uint8).copy()).to(device)
-        return self
+        super().__init__(host, input_hw, packed_bytes)
+        self.stages = int(stages)
 
 
 def augment_stages(flip=True, hue=.5, sat=.5, min_gamma=.8, max_gamma=2., cont=.1):
@@ -1165,46 +1144,12 @@ def augment_batch(packed_u8, table, input_hw, boxes=None, box_count=None, max_bo
     -> (images, boxes_out [B,max_boxes,5], kept [B] int32) as utils.py:208-217,258-293.  random_jpeg_quality, which the reference
     applies by default, is the stage behind this one: ``jpeg_roundtrip_batch``.  ``workspace``: a uint8 CUDA tensor of
     augment_workspace_bytes, made here when None."""
-    if not (isinstance(packed_u8, torch.Tensor) and packed_u8.is_cuda and packed_u8.dtype == torch.uint8 and packed_u8.is_contiguous()):
-        raise ValueError('augment_batch: the packed source must be a contiguous uint8 CUDA tensor')
-    if not isinstance(table, AugmentTable) or table.device is None:
-        raise ValueError('augment_batch: table must be an uploaded AugmentTable (augment_geometry + RaggedStager.upload_table / AugmentTable.upload)')
-    dev = packed_u8.device
-    h, w = int(input_hw[0]), int(input_hw[1])
-    b = table.batch
-    if (h, w) != table.input_hw:
-        raise ValueError('augment_batch: the table was computed for %dx%d, not %dx%d' % (table.input_hw + (h, w)))
+    dev, h, w, b = _ragged_args('augment_batch', packed_u8, table, AugmentTable, input_hw)
     if h * w % 4:
         raise ValueError('augment_batch: H * W must be a multiple of 4, not %dx%d' % (h, w))
-    if table.device.device != dev or table.device.dtype != torch.uint8 or table.device.numel() != b * AUGMENT_GEOM_DTYPE.itemsize:
-        raise ValueError('augment_batch: the table\'s device copy must be %d bytes on %s' % (b * AUGMENT_GEOM_DTYPE.itemsize, dev))
-    if packed_u8.numel() < table.packed_bytes - 15:
-        raise ValueError('augment_batch: the packed source holds %d bytes, the table addresses %d' % (packed_u8.numel(), table.packed_bytes))
-    shape = (b, h, w, 3)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=dev)
-    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
-        raise ValueError('out must be a contiguous float32 tensor %s on the source\'s device' % (shape,))
-    need = augment_workspace_bytes(b, (h, w))
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif not (isinstance(workspace, torch.Tensor) and workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous()
-              and workspace.numel() >= need):
-        raise ValueError('augment_batch: workspace must be a contiguous uint8 tensor of at least %d bytes on %s' % (need, dev))
-    boxes_out = kept = None
-    max_in = 0
-    if boxes is not None:
-        if not (isinstance(boxes, torch.Tensor) and boxes.dtype == torch.float32 and boxes.is_contiguous() and boxes.device == dev
-                and boxes.dim() == 3 and boxes.shape[0] == b and boxes.shape[2] == 5 and 1 <= boxes.shape[1] <= INGEST_MAX_BOXES):
-            raise ValueError('augment_batch: boxes must be a contiguous float32 tensor [B=%d,max_in,5] on %s with 1 <= max_in <= %d'
-                             % (b, dev, INGEST_MAX_BOXES))
-        if not (_is_cuda_i32(box_count) and box_count.device == dev and tuple(box_count.shape) == (b,)):
-            raise ValueError('augment_batch: box_count must be a contiguous int32 [B=%d] tensor on %s' % (b, dev))
-        if int(max_boxes) < 1:
-            raise ValueError('augment_batch: max_boxes must be at least 1, not %d' % max_boxes)
-        max_in = int(boxes.shape[1])
-        boxes_out = torch.empty((b, int(max_boxes), 5), dtype=torch.float32, device=dev)
-        kept = torch.empty((b,), dtype=torch.int32, device=dev)
+    out = _out_like(out, (b, h, w, 3), dev, 'augment_batch')
+    workspace = _workspace_arg(workspace, augment_workspace_bytes(b, (h, w)), dev, 'augment_batch')
+    max_in, boxes_out, kept = (0, None, None) if boxes is None else _ragged_boxes('augment_batch', boxes, box_count, max_boxes, b, dev)
     with torch.cuda.device(dev):
         check(lib().yr_augment_batch(_ptr(packed_u8), _ptr(table.device), b, table.stages, _ptr(out), h, w, _ptr(boxes), _ptr(box_count), max_in,
                                      _ptr(boxes_out), _ptr(kept), int(max_boxes), _ptr(workspace), workspace.numel(), stream_ptr(dev)))
@@ -1234,12 +1179,7 @@ def jpeg_roundtrip_batch(images, quality, workspace=None):
         quality = torch.from_numpy(np.ascontiguousarray(quality.astype(np.int32))).to(dev)
     if not (_is_cuda_i32(quality) and quality.device == dev and tuple(quality.shape) == (b,)):
         raise ValueError('jpeg_roundtrip_batch: quality must be a contiguous int32 [B=%d] tensor on %s' % (b, dev))
-    need = jpeg_workspace_bytes(b, (h, w))
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif not (isinstance(workspace, torch.Tensor) and workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous()
-              and workspace.numel() >= need):
-        raise ValueError('jpeg_roundtrip_batch: workspace must be a contiguous uint8 tensor of at least %d bytes on %s' % (need, dev))
+    workspace = _workspace_arg(workspace, jpeg_workspace_bytes(b, (h, w)), dev, 'jpeg_roundtrip_batch')
     with torch.cuda.device(dev):
         check(lib().yr_jpeg_roundtrip_batch(_ptr(images), _ptr(quality), b, h, w, _ptr(workspace), workspace.numel(), stream_ptr(dev)))
     return images
