@@ -48,11 +48,6 @@ __device__ __forceinline__ float dwl_act(float v, int act) {
 // Loads and stores go through buffer descriptors over ONE image of the map (< 1 GB): a lane whose pixel is padding, whose
 // channels are beyond C or whose column is beyond W passes an offset beyond num_records - the load returns zeros, the store
 // is dropped - so neither needs clamped coordinates, selects or a per-lane branch.
-typedef __amdgpu_buffer_rsrc_t dwl_rsrc;
-__device__ __forceinline__ dwl_rsrc dwl_make_rsrc(const void* base, unsigned bytes) {
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)base), hi = __builtin_amdgcn_readfirstlane((unsigned)((uintptr_t)base >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)hi << 32) | lo), 0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
 constexpr unsigned DWL_DEAD = 0x80000000u;   // load offsets
 
 struct DwpArgs {
@@ -95,7 +90,7 @@ __device__ __forceinline__ void dwp_static_for(F&& f) {
 constexpr unsigned DWP_DEAD = 0x40000000u;   // store offsets: row part + pixel part, either may be dead, the sum must not wrap
 constexpr int DWP_ROUNDS = 7;               // DMA rounds of 32 pixels per tile buffer (208 halo pixels at most)
 template <class T, int K, int ACT, bool SE, int R>
-__device__ __forceinline__ void dwp_band(const unsigned* trow, int tpitch, const dwl_f2 (&w)[K * K], dwl_f2 sc, dwl_f2 sh, int act, dwl_rsrc dst,
+__device__ __forceinline__ void dwp_band(const unsigned* trow, int tpitch, const dwl_f2 (&w)[K * K], dwl_f2 sc, dwl_f2 sh, int act, yr_rsrc dst,
                                          unsigned orow, unsigned opitch, const unsigned (&ooff)[4], int rows_ok, dwl_f2& psum) {
     constexpr int HALO = K - 1, NC = 4 + HALO;
     dwl_f2 acc[K][4];
@@ -187,7 +182,7 @@ __global__ __launch_bounds__(256) void dwp_kernel(DwpArgs a) {
         }
     }
     auto fetch = [&](int tx, int ty, int b, int buf) {
-        const dwl_rsrc src = dwl_make_rsrc(reinterpret_cast<const T*>(a.in) + (size_t)b * a.H * a.W * a.ld_in, (unsigned)(a.H * a.W * a.ld_in) * 2u);
+        const yr_rsrc src = yr_make_rsrc(reinterpret_cast<const T*>(a.in) + (size_t)b * a.H * a.W * a.ld_in, (unsigned)(a.H * a.W * a.ld_in) * 2u);
         const int iy0 = ty * a.th - a.pad_t, ix0 = tx * a.tw - a.pad_l;
         const unsigned tbase = (unsigned)((iy0 * a.W + ix0) * a.ld_in) * 2u;   // (may wrap below zero: the sums of the pixels inside the map do not)
 #pragma unroll
@@ -247,7 +242,7 @@ __global__ __launch_bounds__(256) void dwp_kernel(DwpArgs a) {
 #endif
         stored = __builtin_amdgcn_ballot_w64(live) != 0;   // wave-uniform
         if (stored) {
-            const dwl_rsrc dst = dwl_make_rsrc(reinterpret_cast<T*>(a.out) + (size_t)b * a.H * a.W * a.ld_out, (unsigned)(a.H * a.W * a.ld_out) * 2u);
+            const yr_rsrc dst = yr_make_rsrc(reinterpret_cast<T*>(a.out) + (size_t)b * a.H * a.W * a.ld_out, (unsigned)(a.H * a.W * a.ld_out) * 2u);
             unsigned ooff[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) ooff[i] = chan_ok && xo + i < a.W ? (unsigned)((xo + i) * a.ld_out + cl) * 2u : DWP_DEAD;

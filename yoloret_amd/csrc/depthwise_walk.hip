@@ -40,11 +40,6 @@ __device__ __forceinline__ float dwq_act(float v, int act) {
     else return yr_apply_act_t<T>(v, act);
 }
 
-typedef __amdgpu_buffer_rsrc_t dwq_rsrc;
-__device__ __forceinline__ dwq_rsrc dwq_make_rsrc(const void* base, unsigned bytes) {
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)base), hi = __builtin_amdgcn_readfirstlane((unsigned)((uintptr_t)base >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)hi << 32) | lo), 0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
 constexpr unsigned DWQ_LDEAD = 0x80000000u;   // load offsets beyond any descriptor: the DMA writes zeros
 constexpr unsigned DWQ_SDEAD = 0x40000000u;   // store offsets: row part (< 2^30) + pixel part (dead or < 2^30) never wraps
 
@@ -86,7 +81,7 @@ __device__ __forceinline__ void dwq_static_for(F&& f) {
 // last ones (t >= n: those below) and rows beyond the segment's last input row take only the taps that exist.
 template <class T, int K, int ACT, bool SE, bool GUARD>
 __device__ __forceinline__ void dwq_group(const unsigned* lrow, int rpitch, dwq_f2 (&acc)[K][4], const dwq_f2 (&w)[K * K], dwq_f2 sc, dwq_f2 sh, int act,
-                                          dwq_rsrc dst, unsigned& orow, unsigned opitch, const unsigned (&ooff)[4], int t0, int n, dwq_f2& psum, dwq_f2& psum2) {
+                                          yr_rsrc dst, unsigned& orow, unsigned opitch, const unsigned (&ooff)[4], int t0, int n, dwq_f2& psum, dwq_f2& psum2) {
     constexpr int HALO = K - 1, NC = 4 + HALO;
     unsigned raw[NC];   // the NEXT input row: its reads are issued a step ahead, under the taps of this one
 #pragma unroll
@@ -185,7 +180,7 @@ __global__ __launch_bounds__(256, K == 5 ? (ACT == 2 ? 2 : 3) : 4) void dwq_kern
     const int xb0 = blk * a.spb * 4;                                   // the block's first output column
     const int xl = xb0 - a.pad_l + px;                                  // this lane's map column in pixel group 0
     const unsigned lane_part = (unsigned)(px * a.ld_in) * 2u + (unsigned)(cc * 8 + cv) * 16u;
-    const dwq_rsrc src = dwq_make_rsrc(reinterpret_cast<const T*>(a.in) + (size_t)img0 * a.H * a.W * a.ld_in, (unsigned)nimg * imgbytes_in);
+    const yr_rsrc src = yr_make_rsrc(reinterpret_cast<const T*>(a.in) + (size_t)img0 * a.H * a.W * a.ld_in, (unsigned)nimg * imgbytes_in);
     const int rowwords = a.colsp * 32;
     // A wave's DMA slots of a group - (row of the group x image, 8 pixels), every nw-th of the K * ni * U - are the same in every
     // group: their LDS word, row, byte offset from the group's first row and this lane's column check are worked out once
@@ -224,7 +219,7 @@ __global__ __launch_bounds__(256, K == 5 ? (ACT == 2 ? 2 : 3) : 4) void dwq_kern
     };
 
     // ---- the walk
-    const dwq_rsrc dst = dwq_make_rsrc(reinterpret_cast<T*>(a.out) + (size_t)img0 * a.H * a.W * a.ld_out, (unsigned)nimg * imgbytes_out);
+    const yr_rsrc dst = yr_make_rsrc(reinterpret_cast<T*>(a.out) + (size_t)img0 * a.H * a.W * a.ld_out, (unsigned)nimg * imgbytes_out);
     const unsigned opitch = (unsigned)(a.W * a.ld_out) * 2u;
     unsigned ooff[4];
     {

@@ -303,19 +303,13 @@ __global__ __launch_bounds__(256, 2) void head_kernel(HeadArgs h) {
 //   p.wt = the float32 words that hold [NT = ceil(F / 16)][NK chunks][2 planes][64 lanes][8 halves] (compiler.head_pack): lane
 //   (m = l % 16, g = l / 16) of cout tile t, chunk (s, j): W[16 t + m][k of channel 32 j + 8 g + i of source s], zero beyond the
 //   source's channels and beyond F; h plane, then m plane = f16((w - h) 2^11).
-typedef __amdgpu_buffer_rsrc_t head_rsrc;
-__device__ __forceinline__ head_rsrc head_make_rsrc(const void* base, unsigned bytes) {
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)base), hi = __builtin_amdgcn_readfirstlane((unsigned)((uintptr_t)base >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)hi << 32) | lo), 0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
-#define HEAD_DEAD 0x7f000000u   // a byte offset beyond every descriptor's num_records: the load returns zeros
 #define HEAD_ASTAGE (HEAD_BM * 128)                 // bytes of one activation stage: [192 rows][32 floats], 16-byte slots XOR-swizzled
 typedef __attribute__((address_space(3))) void* head_lds_ptr;
 
 // byte offset of source pixel (b, y, x) - the consumer's pixel through the source's transform - or a dead offset
 __device__ __forceinline__ unsigned head_src_off(bool valid, int b, int y, int x, int xform, int sh, int sw, int ld) {
     const int sy = xform == YR_X_UP2 ? y >> 1 : y, sx = xform == YR_X_UP2 ? x >> 1 : x;
-    return valid ? (unsigned)(((b * sh + sy) * sw + sx) * ld) * 4u : HEAD_DEAD;
+    return valid ? (unsigned)(((b * sh + sy) * sw + sx) * ld) * 4u : YR_DEAD;
 }
 
 template <int CT>
@@ -357,20 +351,20 @@ __global__ __launch_bounds__(256, 2) void head2_kernel(HeadArgs h) {
         const int ry = mm / R.RW, rx = mm - ry * R.RW;                                                                            \
         const int y = R.ylo + ry, x = R.xlo + rx;                                                                                 \
         off0[i] = head_src_off(valid, R.b, y, x, a.S.s[0].xform, a.S.s[0].h, a.S.s[0].w, a.S.s[0].ld);                            \
-        off1[i] = a.S.n > 1 ? head_src_off(valid, R.b, y, x, a.S.s[1].xform, a.S.s[1].h, a.S.s[1].w, a.S.s[1].ld) : HEAD_DEAD;    \
-        off2[i] = a.S.n > 2 ? head_src_off(valid, R.b, y, x, a.S.s[2].xform, a.S.s[2].h, a.S.s[2].w, a.S.s[2].ld) : HEAD_DEAD;    \
+        off1[i] = a.S.n > 1 ? head_src_off(valid, R.b, y, x, a.S.s[1].xform, a.S.s[1].h, a.S.s[1].w, a.S.s[1].ld) : YR_DEAD;    \
+        off2[i] = a.S.n > 2 ? head_src_off(valid, R.b, y, x, a.S.s[2].xform, a.S.s[2].h, a.S.s[2].w, a.S.s[2].ld) : YR_DEAD;    \
     }
     HEAD_SLOT(0) HEAD_SLOT(1) HEAD_SLOT(2) HEAD_SLOT(3) HEAD_SLOT(4) HEAD_SLOT(5)
 #undef HEAD_SLOT
     // (whole-batch descriptors: offsets are 32-bit - the launcher checks the sources are below 2 GB)
-    const head_rsrc rs0 = head_make_rsrc(a.S.s[0].ptr, 0x7effffffu);
+    const yr_rsrc rs0 = yr_make_rsrc(a.S.s[0].ptr, 0x7effffffu);
     // (no dynamic index into the kernel arguments: it would make the compiler copy the whole argument block to scratch)
-    const head_rsrc rs1 = head_make_rsrc(a.S.n > 1 ? a.S.s[1].ptr : a.S.s[0].ptr, 0x7effffffu);
-    const head_rsrc rs2 = head_make_rsrc(a.S.n > 2 ? a.S.s[2].ptr : a.S.s[0].ptr, 0x7effffffu);
+    const yr_rsrc rs1 = yr_make_rsrc(a.S.n > 1 ? a.S.s[1].ptr : a.S.s[0].ptr, 0x7effffffu);
+    const yr_rsrc rs2 = yr_make_rsrc(a.S.n > 2 ? a.S.s[2].ptr : a.S.s[0].ptr, 0x7effffffu);
     const unsigned ntiles = (unsigned)((a.N + 15) / 16);
     const int nk = h.nk;
     const unsigned tile0 = (unsigned)(R.n0 / 16);
-    const head_rsrc rsw = head_make_rsrc(a.wt, ntiles * (unsigned)nk * 2048u);
+    const yr_rsrc rsw = yr_make_rsrc(a.wt, ntiles * (unsigned)nk * 2048u);
     const int c0 = a.S.s[0].c, c1 = a.S.n > 1 ? a.S.s[1].c : 0, c2 = a.S.n > 2 ? a.S.s[2].c : 0;
     const int n0c = (c0 + 31) >> 5, n1c = (c1 + 31) >> 5;     // chunks of sources 0, 1
 
@@ -398,7 +392,7 @@ __global__ __launch_bounds__(256, 2) void head2_kernel(HeadArgs h) {
     {                                                                                                                  \
         const int k = kl + 4 * cg[i];                                                                                  \
         const unsigned ro = s == 0 ? off0[i] : s == 1 ? off1[i] : off2[i];                                             \
-        const unsigned vo = k < cq ? ro + (unsigned)k * 4u : HEAD_DEAD;                                                \
+        const unsigned vo = k < cq ? ro + (unsigned)k * 4u : YR_DEAD;                                                \
         const head_lds_ptr dst = (head_lds_ptr)(sb + ((i) * 4 + wave) * 1024);                                         \
         if (s == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, dst, 16, vo, 0, 0, 0);                               \
         else if (s == 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs1, dst, 16, vo, 0, 0, 0);                          \

@@ -83,7 +83,7 @@ __global__ __launch_bounds__(64 * NW) void hstream_kernel(HsArgs a) {
     const int xo = 14 * strip + px - 1;
     const bool out_lane = px >= 1 && px <= 14 && xo < a.W;
 
-    const mbr_rsrc wsrc = mbr_make_rsrc(a.wa, a.wa_bytes);
+    const yr_rsrc wsrc = yr_make_rsrc(a.wa, a.wa_bytes);
     auto issue_chunk = [&](const int q) {
         char* dst = lds_raw + (q & 1) * CHB;
         const int qs = min(q, NQ - 1);
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(64 * NW) void hstream_kernel(HsArgs a) {
     // the tables of all tiles and the conv's BN scale: LDS-direct too (plain loads were 6 - 11 dependent round trips per thread: a quarter of
     // the kernel's cycles, tools/hs_timing.py); the zero rows above the first / below the last wave
     {
-        const mbr_rsrc tsrc = mbr_make_rsrc(a.wt, a.wt_bytes), csrc_ = mbr_make_rsrc(a.scale, (unsigned)a.F * 4u);
+        const yr_rsrc tsrc = yr_make_rsrc(a.wt, a.wt_bytes), csrc_ = yr_make_rsrc(a.scale, (unsigned)a.F * 4u);
         const int ntp = (a.T * MBR_TAB * 4 + 1023) / 1024, ncp = (a.F * 4 + 1023) / 1024;      // (reads beyond a descriptor return zeros)
         for (int p = w; p < ntp; p += NW)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(tsrc, (hs_lds_ptr)(reinterpret_cast<char*>(tabs) + p * 1024), 16, (unsigned)(p * 1024 + lane * 16), 0, 0, 0);
@@ -115,10 +115,10 @@ __global__ __launch_bounds__(64 * NW) void hstream_kernel(HsArgs a) {
 
     // ---- the wave's pixels over the whole k space: gathered once, gated, cut into float16 planes.  ALL loads of a round go out
     // before anything is used (one round trip for the identity sources; three more rounds for the other pixels of pooled sources)
-    const mbr_rsrc rs0 = mbr_make_rsrc(a.src[0], 0x7effffffu);
-    const mbr_rsrc rs1 = mbr_make_rsrc(a.nsrc > 1 ? a.src[1] : a.src[0], 0x7effffffu);
-    const mbr_rsrc rs2 = mbr_make_rsrc(a.nsrc > 2 ? a.src[2] : a.src[0], 0x7effffffu);
-    mbs_u4 xh[ROWS][NK], xm[ROWS][NK];
+    const yr_rsrc rs0 = yr_make_rsrc(a.src[0], 0x7effffffu);
+    const yr_rsrc rs1 = yr_make_rsrc(a.nsrc > 1 ? a.src[1] : a.src[0], 0x7effffffu);
+    const yr_rsrc rs2 = yr_make_rsrc(a.nsrc > 2 ? a.src[2] : a.src[0], 0x7effffffu);
+    v4u xh[ROWS][NK], xm[ROWS][NK];
     float live[ROWS];
     {
         // groups of at most 7 chunks of one row at a time: their raw pixels next to the planes already cut must fit the registers
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(64 * NW) void hstream_kernel(HsArgs a) {
                         const int yy = pool ? 2 * rc + (t >> 1) : rc, xx = pool ? 2 * xc + (t & 1) : xc;
                         const unsigned base = (unsigned)(((b * sh + yy) * sw + xx) * ld + kl) * 4u;
                         const bool want = first || pool;
-                        const unsigned o0 = want && kl < cq ? base : MBR_DEAD, o1 = want && kl + 4 < cq ? base + 16u : MBR_DEAD;
+                        const unsigned o0 = want && kl < cq ? base : YR_DEAD, o1 = want && kl + 4 < cq ? base + 16u : YR_DEAD;
                         v4f l2, h2;
                         if (s == 0) { l2 = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rs0, o0, 0, 0)); h2 = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rs0, o1, 0, 0)); }
                         else if (s == 1) { l2 = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rs1, o0, 0, 0)); h2 = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rs1, o1, 0, 0)); }
@@ -183,16 +183,16 @@ __global__ __launch_bounds__(64 * NW) void hstream_kernel(HsArgs a) {
         }
     }
     HS_T(9)
-    const mbr_rsrc prs = mbr_make_rsrc(PRE ? a.pre + (size_t)b * (a.H >> 1) * (a.W >> 1) * a.pre_ld : a.src[0], PRE ? (unsigned)((a.H >> 1) * (a.W >> 1) * a.pre_ld) * 4u : 0u);
-    const mbr_rsrc osrc = mbr_make_rsrc(a.out + (size_t)b * a.H * a.W * a.ld_out, (unsigned)(a.H * a.W * a.ld_out) * 4u);
-    const mbr_rsrc ssrc = mbr_make_rsrc(a.sums != nullptr ? a.sums + (size_t)b * (a.strips * a.segs * NW) * a.ld_sums : a.src[0],
+    const yr_rsrc prs = yr_make_rsrc(PRE ? a.pre + (size_t)b * (a.H >> 1) * (a.W >> 1) * a.pre_ld : a.src[0], PRE ? (unsigned)((a.H >> 1) * (a.W >> 1) * a.pre_ld) * 4u : 0u);
+    const yr_rsrc osrc = yr_make_rsrc(a.out + (size_t)b * a.H * a.W * a.ld_out, (unsigned)(a.H * a.W * a.ld_out) * 4u);
+    const yr_rsrc ssrc = yr_make_rsrc(a.sums != nullptr ? a.sums + (size_t)b * (a.strips * a.segs * NW) * a.ld_sums : a.src[0],
                                         a.sums != nullptr ? (unsigned)(a.strips * a.segs * NW * a.ld_sums) * 4u : 0u);
     unsigned ppix[ROWS], opix[ROWS];       // byte offsets of the lane's pixel in the addend map / the output map (dead: not stored)
 #pragma unroll
     for (int i = 0; i < ROWS; ++i) {
         const int rc = min(max(rin[i], 0), a.H - 1);
         ppix[i] = PRE ? (unsigned)(((rc >> 1) * (a.W >> 1) + (xc >> 1)) * a.pre_ld + 4 * mg) * 4u : 0u;
-        opix[i] = emit[i] && out_lane ? (unsigned)((rc * a.W + xo) * a.ld_out + 4 * mg) * 4u : MBR_DEAD;
+        opix[i] = emit[i] && out_lane ? (unsigned)((rc * a.W + xo) * a.ld_out + 4 * mg) * 4u : YR_DEAD;
     }
     const unsigned srow = (unsigned)(((strip * a.segs + seg) * NW + w) * a.ld_sums + 4 * mg) * 4u;
     const float actmax = a.act == YR_ACT_RELU6 ? 6.f : 3.0e38f;     // conv activation: ReLU6, or none
@@ -298,24 +298,19 @@ __global__ __launch_bounds__(64 * NW) void hstream_kernel(HsArgs a) {
                     d[i][j][2 * hf + 1] = __builtin_amdgcn_fmed3f(d[i][j][2 * hf + 1], 0.f, 6.f);
                 }
                 if constexpr (hf == 1)
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, d[i][j]), osrc, opix[i] == MBR_DEAD ? MBR_DEAD : opix[i] + 64u * (2 * q + j), 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, d[i][j]), osrc, opix[i] == YR_DEAD ? YR_DEAD : opix[i] + 64u * (2 * q + j), 0, 0);
             } else if constexpr (sl < NV + NX) {
                 // the squeeze-excite sums of tile j: what this wave stored, over its rows and the strip's 14 columns (fixed order)
                 constexpr int j = sl - NV - 2 * ROWS * 2;
                 v4f sacc = (v4f){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int i = 0; i < ROWS; ++i)
-                    if (opix[i] != MBR_DEAD) sacc += d[i][j];
+                    if (opix[i] != YR_DEAD) sacc += d[i][j];
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
-                    float t = sacc[s];
-                    asm("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0xf\n\ts_nop 1\n\t"
-                        "v_add_f32_dpp %0, %0, %0 row_ror:4 row_mask:0xf bank_mask:0xf\n\ts_nop 1\n\t"
-                        "v_add_f32_dpp %0, %0, %0 row_ror:2 row_mask:0xf bank_mask:0xf\n\ts_nop 1\n\t"
-                        "v_add_f32_dpp %0, %0, %0 row_ror:1 row_mask:0xf bank_mask:0xf" : "+v"(t));
-                    sacc[s] = t;
+                    sacc[s] = yr_row_sum16(sacc[s]);
                 }
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, sacc), ssrc, (a.sums != nullptr && px == 0) ? srow + 64u * (2 * q + j) : MBR_DEAD, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, sacc), ssrc, (a.sums != nullptr && px == 0) ? srow + 64u * (2 * q + j) : YR_DEAD, 0, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
         });

@@ -75,18 +75,18 @@ __global__ __launch_bounds__(256, NKE >= 2 && !(PRE && NKE == 4) ? HW_OCC_SHARED
     const bool out_lane = px >= 1 && px <= 14 && xo < a.W;
 
     // ---- stationary: the weight planes of this wave's tiles, conv BN shift / scale, (the source's gate)
-    mbs_u4 weh[NT][NKE], wem[NT][NKE];
+    v4u weh[NT][NKE], wem[NT][NKE];
     v4f se[NT], psc[PRE ? NT : 1];
     unsigned ooff[NT];
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
         const int t = min(t0 + j, a.T - 1);
-        const mbs_u4* pe = reinterpret_cast<const mbs_u4*>(a.wa) + ((size_t)t * NKE) * 2 * 64 + lane;
+        const v4u* pe = reinterpret_cast<const v4u*>(a.wa) + ((size_t)t * NKE) * 2 * 64 + lane;
 #pragma unroll
         for (int c = 0; c < NKE; ++c) { weh[j][c] = pe[(2 * c) * 64]; wem[j][c] = pe[(2 * c + 1) * 64]; }
         se[j] = *reinterpret_cast<const v4f*>(a.wt + (size_t)t * MBR_TAB + 160 + 4 * mg);
         if constexpr (PRE) psc[j] = *reinterpret_cast<const v4f*>(a.scale + 16 * t + 4 * mg);
-        ooff[j] = (t0 + j < a.T && out_lane) ? (16u * (t0 + j) + 4u * mg) * 4u : MBR_DEAD;
+        ooff[j] = (t0 + j < a.T && out_lane) ? (16u * (t0 + j) + 4u * mg) * 4u : YR_DEAD;
     }
     if constexpr (GATED) {
         // The SE gate of the source scales channel k of every pixel of image b - i.e. column k of the weights: W (g . x) = (W diag g) x.
@@ -114,15 +114,15 @@ __global__ __launch_bounds__(256, NKE >= 2 && !(PRE && NKE == 4) ? HW_OCC_SHARED
         }
     }
     // ---- descriptors: the addend, the output image (the sources': one per fetched chunk, below)
-    const mbr_rsrc prs = mbr_make_rsrc(PRE ? a.pre + (size_t)b * (a.H >> 1) * (a.W >> 1) * a.pre_ld : a.src[0], PRE ? (unsigned)((a.H >> 1) * (a.W >> 1) * a.pre_ld) * 4u : 0u);
-    const mbr_rsrc osrc = mbr_make_rsrc(a.out + (size_t)b * a.H * a.W * a.ld_out, (unsigned)(a.H * a.W * a.ld_out) * 4u);
+    const yr_rsrc prs = yr_make_rsrc(PRE ? a.pre + (size_t)b * (a.H >> 1) * (a.W >> 1) * a.pre_ld : a.src[0], PRE ? (unsigned)((a.H >> 1) * (a.W >> 1) * a.pre_ld) * 4u : 0u);
+    const yr_rsrc osrc = yr_make_rsrc(a.out + (size_t)b * a.H * a.W * a.ld_out, (unsigned)(a.H * a.W * a.ld_out) * 4u);
     // The chunks this wave FETCHES.  One chunk (NKE == 1): that chunk, and the wave cuts it for itself (the direct path).  More:
     // the four waves of the workgroup multiply the SAME pixels (same image, strip, segment) with their own tiles, so a chunk of
     // a strip row is fetched and cut ONCE - by wave c % 4 - and handed to all four through LDS: slot i of wave w is chunk w + 4 i.
     // Per slot: byte offset of this lane's 8 channels in its pixel (row offset added per row), or dead; the row pitch of its source.
     constexpr bool SHARED = NKE >= 2;
     constexpr int NOWN = (NKE + 3) / 4;
-    mbr_rsrc rso[NOWN];
+    yr_rsrc rso[NOWN];
     unsigned xsoff[NOWN], xsoff2[NOWN], xpitch[NOWN];
     int vcc[NOWN];
     bool own[NOWN];
@@ -136,9 +136,9 @@ __global__ __launch_bounds__(256, NKE >= 2 && !(PRE && NKE == 4) ? HW_OCC_SHARED
         const int cs = s == 0 ? a.cs[0] : s == 1 ? a.cs[1] : a.cs[2], ld = s == 0 ? a.ld[0] : s == 1 ? a.ld[1] : a.ld[2];
         const int cq = (cs + 3) & ~3;
         const unsigned base = (unsigned)((b * a.H * a.W + xc) * ld + kl) * 4u;
-        rso[i] = mbr_make_rsrc(s == 0 ? a.src[0] : s == 1 ? a.src[1] : a.src[2], 0x7effffffu);   // (whole batch: offsets are 32-bit, the launcher checks the sizes)
-        xsoff[i] = own[i] && kl < cq ? base : MBR_DEAD;
-        xsoff2[i] = own[i] && kl + 4 < cq ? base + 16u : MBR_DEAD;
+        rso[i] = yr_make_rsrc(s == 0 ? a.src[0] : s == 1 ? a.src[1] : a.src[2], 0x7effffffu);   // (whole batch: offsets are 32-bit, the launcher checks the sizes)
+        xsoff[i] = own[i] && kl < cq ? base : YR_DEAD;
+        xsoff2[i] = own[i] && kl + 4 < cq ? base + 16u : YR_DEAD;
         xpitch[i] = (unsigned)(a.W * ld) * 4u;
         vcc[i] = cs - a.ckl[cc];                // valid channels of the chunk (>= 32: all)
     }
@@ -163,11 +163,11 @@ __global__ __launch_bounds__(256, NKE >= 2 && !(PRE && NKE == 4) ? HW_OCC_SHARED
             const unsigned so = (unsigned)((rc >> 1) * (a.W >> 1) * a.pre_ld) * 4u;
 #pragma unroll
             for (int j = 0; j < NT; ++j)
-                x.p[j] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(prs, t0 + j < a.T ? pcol + 64u * (t0 + j) : MBR_DEAD, so, 0));
+                x.p[j] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(prs, t0 + j < a.T ? pcol + 64u * (t0 + j) : YR_DEAD, so, 0));
         }
     };
     // the float16 planes of slot i of a fetched row (a source's last chunk: the lanes of a partial quad may hold anything - pad channels)
-    auto cut = [&](const XRow& x, const int i, mbs_u4& xh, mbs_u4& xm) __attribute__((always_inline)) {
+    auto cut = [&](const XRow& x, const int i, v4u& xh, v4u& xm) __attribute__((always_inline)) {
         float v[8] = {x.m[2 * i][0], x.m[2 * i][1], x.m[2 * i][2], x.m[2 * i][3], x.m[2 * i + 1][0], x.m[2 * i + 1][1], x.m[2 * i + 1][2], x.m[2 * i + 1][3]};
         if (vcc[i] < 32) {   // uniform
 #pragma unroll
@@ -179,14 +179,14 @@ __global__ __launch_bounds__(256, NKE >= 2 && !(PRE && NKE == 4) ? HW_OCC_SHARED
     // operand.  In step k a wave fetches its slots of row k + 2, cuts those of row k + 1 (fetched a step ago) into buffer (k + 1) & 1
     // and multiplies row k out of buffer k & 1; ONE barrier per row: the buffer written in step k was last read in step k - 1.
     // Only the LDS traffic is waited for (lgkmcnt(0)) - the row in flight and the output stores stay in flight across the barrier.
-    mbs_u4* const xl = reinterpret_cast<mbs_u4*>(tab + a.T * MBR_TAB) + lane;
+    v4u* const xl = reinterpret_cast<v4u*>(tab + a.T * MBR_TAB) + lane;
     auto park = [&](const XRow& x, const int buf) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < NOWN; ++i)
             if (own[i]) {
-                mbs_u4 xh, xm;
+                v4u xh, xm;
                 cut(x, i, xh, xm);
-                mbs_u4* const w = xl + ((buf * NKE + wave + 4 * i) * 2) * 64;
+                v4u* const w = xl + ((buf * NKE + wave + 4 * i) * 2) * 64;
                 w[0] = xh;
                 w[64] = xm;
             }
@@ -232,9 +232,9 @@ __global__ __launch_bounds__(256, NKE >= 2 && !(PRE && NKE == 4) ? HW_OCC_SHARED
         }
 #pragma unroll
         for (int c = 0; c < NKE; ++c) {
-            mbs_u4 xh, xm;
+            v4u xh, xm;
             if constexpr (SHARED) {
-                const mbs_u4* const rd = xl + ((PAR * NKE + c) * 2) * 64;
+                const v4u* const rd = xl + ((PAR * NKE + c) * 2) * 64;
                 xh = rd[0];
                 xm = rd[64];
             } else {
@@ -271,8 +271,8 @@ __global__ __launch_bounds__(256, NKE >= 2 && !(PRE && NKE == 4) ? HW_OCC_SHARED
 #pragma unroll
                     for (int i = 0; i < 4; ++i) d[i] = __builtin_amdgcn_fmed3f(d[i], 0.f, 6.f);
                 }
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, d), osrc, ooff[j] == MBR_DEAD ? MBR_DEAD : opix + ooff[j], 0, 0);
-                if (ooff[j] != MBR_DEAD) psum[j] += d;
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, d), osrc, ooff[j] == YR_DEAD ? YR_DEAD : opix + ooff[j], 0, 0);
+                if (ooff[j] != YR_DEAD) psum[j] += d;
             }
         }
 #pragma unroll

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256, 2) void hwalkh_kernel(HwhArgs a) {
         for (int c = 0; c < NKE; ++c) wf[j][c] = pe[c * 64];
         se[j] = *reinterpret_cast<const v4f*>(a.wt + (size_t)t * MBR_TAB + 160 + 4 * mg);
         psc[j] = *reinterpret_cast<const v4f*>(a.scale + 16 * t + 4 * mg);
-        ooff[j] = (t0 + j < a.T && out_lane) ? (16u * (t0 + j) + 4u * mg) * 2u : MBR_DEAD;
+        ooff[j] = (t0 + j < a.T && out_lane) ? (16u * (t0 + j) + 4u * mg) * 2u : YR_DEAD;
     }
     if constexpr (GATED) {
         // W (g . x) = (W diag g) x and the wave works on ONE image: its fragments take the gate once (float32 product, one rounding)
@@ -83,11 +83,11 @@ __global__ __launch_bounds__(256, 2) void hwalkh_kernel(HwhArgs a) {
         }
     }
     // ---- descriptors: one per source (whole batch: 32-bit offsets, the launcher checks the sizes), the addend, the output image
-    const mbr_rsrc rs0 = mbr_make_rsrc(a.src[0], 0x7effffffu);
-    const mbr_rsrc rs1 = mbr_make_rsrc(a.nsrc > 1 ? a.src[1] : a.src[0], 0x7effffffu);
-    const mbr_rsrc rs2 = mbr_make_rsrc(a.nsrc > 2 ? a.src[2] : a.src[0], 0x7effffffu);
-    const mbr_rsrc prs = mbr_make_rsrc(PRE ? (const void*)(a.pre + (size_t)b * (a.H >> 1) * (a.W >> 1) * a.pre_ld) : a.src[0], PRE ? (unsigned)((a.H >> 1) * (a.W >> 1) * a.pre_ld) * 4u : 0u);
-    const mbr_rsrc osrc = mbr_make_rsrc(reinterpret_cast<char*>(a.out) + (size_t)b * a.H * a.W * a.ld_out * 2, (unsigned)(a.H * a.W * a.ld_out) * 2u);
+    const yr_rsrc rs0 = yr_make_rsrc(a.src[0], 0x7effffffu);
+    const yr_rsrc rs1 = yr_make_rsrc(a.nsrc > 1 ? a.src[1] : a.src[0], 0x7effffffu);
+    const yr_rsrc rs2 = yr_make_rsrc(a.nsrc > 2 ? a.src[2] : a.src[0], 0x7effffffu);
+    const yr_rsrc prs = yr_make_rsrc(PRE ? (const void*)(a.pre + (size_t)b * (a.H >> 1) * (a.W >> 1) * a.pre_ld) : a.src[0], PRE ? (unsigned)((a.H >> 1) * (a.W >> 1) * a.pre_ld) * 4u : 0u);
+    const yr_rsrc osrc = yr_make_rsrc(reinterpret_cast<char*>(a.out) + (size_t)b * a.H * a.W * a.ld_out * 2, (unsigned)(a.H * a.W * a.ld_out) * 2u);
     // per chunk: byte offset of this lane's 8 channels in its pixel (row offset added per row), or dead; the row pitch of its source
     unsigned xsoff[NKE], xpitch[NKE];
     int vcc[NKE];
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(256, 2) void hwalkh_kernel(HwhArgs a) {
     for (int c = 0; c < NKE; ++c) {
         const int s = a.csrc[c], kl = a.ckl[c] + 8 * mg;
         const int cs = s == 0 ? a.cs[0] : s == 1 ? a.cs[1] : a.cs[2], ld = s == 0 ? a.ld[0] : s == 1 ? a.ld[1] : a.ld[2];
-        xsoff[c] = kl < ((cs + 7) & ~7) ? (unsigned)((b * a.H * a.W + xc) * ld + kl) * 2u : MBR_DEAD;
+        xsoff[c] = kl < ((cs + 7) & ~7) ? (unsigned)((b * a.H * a.W + xc) * ld + kl) * 2u : YR_DEAD;
         xpitch[c] = (unsigned)(a.W * ld) * 2u;
         vcc[c] = cs - a.ckl[c];                 // valid channels of the chunk (>= 32: all)
     }
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(256, 2) void hwalkh_kernel(HwhArgs a) {
             const unsigned so = (unsigned)((rc >> 1) * (a.W >> 1) * a.pre_ld) * 4u;
 #pragma unroll
             for (int j = 0; j < NT; ++j)
-                x.p[j] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(prs, t0 + j < a.T ? pcol + 64u * (t0 + j) : MBR_DEAD, so, 0));
+                x.p[j] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(prs, t0 + j < a.T ? pcol + 64u * (t0 + j) : YR_DEAD, so, 0));
         }
     };
     const int rbeg = yo0 - 1, nout = yo1 - yo0;
@@ -172,8 +172,8 @@ __global__ __launch_bounds__(256, 2) void hwalkh_kernel(HwhArgs a) {
                     for (int i = 0; i < 4; ++i) d[i] = __builtin_amdgcn_fmed3f(d[i], 0.f, 6.f);
                 }
                 const t4 q = __builtin_convertvector(d, t4);         // the one rounding to the 16-bit type
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, q), osrc, ooff[j] == MBR_DEAD ? MBR_DEAD : opix + ooff[j], 0, 0);
-                if (ooff[j] != MBR_DEAD) psum[j] += __builtin_convertvector(q, v4f);   // sums of what was stored
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, q), osrc, ooff[j] == YR_DEAD ? YR_DEAD : opix + ooff[j], 0, 0);
+                if (ooff[j] != YR_DEAD) psum[j] += __builtin_convertvector(q, v4f);   // sums of what was stored
             }
         }
 #pragma unroll

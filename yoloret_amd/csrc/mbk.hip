@@ -100,9 +100,9 @@ __global__ __launch_bounds__(64 * NW) void mbk_kernel(MbkArgs a) {
     const int xo = NOUT * strip + (S == 2 ? (px & 7) : px - 1);
     const bool out_lane = (S == 2 ? px < 7 : (px >= 1 && px <= 14)) && xo < a.Wo;
 
-    const mbr_rsrc xsrc = mbr_make_rsrc(a.x + (size_t)b * a.H * a.W * a.ld_in, (unsigned)(a.H * a.W * a.ld_in) * 4u);
-    const mbr_rsrc osrc = mbr_make_rsrc(a.out + (size_t)b * a.Ho * a.Wo * a.ld_out, (unsigned)(a.Ho * a.Wo * a.ld_out) * 4u);
-    const mbr_rsrc wsrc = mbr_make_rsrc(a.wa, a.wa_bytes);
+    const yr_rsrc xsrc = yr_make_rsrc(a.x + (size_t)b * a.H * a.W * a.ld_in, (unsigned)(a.H * a.W * a.ld_in) * 4u);
+    const yr_rsrc osrc = yr_make_rsrc(a.out + (size_t)b * a.Ho * a.Wo * a.ld_out, (unsigned)(a.Ho * a.Wo * a.ld_out) * 4u);
+    const yr_rsrc wsrc = yr_make_rsrc(a.wa, a.wa_bytes);
 
     // ---- the weight stream: chunk q -> buffer q & 1, 1 KB pieces shared out over the waves
     auto issue_chunk = [&](const int q) {
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(64 * NW) void mbk_kernel(MbkArgs a) {
     }
 
     // ---- the wave's pixels: float16 planes of its rows, cut once (step c = the lane's channels 32 c + 8 mg .. + 7; zeros beyond the block input)
-    mbs_u4 xh[ROWS][NKE], xm[ROWS][NKE];
+    v4u xh[ROWS][NKE], xm[ROWS][NKE];
     float hr[ROWS];
 #pragma unroll
     for (int i = 0; i < ROWS; ++i) {
@@ -140,9 +140,9 @@ __global__ __launch_bounds__(64 * NW) void mbk_kernel(MbkArgs a) {
         v4f lo[NKE], hi[NKE];
 #pragma unroll
         for (int c = 0; c < NKE; ++c) {
-            const unsigned off = 32 * c + 8 * mg < CIN ? ((unsigned)xc * (unsigned)a.ld_in + 32u * c + 8u * mg) * 4u : MBR_DEAD;
+            const unsigned off = 32 * c + 8 * mg < CIN ? ((unsigned)xc * (unsigned)a.ld_in + 32u * c + 8u * mg) * 4u : YR_DEAD;
             lo[c] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(xsrc, off, so, 0));
-            hi[c] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(xsrc, off == MBR_DEAD ? MBR_DEAD : off + 16u, so, 0));
+            hi[c] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(xsrc, off == YR_DEAD ? YR_DEAD : off + 16u, so, 0));
         }
 #pragma unroll
         for (int c = 0; c < NKE; ++c) {
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(64 * NW) void mbk_kernel(MbkArgs a) {
 #pragma unroll
                 for (int s = 0; s < 4; ++s) d[i][j][s] = __builtin_amdgcn_fmed3f(d[i][j][s], 0.f, 6.f);
         }
-        mbs_u4 bh[NE], bm[NE];
+        v4u bh[NE], bm[NE];
 #pragma unroll
         for (int i = 0; i < NE; ++i) {
             const float v[8] = {d[i][0][0], d[i][0][1], d[i][0][2], d[i][0][3], d[i][1][0], d[i][1][1], d[i][1][2], d[i][1][3]};
@@ -337,7 +337,7 @@ __global__ __launch_bounds__(64 * NW) void mbk_kernel(MbkArgs a) {
         // phase 2 (VALU): ReLU6 of the depthwise results, the float16 planes of the pair's 8 values per lane
         u4 pf[2][2];
         pf[0][0] = fp[0]; pf[0][1] = fp[64];
-        mbs_u4 bh[NE], bm[NE];
+        v4u bh[NE], bm[NE];
 #pragma unroll
         for (int i = 0; i < NE; ++i) {
 #pragma unroll
@@ -417,11 +417,11 @@ __global__ __launch_bounds__(64 * NW) void mbk_kernel(MbkArgs a) {
         const int y = S == 1 ? rin[i] : yo;
         const bool live = emit[i] && out_lane;
         const unsigned opix = ((unsigned)max(y, 0) * (unsigned)a.Wo + (unsigned)xo);
-        oaddr[i] = live ? opix * (unsigned)a.ld_out * 4u : MBR_DEAD;
+        oaddr[i] = live ? opix * (unsigned)a.ld_out * 4u : YR_DEAD;
         if constexpr (RES) {
 #pragma unroll
             for (int t = 0; t < TO; ++t)
-                res[i][t] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(xsrc, live && 16 * t + 4 * mg < COUT ? (opix * (unsigned)a.ld_in + 16u * t + 4u * mg) * 4u : MBR_DEAD, 0, 0));
+                res[i][t] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(xsrc, live && 16 * t + 4 * mg < COUT ? (opix * (unsigned)a.ld_in + 16u * t + 4u * mg) * 4u : YR_DEAD, 0, 0));
         }
     }
 #pragma unroll
@@ -438,7 +438,7 @@ __global__ __launch_bounds__(64 * NW) void mbk_kernel(MbkArgs a) {
             const int co = 16 * t + 4 * mg;
             v4f v = __builtin_elementwise_fma(P1[i][t], k11, P[i][t]) + psh[t];
             if constexpr (RES) v += res[i][t];
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, v), osrc, oaddr[i] != MBR_DEAD && co < COUT ? oaddr[i] + (unsigned)co * 4u : MBR_DEAD, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, v), osrc, oaddr[i] != YR_DEAD && co < COUT ? oaddr[i] + (unsigned)co * 4u : YR_DEAD, 0, 0);
         }
     }
 #ifdef MBK_TIMING
@@ -472,22 +472,8 @@ static int launch_mbk(const MbkArgs& a0, int batch, hipStream_t s) {
     a.segs = mbk_segs(S, a.H, a.Ho, a.pad_t, NW, ROWS);
     a.wa_bytes = (unsigned)NQ * CHB;
     const size_t lds = (size_t)3 * CHB + (size_t)2 * (NW + 2) * (S == 1 && ROWS > 1 ? 2 : 1) * 2 * 1024;
-    static char nm[64];
-    static const int nm_len = snprintf(nm, sizeof(nm), "mbk_kernel<%d,%d,%d,%d,%d,%d,%d>", CIN, CEXP, COUT, S, ROWS, NW, (int)RES);
-    (void)nm_len;
-    yr_note_kernel(nm);
-    auto kern = mbk_kernel<CIN, CEXP, COUT, S, ROWS, NW, RES, EXP>;
-    static bool attr_set_dev[64] = {};   // per device
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    bool& attr_set = attr_set_dev[cur_dev & 63];
-    if (!attr_set) {
-        YR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(batch * a.strips * a.segs)), dim3(64 * NW), lds, s, a);
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+    return ch_launch<mbk_kernel<CIN, CEXP, COUT, S, ROWS, NW, RES, EXP>>(dim3((unsigned)(batch * a.strips * a.segs)), dim3(64 * NW), lds, lds, s, a,
+                                                                         "mbk_kernel<%d,%d,%d,%d,%d,%d,%d>", CIN, CEXP, COUT, S, ROWS, NW, (int)RES);
 }
 
 // YR_OP_MBR with YR_MBR_STREAM (and YR_MBR_SPLIT: the operands are float16 planes): the weight-streaming form.  Op fields as YR_OP_MBR; YR_MBR_NW_MASK =

@@ -70,7 +70,7 @@ __device__ __forceinline__ void mbr_body(const MbrArgs& a, const int t0, const i
 
     // ---- stationary A fragments of this wave's tiles
     float we[SP ? 1 : NT][SP ? 1 : KE], wp[SP ? 1 : NT][TO][4];
-    mbs_u4 weh[SP ? NT : 1][NKE], wem[SP ? NT : 1][NKE], wph[SP ? NP : 1][TO], wpm[SP ? NP : 1][TO];
+    v4u weh[SP ? NT : 1][NKE], wem[SP ? NT : 1][NKE], wph[SP ? NP : 1][TO], wpm[SP ? NP : 1][TO];
     v4f se[NT];
     if constexpr (!SP) {
 #pragma unroll
@@ -84,7 +84,7 @@ __device__ __forceinline__ void mbr_body(const MbrArgs& a, const int t0, const i
                 for (int s = 0; s < 4; ++s) wp[j][t][s] = p[(KE + 4 * t + s) * 64];
         }
     } else {   // [T][NKE][2 planes][64 lanes] x 16 bytes, then per (wave's tile pair)[TO][2 planes][64] (compiler.mbs_pack)
-        const mbs_u4* pe = reinterpret_cast<const mbs_u4*>(a.wa);
+        const v4u* pe = reinterpret_cast<const v4u*>(a.wa);
 #pragma unroll
         for (int j = 0; j < NT; ++j)
 #pragma unroll
@@ -94,7 +94,7 @@ __device__ __forceinline__ void mbr_body(const MbrArgs& a, const int t0, const i
             }
         constexpr int TT = CEXP / 16, NTL_ = TT / NW, R_ = TT % NW, NTH_ = NTL_ + (R_ ? 1 : 0);
         const int pair0 = w < R_ ? w * ((NTH_ + 1) / 2) : R_ * ((NTH_ + 1) / 2) + (w - R_) * ((NTL_ + 1) / 2);   // the pairs of the waves before this one
-        const mbs_u4* pp = pe + (size_t)TT * NKE * 2 * 64;
+        const v4u* pp = pe + (size_t)TT * NKE * 2 * 64;
 #pragma unroll
         for (int q = 0; q < NP; ++q)
 #pragma unroll
@@ -114,8 +114,8 @@ __device__ __forceinline__ void mbr_body(const MbrArgs& a, const int t0, const i
     // Every global access of the walk is UNCONDITIONAL, through buffer descriptors (dead lanes pass an offset beyond
     // num_records): the compiler can then COUNT the outstanding operations, and the wait for the next row's pixels does
     // not wait for the store just issued (a store under a per-lane branch turns every later wait into vmcnt(0)).
-    const mbr_rsrc xsrc = mbr_make_rsrc(a.x + (size_t)b * a.H * a.W * a.ld_in, (unsigned)(a.H * a.W * a.ld_in) * 4u);
-    const mbr_rsrc osrc = mbr_make_rsrc(a.out + (size_t)b * a.Ho * a.Wo * a.ld_out, (unsigned)(a.Ho * a.Wo * a.ld_out) * 4u);
+    const yr_rsrc xsrc = yr_make_rsrc(a.x + (size_t)b * a.H * a.W * a.ld_in, (unsigned)(a.H * a.W * a.ld_in) * 4u);
+    const yr_rsrc osrc = yr_make_rsrc(a.out + (size_t)b * a.Ho * a.Wo * a.ld_out, (unsigned)(a.Ho * a.Wo * a.ld_out) * 4u);
     const int rbeg = S * yo0 - a.pad_t, nout = yo1 - yo0;
     const unsigned xoff = ((unsigned)xc * (unsigned)a.ld_in + 4u * mg) * 4u, xtoff = ((unsigned)xc * (unsigned)a.ld_in + 16u * NMAIN + 2u * mg) * 4u;
     const unsigned xrow = (unsigned)(a.W * a.ld_in) * 4u;
@@ -126,7 +126,7 @@ __device__ __forceinline__ void mbr_body(const MbrArgs& a, const int t0, const i
     unsigned xsoff[SP ? NKE : 1];
     if constexpr (SP) {
 #pragma unroll
-        for (int c = 0; c < NKE; ++c) xsoff[c] = 32 * c + 8 * mg < CIN ? ((unsigned)xc * (unsigned)a.ld_in + 32u * c + 8u * mg) * 4u : MBR_DEAD;
+        for (int c = 0; c < NKE; ++c) xsoff[c] = 32 * c + 8 * mg < CIN ? ((unsigned)xc * (unsigned)a.ld_in + 32u * c + 8u * mg) * 4u : YR_DEAD;
     }
     auto load_row = [&](XRow& x, int r) {
         const unsigned so = (unsigned)min(max(r, 0), a.H - 1) * xrow;
@@ -134,7 +134,7 @@ __device__ __forceinline__ void mbr_body(const MbrArgs& a, const int t0, const i
 #pragma unroll
             for (int c = 0; c < NKE; ++c) {
                 x.m[2 * c] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xsoff[c], so, 0));
-                x.m[2 * c + 1] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xsoff[c] == MBR_DEAD ? MBR_DEAD : xsoff[c] + 16u, so, 0));
+                x.m[2 * c + 1] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xsoff[c] == YR_DEAD ? YR_DEAD : xsoff[c] + 16u, so, 0));
             }
         } else {
 #pragma unroll
@@ -170,7 +170,7 @@ __device__ __forceinline__ void mbr_body(const MbrArgs& a, const int t0, const i
         const int r = rbeg + k;
         load_row(xn_, r + 1);
         float xq[SP ? 1 : KE];
-        mbs_u4 xh[SP ? NKE : 1], xm[SP ? NKE : 1];
+        v4u xh[SP ? NKE : 1], xm[SP ? NKE : 1];
         if constexpr (SP) {
 #pragma unroll
             for (int c = 0; c < NKE; ++c) {
@@ -185,7 +185,7 @@ __device__ __forceinline__ void mbr_body(const MbrArgs& a, const int t0, const i
         if constexpr (EMIT && RES) {
 #pragma unroll
             for (int tt = 0; tt < NF; ++tt) {
-                const unsigned off = flive[tt] ? (((unsigned)yo * (unsigned)a.Wo + (unsigned)xo) * (unsigned)a.ld_in + 16u * (w + tt * NW) + 4u * mg) * 4u : MBR_DEAD;
+                const unsigned off = flive[tt] ? (((unsigned)yo * (unsigned)a.Wo + (unsigned)xo) * (unsigned)a.ld_in + 16u * (w + tt * NW) + 4u * mg) * 4u : YR_DEAD;
                 fres[tt] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(xsrc, off, 0, 0));
             }
         }
@@ -232,7 +232,7 @@ __device__ __forceinline__ void mbr_body(const MbrArgs& a, const int t0, const i
         // SP: the projection of one tile pair - the 8 depthwise results a lane holds are its 8 k values of the step
         auto project_pair = [&](const int q, const v4f dA, const v4f dB) {
             const float v[8] = {dA[0], dA[1], dA[2], dA[3], dB[0], dB[1], dB[2], dB[3]};
-            mbs_u4 bh, bm;
+            v4u bh, bm;
             mbs_split8(v, bh, bm);
 #pragma unroll
             for (int t = 0; t < TO; ++t) {
@@ -308,7 +308,7 @@ __device__ __forceinline__ void mbr_body(const MbrArgs& a, const int t0, const i
                 for (int t = 0; t < TO; ++t) {
                     v4f v = P[t] + fsh[t];
                     if (RES) v += fres[t];   // (after the sum: the load issued at the row's start is not waited for before here)
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, v), osrc, flive[t] && rlive ? opix + (16u * t + 4u * mg) * 4u : MBR_DEAD, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, v), osrc, flive[t] && rlive ? opix + (16u * t + 4u * mg) * 4u : YR_DEAD, 0, 0);
                 }
             } else {
                 v4f* rb = red + buf * (NW * TO * 64);
@@ -324,7 +324,7 @@ __device__ __forceinline__ void mbr_body(const MbrArgs& a, const int t0, const i
                         for (int ww = 0; ww < NW; ++ww) v += rb[(ww * TO + t) * 64 + lane];
                     }
                     if (RES) v += fres[tt];   // last: the residual load issued at the row's start is waited for only here
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, v), osrc, flive[tt] && rlive ? opix + (16u * t + 4u * mg) * 4u : MBR_DEAD, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, v), osrc, flive[tt] && rlive ? opix + (16u * t + 4u * mg) * 4u : YR_DEAD, 0, 0);
                 }
                 buf ^= 1;
             }
@@ -379,21 +379,9 @@ static int launch_mbr(const MbrArgs& a0, int batch, int want_segs, hipStream_t s
     MbrArgs a = a0;
     constexpr int T = CEXP / 16, TO = (COUT + 15) / 16, NOUT = 14 / S;
     a.strips = (a.Wo + NOUT - 1) / NOUT;
-    // segments: enough workgroups for ~2 generations of the chip's SIMDs, not so many that the 2 halo rows matter
-    const int walks = batch * a.strips;
-    int segs = (2 * 1024 + walks * NW - 1) / (walks * NW);
-    const int max_segs = (a.Ho + 5) / 6;
-    if (segs > max_segs) segs = max_segs;
-    if (segs < 1) segs = 1;
-    if (want_segs > 0) segs = want_segs < a.Ho ? want_segs : a.Ho;
-    a.seg_rows = (a.Ho + segs - 1) / segs;
-    if (S == 2) a.seg_rows += a.seg_rows & 1;   // (output rows are processed in pairs)
-    a.segs = (a.Ho + a.seg_rows - 1) / a.seg_rows;
+    // segments: enough workgroups for ~2 generations of the chip's SIMDs, not so many that the 2 halo rows matter; stride 2 walks pairs of output rows
+    a.seg_rows = ch_row_segments(a.Ho, batch * a.strips, NW, 2 * 1024, 6, S == 2, want_segs, &a.segs);
     const size_t lds = (size_t)T * MBR_TAB * 4 + (NW > 1 ? (size_t)2 * NW * TO * 64 * 16 : 0);
-    static char nm[64];
-    static const int nm_len = snprintf(nm, sizeof(nm), "mbr_kernel<%d,%d,%d,%d,%d,%d,%d>", CIN, CEXP, COUT, S, NW, (int)RES, (int)SP);   // (... SP = 1: the split form)
-    (void)nm_len;
-    yr_note_kernel(nm);
     // waves per SIMD the register allocator must leave room for, from an estimate of what a wave holds: the stationary
     // fragments + BN shifts, ring and new row, projection accumulators, two rows of pixel operands, ~44 others
     constexpr int NTH = (T + NW - 1) / NW, KE = CIN / 4;
@@ -403,18 +391,8 @@ static int launch_mbr(const MbrArgs& a0, int batch, int want_segs, hipStream_t s
     // (SP: measured register counts - the stride-1 three-wave kernels fit 168, the others spill there)
     constexpr int MW = SP ? (S == 1 && NW <= 3 ? 3 : 2) : EST <= 164 ? 3 : EST <= 250 ? 2 : 1;
     static_assert(NW <= 4 * MW, "a workgroup's waves must fit one CU at this register budget");
-    auto kern = mbr_kernel<CIN, CEXP, COUT, S, NW, RES, SP, MW>;   // waves per SIMD the register allocator must leave room for
-    static bool attr_set_dev[64] = {};   // per device: a process that drives several GPUs needs the attribute on each
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    bool& attr_set = attr_set_dev[cur_dev & 63];
-    if (!attr_set && lds > 48 * 1024) {
-        YR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(batch * a.strips * a.segs)), dim3(64 * NW), lds, s, a);
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+    return ch_launch<mbr_kernel<CIN, CEXP, COUT, S, NW, RES, SP, MW>>(dim3((unsigned)(batch * a.strips * a.segs)), dim3(64 * NW), lds, lds, s, a,
+                                                                      "mbr_kernel<%d,%d,%d,%d,%d,%d,%d>", CIN, CEXP, COUT, S, NW, (int)RES, (int)SP);   // (... SP = 1: the split form)
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -455,14 +433,14 @@ __global__ __launch_bounds__(256, MW) void mbe_kernel(MbeArgs a) {
     const bool out_lane = px >= 1 && px <= 14 && (px - 1) % S == 0 && xo < a.Wo;
 
     float we[SP ? 1 : NT][SP ? 1 : KE];
-    mbs_u4 weh[SP ? NT : 1][NKE], wem[SP ? NT : 1][NKE];
+    v4u weh[SP ? NT : 1][NKE], wem[SP ? NT : 1][NKE];
     v4f se[NT];
     unsigned ooff[NT];   // byte offset of this lane's 4 channels of tile j within a pixel, or dead
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
         const int t = min(t0 + j, a.T - 1);           // (a short last group recomputes the last tile; its stores are dead)
         if constexpr (SP) {
-            const mbs_u4* pe = reinterpret_cast<const mbs_u4*>(a.wa) + ((size_t)t * NKE) * 2 * 64 + lane;
+            const v4u* pe = reinterpret_cast<const v4u*>(a.wa) + ((size_t)t * NKE) * 2 * 64 + lane;
 #pragma unroll
             for (int c = 0; c < NKE; ++c) { weh[j][c] = pe[(2 * c) * 64]; wem[j][c] = pe[(2 * c + 1) * 64]; }
         } else {
@@ -471,10 +449,10 @@ __global__ __launch_bounds__(256, MW) void mbe_kernel(MbeArgs a) {
             for (int q = 0; q < KE; ++q) we[j][q] = p[q * 64];
         }
         se[j] = *reinterpret_cast<const v4f*>(a.wt + (size_t)t * MBR_TAB + 160 + 4 * mg);
-        ooff[j] = (t0 + j < a.T && out_lane) ? (16u * (t0 + j) + 4u * mg) * 4u : MBR_DEAD;
+        ooff[j] = (t0 + j < a.T && out_lane) ? (16u * (t0 + j) + 4u * mg) * 4u : YR_DEAD;
     }
-    const mbr_rsrc xsrc = mbr_make_rsrc(a.x + (size_t)b * a.H * a.W * a.ld_in, (unsigned)(a.H * a.W * a.ld_in) * 4u);
-    const mbr_rsrc osrc = mbr_make_rsrc(a.out + (size_t)b * a.Ho * a.Wo * a.ld_out, (unsigned)(a.Ho * a.Wo * a.ld_out) * 4u);
+    const yr_rsrc xsrc = yr_make_rsrc(a.x + (size_t)b * a.H * a.W * a.ld_in, (unsigned)(a.H * a.W * a.ld_in) * 4u);
+    const yr_rsrc osrc = yr_make_rsrc(a.out + (size_t)b * a.Ho * a.Wo * a.ld_out, (unsigned)(a.Ho * a.Wo * a.ld_out) * 4u);
     const int rbeg = S * yo0 - a.pad_t, nout = yo1 - yo0;
     const unsigned xoff = ((unsigned)xc * (unsigned)a.ld_in + 4u * mg) * 4u, xtoff = ((unsigned)xc * (unsigned)a.ld_in + 16u * NMAIN + 2u * mg) * 4u;
     const unsigned xrow = (unsigned)(a.W * a.ld_in) * 4u;
@@ -483,7 +461,7 @@ __global__ __launch_bounds__(256, MW) void mbe_kernel(MbeArgs a) {
     unsigned xsoff[SP ? NKE : 1];   // SP: step c takes the lane's channels 32 c + 8 g .. + 7 (a group beyond the block input reads zeros)
     if constexpr (SP) {
 #pragma unroll
-        for (int c = 0; c < NKE; ++c) xsoff[c] = 32 * c + 8 * mg < CIN ? ((unsigned)xc * (unsigned)a.ld_in + 32u * c + 8u * mg) * 4u : MBR_DEAD;
+        for (int c = 0; c < NKE; ++c) xsoff[c] = 32 * c + 8 * mg < CIN ? ((unsigned)xc * (unsigned)a.ld_in + 32u * c + 8u * mg) * 4u : YR_DEAD;
     }
     auto load_row = [&](XRow& x, int r) {
         const unsigned so = (unsigned)min(max(r, 0), a.H - 1) * xrow;
@@ -491,7 +469,7 @@ __global__ __launch_bounds__(256, MW) void mbe_kernel(MbeArgs a) {
 #pragma unroll
             for (int c = 0; c < NKE; ++c) {
                 x.m[2 * c] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xsoff[c], so, 0));
-                x.m[2 * c + 1] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xsoff[c] == MBR_DEAD ? MBR_DEAD : xsoff[c] + 16u, so, 0));
+                x.m[2 * c + 1] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xsoff[c] == YR_DEAD ? YR_DEAD : xsoff[c] + 16u, so, 0));
             }
         } else {
 #pragma unroll
@@ -519,7 +497,7 @@ __global__ __launch_bounds__(256, MW) void mbe_kernel(MbeArgs a) {
 #pragma unroll
             for (int c = 0; c < NKE; ++c) {
                 const float v[8] = {xc_.m[2 * c][0], xc_.m[2 * c][1], xc_.m[2 * c][2], xc_.m[2 * c][3], xc_.m[2 * c + 1][0], xc_.m[2 * c + 1][1], xc_.m[2 * c + 1][2], xc_.m[2 * c + 1][3]};
-                mbs_u4 xh, xm;
+                v4u xh, xm;
                 mbs_split8(v, xh, xm);
 #pragma unroll
                 for (int j = 0; j < NT; ++j) ec[j] = mbs_mfma(weh[j][c], xh, ec[j]);
@@ -555,7 +533,7 @@ __global__ __launch_bounds__(256, MW) void mbe_kernel(MbeArgs a) {
                 mbr_dw_row(d, ec[j], tb[24], tb[28], tb[32]);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) d[i] = __builtin_amdgcn_fmed3f(d[i], 0.f, 6.f);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, d), osrc, ooff[j] == MBR_DEAD ? MBR_DEAD : opix + ooff[j], 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, d), osrc, ooff[j] == YR_DEAD ? YR_DEAD : opix + ooff[j], 0, 0);
             }
         }
 #pragma unroll
@@ -589,33 +567,13 @@ static int launch_mbe(const MbeArgs& a0, int batch, int want_segs, hipStream_t s
     constexpr int MW = EST <= 150 ? 3 : EST <= 250 ? 2 : 1;
     a.strips = (a.Wo + NOUT - 1) / NOUT;
     a.groups = (a.T + NT - 1) / NT;
-    const int walks = batch * a.strips * a.groups;             // waves at one segment per strip
-    int segs = (3 * 1024 + walks - 1) / walks;                 // ~3 waves per SIMD of the chip
-    const int max_segs = (a.Ho + 5) / 6;
-    if (segs > max_segs) segs = max_segs;
-    if (segs < 1) segs = 1;
-    if (want_segs > 0) segs = want_segs < a.Ho ? want_segs : a.Ho;
-    a.seg_rows = (a.Ho + segs - 1) / segs;
-    a.segs = (a.Ho + a.seg_rows - 1) / a.seg_rows;
+    // waves at one segment per strip: batch * strips * groups; ~3 waves per SIMD of the chip
+    a.seg_rows = ch_row_segments(a.Ho, batch * a.strips * a.groups, 1, 3 * 1024, 6, false, want_segs, &a.segs);
     a.nwaves = batch * a.strips * a.segs * a.groups;
     const size_t lds = (size_t)a.T * MBR_TAB * 4;
     YR_REQUIRE(lds <= 64 * 1024, "mbe: %d expanded channels exceed the depthwise table's LDS budget", a.T * 16);
-    static char nm[48];
-    static const int nm_len = snprintf(nm, sizeof(nm), "mbe_kernel<%d,%d,%d,%d,%d>", CIN, S, NT, MW, (int)SP);   // (... SP = 1: the split form)
-    (void)nm_len;
-    yr_note_kernel(nm);
-    auto kern = mbe_kernel<CIN, S, NT, MW, SP>;
-    static bool attr_set_dev[64] = {};   // per device
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    bool& attr_set = attr_set_dev[cur_dev & 63];
-    if (!attr_set) {
-        YR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)((a.nwaves + 3) / 4)), dim3(256), lds, s, a);
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+    return ch_launch<mbe_kernel<CIN, S, NT, MW, SP>>(dim3((unsigned)((a.nwaves + 3) / 4)), dim3(256), lds, 64 * 1024, s, a,
+                                                     "mbe_kernel<%d,%d,%d,%d,%d>", CIN, S, NT, MW, (int)SP);   // (... SP = 1: the split form)
 }
 
 // op fields: src[0] = block input (float32, c % 16 in {0, 8}); cout = Cexp = width of the stored depthwise map (multiple of 16);

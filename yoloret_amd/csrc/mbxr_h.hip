@@ -18,15 +18,11 @@
 // and tw = row segments per strip (0: the launcher's choice) - yr_autotune times it next to the LDS-tiled tiles.
 // Numerics: expand accumulates in float32, BN in float32, activation (swish: hardware exp2 + rcp, as mbh.hip), the expanded
 // value stays float32 (never rounded), depthwise in float32 with the BN scale folded into the taps, one rounding at the store.
-#include "yr_common.h"
+#include "chained_common.h"
 #include <type_traits>
 #include <cstdlib>
 
-typedef float xr_f4 __attribute__((ext_vector_type(4)));
-typedef unsigned xr_u4 __attribute__((ext_vector_type(4)));
-typedef unsigned xr_u2 __attribute__((ext_vector_type(2)));
 template <class T> using xr_v8 = T __attribute__((ext_vector_type(8)));
-typedef __amdgpu_buffer_rsrc_t xr_rsrc;
 
 struct MbxrArgs {
     const void* x; void* out; const void* we; const float* prm;
@@ -36,14 +32,8 @@ struct MbxrArgs {
     int qrows, nquanta;   // the squeeze sums leave per (strip, quantum of qrows output rows): grouped by the map's SHAPE, whatever the segments
 };
 
-__device__ __forceinline__ xr_rsrc xr_make_rsrc(const void* base, unsigned bytes) {
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)base), hi = __builtin_amdgcn_readfirstlane((unsigned)((uintptr_t)base >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)hi << 32) | lo), 0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
-#define XR_DEAD 0x7f000000u
-
 template <class T>
-__device__ __forceinline__ xr_f4 xr_mfma(xr_u4 w, xr_u4 x, xr_f4 acc) {
+__device__ __forceinline__ v4f xr_mfma(v4u w, v4u x, v4f acc) {
     if constexpr (yr_elem<T>::dtype == YR_BF16)
         return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(xr_v8<__bf16>, w), __builtin_bit_cast(xr_v8<__bf16>, x), acc, 0, 0, 0);
     else
@@ -52,7 +42,7 @@ __device__ __forceinline__ xr_f4 xr_mfma(xr_u4 w, xr_u4 x, xr_f4 acc) {
 
 // ... and the 16-deep step (v_mfma_f32_16x16x16_{bf16,f16}): B = the lane's 4 values of k = 4 g .. 4 g + 3
 template <class T>
-__device__ __forceinline__ xr_f4 xr_mfma16(xr_u2 w, xr_u2 x, xr_f4 acc) {
+__device__ __forceinline__ v4f xr_mfma16(v2u w, v2u x, v4f acc) {
     typedef short xr_s4 __attribute__((ext_vector_type(4)));
     typedef _Float16 xr_h4 __attribute__((ext_vector_type(4)));
     if constexpr (yr_elem<T>::dtype == YR_BF16)
@@ -61,42 +51,21 @@ __device__ __forceinline__ xr_f4 xr_mfma16(xr_u2 w, xr_u2 x, xr_f4 acc) {
         return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(xr_h4, w), __builtin_bit_cast(xr_h4, x), acc, 0, 0, 0);
 }
 
-// one tap ROW of the depthwise conv for the lane's 4 channels (see mbr.hip: the DPP shift rides on v_fmac's first operand,
-// the four channels' chains interleaved tap-major; s_nop 1 covers the VALU-write -> DPP-read hazard the compiler cannot see)
-#define XR_DPP(ctl) " " ctl " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-__device__ __forceinline__ void xr_row3(xr_f4& acc, const xr_f4 e, const xr_f4 w0, const xr_f4 w1, const xr_f4 w2) {
+// one tap ROW of the depthwise conv for the lane's 4 channels (the DPP tap group and its rules: chained_common.h)
+__device__ __forceinline__ void xr_row3(v4f& acc, const v4f e, const v4f w0, const v4f w1, const v4f w2) {
     float a0 = acc[0], a1 = acc[1], a2 = acc[2], a3 = acc[3];
-    asm("s_nop 1\n\t"
-        "v_fmac_f32_dpp %0, %4, %8" XR_DPP("row_shr:1") "v_fmac_f32_dpp %1, %5, %9" XR_DPP("row_shr:1")
-        "v_fmac_f32_dpp %2, %6, %10" XR_DPP("row_shr:1") "v_fmac_f32_dpp %3, %7, %11" XR_DPP("row_shr:1")
-        "v_fmac_f32 %0, %4, %12\n\t" "v_fmac_f32 %1, %5, %13\n\t" "v_fmac_f32 %2, %6, %14\n\t" "v_fmac_f32 %3, %7, %15\n\t"
-        "v_fmac_f32_dpp %0, %4, %16" XR_DPP("row_shl:1") "v_fmac_f32_dpp %1, %5, %17" XR_DPP("row_shl:1")
-        "v_fmac_f32_dpp %2, %6, %18" XR_DPP("row_shl:1") "v_fmac_f32_dpp %3, %7, %19" XR_DPP("row_shl:1")
-        : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3)
-        : "v"(e[0]), "v"(e[1]), "v"(e[2]), "v"(e[3]), "v"(w0[0]), "v"(w0[1]), "v"(w0[2]), "v"(w0[3]),
-          "v"(w1[0]), "v"(w1[1]), "v"(w1[2]), "v"(w1[3]), "v"(w2[0]), "v"(w2[1]), "v"(w2[2]), "v"(w2[3]));
-    acc = (xr_f4){a0, a1, a2, a3};
+    asm("s_nop 1\n\t" CH_FMAC_DPP(w0, CH_DPP("row_shr:1")) CH_FMAC(w1) CH_FMAC_DPP(w2, CH_DPP("row_shl:1"))
+        : CH_ACC4(a, a) : CH_IN4(e, e), CH_IN4(w0, w0), CH_IN4(w1, w1), CH_IN4(w2, w2));
+    acc = (v4f){a0, a1, a2, a3};
 }
-// five taps: two asm blocks (an asm statement takes at most 30 operands): taps 0..2 at row_shr:2, row_shr:1, 0; taps 3..4 at row_shl:1, row_shl:2
-__device__ __forceinline__ void xr_row5(xr_f4& acc, const xr_f4 e, const xr_f4 w0, const xr_f4 w1, const xr_f4 w2, const xr_f4 w3, const xr_f4 w4) {
+// five taps, two statements: taps 0..2 at row_shr:2, row_shr:1, 0; taps 3..4 at row_shl:1, row_shl:2
+__device__ __forceinline__ void xr_row5(v4f& acc, const v4f e, const v4f w0, const v4f w1, const v4f w2, const v4f w3, const v4f w4) {
     float a0 = acc[0], a1 = acc[1], a2 = acc[2], a3 = acc[3];
-    asm("s_nop 1\n\t"
-        "v_fmac_f32_dpp %0, %4, %8" XR_DPP("row_shr:2") "v_fmac_f32_dpp %1, %5, %9" XR_DPP("row_shr:2")
-        "v_fmac_f32_dpp %2, %6, %10" XR_DPP("row_shr:2") "v_fmac_f32_dpp %3, %7, %11" XR_DPP("row_shr:2")
-        "v_fmac_f32_dpp %0, %4, %12" XR_DPP("row_shr:1") "v_fmac_f32_dpp %1, %5, %13" XR_DPP("row_shr:1")
-        "v_fmac_f32_dpp %2, %6, %14" XR_DPP("row_shr:1") "v_fmac_f32_dpp %3, %7, %15" XR_DPP("row_shr:1")
-        "v_fmac_f32 %0, %4, %16\n\t" "v_fmac_f32 %1, %5, %17\n\t" "v_fmac_f32 %2, %6, %18\n\t" "v_fmac_f32 %3, %7, %19\n\t"
-        : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3)
-        : "v"(e[0]), "v"(e[1]), "v"(e[2]), "v"(e[3]), "v"(w0[0]), "v"(w0[1]), "v"(w0[2]), "v"(w0[3]),
-          "v"(w1[0]), "v"(w1[1]), "v"(w1[2]), "v"(w1[3]), "v"(w2[0]), "v"(w2[1]), "v"(w2[2]), "v"(w2[3]));
-    asm("v_fmac_f32_dpp %0, %4, %8" XR_DPP("row_shl:1") "v_fmac_f32_dpp %1, %5, %9" XR_DPP("row_shl:1")
-        "v_fmac_f32_dpp %2, %6, %10" XR_DPP("row_shl:1") "v_fmac_f32_dpp %3, %7, %11" XR_DPP("row_shl:1")
-        "v_fmac_f32_dpp %0, %4, %12" XR_DPP("row_shl:2") "v_fmac_f32_dpp %1, %5, %13" XR_DPP("row_shl:2")
-        "v_fmac_f32_dpp %2, %6, %14" XR_DPP("row_shl:2") "v_fmac_f32_dpp %3, %7, %15" XR_DPP("row_shl:2")
-        : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3)
-        : "v"(e[0]), "v"(e[1]), "v"(e[2]), "v"(e[3]), "v"(w3[0]), "v"(w3[1]), "v"(w3[2]), "v"(w3[3]),
-          "v"(w4[0]), "v"(w4[1]), "v"(w4[2]), "v"(w4[3]));
-    acc = (xr_f4){a0, a1, a2, a3};
+    asm("s_nop 1\n\t" CH_FMAC_DPP(w0, CH_DPP("row_shr:2")) CH_FMAC_DPP(w1, CH_DPP("row_shr:1")) CH_FMAC(w2)
+        : CH_ACC4(a, a) : CH_IN4(e, e), CH_IN4(w0, w0), CH_IN4(w1, w1), CH_IN4(w2, w2));
+    asm(CH_FMAC_DPP(w3, CH_DPP("row_shl:1")) CH_FMAC_DPP(w4, CH_DPP("row_shl:2"))
+        : CH_ACC4(a, a) : CH_IN4(e, e), CH_IN4(w3, w3), CH_IN4(w4, w4));
+    acc = (v4f){a0, a1, a2, a3};
 }
 
 template <int ACT>
@@ -109,21 +78,20 @@ __device__ __forceinline__ float xr_act(float v, float hi) {   // hi: 6 (relu6) 
 // v_pk_fma_f32: two values per issue slot, each IEEE-exact like its scalar form, so results are bit-identical to xr_act).  These
 // kernels are bound by VALU issue, and with a 3x3 depthwise conv the two swishes are 60 % of it (tools/valu_rate.hip: v_exp_f32 and
 // v_rcp_f32 cost two slots each on gfx950, everything else one): 9 -> 6.5 slots per expanded value, 8 -> 6 per stored value.
-typedef float xr_f2 __attribute__((ext_vector_type(2)));
 template <int ACT>
-__device__ __forceinline__ xr_f4 xr_act4(const xr_f4 v, const float hi) {
-    xr_f4 o;
+__device__ __forceinline__ v4f xr_act4(const v4f v, const float hi) {
+    v4f o;
     if constexpr (ACT == 0) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) o[i] = __builtin_amdgcn_fmed3f(v[i], 0.0f, hi);
     } else {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            const xr_f2 x = {v[2 * h], v[2 * h + 1]};
-            const xr_f2 u = x * (xr_f2){-1.44269504088896341f, -1.44269504088896341f};
-            const xr_f2 e = (xr_f2){__builtin_amdgcn_exp2f(u[0]), __builtin_amdgcn_exp2f(u[1])} + (xr_f2){1.0f, 1.0f};
-            const xr_f2 r = {__builtin_amdgcn_rcpf(e[0]), __builtin_amdgcn_rcpf(e[1])};
-            const xr_f2 y = (xr_f2){hi, hi} * (x * r);
+            const v2f x = {v[2 * h], v[2 * h + 1]};
+            const v2f u = x * (v2f){-1.44269504088896341f, -1.44269504088896341f};
+            const v2f e = (v2f){__builtin_amdgcn_exp2f(u[0]), __builtin_amdgcn_exp2f(u[1])} + (v2f){1.0f, 1.0f};
+            const v2f r = {__builtin_amdgcn_rcpf(e[0]), __builtin_amdgcn_rcpf(e[1])};
+            const v2f y = (v2f){hi, hi} * (x * r);
             o[2 * h] = y[0]; o[2 * h + 1] = y[1];
         }
     }
@@ -131,11 +99,11 @@ __device__ __forceinline__ xr_f4 xr_act4(const xr_f4 v, const float hi) {
 }
 // ... behind the expand conv's BatchNorm: act(d * scale + shift)
 template <int ACT>
-__device__ __forceinline__ xr_f4 xr_bn_act4(const xr_f4 d, const xr_f4 sc, const xr_f4 sh, const float hi) {
-    xr_f4 t;
+__device__ __forceinline__ v4f xr_bn_act4(const v4f d, const v4f sc, const v4f sh, const float hi) {
+    v4f t;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        const xr_f2 y = __builtin_elementwise_fma((xr_f2){d[2 * h], d[2 * h + 1]}, (xr_f2){sc[2 * h], sc[2 * h + 1]}, (xr_f2){sh[2 * h], sh[2 * h + 1]});
+        const v2f y = __builtin_elementwise_fma((v2f){d[2 * h], d[2 * h + 1]}, (v2f){sc[2 * h], sc[2 * h + 1]}, (v2f){sh[2 * h], sh[2 * h + 1]});
         t[2 * h] = y[0]; t[2 * h + 1] = y[1];
     }
     return xr_act4<ACT>(t, hi);
@@ -147,38 +115,21 @@ __device__ __forceinline__ xr_f4 xr_bn_act4(const xr_f4 d, const xr_f4 sc, const
 // own lane, row_shl:8, row_shl:1, row_shl:9, row_shl:2), the odd row below it in lanes 8..15 of the SAME registers (bank_mask
 // 0xc: row_shr:8, own lane, row_shr:7, row_shl:1, row_shr:6): one activation, one rounding, one store (and in the whole-block
 // kernels one projection and one barrier) per PAIR of output rows, all 16 lanes of it useful (14 / 12 of 16 for 3x3 / 5x5).
-#define XR_DPPM(ctl, bank) " " ctl " row_mask:0xf bank_mask:" bank " bound_ctrl:1\n\t"
-#define XR_PAIR3(c0, c1, c2, bank)                                                                                                   \
-    asm("s_nop 1\n\t"                                                                                                                \
-        "v_fmac_f32_dpp %0, %4, %8" XR_DPPM(c0, bank) "v_fmac_f32_dpp %1, %5, %9" XR_DPPM(c0, bank)                                 \
-        "v_fmac_f32_dpp %2, %6, %10" XR_DPPM(c0, bank) "v_fmac_f32_dpp %3, %7, %11" XR_DPPM(c0, bank)                               \
-        "v_fmac_f32_dpp %0, %4, %12" XR_DPPM(c1, bank) "v_fmac_f32_dpp %1, %5, %13" XR_DPPM(c1, bank)                               \
-        "v_fmac_f32_dpp %2, %6, %14" XR_DPPM(c1, bank) "v_fmac_f32_dpp %3, %7, %15" XR_DPPM(c1, bank)                               \
-        "v_fmac_f32_dpp %0, %4, %16" XR_DPPM(c2, bank) "v_fmac_f32_dpp %1, %5, %17" XR_DPPM(c2, bank)                               \
-        "v_fmac_f32_dpp %2, %6, %18" XR_DPPM(c2, bank) "v_fmac_f32_dpp %3, %7, %19" XR_DPPM(c2, bank)                               \
-        : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3)                                                                                     \
-        : "v"(e[0]), "v"(e[1]), "v"(e[2]), "v"(e[3]), "v"(w[0][0]), "v"(w[0][1]), "v"(w[0][2]), "v"(w[0][3]),                        \
-          "v"(w[1][0]), "v"(w[1][1]), "v"(w[1][2]), "v"(w[1][3]), "v"(w[2][0]), "v"(w[2][1]), "v"(w[2][2]), "v"(w[2][3]))
-#define XR_PAIR2(c3, c4, bank)                                                                                                       \
-    asm("v_fmac_f32_dpp %0, %4, %8" XR_DPPM(c3, bank) "v_fmac_f32_dpp %1, %5, %9" XR_DPPM(c3, bank)                                 \
-        "v_fmac_f32_dpp %2, %6, %10" XR_DPPM(c3, bank) "v_fmac_f32_dpp %3, %7, %11" XR_DPPM(c3, bank)                               \
-        "v_fmac_f32_dpp %0, %4, %12" XR_DPPM(c4, bank) "v_fmac_f32_dpp %1, %5, %13" XR_DPPM(c4, bank)                               \
-        "v_fmac_f32_dpp %2, %6, %14" XR_DPPM(c4, bank) "v_fmac_f32_dpp %3, %7, %15" XR_DPPM(c4, bank)                               \
-        : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3)                                                                                     \
-        : "v"(e[0]), "v"(e[1]), "v"(e[2]), "v"(e[3]), "v"(w[3][0]), "v"(w[3][1]), "v"(w[3][2]), "v"(w[3][3]),                        \
-          "v"(w[4][0]), "v"(w[4][1]), "v"(w[4][2]), "v"(w[4][3]))
+// (the three-tap statement is chained_common.h's CH_PAIR3; taps 3..4 of a five-tap row are a statement of their own)
+#define XR_PAIR2(c3, c4, bank) \
+    asm(CH_FMAC_DPP(w3, CH_DPPM(c3, bank)) CH_FMAC_DPP(w4, CH_DPPM(c4, bank)) : CH_ACC4(a, a) : CH_IN4(e, e), CH_IN4(w3, w[3]), CH_IN4(w4, w[4]))
 // one tap row (K taps at w[0..K-1]) of the paired form: ODD = the odd output row of the pair (lanes 8..15)
 template <int K, bool ODD>
-__device__ __forceinline__ void xr_row_pair(xr_f4& acc, const xr_f4 e, const xr_f4* w) {
+__device__ __forceinline__ void xr_row_pair(v4f& acc, const v4f e, const v4f* w) {
     float a0 = acc[0], a1 = acc[1], a2 = acc[2], a3 = acc[3];
     if constexpr (K == 3) {
-        if constexpr (!ODD) XR_PAIR3("quad_perm:[0,1,2,3]", "row_shl:8", "row_shl:1", "0x3");
-        else XR_PAIR3("row_shr:8", "quad_perm:[0,1,2,3]", "row_shr:7", "0xc");
+        if constexpr (!ODD) CH_PAIR3(CH_OWN, "row_shl:8", "row_shl:1", "0x3", w[0], w[1], w[2]);
+        else CH_PAIR3("row_shr:8", CH_OWN, "row_shr:7", "0xc", w[0], w[1], w[2]);
     } else {
-        if constexpr (!ODD) { XR_PAIR3("quad_perm:[0,1,2,3]", "row_shl:8", "row_shl:1", "0x3"); XR_PAIR2("row_shl:9", "row_shl:2", "0x3"); }
-        else { XR_PAIR3("row_shr:8", "quad_perm:[0,1,2,3]", "row_shr:7", "0xc"); XR_PAIR2("row_shl:1", "row_shr:6", "0xc"); }
+        if constexpr (!ODD) { CH_PAIR3(CH_OWN, "row_shl:8", "row_shl:1", "0x3", w[0], w[1], w[2]); XR_PAIR2("row_shl:9", "row_shl:2", "0x3"); }
+        else { CH_PAIR3("row_shr:8", CH_OWN, "row_shr:7", "0xc", w[0], w[1], w[2]); XR_PAIR2("row_shl:1", "row_shr:6", "0xc"); }
     }
-    acc = (xr_f4){a0, a1, a2, a3};
+    acc = (v4f){a0, a1, a2, a3};
 }
 
 // 5x5 depthwise taps WITHOUT a register per tap: the 25 taps of a channel live in TWO registers, lane p of every 16-lane row
@@ -189,333 +140,63 @@ __device__ __forceinline__ void xr_row_pair(xr_f4& acc, const xr_f4 e, const xr_
 //   out = shift + S_2 + shr2(S_0) + shr1(S_1) + shl1(S_3) + shl2(S_4)
 // 30 instead of 25 instructions per channel and output row, 8 instead of 100 tap registers per tile, no LDS table (an LDS table
 // read where it is used costs 25 ds_read_b128 per tile and output row: 0.31 ms on EfficientNet-lite0's stage-3 entry, LDS-bound).
-template <int KY> __device__ __forceinline__ void xr_bc5_row(float (&S)[5][4], const xr_f4 e, const xr_f4 t0, const xr_f4 t1);
-template <> __device__ __forceinline__ void xr_bc5_row<0>(float (&S)[5][4], const xr_f4 e, const xr_f4 t0, const xr_f4 t1) {
-    asm("v_mul_f32_dpp %0, %16, %12 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f32_dpp %1, %17, %13 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f32_dpp %2, %18, %14 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f32_dpp %3, %19, %15 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f32_dpp %4, %16, %12 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f32_dpp %5, %17, %13 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f32_dpp %6, %18, %14 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f32_dpp %7, %19, %15 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f32_dpp %8, %16, %12 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f32_dpp %9, %17, %13 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f32_dpp %10, %18, %14 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f32_dpp %11, %19, %15 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-        : "=&v"(S[0][0]), "=&v"(S[0][1]), "=&v"(S[0][2]), "=&v"(S[0][3]), "=&v"(S[1][0]), "=&v"(S[1][1]), "=&v"(S[1][2]), "=&v"(S[1][3]), "=&v"(S[2][0]), "=&v"(S[2][1]), "=&v"(S[2][2]), "=&v"(S[2][3])
-        : "v"(e[0]), "v"(e[1]), "v"(e[2]), "v"(e[3]), "v"(t0[0]), "v"(t0[1]), "v"(t0[2]), "v"(t0[3]), "v"(t1[0]), "v"(t1[1]), "v"(t1[2]), "v"(t1[3]));
-    asm("v_mul_f32_dpp %0, %12, %8 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f32_dpp %1, %13, %9 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f32_dpp %2, %14, %10 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f32_dpp %3, %15, %11 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f32_dpp %4, %12, %8 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f32_dpp %5, %13, %9 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f32_dpp %6, %14, %10 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f32_dpp %7, %15, %11 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-        : "=&v"(S[3][0]), "=&v"(S[3][1]), "=&v"(S[3][2]), "=&v"(S[3][3]), "=&v"(S[4][0]), "=&v"(S[4][1]), "=&v"(S[4][2]), "=&v"(S[4][3])
-        : "v"(e[0]), "v"(e[1]), "v"(e[2]), "v"(e[3]), "v"(t0[0]), "v"(t0[1]), "v"(t0[2]), "v"(t0[3]), "v"(t1[0]), "v"(t1[1]), "v"(t1[2]), "v"(t1[3]));
-}
-template <> __device__ __forceinline__ void xr_bc5_row<1>(float (&S)[5][4], const xr_f4 e, const xr_f4 t0, const xr_f4 t1) {
-    asm("v_fmac_f32_dpp %0, %16, %12 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %1, %17, %13 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %2, %18, %14 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %3, %19, %15 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %4, %16, %12 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %5, %17, %13 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %6, %18, %14 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %7, %19, %15 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %8, %16, %12 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %9, %17, %13 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %10, %18, %14 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %11, %19, %15 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
-        : "+v"(S[0][0]), "+v"(S[0][1]), "+v"(S[0][2]), "+v"(S[0][3]), "+v"(S[1][0]), "+v"(S[1][1]), "+v"(S[1][2]), "+v"(S[1][3]), "+v"(S[2][0]), "+v"(S[2][1]), "+v"(S[2][2]), "+v"(S[2][3])
-        : "v"(e[0]), "v"(e[1]), "v"(e[2]), "v"(e[3]), "v"(t0[0]), "v"(t0[1]), "v"(t0[2]), "v"(t0[3]), "v"(t1[0]), "v"(t1[1]), "v"(t1[2]), "v"(t1[3]));
-    asm("v_fmac_f32_dpp %0, %12, %8 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %1, %13, %9 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %2, %14, %10 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %3, %15, %11 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %4, %12, %8 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %5, %13, %9 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %6, %14, %10 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %7, %15, %11 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
-        : "+v"(S[3][0]), "+v"(S[3][1]), "+v"(S[3][2]), "+v"(S[3][3]), "+v"(S[4][0]), "+v"(S[4][1]), "+v"(S[4][2]), "+v"(S[4][3])
-        : "v"(e[0]), "v"(e[1]), "v"(e[2]), "v"(e[3]), "v"(t0[0]), "v"(t0[1]), "v"(t0[2]), "v"(t0[3]), "v"(t1[0]), "v"(t1[1]), "v"(t1[2]), "v"(t1[3]));
-}
-template <> __device__ __forceinline__ void xr_bc5_row<2>(float (&S)[5][4], const xr_f4 e, const xr_f4 t0, const xr_f4 t1) {
-    asm("v_fmac_f32_dpp %0, %16, %12 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %1, %17, %13 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %2, %18, %14 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %3, %19, %15 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %4, %16, %12 row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %5, %17, %13 row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %6, %18, %14 row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %7, %19, %15 row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %8, %16, %12 row_newbcast:12 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %9, %17, %13 row_newbcast:12 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %10, %18, %14 row_newbcast:12 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %11, %19, %15 row_newbcast:12 row_mask:0xf bank_mask:0xf\n\t"
-        : "+v"(S[0][0]), "+v"(S[0][1]), "+v"(S[0][2]), "+v"(S[0][3]), "+v"(S[1][0]), "+v"(S[1][1]), "+v"(S[1][2]), "+v"(S[1][3]), "+v"(S[2][0]), "+v"(S[2][1]), "+v"(S[2][2]), "+v"(S[2][3])
-        : "v"(e[0]), "v"(e[1]), "v"(e[2]), "v"(e[3]), "v"(t0[0]), "v"(t0[1]), "v"(t0[2]), "v"(t0[3]), "v"(t1[0]), "v"(t1[1]), "v"(t1[2]), "v"(t1[3]));
-    asm("v_fmac_f32_dpp %0, %12, %8 row_newbcast:13 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %1, %13, %9 row_newbcast:13 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %2, %14, %10 row_newbcast:13 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %3, %15, %11 row_newbcast:13 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %4, %12, %8 row_newbcast:14 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %5, %13, %9 row_newbcast:14 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %6, %14, %10 row_newbcast:14 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %7, %15, %11 row_newbcast:14 row_mask:0xf bank_mask:0xf\n\t"
-        : "+v"(S[3][0]), "+v"(S[3][1]), "+v"(S[3][2]), "+v"(S[3][3]), "+v"(S[4][0]), "+v"(S[4][1]), "+v"(S[4][2]), "+v"(S[4][3])
-        : "v"(e[0]), "v"(e[1]), "v"(e[2]), "v"(e[3]), "v"(t0[0]), "v"(t0[1]), "v"(t0[2]), "v"(t0[3]), "v"(t1[0]), "v"(t1[1]), "v"(t1[2]), "v"(t1[3]));
-}
-template <> __device__ __forceinline__ void xr_bc5_row<3>(float (&S)[5][4], const xr_f4 e, const xr_f4 t0, const xr_f4 t1) {
-    asm("v_fmac_f32_dpp %0, %16, %12 row_newbcast:15 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %1, %17, %13 row_newbcast:15 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %2, %18, %14 row_newbcast:15 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %3, %19, %15 row_newbcast:15 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %4, %20, %12 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %5, %21, %13 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %6, %22, %14 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %7, %23, %15 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %8, %20, %12 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %9, %21, %13 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %10, %22, %14 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %11, %23, %15 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-        : "+v"(S[0][0]), "+v"(S[0][1]), "+v"(S[0][2]), "+v"(S[0][3]), "+v"(S[1][0]), "+v"(S[1][1]), "+v"(S[1][2]), "+v"(S[1][3]), "+v"(S[2][0]), "+v"(S[2][1]), "+v"(S[2][2]), "+v"(S[2][3])
-        : "v"(e[0]), "v"(e[1]), "v"(e[2]), "v"(e[3]), "v"(t0[0]), "v"(t0[1]), "v"(t0[2]), "v"(t0[3]), "v"(t1[0]), "v"(t1[1]), "v"(t1[2]), "v"(t1[3]));
-    asm("v_fmac_f32_dpp %0, %16, %8 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %1, %17, %9 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %2, %18, %10 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %3, %19, %11 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %4, %16, %8 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %5, %17, %9 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %6, %18, %10 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %7, %19, %11 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-        : "+v"(S[3][0]), "+v"(S[3][1]), "+v"(S[3][2]), "+v"(S[3][3]), "+v"(S[4][0]), "+v"(S[4][1]), "+v"(S[4][2]), "+v"(S[4][3])
-        : "v"(e[0]), "v"(e[1]), "v"(e[2]), "v"(e[3]), "v"(t0[0]), "v"(t0[1]), "v"(t0[2]), "v"(t0[3]), "v"(t1[0]), "v"(t1[1]), "v"(t1[2]), "v"(t1[3]));
-}
-template <> __device__ __forceinline__ void xr_bc5_row<4>(float (&S)[5][4], const xr_f4 e, const xr_f4 t0, const xr_f4 t1) {
-    asm("v_fmac_f32_dpp %0, %20, %12 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %1, %21, %13 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %2, %22, %14 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %3, %23, %15 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %4, %20, %12 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %5, %21, %13 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %6, %22, %14 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %7, %23, %15 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %8, %20, %12 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %9, %21, %13 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %10, %22, %14 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %11, %23, %15 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-        : "+v"(S[0][0]), "+v"(S[0][1]), "+v"(S[0][2]), "+v"(S[0][3]), "+v"(S[1][0]), "+v"(S[1][1]), "+v"(S[1][2]), "+v"(S[1][3]), "+v"(S[2][0]), "+v"(S[2][1]), "+v"(S[2][2]), "+v"(S[2][3])
-        : "v"(e[0]), "v"(e[1]), "v"(e[2]), "v"(e[3]), "v"(t0[0]), "v"(t0[1]), "v"(t0[2]), "v"(t0[3]), "v"(t1[0]), "v"(t1[1]), "v"(t1[2]), "v"(t1[3]));
-    asm("v_fmac_f32_dpp %0, %16, %8 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %1, %17, %9 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %2, %18, %10 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %3, %19, %11 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %4, %16, %8 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %5, %17, %9 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %6, %18, %10 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f32_dpp %7, %19, %11 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-        : "+v"(S[3][0]), "+v"(S[3][1]), "+v"(S[3][2]), "+v"(S[3][3]), "+v"(S[4][0]), "+v"(S[4][1]), "+v"(S[4][2]), "+v"(S[4][3])
-        : "v"(e[0]), "v"(e[1]), "v"(e[2]), "v"(e[3]), "v"(t0[0]), "v"(t0[1]), "v"(t0[2]), "v"(t0[3]), "v"(t1[0]), "v"(t1[1]), "v"(t1[2]), "v"(t1[3]));
-}
-__device__ __forceinline__ xr_f4 xr_bc5_finish(const float (&S)[5][4], const xr_f4 shift) {
+//
+// WHERE THE TAPS SIT: tap q = 5 KY + dx (row KY, column dx) of a channel is lane q % 16 of register q / 16 (t0 | t1).  One line
+// per KY: how the full row treats the sums (row 0 starts them), then (register, lane) of the columns dx = 0 .. 4.
+#define XR_BC5_TAPS(F)                                                     \
+    F(0, "v_mul_f32_dpp", "=&v", t0, 0, t0, 1, t0, 2, t0, 3, t0, 4)        \
+    F(1, "v_fmac_f32_dpp", "+v", t0, 5, t0, 6, t0, 7, t0, 8, t0, 9)        \
+    F(2, "v_fmac_f32_dpp", "+v", t0, 10, t0, 11, t0, 12, t0, 13, t0, 14)   \
+    F(3, "v_fmac_f32_dpp", "+v", t0, 15, t1, 0, t1, 1, t1, 2, t1, 3)       \
+    F(4, "v_fmac_f32_dpp", "+v", t1, 4, t1, 5, t1, 6, t1, 7, t1, 8)
+// one column: sums s (op)= tap (register r, lane l, broadcast to the row) * the row e, in the lanes of `bank`
+#define XR_BC5_COL(op, s, r, l, bank) CH_TAP4(op, s, r, e, CH_BCAST(l, bank))
+#define XR_BC5_IN CH_IN4(e, e), CH_IN4(t0, t0), CH_IN4(t1, t1)
+// input row KY of an output row: the five column sums S[dx] (two statements, columns 0..2 and 3..4: the 30-operand limit)
+template <int KY> __device__ __forceinline__ void xr_bc5_row(float (&S)[5][4], const v4f e, const v4f t0, const v4f t1);
+#define XR_BC5_ROW(KY, op, c, r0, l0, r1, l1, r2, l2, r3, l3, r4, l4)                                                               \
+    template <> __device__ __forceinline__ void xr_bc5_row<KY>(float (&S)[5][4], const v4f e, const v4f t0, const v4f t1) {         \
+        asm(XR_BC5_COL(op, s0, r0, l0, "0xf") XR_BC5_COL(op, s1, r1, l1, "0xf") XR_BC5_COL(op, s2, r2, l2, "0xf")                   \
+            : CH_OUT4(c, s0, S[0]), CH_OUT4(c, s1, S[1]), CH_OUT4(c, s2, S[2]) : XR_BC5_IN);                                        \
+        asm(XR_BC5_COL(op, s3, r3, l3, "0xf") XR_BC5_COL(op, s4, r4, l4, "0xf")                                                     \
+            : CH_OUT4(c, s3, S[3]), CH_OUT4(c, s4, S[4]) : XR_BC5_IN);                                                              \
+    }
+XR_BC5_TAPS(XR_BC5_ROW)
+#undef XR_BC5_ROW
+// the shifts, applied once per output row to the sums: o += the row s as the modifiers deliver it
+#define XR_ADD_DPP(s, mods) CH_TAP4("v_add_f32_dpp", o, s, o, mods)
+__device__ __forceinline__ v4f xr_bc5_finish(const float (&S)[5][4], const v4f shift) {
     float o0 = shift[0] + S[2][0], o1 = shift[1] + S[2][1], o2 = shift[2] + S[2][2], o3 = shift[3] + S[2][3];
-    asm("s_nop 1\n\t"
-        "v_add_f32_dpp %0, %4, %0 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_add_f32_dpp %1, %5, %1 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_add_f32_dpp %2, %6, %2 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_add_f32_dpp %3, %7, %3 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_add_f32_dpp %0, %8, %0 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_add_f32_dpp %1, %9, %1 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_add_f32_dpp %2, %10, %2 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_add_f32_dpp %3, %11, %3 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_add_f32_dpp %0, %12, %0 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_add_f32_dpp %1, %13, %1 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_add_f32_dpp %2, %14, %2 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_add_f32_dpp %3, %15, %3 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_add_f32_dpp %0, %16, %0 row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_add_f32_dpp %1, %17, %1 row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_add_f32_dpp %2, %18, %2 row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_add_f32_dpp %3, %19, %3 row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        : "+v"(o0), "+v"(o1), "+v"(o2), "+v"(o3)
-        : "v"(S[0][0]), "v"(S[0][1]), "v"(S[0][2]), "v"(S[0][3]), "v"(S[1][0]), "v"(S[1][1]), "v"(S[1][2]), "v"(S[1][3]), "v"(S[3][0]), "v"(S[3][1]), "v"(S[3][2]), "v"(S[3][3]), "v"(S[4][0]), "v"(S[4][1]), "v"(S[4][2]), "v"(S[4][3]));
-    return (xr_f4){o0, o1, o2, o3};
+    asm("s_nop 1\n\t" XR_ADD_DPP(s0, CH_DPP("row_shr:2")) XR_ADD_DPP(s1, CH_DPP("row_shr:1")) XR_ADD_DPP(s3, CH_DPP("row_shl:1")) XR_ADD_DPP(s4, CH_DPP("row_shl:2"))
+        : CH_ACC4(o, o) : CH_IN4(s0, S[0]), CH_IN4(s1, S[1]), CH_IN4(s3, S[3]), CH_IN4(s4, S[4]));
+    return (v4f){o0, o1, o2, o3};
 }
 
 // ... and the broadcast-tap form for PAIRED output rows (stride 2, even input columns E in lanes 0..7, odd ones O in 8..15).  The
 // column sums live at their INPUT lane: S_dx with dx even is only ever needed at E lanes, with dx odd only at O lanes, so S_0 | S_1
 // share a register (lanes 0..7 | 8..15, bank masks), S_2 | S_3 the next, S_4 a third: three registers per channel and output row of
 // the pair.  An input row feeds the even output row's sums with its taps ky and the odd row's sums with ky - 2 (same code, other array).
-template <int KY> __device__ __forceinline__ void xr_bc5_half_row(float (&S)[3][4], const xr_f4 e, const xr_f4 t0, const xr_f4 t1);
-template <> __device__ __forceinline__ void xr_bc5_half_row<0>(float (&S)[3][4], const xr_f4 e, const xr_f4 t0, const xr_f4 t1) {
-    asm("v_fmac_f32_dpp %0, %16, %12 row_newbcast:0 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %1, %17, %13 row_newbcast:0 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %2, %18, %14 row_newbcast:0 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %3, %19, %15 row_newbcast:0 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %0, %16, %12 row_newbcast:1 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %1, %17, %13 row_newbcast:1 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %2, %18, %14 row_newbcast:1 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %3, %19, %15 row_newbcast:1 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %4, %16, %12 row_newbcast:2 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %5, %17, %13 row_newbcast:2 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %6, %18, %14 row_newbcast:2 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %7, %19, %15 row_newbcast:2 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %4, %16, %12 row_newbcast:3 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %5, %17, %13 row_newbcast:3 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %6, %18, %14 row_newbcast:3 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %7, %19, %15 row_newbcast:3 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %8, %16, %12 row_newbcast:4 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %9, %17, %13 row_newbcast:4 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %10, %18, %14 row_newbcast:4 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %11, %19, %15 row_newbcast:4 row_mask:0xf bank_mask:0x3\n\t"
-        : "+v"(S[0][0]), "+v"(S[0][1]), "+v"(S[0][2]), "+v"(S[0][3]), "+v"(S[1][0]), "+v"(S[1][1]), "+v"(S[1][2]), "+v"(S[1][3]), "+v"(S[2][0]), "+v"(S[2][1]), "+v"(S[2][2]), "+v"(S[2][3])
-        : "v"(e[0]), "v"(e[1]), "v"(e[2]), "v"(e[3]), "v"(t0[0]), "v"(t0[1]), "v"(t0[2]), "v"(t0[3]), "v"(t1[0]), "v"(t1[1]), "v"(t1[2]), "v"(t1[3]));
-}
-template <> __device__ __forceinline__ void xr_bc5_half_row<1>(float (&S)[3][4], const xr_f4 e, const xr_f4 t0, const xr_f4 t1) {
-    asm("v_fmac_f32_dpp %0, %16, %12 row_newbcast:5 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %1, %17, %13 row_newbcast:5 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %2, %18, %14 row_newbcast:5 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %3, %19, %15 row_newbcast:5 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %0, %16, %12 row_newbcast:6 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %1, %17, %13 row_newbcast:6 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %2, %18, %14 row_newbcast:6 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %3, %19, %15 row_newbcast:6 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %4, %16, %12 row_newbcast:7 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %5, %17, %13 row_newbcast:7 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %6, %18, %14 row_newbcast:7 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %7, %19, %15 row_newbcast:7 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %4, %16, %12 row_newbcast:8 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %5, %17, %13 row_newbcast:8 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %6, %18, %14 row_newbcast:8 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %7, %19, %15 row_newbcast:8 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %8, %16, %12 row_newbcast:9 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %9, %17, %13 row_newbcast:9 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %10, %18, %14 row_newbcast:9 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %11, %19, %15 row_newbcast:9 row_mask:0xf bank_mask:0x3\n\t"
-        : "+v"(S[0][0]), "+v"(S[0][1]), "+v"(S[0][2]), "+v"(S[0][3]), "+v"(S[1][0]), "+v"(S[1][1]), "+v"(S[1][2]), "+v"(S[1][3]), "+v"(S[2][0]), "+v"(S[2][1]), "+v"(S[2][2]), "+v"(S[2][3])
-        : "v"(e[0]), "v"(e[1]), "v"(e[2]), "v"(e[3]), "v"(t0[0]), "v"(t0[1]), "v"(t0[2]), "v"(t0[3]), "v"(t1[0]), "v"(t1[1]), "v"(t1[2]), "v"(t1[3]));
-}
-template <> __device__ __forceinline__ void xr_bc5_half_row<2>(float (&S)[3][4], const xr_f4 e, const xr_f4 t0, const xr_f4 t1) {
-    asm("v_fmac_f32_dpp %0, %16, %12 row_newbcast:10 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %1, %17, %13 row_newbcast:10 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %2, %18, %14 row_newbcast:10 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %3, %19, %15 row_newbcast:10 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %0, %16, %12 row_newbcast:11 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %1, %17, %13 row_newbcast:11 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %2, %18, %14 row_newbcast:11 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %3, %19, %15 row_newbcast:11 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %4, %16, %12 row_newbcast:12 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %5, %17, %13 row_newbcast:12 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %6, %18, %14 row_newbcast:12 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %7, %19, %15 row_newbcast:12 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %4, %16, %12 row_newbcast:13 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %5, %17, %13 row_newbcast:13 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %6, %18, %14 row_newbcast:13 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %7, %19, %15 row_newbcast:13 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %8, %16, %12 row_newbcast:14 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %9, %17, %13 row_newbcast:14 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %10, %18, %14 row_newbcast:14 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %11, %19, %15 row_newbcast:14 row_mask:0xf bank_mask:0x3\n\t"
-        : "+v"(S[0][0]), "+v"(S[0][1]), "+v"(S[0][2]), "+v"(S[0][3]), "+v"(S[1][0]), "+v"(S[1][1]), "+v"(S[1][2]), "+v"(S[1][3]), "+v"(S[2][0]), "+v"(S[2][1]), "+v"(S[2][2]), "+v"(S[2][3])
-        : "v"(e[0]), "v"(e[1]), "v"(e[2]), "v"(e[3]), "v"(t0[0]), "v"(t0[1]), "v"(t0[2]), "v"(t0[3]), "v"(t1[0]), "v"(t1[1]), "v"(t1[2]), "v"(t1[3]));
-}
-template <> __device__ __forceinline__ void xr_bc5_half_row<3>(float (&S)[3][4], const xr_f4 e, const xr_f4 t0, const xr_f4 t1) {
-    asm("v_fmac_f32_dpp %0, %16, %12 row_newbcast:15 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %1, %17, %13 row_newbcast:15 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %2, %18, %14 row_newbcast:15 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %3, %19, %15 row_newbcast:15 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %0, %20, %12 row_newbcast:0 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %1, %21, %13 row_newbcast:0 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %2, %22, %14 row_newbcast:0 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %3, %23, %15 row_newbcast:0 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %4, %20, %12 row_newbcast:1 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %5, %21, %13 row_newbcast:1 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %6, %22, %14 row_newbcast:1 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %7, %23, %15 row_newbcast:1 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %4, %20, %12 row_newbcast:2 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %5, %21, %13 row_newbcast:2 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %6, %22, %14 row_newbcast:2 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %7, %23, %15 row_newbcast:2 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %8, %20, %12 row_newbcast:3 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %9, %21, %13 row_newbcast:3 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %10, %22, %14 row_newbcast:3 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %11, %23, %15 row_newbcast:3 row_mask:0xf bank_mask:0x3\n\t"
-        : "+v"(S[0][0]), "+v"(S[0][1]), "+v"(S[0][2]), "+v"(S[0][3]), "+v"(S[1][0]), "+v"(S[1][1]), "+v"(S[1][2]), "+v"(S[1][3]), "+v"(S[2][0]), "+v"(S[2][1]), "+v"(S[2][2]), "+v"(S[2][3])
-        : "v"(e[0]), "v"(e[1]), "v"(e[2]), "v"(e[3]), "v"(t0[0]), "v"(t0[1]), "v"(t0[2]), "v"(t0[3]), "v"(t1[0]), "v"(t1[1]), "v"(t1[2]), "v"(t1[3]));
-}
-template <> __device__ __forceinline__ void xr_bc5_half_row<4>(float (&S)[3][4], const xr_f4 e, const xr_f4 t0, const xr_f4 t1) {
-    asm("v_fmac_f32_dpp %0, %20, %12 row_newbcast:4 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %1, %21, %13 row_newbcast:4 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %2, %22, %14 row_newbcast:4 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %3, %23, %15 row_newbcast:4 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %0, %20, %12 row_newbcast:5 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %1, %21, %13 row_newbcast:5 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %2, %22, %14 row_newbcast:5 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %3, %23, %15 row_newbcast:5 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %4, %20, %12 row_newbcast:6 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %5, %21, %13 row_newbcast:6 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %6, %22, %14 row_newbcast:6 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %7, %23, %15 row_newbcast:6 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %4, %20, %12 row_newbcast:7 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %5, %21, %13 row_newbcast:7 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %6, %22, %14 row_newbcast:7 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %7, %23, %15 row_newbcast:7 row_mask:0xf bank_mask:0xc\n\t"
-        "v_fmac_f32_dpp %8, %20, %12 row_newbcast:8 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %9, %21, %13 row_newbcast:8 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %10, %22, %14 row_newbcast:8 row_mask:0xf bank_mask:0x3\n\t"
-        "v_fmac_f32_dpp %11, %23, %15 row_newbcast:8 row_mask:0xf bank_mask:0x3\n\t"
-        : "+v"(S[0][0]), "+v"(S[0][1]), "+v"(S[0][2]), "+v"(S[0][3]), "+v"(S[1][0]), "+v"(S[1][1]), "+v"(S[1][2]), "+v"(S[1][3]), "+v"(S[2][0]), "+v"(S[2][1]), "+v"(S[2][2]), "+v"(S[2][3])
-        : "v"(e[0]), "v"(e[1]), "v"(e[2]), "v"(e[3]), "v"(t0[0]), "v"(t0[1]), "v"(t0[2]), "v"(t0[3]), "v"(t1[0]), "v"(t1[1]), "v"(t1[2]), "v"(t1[3]));
-}
+template <int KY> __device__ __forceinline__ void xr_bc5_half_row(float (&S)[3][4], const v4f e, const v4f t0, const v4f t1);
+#define XR_BC5_HALF_ROW(KY, op, c, r0, l0, r1, l1, r2, l2, r3, l3, r4, l4)                                                          \
+    template <> __device__ __forceinline__ void xr_bc5_half_row<KY>(float (&S)[3][4], const v4f e, const v4f t0, const v4f t1) {    \
+        asm(XR_BC5_COL("v_fmac_f32_dpp", s0, r0, l0, "0x3") XR_BC5_COL("v_fmac_f32_dpp", s0, r1, l1, "0xc")                         \
+            XR_BC5_COL("v_fmac_f32_dpp", s1, r2, l2, "0x3") XR_BC5_COL("v_fmac_f32_dpp", s1, r3, l3, "0xc")                         \
+            XR_BC5_COL("v_fmac_f32_dpp", s2, r4, l4, "0x3")                                                                         \
+            : CH_OUT4("+v", s0, S[0]), CH_OUT4("+v", s1, S[1]), CH_OUT4("+v", s2, S[2]) : XR_BC5_IN);                               \
+    }
+XR_BC5_TAPS(XR_BC5_HALF_ROW)
+#undef XR_BC5_HALF_ROW
 // the pair's depthwise results: the even row's in lanes 0..7, the odd row's in lanes 8..15
-__device__ __forceinline__ xr_f4 xr_bc5_pair_finish(const float (&SA)[3][4], const float (&SB)[3][4], const xr_f4 shift) {
+__device__ __forceinline__ v4f xr_bc5_pair_finish(const float (&SA)[3][4], const float (&SB)[3][4], const v4f shift) {
     float o0 = shift[0], o1 = shift[1], o2 = shift[2], o3 = shift[3];
     asm("s_nop 1\n\t"
-        "v_add_f32_dpp %0, %4, %0 quad_perm:[0,1,2,3] row_mask:0xf bank_mask:0x3 bound_ctrl:1\n\t"
-        "v_add_f32_dpp %1, %5, %1 quad_perm:[0,1,2,3] row_mask:0xf bank_mask:0x3 bound_ctrl:1\n\t"
-        "v_add_f32_dpp %2, %6, %2 quad_perm:[0,1,2,3] row_mask:0xf bank_mask:0x3 bound_ctrl:1\n\t"
-        "v_add_f32_dpp %3, %7, %3 quad_perm:[0,1,2,3] row_mask:0xf bank_mask:0x3 bound_ctrl:1\n\t"
-        "v_add_f32_dpp %0, %4, %0 row_shl:8 row_mask:0xf bank_mask:0x3 bound_ctrl:1\n\t"
-        "v_add_f32_dpp %1, %5, %1 row_shl:8 row_mask:0xf bank_mask:0x3 bound_ctrl:1\n\t"
-        "v_add_f32_dpp %2, %6, %2 row_shl:8 row_mask:0xf bank_mask:0x3 bound_ctrl:1\n\t"
-        "v_add_f32_dpp %3, %7, %3 row_shl:8 row_mask:0xf bank_mask:0x3 bound_ctrl:1\n\t"
-        "v_add_f32_dpp %0, %8, %0 row_shl:1 row_mask:0xf bank_mask:0x3 bound_ctrl:1\n\t"
-        "v_add_f32_dpp %1, %9, %1 row_shl:1 row_mask:0xf bank_mask:0x3 bound_ctrl:1\n\t"
-        "v_add_f32_dpp %2, %10, %2 row_shl:1 row_mask:0xf bank_mask:0x3 bound_ctrl:1\n\t"
-        "v_add_f32_dpp %3, %11, %3 row_shl:1 row_mask:0xf bank_mask:0x3 bound_ctrl:1\n\t"
-        "v_add_f32_dpp %0, %8, %0 row_shl:9 row_mask:0xf bank_mask:0x3 bound_ctrl:1\n\t"
-        "v_add_f32_dpp %1, %9, %1 row_shl:9 row_mask:0xf bank_mask:0x3 bound_ctrl:1\n\t"
-        "v_add_f32_dpp %2, %10, %2 row_shl:9 row_mask:0xf bank_mask:0x3 bound_ctrl:1\n\t"
-        "v_add_f32_dpp %3, %11, %3 row_shl:9 row_mask:0xf bank_mask:0x3 bound_ctrl:1\n\t"
-        "v_add_f32_dpp %0, %12, %0 row_shl:2 row_mask:0xf bank_mask:0x3 bound_ctrl:1\n\t"
-        "v_add_f32_dpp %1, %13, %1 row_shl:2 row_mask:0xf bank_mask:0x3 bound_ctrl:1\n\t"
-        "v_add_f32_dpp %2, %14, %2 row_shl:2 row_mask:0xf bank_mask:0x3 bound_ctrl:1\n\t"
-        "v_add_f32_dpp %3, %15, %3 row_shl:2 row_mask:0xf bank_mask:0x3 bound_ctrl:1\n\t"
-        "v_add_f32_dpp %0, %16, %0 row_shr:8 row_mask:0xf bank_mask:0xc bound_ctrl:1\n\t"
-        "v_add_f32_dpp %1, %17, %1 row_shr:8 row_mask:0xf bank_mask:0xc bound_ctrl:1\n\t"
-        "v_add_f32_dpp %2, %18, %2 row_shr:8 row_mask:0xf bank_mask:0xc bound_ctrl:1\n\t"
-        "v_add_f32_dpp %3, %19, %3 row_shr:8 row_mask:0xf bank_mask:0xc bound_ctrl:1\n\t"
-        "v_add_f32_dpp %0, %16, %0 quad_perm:[0,1,2,3] row_mask:0xf bank_mask:0xc bound_ctrl:1\n\t"
-        "v_add_f32_dpp %1, %17, %1 quad_perm:[0,1,2,3] row_mask:0xf bank_mask:0xc bound_ctrl:1\n\t"
-        "v_add_f32_dpp %2, %18, %2 quad_perm:[0,1,2,3] row_mask:0xf bank_mask:0xc bound_ctrl:1\n\t"
-        "v_add_f32_dpp %3, %19, %3 quad_perm:[0,1,2,3] row_mask:0xf bank_mask:0xc bound_ctrl:1\n\t"
-        "v_add_f32_dpp %0, %20, %0 row_shr:7 row_mask:0xf bank_mask:0xc bound_ctrl:1\n\t"
-        "v_add_f32_dpp %1, %21, %1 row_shr:7 row_mask:0xf bank_mask:0xc bound_ctrl:1\n\t"
-        "v_add_f32_dpp %2, %22, %2 row_shr:7 row_mask:0xf bank_mask:0xc bound_ctrl:1\n\t"
-        "v_add_f32_dpp %3, %23, %3 row_shr:7 row_mask:0xf bank_mask:0xc bound_ctrl:1\n\t"
-        "v_add_f32_dpp %0, %20, %0 row_shl:1 row_mask:0xf bank_mask:0xc bound_ctrl:1\n\t"
-        "v_add_f32_dpp %1, %21, %1 row_shl:1 row_mask:0xf bank_mask:0xc bound_ctrl:1\n\t"
-        "v_add_f32_dpp %2, %22, %2 row_shl:1 row_mask:0xf bank_mask:0xc bound_ctrl:1\n\t"
-        "v_add_f32_dpp %3, %23, %3 row_shl:1 row_mask:0xf bank_mask:0xc bound_ctrl:1\n\t"
-        "v_add_f32_dpp %0, %24, %0 row_shr:6 row_mask:0xf bank_mask:0xc bound_ctrl:1\n\t"
-        "v_add_f32_dpp %1, %25, %1 row_shr:6 row_mask:0xf bank_mask:0xc bound_ctrl:1\n\t"
-        "v_add_f32_dpp %2, %26, %2 row_shr:6 row_mask:0xf bank_mask:0xc bound_ctrl:1\n\t"
-        "v_add_f32_dpp %3, %27, %3 row_shr:6 row_mask:0xf bank_mask:0xc bound_ctrl:1\n\t"
-        : "+v"(o0), "+v"(o1), "+v"(o2), "+v"(o3)
-        : "v"(SA[0][0]), "v"(SA[0][1]), "v"(SA[0][2]), "v"(SA[0][3]), "v"(SA[1][0]), "v"(SA[1][1]), "v"(SA[1][2]), "v"(SA[1][3]), "v"(SA[2][0]), "v"(SA[2][1]), "v"(SA[2][2]), "v"(SA[2][3]), "v"(SB[0][0]), "v"(SB[0][1]), "v"(SB[0][2]), "v"(SB[0][3]), "v"(SB[1][0]), "v"(SB[1][1]), "v"(SB[1][2]), "v"(SB[1][3]), "v"(SB[2][0]), "v"(SB[2][1]), "v"(SB[2][2]), "v"(SB[2][3]));
-    return (xr_f4){o0, o1, o2, o3};
+        XR_ADD_DPP(a0, CH_DPPM(CH_OWN, "0x3")) XR_ADD_DPP(a0, CH_DPPM("row_shl:8", "0x3")) XR_ADD_DPP(a1, CH_DPPM("row_shl:1", "0x3"))
+        XR_ADD_DPP(a1, CH_DPPM("row_shl:9", "0x3")) XR_ADD_DPP(a2, CH_DPPM("row_shl:2", "0x3"))
+        XR_ADD_DPP(b0, CH_DPPM("row_shr:8", "0xc")) XR_ADD_DPP(b0, CH_DPPM(CH_OWN, "0xc")) XR_ADD_DPP(b1, CH_DPPM("row_shr:7", "0xc"))
+        XR_ADD_DPP(b1, CH_DPPM("row_shl:1", "0xc")) XR_ADD_DPP(b2, CH_DPPM("row_shr:6", "0xc"))
+        : CH_ACC4(o, o)
+        : CH_IN4(a0, SA[0]), CH_IN4(a1, SA[1]), CH_IN4(a2, SA[2]), CH_IN4(b0, SB[0]), CH_IN4(b1, SB[1]), CH_IN4(b2, SB[2]));
+    return (v4f){o0, o1, o2, o3};
 }
 
 // K: depthwise kernel, S: stride, ACT: 0 relu6 / 1 swish (both activations), NC: 32-channel chunks of the block input, NT: tiles per wave
@@ -543,11 +224,11 @@ __global__ __launch_bounds__(256, MW) void mbxr_kernel(MbxrArgs a) {
     const float omask = out_lane ? 1.f : 0.f;
 
     // ---- stationary: expand A fragments, BN rows, taps (times the depthwise BN scale) of this wave's tiles
-    xr_u4 aw[NT][NC];
+    v4u aw[NT][NC];
     // 5x5 behind four input chunks: the broadcast-tap form (lane p of a row holds tap p / tap 16 + p, xr_bc5_row) - a register per tap
     // leaves those blocks two waves per SIMD at 242 registers; with fewer chunks the 20 % more instructions of that form cost more
     // than the registers (measured, batch 128: 24 -> 144 s2 0.227 vs 0.270 ms; 112 -> 672 s2 0.126 vs 0.107)
-    xr_f4 es[NT], eh[NT], dh[NT], tp[NT][BC5 ? 2 : KK], ssum[NT];
+    v4f es[NT], eh[NT], dh[NT], tp[NT][BC5 ? 2 : KK], ssum[NT];
     unsigned ooff[NT];
     bool tlive[NT];
 #pragma unroll
@@ -557,71 +238,66 @@ __global__ __launch_bounds__(256, MW) void mbxr_kernel(MbxrArgs a) {
         const int ch = 16 * t + 4 * mg;                                   // this lane's 4 expanded channels of tile j
         const char* wrow = reinterpret_cast<const char*>(a.we) + ((size_t)(16 * t + px) * a.KP + 8 * mg) * 2;
 #pragma unroll
-        for (int c = 0; c < NC; ++c) aw[j][c] = *reinterpret_cast<const xr_u4*>(wrow + 64 * c);
-        const xr_f4 dsc = *reinterpret_cast<const xr_f4*>(a.prm + (size_t)KK * a.CexpP + ch);
-        dh[j] = *reinterpret_cast<const xr_f4*>(a.prm + (size_t)(KK + 1) * a.CexpP + ch);
-        es[j] = *reinterpret_cast<const xr_f4*>(a.prm + (size_t)(KK + 2) * a.CexpP + ch);
-        eh[j] = *reinterpret_cast<const xr_f4*>(a.prm + (size_t)(KK + 3) * a.CexpP + ch);
+        for (int c = 0; c < NC; ++c) aw[j][c] = *reinterpret_cast<const v4u*>(wrow + 64 * c);
+        const v4f dsc = *reinterpret_cast<const v4f*>(a.prm + (size_t)KK * a.CexpP + ch);
+        dh[j] = *reinterpret_cast<const v4f*>(a.prm + (size_t)(KK + 1) * a.CexpP + ch);
+        es[j] = *reinterpret_cast<const v4f*>(a.prm + (size_t)(KK + 2) * a.CexpP + ch);
+        eh[j] = *reinterpret_cast<const v4f*>(a.prm + (size_t)(KK + 3) * a.CexpP + ch);
         if constexpr (BC5) {
-            tp[j][0] = *reinterpret_cast<const xr_f4*>(a.prm + (size_t)px * a.CexpP + ch) * dsc;
-            tp[j][1] = 16 + px < KK ? *reinterpret_cast<const xr_f4*>(a.prm + (size_t)(16 + px) * a.CexpP + ch) * dsc : (xr_f4){0.f, 0.f, 0.f, 0.f};
+            tp[j][0] = *reinterpret_cast<const v4f*>(a.prm + (size_t)px * a.CexpP + ch) * dsc;
+            tp[j][1] = 16 + px < KK ? *reinterpret_cast<const v4f*>(a.prm + (size_t)(16 + px) * a.CexpP + ch) * dsc : (v4f){0.f, 0.f, 0.f, 0.f};
         } else {
 #pragma unroll
-            for (int q = 0; q < KK; ++q) tp[j][q] = *reinterpret_cast<const xr_f4*>(a.prm + (size_t)q * a.CexpP + ch) * dsc;
+            for (int q = 0; q < KK; ++q) tp[j][q] = *reinterpret_cast<const v4f*>(a.prm + (size_t)q * a.CexpP + ch) * dsc;
         }
-        ssum[j] = (xr_f4){0.f, 0.f, 0.f, 0.f};
-        ooff[j] = (tlive[j] && out_lane) ? (unsigned)ch * 2u : XR_DEAD;
+        ssum[j] = (v4f){0.f, 0.f, 0.f, 0.f};
+        ooff[j] = (tlive[j] && out_lane) ? (unsigned)ch * 2u : YR_DEAD;
     }
-    const xr_rsrc xsrc = xr_make_rsrc(reinterpret_cast<const T*>(a.x) + (size_t)b * a.H * a.W * a.ld_in, (unsigned)(a.H * a.W * a.ld_in) * 2u);
-    const xr_rsrc osrc = xr_make_rsrc(reinterpret_cast<T*>(a.out) + (size_t)b * a.Ho * a.Wo * a.ld_out, (unsigned)(a.Ho * a.Wo * a.ld_out) * 2u);
+    const yr_rsrc xsrc = yr_make_rsrc(reinterpret_cast<const T*>(a.x) + (size_t)b * a.H * a.W * a.ld_in, (unsigned)(a.H * a.W * a.ld_in) * 2u);
+    const yr_rsrc osrc = yr_make_rsrc(reinterpret_cast<T*>(a.out) + (size_t)b * a.Ho * a.Wo * a.ld_out, (unsigned)(a.Ho * a.Wo * a.ld_out) * 2u);
     const int rbeg = S * yo0 - a.pad_t, nout = yo1 - yo0;
     unsigned xoff[NC];     // the lane's 16 bytes of chunk c within the row; k groups beyond the input's channels read zeros (dead offset)
 #pragma unroll
-    for (int c = 0; c < NC; ++c) xoff[c] = (32 * c + 8 * mg < a.Cin) ? ((unsigned)xc * (unsigned)a.ld_in + 32u * c + 8u * mg) * 2u : XR_DEAD;
+    for (int c = 0; c < NC; ++c) xoff[c] = (32 * c + 8 * mg < a.Cin) ? ((unsigned)xc * (unsigned)a.ld_in + 32u * c + 8u * mg) * 2u : YR_DEAD;
     const unsigned xrow = (unsigned)(a.W * a.ld_in) * 2u;
-    struct XRow { xr_u4 m[NC]; };
+    struct XRow { v4u m[NC]; };
     XRow xa, xb;
     auto load_row = [&](XRow& x, int r) {
         const unsigned so = (unsigned)min(max(r, 0), a.H - 1) * xrow;
 #pragma unroll
-        for (int c = 0; c < NC; ++c) x.m[c] = __builtin_bit_cast(xr_u4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xoff[c], so, 0));
+        for (int c = 0; c < NC; ++c) x.m[c] = __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xoff[c], so, 0));
     };
     load_row(xa, rbeg);
-    xr_f4 ring[NT][K - 1];
+    v4f ring[NT][K - 1];
 #pragma unroll
     for (int j = 0; j < NT; ++j)
 #pragma unroll
-        for (int q = 0; q < K - 1; ++q) ring[j][q] = (xr_f4){0.f, 0.f, 0.f, 0.f};
+        for (int q = 0; q < K - 1; ++q) ring[j][q] = (v4f){0.f, 0.f, 0.f, 0.f};
 
     // ---- the squeeze: the wave's channel sums over one QUANTUM of output rows -> row (strip, quantum) of the partial-sum buffer.  Segments
     // are whole quanta (launch_mbxr), so which wave sums a quantum changes with the tuned segmentation, WHAT is summed in which order
     // does not: the gate - and with it the model's result - is the same for every tuning table and batch size.
-    const xr_rsrc psrc = xr_make_rsrc(a.part != nullptr ? a.part + (size_t)b * a.rows_cap * a.ld_part : reinterpret_cast<const float*>(a.x), a.part != nullptr ? (unsigned)(a.rows_cap * a.ld_part) * 4u : 0u);
+    const yr_rsrc psrc = yr_make_rsrc(a.part != nullptr ? a.part + (size_t)b * a.rows_cap * a.ld_part : reinterpret_cast<const float*>(a.x), a.part != nullptr ? (unsigned)(a.rows_cap * a.ld_part) * 4u : 0u);
     // (the lane that stores a tile's sums: pixel 0 of its DPP row; byte offset of the lane's 4 channels of tile j within a buffer row: pch + 64 j)
     const unsigned pch = (unsigned)(16 * t0 + 4 * mg) * 4u;
-    auto poff = [&](const int j) { return (tlive[j] && px == 0 && 16 * (t0 + j) + 4 * mg < a.ld_part) ? pch + 64u * j : XR_DEAD; };
+    auto poff = [&](const int j) { return (tlive[j] && px == 0 && 16 * (t0 + j) + 4 * mg < a.ld_part) ? pch + 64u * j : YR_DEAD; };
     if (a.part != nullptr && strip == 0 && seg == 0) {     // rows no (strip, quantum) owns: zero (the buffer is sized for the LDS-tiled form's smallest tile)
         for (int rr = a.strips * a.nquanta; rr < a.rows_cap; ++rr)
 #pragma unroll
             for (int j = 0; j < NT; ++j)
-                __builtin_amdgcn_raw_buffer_store_b128((xr_u4){0u, 0u, 0u, 0u}, psrc, poff(j) == XR_DEAD ? XR_DEAD : (unsigned)(rr * a.ld_part) * 4u + poff(j), 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128((v4u){0u, 0u, 0u, 0u}, psrc, poff(j) == YR_DEAD ? YR_DEAD : (unsigned)(rr * a.ld_part) * 4u + poff(j), 0, 0);
     }
     auto flush = [&](const int qi) {
         const unsigned prow_ = (unsigned)((strip * a.nquanta + qi) * a.ld_part) * 4u;
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-            xr_f4 v = ssum[j];
+            v4f v = ssum[j];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {   // fixed tree over the 16 pixels of the DPP row (rotations by 8, 4, 2, 1: every lane ends with the total): deterministic
-                float t = v[i];
-                asm("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0xf\n\ts_nop 1\n\t"
-                    "v_add_f32_dpp %0, %0, %0 row_ror:4 row_mask:0xf bank_mask:0xf\n\ts_nop 1\n\t"
-                    "v_add_f32_dpp %0, %0, %0 row_ror:2 row_mask:0xf bank_mask:0xf\n\ts_nop 1\n\t"
-                    "v_add_f32_dpp %0, %0, %0 row_ror:1 row_mask:0xf bank_mask:0xf" : "+v"(t));
-                v[i] = t;
+                v[i] = yr_row_sum16(v[i]);
             }
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(xr_u4, v), psrc, poff(j) == XR_DEAD ? XR_DEAD : prow_ + poff(j), 0, 0);
-            ssum[j] = (xr_f4){0.f, 0.f, 0.f, 0.f};
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, v), psrc, poff(j) == YR_DEAD ? YR_DEAD : prow_ + poff(j), 0, 0);
+            ssum[j] = (v4f){0.f, 0.f, 0.f, 0.f};
         }
     };
     auto row = [&](auto emit_c, const int k, const int yo, const XRow& xc_, XRow& xn_) {
@@ -629,10 +305,10 @@ __global__ __launch_bounds__(256, MW) void mbxr_kernel(MbxrArgs a) {
         const int r = rbeg + k;
         load_row(xn_, r + 1);
         const float hr = (r >= 0 && r < a.H) ? hi : 0.f;
-        xr_f4 ec[NT];
+        v4f ec[NT];
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-            xr_f4 d = (xr_f4){0.f, 0.f, 0.f, 0.f};
+            v4f d = (v4f){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int c = 0; c < NC; ++c) d = xr_mfma<T>(aw[j][c], xc_.m[c], d);
             ec[j] = xr_bn_act4<ACT>(d, es[j], eh[j], hr);
@@ -641,7 +317,7 @@ __global__ __launch_bounds__(256, MW) void mbxr_kernel(MbxrArgs a) {
             const unsigned opix = ((unsigned)yo * (unsigned)a.Wo + (unsigned)xo) * (unsigned)a.ld_out * 2u;
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
-                xr_f4 d = dh[j];
+                v4f d = dh[j];
                 if constexpr (K == 3) {
                     xr_row3(d, ring[j][0], tp[j][0], tp[j][1], tp[j][2]);
                     xr_row3(d, ring[j][1], tp[j][3], tp[j][4], tp[j][5]);
@@ -660,10 +336,10 @@ __global__ __launch_bounds__(256, MW) void mbxr_kernel(MbxrArgs a) {
                     d = xr_bc5_finish(cs, d);
                 }
                 typedef T t4 __attribute__((ext_vector_type(4)));
-                const xr_f4 v = xr_act4<ACT>(d, HI);
+                const v4f v = xr_act4<ACT>(d, HI);
                 const t4 o = __builtin_convertvector(v, t4);
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(xr_u2, o), osrc, ooff[j] == XR_DEAD ? XR_DEAD : opix + ooff[j], 0, 0);
-                const xr_f4 stored = __builtin_convertvector(o, xr_f4);   // the squeeze sums what was STORED (rounded)
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, o), osrc, ooff[j] == YR_DEAD ? YR_DEAD : opix + ooff[j], 0, 0);
+                const v4f stored = __builtin_convertvector(o, v4f);   // the squeeze sums what was STORED (rounded)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) ssum[j][i] = __builtin_fmaf(stored[i], omask, ssum[j][i]);
             }
@@ -681,20 +357,20 @@ __global__ __launch_bounds__(256, MW) void mbxr_kernel(MbxrArgs a) {
         // A pair of output rows (y, y + 1) reads input rows rho = 0 .. K + 1 (counted from 2 y - pad_t): row y taps ky = rho, row
         // y + 1 taps ky = rho - 2.  The first K - 2 of them are the last rows of the previous pair (cr), four are new; the
         // accumulators of the pair (d2) take every row's contribution as soon as the row is expanded.
-        xr_f4 d2[NT], cr[NT][K - 2];
+        v4f d2[NT], cr[NT][K - 2];
 #pragma unroll
         for (int j = 0; j < NT; ++j)
 #pragma unroll
-            for (int q = 0; q < K - 2; ++q) cr[j][q] = (xr_f4){0.f, 0.f, 0.f, 0.f};
+            for (int q = 0; q < K - 2; ++q) cr[j][q] = (v4f){0.f, 0.f, 0.f, 0.f};
         auto prow = [&](auto ph_c, const int k, const int yo, const XRow& xc_, XRow& xn_) {
             constexpr int PH = decltype(ph_c)::value;   // 0: warm-up row; 1..4: the pair's new rows rho = K - 3 + PH
             const int r = rbeg + k;
             load_row(xn_, r + 1);
             const float hr = (r >= 0 && r < a.H) ? hi : 0.f;
-            xr_f4 ec[NT];
+            v4f ec[NT];
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
-                xr_f4 d = (xr_f4){0.f, 0.f, 0.f, 0.f};
+                v4f d = (v4f){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int c = 0; c < NC; ++c) d = xr_mfma<T>(aw[j][c], xc_.m[c], d);
                 ec[j] = xr_bn_act4<ACT>(d, es[j], eh[j], hr);
@@ -723,10 +399,10 @@ __global__ __launch_bounds__(256, MW) void mbxr_kernel(MbxrArgs a) {
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
                     typedef T t4 __attribute__((ext_vector_type(4)));
-                    const xr_f4 v = xr_act4<ACT>(d2[j], HI);
+                    const v4f v = xr_act4<ACT>(d2[j], HI);
                     const t4 o = __builtin_convertvector(v, t4);
-                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(xr_u2, o), osrc, (ooff[j] == XR_DEAD || !rlive) ? XR_DEAD : opix + ooff[j], 0, 0);
-                    const xr_f4 stored = __builtin_convertvector(o, xr_f4);   // the squeeze sums what was STORED (rounded)
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, o), osrc, (ooff[j] == YR_DEAD || !rlive) ? YR_DEAD : opix + ooff[j], 0, 0);
+                    const v4f stored = __builtin_convertvector(o, v4f);   // the squeeze sums what was STORED (rounded)
 #pragma unroll
                     for (int i = 0; i < 4; ++i) ssum[j][i] = __builtin_fmaf(stored[i], om, ssum[j][i]);
                 }
@@ -802,14 +478,7 @@ static int launch_mbxr(const MbxrArgs& a0, int batch, int want_segs, hipStream_t
     constexpr int MW = EST <= 120 ? 4 : EST <= 160 ? 3 : EST <= 250 ? 2 : 1;
     a.strips = (a.Wo + NOUT - 1) / NOUT;
     a.groups = (a.T + NT - 1) / NT;
-    const int walks = batch * a.strips * a.groups;
-    int segs = (3 * 1024 + walks - 1) / walks;
-    const int max_segs = (a.Ho + 5) / 6;
-    if (segs > max_segs) segs = max_segs;
-    if (segs < 1) segs = 1;
-    if (want_segs > 0) segs = want_segs < a.Ho ? want_segs : a.Ho;
-    a.seg_rows = (a.Ho + segs - 1) / segs;
-    if (S == 2 && !BC5) a.seg_rows += a.seg_rows & 1;   // (output rows are processed in pairs)
+    a.seg_rows = ch_row_segments(a.Ho, batch * a.strips * a.groups, 1, 3 * 1024, 6, S == 2 && !BC5, want_segs, &a.segs);   // (stride 2 walks pairs of output rows, except in the broadcast-tap form)
     a.qrows = a.seg_rows + (a.seg_rows & 1); a.nquanta = 0;     // (no sums: the quantum loop runs once)
     if (a.part != nullptr) {
         // one row of the partial-sum buffer per (strip, quantum): the smallest even quantum from 4 rows on that fits the buffer - a
@@ -819,16 +488,11 @@ static int launch_mbxr(const MbxrArgs& a0, int batch, int want_segs, hipStream_t
         YR_REQUIRE(a.strips * ((a.Ho + q - 1) / q) <= a.rows_cap, "mbxr: %d strips exceed the %d rows of the partial-sum buffer", a.strips, a.rows_cap);
         a.qrows = q; a.nquanta = (a.Ho + q - 1) / q;
         a.seg_rows = (a.seg_rows + q - 1) / q * q;
+        a.segs = (a.Ho + a.seg_rows - 1) / a.seg_rows;
     }
-    a.segs = (a.Ho + a.seg_rows - 1) / a.seg_rows;
     a.nwaves = batch * a.strips * a.segs * a.groups;
-    static char nm[64];
-    static const int nm_len = snprintf(nm, sizeof(nm), "mbxr_kernel<%s,%d,%d,%d,%d,%d,%d>", yr_dtype_name(yr_elem<T>::dtype), K, S, ACT, NC, NT, MW);
-    (void)nm_len;
-    yr_note_kernel(nm);
-    hipLaunchKernelGGL((mbxr_kernel<T, K, S, ACT, NC, NT, MW>), dim3((unsigned)((a.nwaves + 3) / 4)), dim3(256), 0, s, a);
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+    return ch_launch<mbxr_kernel<T, K, S, ACT, NC, NT, MW>>(dim3((unsigned)((a.nwaves + 3) / 4)), dim3(256), 0, 0, s, a,
+                                                            "mbxr_kernel<%s,%d,%d,%d,%d,%d,%d>", yr_dtype_name(yr_elem<T>::dtype), K, S, ACT, NC, NT, MW);
 }
 
 template <class T, int K, int S, int ACT>
@@ -879,8 +543,8 @@ __global__ __launch_bounds__(256, 2) void stemxr_kernel(StemxrArgs a) {
     typedef float f2 __attribute__((ext_vector_type(2)));
 
     // ---- stationary: stem A fragments (gathered from the pair-packed float32 rows, rounded), shifts, depthwise taps
-    xr_u4 aw[NT];
-    xr_f4 sh[NT], dh[NT], tp[NT][9], ssum[NT];
+    v4u aw[NT];
+    v4f sh[NT], dh[NT], tp[NT][9], ssum[NT];
     unsigned ooff[NT];
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
@@ -896,7 +560,7 @@ __global__ __launch_bounds__(256, 2) void stemxr_kernel(StemxrArgs a) {
             unsigned u[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) u[i] = __builtin_bit_cast(unsigned, __builtin_convertvector((f2){v[2 * i], v[2 * i + 1]}, t2));
-            aw[j] = (xr_u4){u[0], u[1], u[2], u[3]};
+            aw[j] = (v4u){u[0], u[1], u[2], u[3]};
         }
         const int ch = 16 * j + 4 * mg;                    // this lane's 4 channels of tile j in the MFMA result
 #pragma unroll
@@ -910,30 +574,30 @@ __global__ __launch_bounds__(256, 2) void stemxr_kernel(StemxrArgs a) {
 #pragma unroll
             for (int q = 0; q < 9; ++q) tp[j][q][i] = live ? dr[2 * q] : 0.f;
         }
-        ssum[j] = (xr_f4){0.f, 0.f, 0.f, 0.f};
-        ooff[j] = (out_lane && ch < a.C1) ? (unsigned)ch * 2u : XR_DEAD;
+        ssum[j] = (v4f){0.f, 0.f, 0.f, 0.f};
+        ooff[j] = (out_lane && ch < a.C1) ? (unsigned)ch * 2u : YR_DEAD;
     }
-    const xr_rsrc isrc = xr_make_rsrc(a.img + (size_t)b * a.Hi * a.Wi * 3, (unsigned)(a.Hi * a.Wi * 3) * 4u);
-    const xr_rsrc osrc = xr_make_rsrc(reinterpret_cast<T*>(a.out) + (size_t)b * a.Ho * a.Wo * a.ld_out, (unsigned)(a.Ho * a.Wo * a.ld_out) * 2u);
+    const yr_rsrc isrc = yr_make_rsrc(a.img + (size_t)b * a.Hi * a.Wi * 3, (unsigned)(a.Hi * a.Wi * 3) * 4u);
+    const yr_rsrc osrc = yr_make_rsrc(reinterpret_cast<T*>(a.out) + (size_t)b * a.Ho * a.Wo * a.ld_out, (unsigned)(a.Ho * a.Wo * a.ld_out) * 2u);
     const unsigned irow = (unsigned)a.Wi * 12u;            // bytes per image row
     const unsigned icol = (unsigned)(2 * xsc) * 12u;       // the window's first byte within a row (even sizes: no left padding)
     const bool last_col = 2 * xsc + 2 >= a.Wi;             // kx = 2 lies beyond the row: values 6, 7 (k groups 0..2) and group 3 are padding
     // the B operand of stem row ys for this lane: 8 image values of its k group, rounded
-    auto load_b = [&](int ys) -> xr_u4 {
+    auto load_b = [&](int ys) -> v4u {
         const int ysc = min(max(ys, 0), a.Ho - 1);
         float v[8];
         if (mg < 3) {
             const int iy = 2 * ysc + mg;
-            const unsigned off = iy < a.Hi ? (unsigned)iy * irow + icol : XR_DEAD;
-            const xr_f4 lo = __builtin_bit_cast(xr_f4, __builtin_amdgcn_raw_buffer_load_b128(isrc, off, 0, 0));
-            const xr_f4 hi4 = __builtin_bit_cast(xr_f4, __builtin_amdgcn_raw_buffer_load_b128(isrc, off == XR_DEAD ? XR_DEAD : off + 16u, 0, 0));
+            const unsigned off = iy < a.Hi ? (unsigned)iy * irow + icol : YR_DEAD;
+            const v4f lo = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(isrc, off, 0, 0));
+            const v4f hi4 = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(isrc, off == YR_DEAD ? YR_DEAD : off + 16u, 0, 0));
             v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3]; v[4] = hi4[0]; v[5] = hi4[1];
             v[6] = last_col ? 0.f : hi4[2]; v[7] = last_col ? 0.f : hi4[3];
         } else {
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
                 const int iy = 2 * ysc + i;
-                const unsigned off = (iy < a.Hi && !last_col) ? (unsigned)iy * irow + icol + 32u : XR_DEAD;
+                const unsigned off = (iy < a.Hi && !last_col) ? (unsigned)iy * irow + icol + 32u : YR_DEAD;
                 v[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(isrc, off, 0, 0));
             }
             v[3] = v[4] = v[5] = v[6] = v[7] = 0.f;
@@ -941,21 +605,21 @@ __global__ __launch_bounds__(256, 2) void stemxr_kernel(StemxrArgs a) {
         unsigned u[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) u[i] = __builtin_bit_cast(unsigned, __builtin_convertvector((f2){v[2 * i], v[2 * i + 1]}, t2));
-        return (xr_u4){u[0], u[1], u[2], u[3]};
+        return (v4u){u[0], u[1], u[2], u[3]};
     };
     const int rbeg = yo0 - 1, nout = yo1 - yo0;
-    xr_f4 ring[NT][2];
+    v4f ring[NT][2];
 #pragma unroll
-    for (int j = 0; j < NT; ++j) { ring[j][0] = (xr_f4){0.f, 0.f, 0.f, 0.f}; ring[j][1] = ring[j][0]; }
-    xr_u4 bcur = load_b(rbeg);
+    for (int j = 0; j < NT; ++j) { ring[j][0] = (v4f){0.f, 0.f, 0.f, 0.f}; ring[j][1] = ring[j][0]; }
+    v4u bcur = load_b(rbeg);
     for (int k = 0; k < nout + 2; ++k) {
         const int ys = rbeg + k;
-        const xr_u4 bnext = load_b(ys + 1);
+        const v4u bnext = load_b(ys + 1);
         const float hr = (ys >= 0 && ys < a.Ho) ? hi : 0.f;
-        xr_f4 ec[NT];
+        v4f ec[NT];
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-            const xr_f4 d = xr_mfma<T>(aw[j], bcur, sh[j]);       // (the BN shift is the accumulator's initial value)
+            const v4f d = xr_mfma<T>(aw[j], bcur, sh[j]);       // (the BN shift is the accumulator's initial value)
             ec[j] = xr_act4<ACT>(d, hr);
         }
         if (k >= 2) {
@@ -963,14 +627,14 @@ __global__ __launch_bounds__(256, 2) void stemxr_kernel(StemxrArgs a) {
             const unsigned opix = ((unsigned)yo * (unsigned)a.Wo + (unsigned)xo) * (unsigned)a.ld_out * 2u;
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
-                xr_f4 d = dh[j];
+                v4f d = dh[j];
                 xr_row3(d, ring[j][0], tp[j][0], tp[j][1], tp[j][2]);
                 xr_row3(d, ring[j][1], tp[j][3], tp[j][4], tp[j][5]);
                 xr_row3(d, ec[j], tp[j][6], tp[j][7], tp[j][8]);
-                const xr_f4 v = xr_act4<ACT>(d, HI);
+                const v4f v = xr_act4<ACT>(d, HI);
                 const t4 o = __builtin_convertvector(v, t4);
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(xr_u2, o), osrc, ooff[j] == XR_DEAD ? XR_DEAD : opix + ooff[j], 0, 0);
-                const xr_f4 stored = __builtin_convertvector(o, xr_f4);
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, o), osrc, ooff[j] == YR_DEAD ? YR_DEAD : opix + ooff[j], 0, 0);
+                const v4f stored = __builtin_convertvector(o, v4f);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) ssum[j][i] = __builtin_fmaf(stored[i], omask, ssum[j][i]);
             }
@@ -983,7 +647,7 @@ __global__ __launch_bounds__(256, 2) void stemxr_kernel(StemxrArgs a) {
         const int prow = ty * a.tiles_x + tx;
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-            xr_f4 v = ssum[j];
+            v4f v = ssum[j];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 v[i] += __shfl_xor(v[i], 8, 16);
@@ -1020,19 +684,12 @@ static int launch_stemxr_t(const yr_op& op, int batch, hipStream_t s) {
     a.tiles_x = (a.Wo + 13) / 14; a.tiles_y = (a.Ho + 13) / 14;
     a.nwaves = batch * a.tiles_x * a.tiles_y;
     const int nt = (a.C1 + 15) / 16, act = op.act == YR_ACT_RELU6 ? 0 : 1;
-    static char nm[48];
-    snprintf(nm, sizeof(nm), "stemxr_kernel<%s,%d,%d>", yr_dtype_name(yr_elem<T>::dtype), nt, act);
-    yr_note_kernel(nm);
     const dim3 grid((unsigned)((a.nwaves + 3) / 4));
-#define SX_GO(NTV)                                                                                   \
-    do {                                                                                            \
-        if (act == 0) hipLaunchKernelGGL((stemxr_kernel<T, NTV, 0>), grid, dim3(256), 0, s, a);    \
-        else hipLaunchKernelGGL((stemxr_kernel<T, NTV, 1>), grid, dim3(256), 0, s, a);             \
-    } while (0)
-    if (nt == 2) SX_GO(2); else if (nt == 3) SX_GO(3); else SX_GO(1);
+#define SX_GO(NTV, ACTV) ch_launch<stemxr_kernel<T, NTV, ACTV>>(grid, dim3(256), 0, 0, s, a, "stemxr_kernel<%s,%d,%d>", yr_dtype_name(yr_elem<T>::dtype), NTV, ACTV)
+    if (nt == 2) return act == 0 ? SX_GO(2, 0) : SX_GO(2, 1);
+    if (nt == 3) return act == 0 ? SX_GO(3, 0) : SX_GO(3, 1);
+    return act == 0 ? SX_GO(1, 0) : SX_GO(1, 1);
 #undef SX_GO
-    YR_LAUNCH_CHECK();
-    return YR_OK;
 }
 
 int yr_launch_stemxr(const yr_op& op, int batch, hipStream_t s) {
@@ -1073,51 +730,51 @@ __global__ __launch_bounds__(256, 2) void stemxp_kernel(StemxpArgs a) {
     typedef float f2 __attribute__((ext_vector_type(2)));
 
     // ---- stationary: stem A fragments, stem BN rows, depthwise taps (times the BN scale) and shift, projection A fragments
-    xr_u4 aw[NT];
-    xr_u2 wpf[NT][TO];
-    xr_f4 es[NT], eh[NT], dh[NT], tp[NT][9];
+    v4u aw[NT];
+    v2u wpf[NT][TO];
+    v4f es[NT], eh[NT], dh[NT], tp[NT][9];
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
-        aw[j] = *reinterpret_cast<const xr_u4*>(reinterpret_cast<const char*>(a.ws) + ((size_t)(16 * j + px) * 32 + 8 * mg) * 2);
+        aw[j] = *reinterpret_cast<const v4u*>(reinterpret_cast<const char*>(a.ws) + ((size_t)(16 * j + px) * 32 + 8 * mg) * 2);
         const int ch = 16 * j + 4 * mg;                    // this lane's 4 channels of tile j in the MFMA result (< C1P: zero padded)
-        es[j] = *reinterpret_cast<const xr_f4*>(a.ssc + ch);
-        eh[j] = *reinterpret_cast<const xr_f4*>(a.ssh + ch);
+        es[j] = *reinterpret_cast<const v4f*>(a.ssc + ch);
+        eh[j] = *reinterpret_cast<const v4f*>(a.ssh + ch);
 #pragma unroll
-        for (int q = 0; q < 9; ++q) tp[j][q] = *reinterpret_cast<const xr_f4*>(a.wd + (size_t)q * a.C1P + ch);
-        dh[j] = *reinterpret_cast<const xr_f4*>(a.wd + (size_t)9 * a.C1P + ch);
+        for (int q = 0; q < 9; ++q) tp[j][q] = *reinterpret_cast<const v4f*>(a.wd + (size_t)q * a.C1P + ch);
+        dh[j] = *reinterpret_cast<const v4f*>(a.wd + (size_t)9 * a.C1P + ch);
 #pragma unroll
         for (int t = 0; t < TO; ++t)
-            wpf[j][t] = *reinterpret_cast<const xr_u2*>(reinterpret_cast<const char*>(a.wp) + ((size_t)(16 * t + px) * a.C1P + ch) * 2);
+            wpf[j][t] = *reinterpret_cast<const v2u*>(reinterpret_cast<const char*>(a.wp) + ((size_t)(16 * t + px) * a.C1P + ch) * 2);
     }
-    xr_f4 psc[TO], psh[TO];
+    v4f psc[TO], psh[TO];
     unsigned ooff[TO];
 #pragma unroll
     for (int t = 0; t < TO; ++t) {
         const int co = 16 * t + 4 * mg;
-        psc[t] = *reinterpret_cast<const xr_f4*>(a.bp + co);
-        psh[t] = *reinterpret_cast<const xr_f4*>(a.bp + a.COP + co);
-        ooff[t] = (out_lane && co < a.Cout) ? (unsigned)co * 2u : XR_DEAD;
+        psc[t] = *reinterpret_cast<const v4f*>(a.bp + co);
+        psh[t] = *reinterpret_cast<const v4f*>(a.bp + a.COP + co);
+        ooff[t] = (out_lane && co < a.Cout) ? (unsigned)co * 2u : YR_DEAD;
     }
-    const xr_rsrc isrc = xr_make_rsrc(a.img + (size_t)b * a.Hi * a.Wi * 3, (unsigned)(a.Hi * a.Wi * 3) * 4u);
-    const xr_rsrc osrc = xr_make_rsrc(reinterpret_cast<T*>(a.out) + (size_t)b * a.Ho * a.Wo * a.ld_out, (unsigned)(a.Ho * a.Wo * a.ld_out) * 2u);
+    const yr_rsrc isrc = yr_make_rsrc(a.img + (size_t)b * a.Hi * a.Wi * 3, (unsigned)(a.Hi * a.Wi * 3) * 4u);
+    const yr_rsrc osrc = yr_make_rsrc(reinterpret_cast<T*>(a.out) + (size_t)b * a.Ho * a.Wo * a.ld_out, (unsigned)(a.Ho * a.Wo * a.ld_out) * 2u);
     const unsigned irow = (unsigned)a.Wi * 12u;            // bytes per image row
     const unsigned icol = (unsigned)(2 * xsc) * 12u;       // the window's first byte within a row (even sizes: no left padding)
     const bool last_col = 2 * xsc + 2 >= a.Wi;             // kx = 2 lies beyond the row: values 6, 7 (k groups 0..2) and group 3 are padding
-    auto load_b = [&](int ys) -> xr_u4 {                   // (as stemxr_kernel: 8 image values of the lane's k group, rounded)
+    auto load_b = [&](int ys) -> v4u {                   // (as stemxr_kernel: 8 image values of the lane's k group, rounded)
         const int ysc = min(max(ys, 0), a.Ho - 1);
         float v[8];
         if (mg < 3) {
             const int iy = 2 * ysc + mg;
-            const unsigned off = iy < a.Hi ? (unsigned)iy * irow + icol : XR_DEAD;
-            const xr_f4 lo = __builtin_bit_cast(xr_f4, __builtin_amdgcn_raw_buffer_load_b128(isrc, off, 0, 0));
-            const xr_f4 hi4 = __builtin_bit_cast(xr_f4, __builtin_amdgcn_raw_buffer_load_b128(isrc, off == XR_DEAD ? XR_DEAD : off + 16u, 0, 0));
+            const unsigned off = iy < a.Hi ? (unsigned)iy * irow + icol : YR_DEAD;
+            const v4f lo = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(isrc, off, 0, 0));
+            const v4f hi4 = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(isrc, off == YR_DEAD ? YR_DEAD : off + 16u, 0, 0));
             v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3]; v[4] = hi4[0]; v[5] = hi4[1];
             v[6] = last_col ? 0.f : hi4[2]; v[7] = last_col ? 0.f : hi4[3];
         } else {
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
                 const int iy = 2 * ysc + i;
-                const unsigned off = (iy < a.Hi && !last_col) ? (unsigned)iy * irow + icol + 32u : XR_DEAD;
+                const unsigned off = (iy < a.Hi && !last_col) ? (unsigned)iy * irow + icol + 32u : YR_DEAD;
                 v[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(isrc, off, 0, 0));
             }
             v[3] = v[4] = v[5] = v[6] = v[7] = 0.f;
@@ -1125,42 +782,42 @@ __global__ __launch_bounds__(256, 2) void stemxp_kernel(StemxpArgs a) {
         unsigned u[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) u[i] = __builtin_bit_cast(unsigned, __builtin_convertvector((f2){v[2 * i], v[2 * i + 1]}, t2));
-        return (xr_u4){u[0], u[1], u[2], u[3]};
+        return (v4u){u[0], u[1], u[2], u[3]};
     };
     const int rbeg = yo0 - 1, nout = yo1 - yo0;
-    xr_f4 ring[NT][2];
+    v4f ring[NT][2];
 #pragma unroll
-    for (int j = 0; j < NT; ++j) { ring[j][0] = (xr_f4){0.f, 0.f, 0.f, 0.f}; ring[j][1] = ring[j][0]; }
-    xr_u4 bcur = load_b(rbeg);
+    for (int j = 0; j < NT; ++j) { ring[j][0] = (v4f){0.f, 0.f, 0.f, 0.f}; ring[j][1] = ring[j][0]; }
+    v4u bcur = load_b(rbeg);
     for (int k = 0; k < nout + 2; ++k) {
         const int ys = rbeg + k;
-        const xr_u4 bnext = load_b(ys + 1);
+        const v4u bnext = load_b(ys + 1);
         const float hr = (ys >= 0 && ys < a.Ho) ? hi : 0.f;
-        xr_f4 ec[NT];
+        v4f ec[NT];
 #pragma unroll
-        for (int j = 0; j < NT; ++j) ec[j] = xr_bn_act4<ACT>(xr_mfma<T>(aw[j], bcur, (xr_f4){0.f, 0.f, 0.f, 0.f}), es[j], eh[j], hr);
+        for (int j = 0; j < NT; ++j) ec[j] = xr_bn_act4<ACT>(xr_mfma<T>(aw[j], bcur, (v4f){0.f, 0.f, 0.f, 0.f}), es[j], eh[j], hr);
         if (k >= 2) {
             const int yo = yo0 + k - 2;
-            xr_f4 P[TO];
+            v4f P[TO];
 #pragma unroll
-            for (int t = 0; t < TO; ++t) P[t] = (xr_f4){0.f, 0.f, 0.f, 0.f};
+            for (int t = 0; t < TO; ++t) P[t] = (v4f){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
-                xr_f4 d = dh[j];
+                v4f d = dh[j];
                 xr_row3(d, ring[j][0], tp[j][0], tp[j][1], tp[j][2]);
                 xr_row3(d, ring[j][1], tp[j][3], tp[j][4], tp[j][5]);
                 xr_row3(d, ec[j], tp[j][6], tp[j][7], tp[j][8]);
-                const xr_u2 bop = __builtin_bit_cast(xr_u2, __builtin_convertvector(xr_act4<ACT>(d, HI), t4));   // rounded: the projection's operand type
+                const v2u bop = __builtin_bit_cast(v2u, __builtin_convertvector(xr_act4<ACT>(d, HI), t4));   // rounded: the projection's operand type
 #pragma unroll
                 for (int t = 0; t < TO; ++t) P[t] = xr_mfma16<T>(wpf[j][t], bop, P[t]);
             }
             const unsigned opix = ((unsigned)yo * (unsigned)a.Wo + (unsigned)xo) * (unsigned)a.ld_out * 2u;
 #pragma unroll
             for (int t = 0; t < TO; ++t) {
-                xr_f4 v;
+                v4f v;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) v[i] = __builtin_fmaf(P[t][i], psc[t][i], psh[t][i]);
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(xr_u2, __builtin_convertvector(v, t4)), osrc, ooff[t] == XR_DEAD ? XR_DEAD : opix + ooff[t], 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, __builtin_convertvector(v, t4)), osrc, ooff[t] == YR_DEAD ? YR_DEAD : opix + ooff[t], 0, 0);
             }
         }
 #pragma unroll
@@ -1190,20 +847,13 @@ static int launch_stemxp_t(const yr_op& op, int batch, hipStream_t s) {
     a.tiles_x = (a.Wo + 13) / 14; a.tiles_y = (a.Ho + 13) / 14;
     a.nwaves = batch * a.tiles_x * a.tiles_y;
     const int nt = (a.C1 + 15) / 16, to = a.COP / 16, act = op.act == YR_ACT_RELU6 ? 0 : 1;
-    static char nm[48];
-    snprintf(nm, sizeof(nm), "stemxp_kernel<%s,%d,%d,%d>", yr_dtype_name(yr_elem<T>::dtype), nt, to, act);
-    yr_note_kernel(nm);
     const dim3 grid((unsigned)((a.nwaves + 3) / 4));
-#define SP_GO(NTV, TOV)                                                                                   \
-    do {                                                                                                 \
-        if (act == 0) hipLaunchKernelGGL((stemxp_kernel<T, NTV, TOV, 0>), grid, dim3(256), 0, s, a);    \
-        else hipLaunchKernelGGL((stemxp_kernel<T, NTV, TOV, 1>), grid, dim3(256), 0, s, a);             \
-    } while (0)
-    if (to == 1) { if (nt == 3) SP_GO(3, 1); else if (nt == 2) SP_GO(2, 1); else SP_GO(1, 1); }
-    else { if (nt == 3) SP_GO(3, 2); else if (nt == 2) SP_GO(2, 2); else SP_GO(1, 2); }
+#define SP_ACT(NTV, TOV, ACTV) ch_launch<stemxp_kernel<T, NTV, TOV, ACTV>>(grid, dim3(256), 0, 0, s, a, "stemxp_kernel<%s,%d,%d,%d>", yr_dtype_name(yr_elem<T>::dtype), NTV, TOV, ACTV)
+#define SP_GO(NTV, TOV) (act == 0 ? SP_ACT(NTV, TOV, 0) : SP_ACT(NTV, TOV, 1))
+    if (to == 1) return nt == 3 ? SP_GO(3, 1) : nt == 2 ? SP_GO(2, 1) : SP_GO(1, 1);
+    return nt == 3 ? SP_GO(3, 2) : nt == 2 ? SP_GO(2, 2) : SP_GO(1, 2);
 #undef SP_GO
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+#undef SP_ACT
 }
 
 int yr_launch_stemxp(const yr_op& op, int batch, hipStream_t s) {
@@ -1229,7 +879,7 @@ template <class T, int S, int ACT, int NC, int TO, int NW, int MW>
 __global__ __launch_bounds__(64 * NW, MW) void mbhr_kernel(MbhrArgs a) {
     constexpr int K = 3, KK = 9, NOUT = (16 - K) / S + 1;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    xr_f4* red = reinterpret_cast<xr_f4*>(lds);            // [2][NW][TO][64]
+    v4f* red = reinterpret_cast<v4f*>(lds);            // [2][NW][TO][64]
     const int lane = threadIdx.x & 63, px = lane & 15, mg = lane >> 4;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int bid = (int)yr_xcd_swizzle(blockIdx.x, gridDim.x);
@@ -1245,57 +895,57 @@ __global__ __launch_bounds__(64 * NW, MW) void mbhr_kernel(MbhrArgs a) {
     const bool out_lane = px >= 1 && (px - 1) % S == 0 && jo < NOUT && xo < a.Wo;
 
     // ---- stationary: the wave's two expanded tiles (a tile beyond T: all-zero parameters -> its depthwise result is act(0) = 0)
-    xr_u4 aw[2][NC], wpf[TO];
-    xr_f4 es[2], eh[2], dh[2], tp[2][KK];
+    v4u aw[2][NC], wpf[TO];
+    v4f es[2], eh[2], dh[2], tp[2][KK];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int t = 2 * w + j;
         const bool live = t < a.T;
         const int tc = live ? t : 0, ch = 16 * tc + 4 * mg;
         const char* wrow = reinterpret_cast<const char*>(a.we) + ((size_t)(16 * tc + px) * a.KP + 8 * mg) * 2;
-        const xr_f4 z = {0.f, 0.f, 0.f, 0.f};
+        const v4f z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int c = 0; c < NC; ++c) aw[j][c] = live ? *reinterpret_cast<const xr_u4*>(wrow + 64 * c) : (xr_u4){0u, 0u, 0u, 0u};
-        const xr_f4 dsc = *reinterpret_cast<const xr_f4*>(a.prm + (size_t)KK * a.CexpP + ch);
-        dh[j] = live ? *reinterpret_cast<const xr_f4*>(a.prm + (size_t)(KK + 1) * a.CexpP + ch) : z;
-        es[j] = live ? *reinterpret_cast<const xr_f4*>(a.prm + (size_t)(KK + 2) * a.CexpP + ch) : z;
-        eh[j] = live ? *reinterpret_cast<const xr_f4*>(a.prm + (size_t)(KK + 3) * a.CexpP + ch) : z;
+        for (int c = 0; c < NC; ++c) aw[j][c] = live ? *reinterpret_cast<const v4u*>(wrow + 64 * c) : (v4u){0u, 0u, 0u, 0u};
+        const v4f dsc = *reinterpret_cast<const v4f*>(a.prm + (size_t)KK * a.CexpP + ch);
+        dh[j] = live ? *reinterpret_cast<const v4f*>(a.prm + (size_t)(KK + 1) * a.CexpP + ch) : z;
+        es[j] = live ? *reinterpret_cast<const v4f*>(a.prm + (size_t)(KK + 2) * a.CexpP + ch) : z;
+        eh[j] = live ? *reinterpret_cast<const v4f*>(a.prm + (size_t)(KK + 3) * a.CexpP + ch) : z;
 #pragma unroll
-        for (int q = 0; q < KK; ++q) tp[j][q] = live ? *reinterpret_cast<const xr_f4*>(a.prm + (size_t)q * a.CexpP + ch) * dsc : z;
+        for (int q = 0; q < KK; ++q) tp[j][q] = live ? *reinterpret_cast<const v4f*>(a.prm + (size_t)q * a.CexpP + ch) * dsc : z;
     }
 #pragma unroll
     for (int t = 0; t < TO; ++t) {   // project A fragment of cout tile t for this wave's k step: W[16 t + m][16 (2w) + 4 g ..] ++ W[..][16 (2w + 1) + 4 g ..]
         const int co = 16 * t + px;
         const char* prow = reinterpret_cast<const char*>(a.wp) + ((size_t)(co < a.Cout ? co : 0) * a.CexpP + 32 * w + 4 * mg) * 2;
-        xr_u2 lo = *reinterpret_cast<const xr_u2*>(prow), hi2 = *reinterpret_cast<const xr_u2*>(prow + 32);
-        if (co >= a.Cout) { lo = (xr_u2){0u, 0u}; hi2 = lo; }
-        wpf[t] = (xr_u4){lo[0], lo[1], hi2[0], hi2[1]};
+        v2u lo = *reinterpret_cast<const v2u*>(prow), hi2 = *reinterpret_cast<const v2u*>(prow + 32);
+        if (co >= a.Cout) { lo = (v2u){0u, 0u}; hi2 = lo; }
+        wpf[t] = (v4u){lo[0], lo[1], hi2[0], hi2[1]};
     }
     // the cout tile this wave finishes (t = w, if w < TO): project BN rows
     const int fco = 16 * w + 4 * mg;
     const bool flive = w < TO && out_lane && fco < a.Cout;
     const bool rlive = flive && a.has_res;
-    xr_f4 fsc = {0.f, 0.f, 0.f, 0.f}, fsh = fsc;
-    if (w < TO && fco < a.Cout) { fsc = *reinterpret_cast<const xr_f4*>(a.sp + fco); fsh = *reinterpret_cast<const xr_f4*>(a.hp + fco); }
+    v4f fsc = {0.f, 0.f, 0.f, 0.f}, fsh = fsc;
+    if (w < TO && fco < a.Cout) { fsc = *reinterpret_cast<const v4f*>(a.sp + fco); fsh = *reinterpret_cast<const v4f*>(a.hp + fco); }
 
-    const xr_rsrc xsrc = xr_make_rsrc(reinterpret_cast<const T*>(a.x) + (size_t)b * a.H * a.W * a.ld_in, (unsigned)(a.H * a.W * a.ld_in) * 2u);
-    const xr_rsrc osrc = xr_make_rsrc(reinterpret_cast<T*>(a.out) + (size_t)b * a.Ho * a.Wo * a.ld_out, (unsigned)(a.Ho * a.Wo * a.ld_out) * 2u);
+    const yr_rsrc xsrc = yr_make_rsrc(reinterpret_cast<const T*>(a.x) + (size_t)b * a.H * a.W * a.ld_in, (unsigned)(a.H * a.W * a.ld_in) * 2u);
+    const yr_rsrc osrc = yr_make_rsrc(reinterpret_cast<T*>(a.out) + (size_t)b * a.Ho * a.Wo * a.ld_out, (unsigned)(a.Ho * a.Wo * a.ld_out) * 2u);
     const int rbeg = S * yo0 - a.pad_t, nout = yo1 - yo0;
     unsigned xoff[NC];
 #pragma unroll
-    for (int c = 0; c < NC; ++c) xoff[c] = (32 * c + 8 * mg < a.Cin) ? ((unsigned)xc * (unsigned)a.ld_in + 32u * c + 8u * mg) * 2u : XR_DEAD;
+    for (int c = 0; c < NC; ++c) xoff[c] = (32 * c + 8 * mg < a.Cin) ? ((unsigned)xc * (unsigned)a.ld_in + 32u * c + 8u * mg) * 2u : YR_DEAD;
     const unsigned xrow = (unsigned)(a.W * a.ld_in) * 2u;
-    struct XRow { xr_u4 m[NC]; };
+    struct XRow { v4u m[NC]; };
     XRow xa, xb;
     auto load_row = [&](XRow& x, int r) {
         const unsigned so = (unsigned)min(max(r, 0), a.H - 1) * xrow;
 #pragma unroll
-        for (int c = 0; c < NC; ++c) x.m[c] = __builtin_bit_cast(xr_u4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xoff[c], so, 0));
+        for (int c = 0; c < NC; ++c) x.m[c] = __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xoff[c], so, 0));
     };
     load_row(xa, rbeg);
-    xr_f4 ring[2][2];
+    v4f ring[2][2];
 #pragma unroll
-    for (int j = 0; j < 2; ++j) { ring[j][0] = (xr_f4){0.f, 0.f, 0.f, 0.f}; ring[j][1] = ring[j][0]; }
+    for (int j = 0; j < 2; ++j) { ring[j][0] = (v4f){0.f, 0.f, 0.f, 0.f}; ring[j][1] = ring[j][0]; }
     int buf = 0;
     typedef T t4 __attribute__((ext_vector_type(4)));
 
@@ -1303,15 +953,15 @@ __global__ __launch_bounds__(64 * NW, MW) void mbhr_kernel(MbhrArgs a) {
         constexpr bool EMIT = decltype(emit_c)::value;
         const int r = rbeg + k;
         load_row(xn_, r + 1);
-        xr_u2 resv = {0u, 0u};
+        v2u resv = {0u, 0u};
         if constexpr (EMIT)   // UNCONDITIONAL (a dead offset reads zeros without a residual): a load under a branch makes every later wait vmcnt(0)
-            resv = __builtin_bit_cast(xr_u2, __builtin_amdgcn_raw_buffer_load_b64(xsrc, rlive ? (((unsigned)yo * (unsigned)a.Wo + (unsigned)xo) * (unsigned)a.ld_in + (unsigned)fco) * 2u : XR_DEAD, 0, 0));
+            resv = __builtin_bit_cast(v2u, __builtin_amdgcn_raw_buffer_load_b64(xsrc, rlive ? (((unsigned)yo * (unsigned)a.Wo + (unsigned)xo) * (unsigned)a.ld_in + (unsigned)fco) * 2u : YR_DEAD, 0, 0));
         __builtin_amdgcn_sched_barrier(0);   // (both loads are issued HERE: left alone the scheduler sinks the residual load to its use behind the barrier)
         const float hr = (r >= 0 && r < a.H) ? hi : 0.f;
-        xr_f4 ec[2];
+        v4f ec[2];
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            xr_f4 d = (xr_f4){0.f, 0.f, 0.f, 0.f};
+            v4f d = (v4f){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int c = 0; c < NC; ++c) d = xr_mfma<T>(aw[j][c], xc_.m[c], d);
             ec[j] = xr_bn_act4<ACT>(d, es[j], eh[j], hr);
@@ -1320,31 +970,31 @@ __global__ __launch_bounds__(64 * NW, MW) void mbhr_kernel(MbhrArgs a) {
             t4 dq[2];
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                xr_f4 d = dh[j];
+                v4f d = dh[j];
                 xr_row3(d, ring[j][0], tp[j][0], tp[j][1], tp[j][2]);
                 xr_row3(d, ring[j][1], tp[j][3], tp[j][4], tp[j][5]);
                 xr_row3(d, ec[j], tp[j][6], tp[j][7], tp[j][8]);
-                const xr_f4 v = xr_act4<ACT>(d, HI);
+                const v4f v = xr_act4<ACT>(d, HI);
                 dq[j] = __builtin_convertvector(v, t4);      // rounded: the projection's operand type
             }
-            const xr_u2 b0 = __builtin_bit_cast(xr_u2, dq[0]), b1 = __builtin_bit_cast(xr_u2, dq[1]);
-            const xr_u4 bop = {b0[0], b0[1], b1[0], b1[1]};
-            xr_f4* rb = red + buf * (NW * TO * 64);
+            const v2u b0 = __builtin_bit_cast(v2u, dq[0]), b1 = __builtin_bit_cast(v2u, dq[1]);
+            const v4u bop = {b0[0], b0[1], b1[0], b1[1]};
+            v4f* rb = red + buf * (NW * TO * 64);
 #pragma unroll
-            for (int t = 0; t < TO; ++t) rb[(w * TO + t) * 64 + lane] = xr_mfma<T>(wpf[t], bop, (xr_f4){0.f, 0.f, 0.f, 0.f});
+            for (int t = 0; t < TO; ++t) rb[(w * TO + t) * 64 + lane] = xr_mfma<T>(wpf[t], bop, (v4f){0.f, 0.f, 0.f, 0.f});
             __syncthreads();
-            xr_f4 acc = {0.f, 0.f, 0.f, 0.f};
+            v4f acc = {0.f, 0.f, 0.f, 0.f};
             if (w < TO) {
 #pragma unroll
                 for (int ww = 0; ww < NW; ++ww) acc += rb[(ww * TO + w) * 64 + lane];
             }
-            xr_f4 v;
+            v4f v;
 #pragma unroll
             for (int i = 0; i < 4; ++i) v[i] = __builtin_fmaf(acc[i], fsc[i], fsh[i]);
-            v += __builtin_convertvector(__builtin_bit_cast(t4, resv), xr_f4);   // (zeros without a residual)
+            v += __builtin_convertvector(__builtin_bit_cast(t4, resv), v4f);   // (zeros without a residual)
             const t4 o = __builtin_convertvector(v, t4);
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(xr_u2, o), osrc,
-                                                  flive ? (((unsigned)yo * (unsigned)a.Wo + (unsigned)xo) * (unsigned)a.ld_out + (unsigned)fco) * 2u : XR_DEAD, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, o), osrc,
+                                                  flive ? (((unsigned)yo * (unsigned)a.Wo + (unsigned)xo) * (unsigned)a.ld_out + (unsigned)fco) * 2u : YR_DEAD, 0, 0);
             buf ^= 1;
         }
 #pragma unroll
@@ -1377,31 +1027,10 @@ static int launch_mbhr(const MbhrArgs& a0, int batch, int want_segs, hipStream_t
     constexpr int MW = (NW <= 6 && S == 2) ? 3 : 2;   // (measured allocations: 161-180 registers for the one-chunk blocks - three waves per SIMD take 168)
     static_assert(NW <= 4 * MW, "the workgroup's waves must fit one CU");
     a.strips = (a.Wo + NOUT - 1) / NOUT;
-    const int walks = batch * a.strips;
-    int segs = (2 * 1024 + walks * NW - 1) / (walks * NW);
-    const int max_segs = (a.Ho + 5) / 6;
-    if (segs > max_segs) segs = max_segs;
-    if (segs < 1) segs = 1;
-    if (want_segs > 0) segs = want_segs < a.Ho ? want_segs : a.Ho;
-    a.seg_rows = (a.Ho + segs - 1) / segs;
-    a.segs = (a.Ho + a.seg_rows - 1) / a.seg_rows;
+    a.seg_rows = ch_row_segments(a.Ho, batch * a.strips, NW, 2 * 1024, 6, false, want_segs, &a.segs);
     const size_t lds = (size_t)2 * NW * TO * 64 * 16;
-    static char nm[64];
-    static const int nm_len = snprintf(nm, sizeof(nm), "mbhr_kernel<%s,%d,%d,%d,%d,%d,%d>", yr_dtype_name(yr_elem<T>::dtype), S, ACT, NC, TO, NW, MW);
-    (void)nm_len;
-    yr_note_kernel(nm);
-    auto kern = mbhr_kernel<T, S, ACT, NC, TO, NW, MW>;
-    static bool attr_set_dev[64] = {};   // per device: a process that drives several GPUs needs the attribute on each
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    bool& attr_set = attr_set_dev[cur_dev & 63];
-    if (!attr_set && lds > 48 * 1024) {
-        YR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(batch * a.strips * a.segs)), dim3(64 * NW), lds, s, a);
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+    return ch_launch<mbhr_kernel<T, S, ACT, NC, TO, NW, MW>>(dim3((unsigned)(batch * a.strips * a.segs)), dim3(64 * NW), lds, lds, s, a,
+                                                             "mbhr_kernel<%s,%d,%d,%d,%d,%d,%d>", yr_dtype_name(yr_elem<T>::dtype), S, ACT, NC, TO, NW, MW);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -1417,7 +1046,7 @@ template <class T, int K, int S, int ACT, int NC, int TO, int NT, int NW, int MW
 __global__ __launch_bounds__(64 * NW, MW) void mbhq_kernel(MbhrArgs a) {
     constexpr int KK = K * K, PAD = K / 2, NOUT = (16 - K) / S + 1;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    xr_f4* red = reinterpret_cast<xr_f4*>(lds);            // [2][NW][TO][64]
+    v4f* red = reinterpret_cast<v4f*>(lds);            // [2][NW][TO][64]
     const int lane = threadIdx.x & 63, px = lane & 15, mg = lane >> 4;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int bid = (int)yr_xcd_swizzle(blockIdx.x, gridDim.x);
@@ -1435,36 +1064,36 @@ __global__ __launch_bounds__(64 * NW, MW) void mbhq_kernel(MbhrArgs a) {
     const bool out_lane = (PAIR ? true : (px >= PAD && (px - PAD) % S == 0)) && jo < NOUT && xo < a.Wo;
 
     // ---- stationary: the wave's NT expanded tiles (a tile beyond T: all-zero parameters -> its depthwise result is act(0) = 0)
-    xr_u4 aw[NT][NC];
-    xr_u2 wpf[NT][TO];
+    v4u aw[NT][NC];
+    v2u wpf[NT][TO];
     constexpr bool BC5 = K == 5;   // 5x5: lane p of a row holds tap p / tap 16 + p (xr_bc5_row, xr_bc5_pair_row); 3x3: a register per tap
-    xr_f4 es[NT], eh[NT], dh[NT], tp[NT][BC5 ? 2 : KK];
+    v4f es[NT], eh[NT], dh[NT], tp[NT][BC5 ? 2 : KK];
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
         const int t = NT * w + j;
         const bool live = t < a.T;
         const int tc = live ? t : 0, ch = 16 * tc + 4 * mg;
         const char* wrow = reinterpret_cast<const char*>(a.we) + ((size_t)(16 * tc + px) * a.KP + 8 * mg) * 2;
-        const xr_f4 z = {0.f, 0.f, 0.f, 0.f};
+        const v4f z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int c = 0; c < NC; ++c) aw[j][c] = live ? *reinterpret_cast<const xr_u4*>(wrow + 64 * c) : (xr_u4){0u, 0u, 0u, 0u};
-        dh[j] = live ? *reinterpret_cast<const xr_f4*>(a.prm + (size_t)(KK + 1) * a.CexpP + ch) : z;
-        es[j] = live ? *reinterpret_cast<const xr_f4*>(a.prm + (size_t)(KK + 2) * a.CexpP + ch) : z;
-        eh[j] = live ? *reinterpret_cast<const xr_f4*>(a.prm + (size_t)(KK + 3) * a.CexpP + ch) : z;
-        const xr_f4 dsc = *reinterpret_cast<const xr_f4*>(a.prm + (size_t)KK * a.CexpP + ch);
+        for (int c = 0; c < NC; ++c) aw[j][c] = live ? *reinterpret_cast<const v4u*>(wrow + 64 * c) : (v4u){0u, 0u, 0u, 0u};
+        dh[j] = live ? *reinterpret_cast<const v4f*>(a.prm + (size_t)(KK + 1) * a.CexpP + ch) : z;
+        es[j] = live ? *reinterpret_cast<const v4f*>(a.prm + (size_t)(KK + 2) * a.CexpP + ch) : z;
+        eh[j] = live ? *reinterpret_cast<const v4f*>(a.prm + (size_t)(KK + 3) * a.CexpP + ch) : z;
+        const v4f dsc = *reinterpret_cast<const v4f*>(a.prm + (size_t)KK * a.CexpP + ch);
         if constexpr (!BC5) {
 #pragma unroll
-            for (int q = 0; q < KK; ++q) tp[j][q] = live ? *reinterpret_cast<const xr_f4*>(a.prm + (size_t)q * a.CexpP + ch) * dsc : z;
+            for (int q = 0; q < KK; ++q) tp[j][q] = live ? *reinterpret_cast<const v4f*>(a.prm + (size_t)q * a.CexpP + ch) * dsc : z;
         } else {
-            tp[j][0] = live ? *reinterpret_cast<const xr_f4*>(a.prm + (size_t)px * a.CexpP + ch) * dsc : z;
-            tp[j][1] = (live && 16 + px < KK) ? *reinterpret_cast<const xr_f4*>(a.prm + (size_t)(16 + px) * a.CexpP + ch) * dsc : z;
+            tp[j][0] = live ? *reinterpret_cast<const v4f*>(a.prm + (size_t)px * a.CexpP + ch) * dsc : z;
+            tp[j][1] = (live && 16 + px < KK) ? *reinterpret_cast<const v4f*>(a.prm + (size_t)(16 + px) * a.CexpP + ch) * dsc : z;
         }
 #pragma unroll
         for (int t2 = 0; t2 < TO; ++t2) {   // project A fragment of cout tile t2 for this tile's 16-deep k step: W[16 t2 + m][16 t + 4 g ..]
             const int co = 16 * t2 + px;
             const char* prow = reinterpret_cast<const char*>(a.wp) + ((size_t)(co < a.Cout ? co : 0) * a.CexpP + 16 * tc + 4 * mg) * 2;
-            xr_u2 v = *reinterpret_cast<const xr_u2*>(prow);
-            if (co >= a.Cout || !live) v = (xr_u2){0u, 0u};
+            v2u v = *reinterpret_cast<const v2u*>(prow);
+            if (co >= a.Cout || !live) v = (v2u){0u, 0u};
             wpf[j][t2] = v;
         }
     }
@@ -1472,37 +1101,37 @@ __global__ __launch_bounds__(64 * NW, MW) void mbhq_kernel(MbhrArgs a) {
     constexpr int NF = (TO + NW - 1) / NW;
     bool flive[NF];
     int fco[NF];
-    xr_f4 fsc[NF], fsh[NF];
+    v4f fsc[NF], fsh[NF];
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
         const int t = w + f * NW;
         fco[f] = 16 * t + 4 * mg;
         const bool in = t < TO && fco[f] < a.Cout;
         flive[f] = in && out_lane;
-        fsc[f] = in ? *reinterpret_cast<const xr_f4*>(a.sp + fco[f]) : (xr_f4){0.f, 0.f, 0.f, 0.f};
-        fsh[f] = in ? *reinterpret_cast<const xr_f4*>(a.hp + fco[f]) : (xr_f4){0.f, 0.f, 0.f, 0.f};
+        fsc[f] = in ? *reinterpret_cast<const v4f*>(a.sp + fco[f]) : (v4f){0.f, 0.f, 0.f, 0.f};
+        fsh[f] = in ? *reinterpret_cast<const v4f*>(a.hp + fco[f]) : (v4f){0.f, 0.f, 0.f, 0.f};
     }
 
-    const xr_rsrc xsrc = xr_make_rsrc(reinterpret_cast<const T*>(a.x) + (size_t)b * a.H * a.W * a.ld_in, (unsigned)(a.H * a.W * a.ld_in) * 2u);
-    const xr_rsrc osrc = xr_make_rsrc(reinterpret_cast<T*>(a.out) + (size_t)b * a.Ho * a.Wo * a.ld_out, (unsigned)(a.Ho * a.Wo * a.ld_out) * 2u);
+    const yr_rsrc xsrc = yr_make_rsrc(reinterpret_cast<const T*>(a.x) + (size_t)b * a.H * a.W * a.ld_in, (unsigned)(a.H * a.W * a.ld_in) * 2u);
+    const yr_rsrc osrc = yr_make_rsrc(reinterpret_cast<T*>(a.out) + (size_t)b * a.Ho * a.Wo * a.ld_out, (unsigned)(a.Ho * a.Wo * a.ld_out) * 2u);
     const int rbeg = S * yo0 - a.pad_t, nout = yo1 - yo0;
     unsigned xoff[NC];
 #pragma unroll
-    for (int c = 0; c < NC; ++c) xoff[c] = (32 * c + 8 * mg < a.Cin) ? ((unsigned)xc * (unsigned)a.ld_in + 32u * c + 8u * mg) * 2u : XR_DEAD;
+    for (int c = 0; c < NC; ++c) xoff[c] = (32 * c + 8 * mg < a.Cin) ? ((unsigned)xc * (unsigned)a.ld_in + 32u * c + 8u * mg) * 2u : YR_DEAD;
     const unsigned xrow = (unsigned)(a.W * a.ld_in) * 2u;
-    struct XRow { xr_u4 m[NC]; };
+    struct XRow { v4u m[NC]; };
     XRow xa, xb;
     auto load_row = [&](XRow& x, int r) {
         const unsigned so = (unsigned)min(max(r, 0), a.H - 1) * xrow;
 #pragma unroll
-        for (int c = 0; c < NC; ++c) x.m[c] = __builtin_bit_cast(xr_u4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xoff[c], so, 0));
+        for (int c = 0; c < NC; ++c) x.m[c] = __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xoff[c], so, 0));
     };
     load_row(xa, rbeg);
-    xr_f4 ring[NT][K - 1];
+    v4f ring[NT][K - 1];
 #pragma unroll
     for (int j = 0; j < NT; ++j)
 #pragma unroll
-        for (int q = 0; q < K - 1; ++q) ring[j][q] = (xr_f4){0.f, 0.f, 0.f, 0.f};
+        for (int q = 0; q < K - 1; ++q) ring[j][q] = (v4f){0.f, 0.f, 0.f, 0.f};
     int buf = 0;
     typedef T t4 __attribute__((ext_vector_type(4)));
 
@@ -1510,29 +1139,29 @@ __global__ __launch_bounds__(64 * NW, MW) void mbhq_kernel(MbhrArgs a) {
         constexpr bool EMIT = decltype(emit_c)::value;
         const int r = rbeg + k;
         load_row(xn_, r + 1);
-        xr_u2 resv[NF];
+        v2u resv[NF];
         if constexpr (EMIT) {   // UNCONDITIONAL (a dead offset reads zeros without a residual): a load under a branch makes every later wait vmcnt(0)
 #pragma unroll
             for (int f = 0; f < NF; ++f)
-                resv[f] = __builtin_bit_cast(xr_u2, __builtin_amdgcn_raw_buffer_load_b64(xsrc, (flive[f] && a.has_res) ? (((unsigned)yo * (unsigned)a.Wo + (unsigned)xo) * (unsigned)a.ld_in + (unsigned)fco[f]) * 2u : XR_DEAD, 0, 0));
+                resv[f] = __builtin_bit_cast(v2u, __builtin_amdgcn_raw_buffer_load_b64(xsrc, (flive[f] && a.has_res) ? (((unsigned)yo * (unsigned)a.Wo + (unsigned)xo) * (unsigned)a.ld_in + (unsigned)fco[f]) * 2u : YR_DEAD, 0, 0));
         }
         __builtin_amdgcn_sched_barrier(0);   // (the loads are issued HERE: left alone the scheduler sinks the residual load to its use behind the barrier)
         const float hr = (r >= 0 && r < a.H) ? hi : 0.f;
-        xr_f4 ec[NT];
+        v4f ec[NT];
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-            xr_f4 d = (xr_f4){0.f, 0.f, 0.f, 0.f};
+            v4f d = (v4f){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int c = 0; c < NC; ++c) d = xr_mfma<T>(aw[j][c], xc_.m[c], d);
             ec[j] = xr_bn_act4<ACT>(d, es[j], eh[j], hr);
         }
         if constexpr (EMIT) {
-            xr_f4 P[TO];
+            v4f P[TO];
 #pragma unroll
-            for (int t = 0; t < TO; ++t) P[t] = (xr_f4){0.f, 0.f, 0.f, 0.f};
+            for (int t = 0; t < TO; ++t) P[t] = (v4f){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
-                xr_f4 d = dh[j];
+                v4f d = dh[j];
                 if constexpr (K == 3) {
                     xr_row3(d, ring[j][0], tp[j][0], tp[j][1], tp[j][2]);
                     xr_row3(d, ring[j][1], tp[j][3], tp[j][4], tp[j][5]);
@@ -1546,12 +1175,12 @@ __global__ __launch_bounds__(64 * NW, MW) void mbhq_kernel(MbhrArgs a) {
                     xr_bc5_row<4>(cs, ec[j], tp[j][0], tp[j][1]);
                     d = xr_bc5_finish(cs, d);
                 }
-                const xr_f4 v = xr_act4<ACT>(d, HI);
-                const xr_u2 bop = __builtin_bit_cast(xr_u2, __builtin_convertvector(v, t4));   // rounded: the projection's operand type
+                const v4f v = xr_act4<ACT>(d, HI);
+                const v2u bop = __builtin_bit_cast(v2u, __builtin_convertvector(v, t4));   // rounded: the projection's operand type
 #pragma unroll
                 for (int t = 0; t < TO; ++t) P[t] = xr_mfma16<T>(wpf[j][t], bop, P[t]);
             }
-            xr_f4* rb = red + buf * (NW * TO * 64);
+            v4f* rb = red + buf * (NW * TO * 64);
 #pragma unroll
             for (int t = 0; t < TO; ++t) rb[(w * TO + t) * 64 + lane] = P[t];
             __syncthreads();
@@ -1559,17 +1188,17 @@ __global__ __launch_bounds__(64 * NW, MW) void mbhq_kernel(MbhrArgs a) {
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
                 const int t = w + f * NW;
-                xr_f4 acc = {0.f, 0.f, 0.f, 0.f};
+                v4f acc = {0.f, 0.f, 0.f, 0.f};
                 if (t < TO) {
 #pragma unroll
                     for (int ww = 0; ww < NW; ++ww) acc += rb[(ww * TO + t) * 64 + lane];
                 }
-                xr_f4 v;
+                v4f v;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) v[i] = __builtin_fmaf(acc[i], fsc[f][i], fsh[f][i]);
-                v += __builtin_convertvector(__builtin_bit_cast(t4, resv[f]), xr_f4);   // (zeros without a residual)
+                v += __builtin_convertvector(__builtin_bit_cast(t4, resv[f]), v4f);   // (zeros without a residual)
                 const t4 o = __builtin_convertvector(v, t4);
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(xr_u2, o), osrc, flive[f] ? (opix + (unsigned)fco[f]) * 2u : XR_DEAD, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, o), osrc, flive[f] ? (opix + (unsigned)fco[f]) * 2u : YR_DEAD, 0, 0);
             }
             buf ^= 1;
         }
@@ -1584,21 +1213,21 @@ __global__ __launch_bounds__(64 * NW, MW) void mbhq_kernel(MbhrArgs a) {
     constexpr std::false_type N{};
     if constexpr (PAIR) {
         // (see mbxr_kernel: a pair of output rows reads input rows rho = 0 .. K + 1; the first K - 2 are carried over, four are new)
-        xr_f4 d2[NT], cr[NT][K - 2];
+        v4f d2[NT], cr[NT][K - 2];
         float csa[NT][3][4], csb[NT][3][4];   // (5x5: the column sums of the pair's even / odd row)
 #pragma unroll
         for (int j = 0; j < NT; ++j)
 #pragma unroll
-            for (int q = 0; q < K - 2; ++q) cr[j][q] = (xr_f4){0.f, 0.f, 0.f, 0.f};
+            for (int q = 0; q < K - 2; ++q) cr[j][q] = (v4f){0.f, 0.f, 0.f, 0.f};
         auto prow = [&](auto ph_c, const int k, const int yo, const XRow& xc_, XRow& xn_) {
             constexpr int PH = decltype(ph_c)::value;
             const int r = rbeg + k;
             load_row(xn_, r + 1);
             const float hr = (r >= 0 && r < a.H) ? hi : 0.f;
-            xr_f4 ec[NT];
+            v4f ec[NT];
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
-                xr_f4 d = (xr_f4){0.f, 0.f, 0.f, 0.f};
+                v4f d = (v4f){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int c = 0; c < NC; ++c) d = xr_mfma<T>(aw[j][c], xc_.m[c], d);
                 ec[j] = xr_bn_act4<ACT>(d, es[j], eh[j], hr);
@@ -1632,17 +1261,17 @@ __global__ __launch_bounds__(64 * NW, MW) void mbhq_kernel(MbhrArgs a) {
                 }
             }
             if constexpr (PH == 4) {
-                xr_f4 P[TO];
+                v4f P[TO];
 #pragma unroll
-                for (int t = 0; t < TO; ++t) P[t] = (xr_f4){0.f, 0.f, 0.f, 0.f};
+                for (int t = 0; t < TO; ++t) P[t] = (v4f){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
-                    const xr_f4 v = xr_act4<ACT>(d2[j], HI);
-                    const xr_u2 bop = __builtin_bit_cast(xr_u2, __builtin_convertvector(v, t4));
+                    const v4f v = xr_act4<ACT>(d2[j], HI);
+                    const v2u bop = __builtin_bit_cast(v2u, __builtin_convertvector(v, t4));
 #pragma unroll
                     for (int t = 0; t < TO; ++t) P[t] = xr_mfma16<T>(wpf[j][t], bop, P[t]);
                 }
-                xr_f4* rb = red + buf * (NW * TO * 64);
+                v4f* rb = red + buf * (NW * TO * 64);
 #pragma unroll
                 for (int t = 0; t < TO; ++t) rb[(w * TO + t) * 64 + lane] = P[t];
                 __syncthreads();
@@ -1652,16 +1281,16 @@ __global__ __launch_bounds__(64 * NW, MW) void mbhq_kernel(MbhrArgs a) {
 #pragma unroll
                 for (int f = 0; f < NF; ++f) {
                     const int t = w + f * NW;
-                    xr_f4 acc = {0.f, 0.f, 0.f, 0.f};
+                    v4f acc = {0.f, 0.f, 0.f, 0.f};
                     if (t < TO) {
 #pragma unroll
                         for (int ww = 0; ww < NW; ++ww) acc += rb[(ww * TO + t) * 64 + lane];
                     }
-                    xr_f4 v;
+                    v4f v;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) v[i] = __builtin_fmaf(acc[i], fsc[f][i], fsh[f][i]);
                     const t4 o = __builtin_convertvector(v, t4);   // (a stride-2 block has no residual)
-                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(xr_u2, o), osrc, (flive[f] && rlive) ? (opix + (unsigned)fco[f]) * 2u : XR_DEAD, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, o), osrc, (flive[f] && rlive) ? (opix + (unsigned)fco[f]) * 2u : YR_DEAD, 0, 0);
                 }
                 buf ^= 1;
             }
@@ -1719,50 +1348,31 @@ static int launch_mbhq(const MbhrArgs& a0, int batch, int want_segs, hipStream_t
     constexpr int MW = 2;
     static_assert(NW <= 4 * MW, "the workgroup's waves must fit one CU");
     a.strips = (a.Wo + NOUT - 1) / NOUT;
-    const int walks = batch * a.strips;
-    int segs = (2 * 1024 + walks * NW - 1) / (walks * NW);
-    const int max_segs = (a.Ho + 3 * K - 1) / (3 * K);   // (a segment recomputes K - S halo rows)
-    if (segs > max_segs) segs = max_segs;
-    if (segs < 1) segs = 1;
-    if (want_segs > 0) segs = want_segs < a.Ho ? want_segs : a.Ho;
-    a.seg_rows = (a.Ho + segs - 1) / segs;
-    if (S == 2) a.seg_rows += a.seg_rows & 1;   // (output rows are processed in pairs)
-    a.segs = (a.Ho + a.seg_rows - 1) / a.seg_rows;
+    a.seg_rows = ch_row_segments(a.Ho, batch * a.strips, NW, 2 * 1024, 3 * K, S == 2, want_segs, &a.segs);   // (a segment recomputes K - S halo rows; stride 2 walks pairs of rows)
     const size_t lds = (size_t)2 * NW * TO * 64 * 16;
-    static char nm[64];
-    static const int nm_len = snprintf(nm, sizeof(nm), "mbhq_kernel<%s,%d,%d,%d,%d,%d,%d,%d>", yr_dtype_name(yr_elem<T>::dtype), K, S, ACT, NC, TO, NT, NW);
-    (void)nm_len;
-    yr_note_kernel(nm);
-    auto kern = mbhq_kernel<T, K, S, ACT, NC, TO, NT, NW, MW>;
-    static bool attr_set_dev[64] = {};   // per device: a process that drives several GPUs needs the attribute on each
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    bool& attr_set = attr_set_dev[cur_dev & 63];
-    if (!attr_set && lds > 48 * 1024) {
-        YR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(batch * a.strips * a.segs)), dim3(64 * NW), lds, s, a);
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+    return ch_launch<mbhq_kernel<T, K, S, ACT, NC, TO, NT, NW, MW>>(dim3((unsigned)(batch * a.strips * a.segs)), dim3(64 * NW), lds, lds, s, a,
+                                                                    "mbhq_kernel<%s,%d,%d,%d,%d,%d,%d,%d>", yr_dtype_name(yr_elem<T>::dtype), K, S, ACT, NC, TO, NT, NW);
 }
 
-// shapes of the tile-wise form: (kernel, input chunks, cout tiles, expanded tiles) -> (tiles per wave, waves)
-struct MbhqShape { int k, s, nc, to, t, nt, nw; };   // (s: the stride the shape is built for, 0 = both)
-static const MbhqShape MBHQ_SHAPES[] = {
-    {5, 0, 1, 3, 9, 3, 3},     // 24 -> 144 -> 40 (EfficientNet-lite0 stage 3 entry, stride 2)
-    {5, 0, 1, 3, 12, 3, 4},    // 32 -> 192 -> 48 (lite3 stage 3 entry, stride 2)
-    {5, 0, 2, 3, 18, 3, 6},    // 48 -> 288 -> 48 (lite3 stage 3)
-    {5, 0, 2, 3, 15, 2, 8},    // 40 -> 240 -> 40 (lite0 stage 3)
-    {3, 0, 1, 2, 9, 3, 3},     // 24 -> 144 -> 24 / 32 (lite0 stage 2, lite3 stage 2 entry, MobileNetV2 x0.75 block_2, 3)
-    // stride-2 blocks the tile-pair form (mbhr_kernel) is also built for: here they walk pairs of output rows
-    {3, 2, 1, 2, 6, 2, 3},     // 16 -> 96 -> 24 (MobileNetV2 block_1, lite0 stage 2 entry)
-    {3, 2, 2, 5, 15, 2, 8},    // 40 -> 240 -> 80 (lite0 stage 4 entry)
-};
+// THE shapes of the tile-wise form - the table, the dispatcher and with them mbhq_built are generated from this list:
+// F(kernel, stride the shape is built for (0 = both), input chunks, cout tiles, expanded tiles, tiles per wave, waves)
+#define MBHQ_SHAPES(F)                                                                                                              \
+    F(5, 0, 1, 3, 9, 3, 3)     /* 24 -> 144 -> 40 (EfficientNet-lite0 stage 3 entry, stride 2) */                                   \
+    F(5, 0, 1, 3, 12, 3, 4)    /* 32 -> 192 -> 48 (lite3 stage 3 entry, stride 2) */                                                \
+    F(5, 0, 2, 3, 18, 3, 6)    /* 48 -> 288 -> 48 (lite3 stage 3) */                                                                \
+    F(5, 0, 2, 3, 15, 2, 8)    /* 40 -> 240 -> 40 (lite0 stage 3) */                                                                \
+    F(3, 0, 1, 2, 9, 3, 3)     /* 24 -> 144 -> 24 / 32 (lite0 stage 2, lite3 stage 2 entry, MobileNetV2 x0.75 block_2, 3) */        \
+    /* stride-2 blocks the tile-pair form (mbhr_kernel) is also built for: here they walk pairs of output rows */                  \
+    F(3, 2, 1, 2, 6, 2, 3)     /* 16 -> 96 -> 24 (MobileNetV2 block_1, lite0 stage 2 entry) */                                      \
+    F(3, 2, 2, 5, 15, 2, 8)    /* 40 -> 240 -> 80 (lite0 stage 4 entry) */
+struct MbhqShape { int k, s, nc, to, t, nt, nw; };
+#define MBHQ_ROW(KV, SV, NCV, TOV, TV, NTV, NWV) {KV, SV, NCV, TOV, TV, NTV, NWV},
+static const MbhqShape MBHQ_TABLE[] = {MBHQ_SHAPES(MBHQ_ROW)};
+#undef MBHQ_ROW
 static const MbhqShape* mbhq_shape(int k, int stride, int cin, int cexp, int cout) {
     static const bool s2 = !(getenv("YOLORET_MBHQ_S2") && atoi(getenv("YOLORET_MBHQ_S2")) == 0);
     const int nc = yr_round_up(cin, 32) / 32, to = (cout + 15) / 16, t = cexp / 16;
-    for (const MbhqShape& sh : MBHQ_SHAPES)
+    for (const MbhqShape& sh : MBHQ_TABLE)
         if (sh.k == k && (sh.s == 0 || (sh.s == stride && s2)) && sh.nc == nc && sh.to == to && sh.t == t) return &sh;
     return nullptr;
 }
@@ -1771,16 +1381,11 @@ template <class T, int S>
 static int launch_mbhq_shape(const MbhrArgs& a, int k, int batch, int segs, hipStream_t s) {
     const MbhqShape* sh = mbhq_shape(k, S, a.Cin, a.T * 16, a.Cout);
     YR_REQUIRE(sh != nullptr, "mbhq: block %d -> %d -> %d (%d x %d) is not built", a.Cin, a.T * 16, a.Cout, k, k);
-#define HQ_CASE(KV, NCV, TOV, TV, NTV, NWV) if (sh->k == KV && sh->nc == NCV && sh->to == TOV && sh->t == TV) return launch_mbhq<T, KV, S, 0, NCV, TOV, NTV, NWV>(a, batch, segs, s);
-    HQ_CASE(5, 1, 3, 9, 3, 3)
-    HQ_CASE(5, 1, 3, 12, 3, 4)
-    HQ_CASE(5, 2, 3, 18, 3, 6)
-    HQ_CASE(5, 2, 3, 15, 2, 8)
-    HQ_CASE(3, 1, 2, 9, 3, 3)
-    if constexpr (S == 2) {
-        HQ_CASE(3, 1, 2, 6, 2, 3)
-        HQ_CASE(3, 2, 5, 15, 2, 8)
-    }
+    // (a shape built for one stride is instantiated for that stride alone)
+#define HQ_CASE(KV, SV, NCV, TOV, TV, NTV, NWV)                                                    \
+    if constexpr (SV == 0 || SV == S)                                                              \
+        if (sh->k == KV && sh->nc == NCV && sh->to == TOV && sh->t == TV) return launch_mbhq<T, KV, S, 0, NCV, TOV, NTV, NWV>(a, batch, segs, s);
+    MBHQ_SHAPES(HQ_CASE)
 #undef HQ_CASE
     return YR_ERR_ARG;
 }
@@ -1792,17 +1397,22 @@ bool yr_mbhr_takes(const yr_op& op) {
            op.cout % 4 == 0 && op.cout <= 80 && op.nsrc == 1 && op.out_ld % 4 == 0;
 }
 
+// THE shapes of the tile-pair form - the dispatcher and mbhr_pair_built are generated from this list:
+// F(input chunks, cout tiles, waves = pairs of expanded tiles)
+// (measured, tools/mbhr_probe.py: the five-wave workgroups of the 144-channel blocks - 24 -> 144 -> 24 / 32 / 48 - lose to the
+// LDS-tiled kernels, 0.29 vs 0.25 ms and 0.44 vs 0.33 ms: one such workgroup per CU at two waves per SIMD; not built)
+#define MBHR_SHAPES(F)                                                                                        \
+    F(1, 2, 3)    /* 16 -> 96 -> 24 (MobileNetV2 block_1, lite0 stage 2 entry): 0.36 -> 0.24 ms at batch 128 */ \
+    F(1, 2, 6)    /* 32 -> 192 -> 32 (lite3 stage 2): 0.23 -> 0.18 ms at batch 32 */                          \
+    F(1, 3, 6)    /* 32 -> 192 -> 48 */                                                                       \
+    F(2, 5, 8)    /* 40 -> 240 -> 80 (lite0 stage 4 entry): 0.16 -> 0.075 ms */                               \
+    F(2, 3, 8)    /* 40 -> 240 -> 40 */
+
 template <class T, int S, int ACT>
 static int launch_mbhr_shape(const MbhrArgs& a, int batch, int segs, hipStream_t s) {
     const int nc = a.KP / 32, to = (a.Cout + 15) / 16, nw = (a.T + 1) / 2;
 #define HR_CASE(NCV, TOV, NWV) if (nc == NCV && to == TOV && nw == NWV) return launch_mbhr<T, S, ACT, NCV, TOV, NWV>(a, batch, segs, s);
-    // (measured, tools/mbhr_probe.py: the five-wave workgroups of the 144-channel blocks - 24 -> 144 -> 24 / 32 / 48 - lose to the
-    // LDS-tiled kernels, 0.29 vs 0.25 ms and 0.44 vs 0.33 ms: one such workgroup per CU at two waves per SIMD; not built)
-    HR_CASE(1, 2, 3)    // 16 -> 96 -> 24 (MobileNetV2 block_1, lite0 stage 2 entry): 0.36 -> 0.24 ms at batch 128
-    HR_CASE(1, 2, 6)    // 32 -> 192 -> 32 (lite3 stage 2): 0.23 -> 0.18 ms at batch 32
-    HR_CASE(1, 3, 6)    // 32 -> 192 -> 48
-    HR_CASE(2, 5, 8)    // 40 -> 240 -> 80 (lite0 stage 4 entry): 0.16 -> 0.075 ms
-    HR_CASE(2, 3, 8)    // 40 -> 240 -> 40
+    MBHR_SHAPES(HR_CASE)
 #undef HR_CASE
     yr_set_error("mbhr: block %d -> %d -> %d is not built", a.Cin, a.T * 16, a.Cout);
     return YR_ERR_ARG;
@@ -1811,8 +1421,9 @@ static int launch_mbhr_shape(const MbhrArgs& a, int batch, int segs, hipStream_t
 static bool mbhr_pair_built(const yr_op& op) {
     if (!yr_mbhr_takes(op)) return false;
     const int nc = yr_round_up(op.cin, 32) / 32, to = (op.cout + 15) / 16, nw = (op.se_reduced / 16 + 1) / 2;
-    const int key = nc * 10000 + to * 100 + nw;
-    return key == 10203 || key == 10206 || key == 10306 || key == 20508 || key == 20308;
+#define HR_BUILT(NCV, TOV, NWV) || (nc == NCV && to == TOV && nw == NWV)
+    return false MBHR_SHAPES(HR_BUILT);
+#undef HR_BUILT
 }
 // the tile-wise form (mbhq_kernel): 3x3 / 5x5, ReLU6, the shapes of MBHQ_SHAPES
 static bool mbhq_built(const yr_op& op) {

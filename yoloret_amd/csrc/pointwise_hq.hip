@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256, 2) void pwhq_kernel(PwArgs a, int nsplit, unsi
     const int kp = a.S.kp;
     const int nst = (kp + 63) >> 6;                         // 64-deep steps
     const int kl = g * 8;
-    const pwh_rsrc orsrc = pwh_out_rsrc(a, out_bytes);
+    const yr_rsrc orsrc = pwh_out_rsrc(a, out_bytes);
 
     PwhRow<MODE, T> row[PT];
 #pragma unroll

@@ -46,7 +46,7 @@ __global__ __launch_bounds__(256, PT == 1 ? 3 : 2) void pwhs_kernel(PwArgs a, in
     const int pb = (int)(L % (unsigned)nsplit) * pairs_per_wg;
     const int pe = pb + pairs_per_wg < npairs ? pb + pairs_per_wg : npairs;
     const int kp = a.S.kp;
-    const pwh_rsrc orsrc = pwh_out_rsrc(a, out_bytes);
+    const yr_rsrc orsrc = pwh_out_rsrc(a, out_bytes);
 
     // ---- weight loader: a wave instruction covers 8 rows x 128 bytes (two chunks); wave w takes tile w & 1, MFMA rows
     // 8 (w >> 1) .. + 7 of every pair.  LDS slot = fragment lane 16 g + i of [chunk][tile]: the 8 lanes of a ds_write_b128
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(256, PT == 1 ? 3 : 2) void pwhs_kernel(PwArgs a, in
     // through a buffer descriptor over the [N][kp] weights: one add per load and turn (these loops are bound by instruction
     // issue; the scalar-offset operand is not range-checked, so it cannot carry the pair) and rows beyond N read as zeros
     // (their couts are never stored)
-    const pwh_rsrc wrsrc = pwh_make_rsrc(a.wt, (unsigned)a.N * (unsigned)kp * 2u);
+    const yr_rsrc wrsrc = yr_make_rsrc(a.wt, (unsigned)a.N * (unsigned)kp * 2u);
     unsigned wvoff[NST];
 #pragma unroll
     for (int st = 0; st < NST; ++st) {
@@ -119,15 +119,15 @@ __global__ __launch_bounds__(256, PT == 1 ? 3 : 2) void pwhs_kernel(PwArgs a, in
                                                g1[MODE == 2 ? ch : 0][MODE == 2 ? p : 0], cv[ch][p]);
     }
     // PLAIN: byte offset of each pixel row of this lane + this lane group's 16 bytes of a pair's 64; a turn adds the pair's
-    // 64 j.  Dead lanes (rows beyond M; in the LAST pair of N, octets beyond N) sit at 0x7f000000, beyond the descriptor's
+    // 64 j.  Dead lanes (rows beyond M; in the LAST pair of N, octets beyond N) sit at YR_DEAD, beyond the descriptor's
     // range (the launcher checks), and a dead turn adds 2 GB: out of range for every lane, no 32-bit wrap either way.
     unsigned rowoff[PT], rowoff_last[PT];
     const bool tail_dead = (npairs - 1) * 32 + g * 8 >= a.N;
 #pragma unroll
     for (int p = 0; p < PT; ++p) {
         const int m = m0 + p * 16 + li;
-        rowoff[p] = m < a.M ? (unsigned)m * (unsigned)a.out_ld * 2u + (unsigned)g * 16u : 0x7f000000u;
-        rowoff_last[p] = tail_dead ? 0x7f000000u : rowoff[p];
+        rowoff[p] = m < a.M ? (unsigned)m * (unsigned)a.out_ld * 2u + (unsigned)g * 16u : YR_DEAD;
+        rowoff_last[p] = tail_dead ? YR_DEAD : rowoff[p];
     }
     // The epilogue of pair j - 1 runs BESIDE the MFMAs of pair j (independent registers: the matrix pipe works while the
     // wave issues the BN / clamp / convert / store instructions); left to follow its own MFMAs it waited for their results

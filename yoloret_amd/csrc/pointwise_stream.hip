@@ -97,7 +97,7 @@ __global__ __launch_bounds__(64 * pwt_waves(NK, ROWS, MODE)) void pwt_kernel(PwA
     // ---- the run's planes: LDS-direct, 1 KB pieces dealt to the waves (beyond the array: zeros); BN scale and shift of the run's
     // couts by plain loads (issued now, written to LDS in front of the barrier)
     {
-        const mbr_rsrc wsrc = mbr_make_rsrc(x.planes, x.plane_bytes);
+        const yr_rsrc wsrc = yr_make_rsrc(x.planes, x.plane_bytes);
         const int npiece = run * NK * 2;
         for (int p = w; p < npiece; p += NW)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(wsrc, (pwt_lds_ptr)(lds_raw + p * 1024), 16, (unsigned)(t0 * TB + p * 1024 + lane * 16), 0, 0, 0);
@@ -113,9 +113,9 @@ __global__ __launch_bounds__(64 * pwt_waves(NK, ROWS, MODE)) void pwt_kernel(PwA
     const int kp = a.S.kp;
     const int stride = x.nwg * NW;
     int tile = wg + x.nwg * w;
-    const mbr_rsrc xsrc = mbr_make_rsrc(a.S.s[0].ptr, x.in_bytes), osrc = mbr_make_rsrc(a.out, x.out_bytes);
-    const mbr_rsrc osrc2 = mbr_make_rsrc(a.out2 ? a.out2 : a.out, a.out2 ? x.out2_bytes : 16u);
-    const mbr_rsrc gsrc = mbr_make_rsrc(MODE == 2 ? a.gate : a.S.s[0].ptr, MODE == 2 ? x.gate_bytes : 16u);
+    const yr_rsrc xsrc = yr_make_rsrc(a.S.s[0].ptr, x.in_bytes), osrc = yr_make_rsrc(a.out, x.out_bytes);
+    const yr_rsrc osrc2 = yr_make_rsrc(a.out2 ? a.out2 : a.out, a.out2 ? x.out2_bytes : 16u);
+    const yr_rsrc gsrc = yr_make_rsrc(MODE == 2 ? a.gate : a.S.s[0].ptr, MODE == 2 ? x.gate_bytes : 16u);
     PwRow<0> row[MODE == 0 ? ROWS : 1];
     float4 xa[ROWS][NK][2];
     int cv[MODE == 0 ? ROWS : 1][MODE == 0 ? NK : 1][2];
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(64 * pwt_waves(NK, ROWS, MODE)) void pwt_kernel(PwA
             pw_unroll<ROWS * GQ * 2>([&](auto U) __attribute__((always_inline)) {
                 constexpr int u = decltype(U)::value, i = u / (2 * GQ), cc = (u / 2) % GQ, q = u % 2, c = j * GQ + cc;
                 const int k = c * 32 + g * 8 + 4 * q;
-                if constexpr (c < NK) gq[j & 1][i][cc][q] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(gsrc, k < kp ? goff[i] + 4u * k : MBR_DEAD, 0, 0));
+                if constexpr (c < NK) gq[j & 1][i][cc][q] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(gsrc, k < kp ? goff[i] + 4u * k : YR_DEAD, 0, 0));
             });
         }
     };
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(64 * pwt_waves(NK, ROWS, MODE)) void pwt_kernel(PwA
                 pw_unroll<NK * 2>([&](auto U) __attribute__((always_inline)) {
                     constexpr int u = decltype(U)::value, c = u / 2, q = u % 2;
                     const int k = c * 32 + g * 8 + 4 * q;
-                    xa[i][c][q] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, (m < a.M && k < kp) ? poff + 4u * k : MBR_DEAD, 0, 0));
+                    xa[i][c][q] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, (m < a.M && k < kp) ? poff + 4u * k : YR_DEAD, 0, 0));
                 });
             }
         }
@@ -219,8 +219,8 @@ __global__ __launch_bounds__(64 * pwt_waves(NK, ROWS, MODE)) void pwt_kernel(PwA
         for (int i = 0; i < ROWS; ++i) {
             const int m = (tile * ROWS + i) * 16 + li;
             const bool keep = m < a.M && (!a.pool || (li & 3) == 0), keep2 = m < a.M && (!a.pool2 || (li & 3) == 0);
-            obase[i] = keep ? (unsigned)(a.pool ? m >> 2 : pix[i]) * (unsigned)a.out_ld * 4u : MBR_DEAD;
-            obase2[i] = keep2 && a.out2 ? (unsigned)(a.pool2 ? m >> 2 : pix[i]) * (unsigned)a.out2_ld * 4u : MBR_DEAD;
+            obase[i] = keep ? (unsigned)(a.pool ? m >> 2 : pix[i]) * (unsigned)a.out_ld * 4u : YR_DEAD;
+            obase2[i] = keep2 && a.out2 ? (unsigned)(a.pool2 ? m >> 2 : pix[i]) * (unsigned)a.out2_ld * 4u : YR_DEAD;
         }
         for (int t = 0; t < run; ++t) {
             const pws_u4* fe = reinterpret_cast<const pws_u4*>(lds_raw + (size_t)t * TB) + lane;     // [NK][2 planes][64]
@@ -259,18 +259,18 @@ __global__ __launch_bounds__(64 * pwt_waves(NK, ROWS, MODE)) void pwt_kernel(PwA
                     }
                 }
                 const unsigned ob = second ? obase2[i] : obase[i];
-                const unsigned off = ob == MBR_DEAD || cnt <= 0 ? MBR_DEAD : ob + 4u * (unsigned)n;
+                const unsigned off = ob == YR_DEAD || cnt <= 0 ? YR_DEAD : ob + 4u * (unsigned)n;
                 if (second) {
                     if (cnt >= 4) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, v), osrc2, off, 0, 0);
                     else {
 #pragma unroll
-                        for (int r = 0; r < 3; ++r) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[r]), osrc2, r < cnt ? off + 4u * r : MBR_DEAD, 0, 0);
+                        for (int r = 0; r < 3; ++r) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[r]), osrc2, r < cnt ? off + 4u * r : YR_DEAD, 0, 0);
                     }
                 } else if (cnt >= 4) {
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, v), osrc, off, 0, 0);
                 } else {          // (the last quad of a dense 75-wide row)
 #pragma unroll
-                    for (int r = 0; r < 3; ++r) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[r]), osrc, r < cnt ? off + 4u * r : MBR_DEAD, 0, 0);
+                    for (int r = 0; r < 3; ++r) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[r]), osrc, r < cnt ? off + 4u * r : YR_DEAD, 0, 0);
                 }
             }
         }
@@ -367,10 +367,10 @@ static int pwt_launch_images(const PwArgs& a, hipStream_t s) {
     x.d_wq = pwt_div_make((unsigned)(a.W >> 1 > 0 ? a.W >> 1 : 1));
     x.d_hwq = pwt_div_make((unsigned)((a.H >> 1) * (a.W >> 1) > 0 ? (a.H >> 1) * (a.W >> 1) : 1));
     const long long inb = (long long)a.M * a.S.s[0].ld * 4, outb = (long long)(a.pool ? a.M / 4 : a.M) * a.out_ld * 4;
-    YR_REQUIRE(inb < 0x7f000000ll && outb < 0x7f000000ll, "pointwise (pixel-stationary form): a map of %lld bytes is beyond the 32-bit offsets", inb > outb ? inb : outb);
+    YR_REQUIRE(inb < (long long)YR_DEAD && outb < (long long)YR_DEAD, "pointwise (pixel-stationary form): a map of %lld bytes is beyond the 32-bit offsets", inb > outb ? inb : outb);
     x.in_bytes = (unsigned)inb; x.out_bytes = (unsigned)outb;
     const long long outb2 = a.out2 ? (long long)(a.pool2 ? a.M / 4 : a.M) * a.out2_ld * 4 : 0;
-    YR_REQUIRE(outb2 < 0x7f000000ll, "pointwise (pixel-stationary form): a second output of %lld bytes is beyond the 32-bit offsets", outb2);
+    YR_REQUIRE(outb2 < (long long)YR_DEAD, "pointwise (pixel-stationary form): a second output of %lld bytes is beyond the 32-bit offsets", outb2);
     x.out2_bytes = (unsigned)outb2;
     x.gate_bytes = a.gate ? (unsigned)((long long)(a.M / (a.H * a.W)) * a.gate_ld * 4) : 0u;
     // 32 pixels per wave (half the fragment reads from LDS) measured behind 16 once the kernel was persistent and lean: bu3's two-output

@@ -235,12 +235,7 @@ __device__ __forceinline__ void pwh_load_bn(const PwArgs& a, int n, float (&sc)[
 // load (the weight block prefetched before this epilogue) then becomes vmcnt(0) and stalls until the stores are
 // acknowledged too.  Through a buffer descriptor the store is unconditional: dead lanes (rows beyond M, couts beyond N,
 // the three non-owner lanes of a pooling window) pass an offset beyond num_records and the hardware drops them.
-typedef __amdgpu_buffer_rsrc_t pwh_rsrc;
-__device__ __forceinline__ pwh_rsrc pwh_make_rsrc(const void* base, unsigned bytes) {
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)base), hi = __builtin_amdgcn_readfirstlane((unsigned)((uintptr_t)base >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)hi << 32) | lo), 0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
-__device__ __forceinline__ pwh_rsrc pwh_out_rsrc(const PwArgs& a, unsigned bytes) { return pwh_make_rsrc(a.out, bytes); }
+__device__ __forceinline__ yr_rsrc pwh_out_rsrc(const PwArgs& a, unsigned bytes) { return yr_make_rsrc(a.out, bytes); }
 
 // ReLU6 of eight ROUNDED 16-bit values, two per dword, as packed 16-bit INTEGER max / min: bf16 and f16 are sign-magnitude,
 // so as signed integers every negative value (and -0) is below +0 = 0x0000 and the non-negative ones order like the numbers;
@@ -262,7 +257,7 @@ __device__ __forceinline__ pwh_u4 pwh_relu6_packed(pwh_u4 v) {
 // partial sums: partial octets, dword-aligned rows) keep the branching stores of pwh_finish_oct, and a run-time switch
 // between the two would make every wait after the join conservative again: such ops do not take these kernels.
 template <class T>
-__device__ __forceinline__ void pwh_finish_oct_b(const PwArgs& a, pwh_rsrc out, const f32x4& lo, const f32x4& hi, const float (&sc)[8],
+__device__ __forceinline__ void pwh_finish_oct_b(const PwArgs& a, yr_rsrc out, const f32x4& lo, const f32x4& hi, const float (&sc)[8],
                                                  const float (&sh)[8], int m, int n, int li) {
     const int cnt = a.N - n;
     const int nld = cnt > 0 ? n : 0;
@@ -304,14 +299,14 @@ __device__ __forceinline__ void pwh_finish_oct_b(const PwArgs& a, pwh_rsrc out, 
     pwh_f8 o;
 #pragma unroll
     for (int r = 0; r < 8; ++r) o[r] = v[r];
-    const unsigned off = keep ? ((unsigned)orow * (unsigned)a.out_ld + (unsigned)n) * 2u : 0x7f000000u;
+    const unsigned off = keep ? ((unsigned)orow * (unsigned)a.out_ld + (unsigned)n) * 2u : YR_DEAD;
     __builtin_amdgcn_raw_buffer_store_b128(pwh_narrow<T>(o), out, off, 0, 0);
 }
 
 // rows of the output that a launch may address through a 32-bit byte offset
 __host__ inline bool pwh_out_fits_rsrc(const PwArgs& a) {
     const unsigned long long rows = a.pool ? (unsigned long long)(a.M >> 2) : (unsigned long long)a.M;
-    return !a.out_f32 && rows * (unsigned long long)a.out_ld * 2ull < 0x7f000000ull;   // (dead lanes sit at 0x7f000000 and beyond)
+    return !a.out_f32 && rows * (unsigned long long)a.out_ld * 2ull < (unsigned long long)YR_DEAD;   // (dead lanes sit at YR_DEAD and beyond)
 }
 __host__ inline unsigned pwh_out_bytes(const PwArgs& a) {
     const unsigned long long rows = a.pool ? (unsigned long long)(a.M >> 2) : (unsigned long long)a.M;

@@ -194,6 +194,27 @@ __device__ __forceinline__ void yr_cut2(float x0, float x1, unsigned& h, unsigne
     asm("v_fma_mixhi_f16 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\ts_nop 1" : "+v"(m) : "v"(h), "s"(c), "v"(xs[1]));
 }
 
+// A buffer descriptor over `bytes` bytes at `base` (wave-uniform; raw, no swizzle) for the raw_buffer loads and stores, and the
+// DEAD byte offset: beyond every descriptor's num_records, so the load returns zeros and the store is dropped - how a lane
+// opts out of an access without a branch.  (A map addressed this way is smaller than YR_DEAD bytes.)
+typedef __amdgpu_buffer_rsrc_t yr_rsrc;
+__device__ __forceinline__ yr_rsrc yr_make_rsrc(const void* base, unsigned bytes) {
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)base), hi = __builtin_amdgcn_readfirstlane((unsigned)((uintptr_t)base >> 32));
+    return __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)hi << 32) | lo), 0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
+}
+#define YR_DEAD 0x7f000000u
+
+// The sum over the 16 lanes of a DPP row as a fixed tree (rotations by 8, 4, 2, 1: every lane ends with the total): the same
+// order whatever runs next to it, so the squeeze-excite sums are deterministic.  s_nop 1: the VALU-write -> DPP-read hazard,
+// which the compiler does not see inside asm.
+__device__ __forceinline__ float yr_row_sum16(float t) {
+    asm("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0xf\n\ts_nop 1\n\t"
+        "v_add_f32_dpp %0, %0, %0 row_ror:4 row_mask:0xf bank_mask:0xf\n\ts_nop 1\n\t"
+        "v_add_f32_dpp %0, %0, %0 row_ror:2 row_mask:0xf bank_mask:0xf\n\ts_nop 1\n\t"
+        "v_add_f32_dpp %0, %0, %0 row_ror:1 row_mask:0xf bank_mask:0xf" : "+v"(t));
+    return t;
+}
+
 // XCD-aware block order (cdna_hip_programming.md T1): hardware block b runs on XCD b % 8, each XCD has
 // its own L2.  Map hardware ids so that every XCD walks a CONTIGUOUS range of logical blocks; logical
 // neighbours (adjacent rows of a depthwise map, the cout tiles of one pixel tile) then share an L2.
