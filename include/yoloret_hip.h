@@ -847,6 +847,58 @@ int yr_bn_train_backward(const float* da, int da_ld, const float* z, int z_ld, c
                          float* dz /*or null: not computed*/, int dz_ld, float* dgamma /*[C]*/, float* dbeta /*[C]*/,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the operators that fuse maps of different scales, forward and backward (yolo3/model.py:117-168, the RFCR module: UpSampling2D,
+ * MaxPooling2D and the learned WeightedSum of four maps in front of a separable convolution, three Concatenates behind it; the FPN and
+ * PANet passes, model.py:240-323, use the same two resampling operators); added under ABI 9 (additive).  csrc/fusegrad.hip has the kernels'
+ * forms, tests/fusegrad_ref.py is the definition (the reference's backward is TensorFlow's tape).  The conventions of the entries above
+ * hold: float32, maps [B][H][W][ld] or rows [pixels][ld] with C <= ld channels taken (pad columns neither read nor written), 4-byte
+ * alignment, no float atomics, nothing read before the call wrote it, every named output element written and nothing else, the same call
+ * gives the same bytes, every operation one IEEE float32 operation in the order written.  YR_ERR_ARG, nothing written, for sizes outside
+ * the contract, a leading dimension below C, a null pointer, byte offsets beyond 2^63, a short or misaligned workspace.  Concatenation
+ * (model.py:166-168) has no arithmetic and no entry: it is a choice of pointer and leading dimension. */
+/* MaxPooling2D((k, k)) (model.py:139-144, :161, :166; stride k, 'valid'), k in {2, 4}: x [B][H][W], y and dy [B][OH][OW], OH = H div k,
+ * OW = W div k, H, W >= k, B * H * W < 2^40.  Rows and columns of x at and past OH * k / OW * k are not read.
+ *   forward   the window is scanned in row-major order: m = x[oy k][ox k]; a later element replaces m only when it is STRICTLY greater;
+ *             y[oy][ox] = m.
+ *   backward  takes dy and the forward's input x; no index map is kept.  The forward's scan is repeated; dx at the FIRST position that
+ *             holds the maximum receives dy[oy][ox], every other position of the window and every position of the trailing strip
+ *             (rows >= OH k, columns >= OW k) receives +0.  Each dx[b][0..H)[0..W)[0..C) is written exactly once.
+ * The tie rule is TensorFlow's MaxPoolGrad as restated from memory (torch.max_pool2d follows the same rule): UNPINNED BY THE REFERENCE,
+ * which has no backward code and whose framework is not available where this is tested.  -0 and +0 compare equal: the first of them
+ * wins.  Non-finite inputs are outside the contract.  One launch each. */
+int yr_maxpool_forward(const float* x, int x_ld, int B, int H, int W, int C, int k, float* y, int y_ld, void* stream);
+int yr_maxpool_backward(const float* dy, int dy_ld, const float* x, int x_ld, int B, int H, int W, int C, int k,
+                        float* dx, int dx_ld, void* stream);
+/* UpSampling2D() (model.py:161, :168; nearest neighbour, x2): x and dx [B][H][W], y and dy [B][2H][2W]; H and W are the SMALL map's,
+ * B * H * W < 2^38.
+ *   forward   y[2i + a][2j + b] = x[i][j] for a, b in {0, 1}.
+ *   backward  dx[i][j] = ((dy[2i][2j] + dy[2i][2j + 1]) + dy[2i + 1][2j]) + dy[2i + 1][2j + 1]: three float32 additions in this order.
+ * One launch each. */
+int yr_upsample2_forward(const float* x, int x_ld, int B, int H, int W, int C, float* y, int y_ld, void* stream);
+int yr_upsample2_backward(const float* dy, int dy_ld, int B, int H, int W, int C, float* dx, int dx_ld, void* stream);
+/* WeightedSum of exactly four maps (model.py:117-137, :161), rows [pixels][ld], alpha [4] on the device; 1 <= pixels < 2^40,
+ * 1 <= C <= 2^30.
+ *   forward   y = ((alpha[0] x0 + alpha[1] x1) + alpha[2] x2) + alpha[3] x3: each product rounded, then the sums left to right - the
+ *             order of model.py:134 and of YR_OP_WSUM, whose float32 bits it returns.  One launch.
+ *   backward  dx_i = alpha[i] * dy; each of the four dx pointers may be null: not computed.  dalpha[i] = sum_{p, c} dy[p][c] * x_i[p][c],
+ *             each term one rounded product added by one rounded addition; dalpha may be null: not computed, then no x_i is read (they
+ *             may be null) and the workspace is not touched (it may be null).  With everything null nothing is launched.
+ *             dalpha is a two-stage sum: stage 1 gives every workgroup a contiguous range of yr_wsum_chunk(pixels, C) pixels - a
+ *             function of its arguments only -, writes the dx_i of the range and one slab of four floats to the workspace (device,
+ *             16-byte aligned, yr_wsum_workspace_bytes(pixels, C) bytes, contents before the call do not matter); within a workgroup
+ *             the order is fixed (csrc/fusegrad.hip: a lane's products in order from +0, the lanes of a wave by a butterfly, the
+ *             waves in order); stage 2 adds the slabs in index order.  Two launches with dalpha, one without.
+ * The two size entries return 0 for sizes the calls refuse. */
+int    yr_wsum_chunk(long long pixels, int C);
+size_t yr_wsum_workspace_bytes(long long pixels, int C);
+int yr_wsum_forward(const float* x0, int x0_ld, const float* x1, int x1_ld, const float* x2, int x2_ld, const float* x3, int x3_ld,
+                    const float* alpha /*device [4]*/, long long pixels, int C, float* y, int y_ld, void* stream);
+int yr_wsum_backward(const float* dy, int dy_ld, const float* x0, int x0_ld, const float* x1, int x1_ld, const float* x2, int x2_ld,
+                     const float* x3, int x3_ld, const float* alpha /*device [4]*/, long long pixels, int C,
+                     float* dx0 /*or null*/, int dx0_ld, float* dx1 /*or null*/, int dx1_ld, float* dx2 /*or null*/, int dx2_ld,
+                     float* dx3 /*or null*/, int dx3_ld, float* dalpha /*device [4], or null*/,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,7 +137,9 @@ EXPORTS = ['yr_jpeg_workspace_bytes', 'yr_jpeg_roundtrip_batch', 'yr_augment_geo
            'yr_linear_forward', 'yr_linear_wgrad_chunk', 'yr_linear_wgrad_workspace_bytes', 'yr_linear_wgrad', 'yr_adam_step',
            'yr_linear_dgrad', 'yr_depthwise_forward', 'yr_depthwise_dgrad', 'yr_depthwise_wgrad_chunk', 'yr_depthwise_wgrad_workspace_bytes', 'yr_depthwise_wgrad',
            'yr_bn_act_forward', 'yr_bn_act_backward',
-           'yr_bn_train_chunk', 'yr_bn_train_workspace_bytes', 'yr_bn_train_forward', 'yr_bn_train_backward']
+           'yr_bn_train_chunk', 'yr_bn_train_workspace_bytes', 'yr_bn_train_forward', 'yr_bn_train_backward',
+           'yr_maxpool_forward', 'yr_maxpool_backward', 'yr_upsample2_forward', 'yr_upsample2_backward',
+           'yr_wsum_chunk', 'yr_wsum_workspace_bytes', 'yr_wsum_forward', 'yr_wsum_backward']
 
 _lib = None
 
@@ -249,6 +251,18 @@ def lib():
                                           ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p]
         L.yr_bn_train_backward.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4 + \
             [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_size_t, ctypes.c_void_p]
+        L.yr_maxpool_forward.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        L.yr_maxpool_backward.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_int] * 5 + \
+            [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        L.yr_upsample2_forward.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        L.yr_upsample2_backward.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        L.yr_wsum_chunk.argtypes = [ctypes.c_longlong, ctypes.c_int]
+        L.yr_wsum_workspace_bytes.restype = ctypes.c_size_t
+        L.yr_wsum_workspace_bytes.argtypes = [ctypes.c_longlong, ctypes.c_int]
+        L.yr_wsum_forward.argtypes = [ctypes.c_void_p, ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                                                          ctypes.c_void_p]
+        L.yr_wsum_backward.argtypes = [ctypes.c_void_p, ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int] + \
+            [ctypes.c_void_p, ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         if L.yr_abi_version() != ABI_VERSION:
             raise YoloretHipError('libyoloret_hip.so ABI version mismatch')
         L.yr_abi_sizeof.argtypes = [ctypes.c_int]
@@ -807,6 +821,131 @@ def bn_train_backward(da, z, gamma, beta, mean, invstd, act, need_dz=True, out=N
         check(lib().yr_bn_train_backward(_ptr(da), c, _ptr(z), c, _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(invstd), pixels, c, a, _ptr(out), c,
                                          _ptr(dgamma), _ptr(dbeta), _ptr(ws), ws.numel(), stream_ptr(dev)))
     return out, dgamma, dbeta
+
+
+# ----------------------------------------------------------------------------- the fusing operators (csrc/fusegrad.hip)
+def _pool_k(k, h, w, name):
+    k = int(k)
+    if k not in (2, 4) or h < k or w < k:
+        raise ValueError('%s: k in {2, 4} and a map of at least k x k, not k %d on %d x %d' % (name, k, h, w))
+    return k
+
+
+def maxpool_forward(x, k, out=None):
+    """Keras MaxPooling2D((k, k)) (yr_maxpool_forward): x [B, H, W, C] float32, k in {2, 4} -> y [B, H // k, W // k, C]; rows and columns
+    past the last whole window are not read.  One launch."""
+    b, h, w, c = _dw_map(x, 'x')
+    k = _pool_k(k, h, w, 'maxpool_forward')
+    out = _out_like(out, (b, h // k, w // k, c), x.device, 'maxpool_forward')
+    with torch.cuda.device(x.device):
+        check(lib().yr_maxpool_forward(_ptr(x), c, b, h, w, c, k, _ptr(out), c, stream_ptr(x.device)))
+    return out
+
+
+def maxpool_backward(dy, x, k, out=None):
+    """The input gradient of ``maxpool_forward`` (yr_maxpool_backward): dy [B, H // k, W // k, C], x the forward's input -> dx of x's
+    shape: dy at the first maximum of each window (row-major scan, strict comparison), +0 everywhere else, the trailing strip included;
+    every element written once.  One launch."""
+    b, h, w, c = _dw_map(x, 'x')
+    k = _pool_k(k, h, w, 'maxpool_backward')
+    _require_cuda_f32(dy, 'dy')
+    if tuple(dy.shape) != (b, h // k, w // k, c) or dy.device != x.device:
+        raise ValueError('maxpool_backward: dy %s on %s, expected %s on %s' % (tuple(dy.shape), dy.device, (b, h // k, w // k, c), x.device))
+    out = _out_like(out, (b, h, w, c), x.device, 'maxpool_backward')
+    with torch.cuda.device(x.device):
+        check(lib().yr_maxpool_backward(_ptr(dy), c, _ptr(x), c, b, h, w, c, k, _ptr(out), c, stream_ptr(x.device)))
+    return out
+
+
+def upsample2_forward(x, out=None):
+    """Keras UpSampling2D() (yr_upsample2_forward): x [B, H, W, C] float32 -> y [B, 2H, 2W, C], nearest neighbour.  One launch."""
+    b, h, w, c = _dw_map(x, 'x')
+    out = _out_like(out, (b, 2 * h, 2 * w, c), x.device, 'upsample2_forward')
+    with torch.cuda.device(x.device):
+        check(lib().yr_upsample2_forward(_ptr(x), c, b, h, w, c, _ptr(out), c, stream_ptr(x.device)))
+    return out
+
+
+def upsample2_backward(dy, out=None):
+    """The input gradient of ``upsample2_forward`` (yr_upsample2_backward): dy [B, 2H, 2W, C] -> dx [B, H, W, C], the four elements of
+    each 2 x 2 block added in row-major order.  One launch."""
+    b, h2, w2, c = _dw_map(dy, 'dy')
+    if h2 % 2 or w2 % 2:
+        raise ValueError('upsample2_backward: dy is %d x %d, expected even sides' % (h2, w2))
+    out = _out_like(out, (b, h2 // 2, w2 // 2, c), dy.device, 'upsample2_backward')
+    with torch.cuda.device(dy.device):
+        check(lib().yr_upsample2_backward(_ptr(dy), c, b, h2 // 2, w2 // 2, c, _ptr(out), c, stream_ptr(dy.device)))
+    return out
+
+
+def wsum_chunk(pixels, c):
+    """Pixels per workgroup of the first stage of ``wsum_backward``'s sums: a function of these numbers only (0: refused sizes)."""
+    return int(lib().yr_wsum_chunk(int(pixels), int(c)))
+
+
+def wsum_workspace_bytes(pixels, c):
+    """Bytes of workspace that ``wsum_backward`` needs for d alpha (0: refused sizes)."""
+    return int(lib().yr_wsum_workspace_bytes(int(pixels), int(c)))
+
+
+def _wsum_args(name, first, what, xs, alpha):
+    """-> (pixels, c, device) of ``first`` [..., C], called ``what`` in messages; xs: four tensors of its shape there (or None: not
+    checked), alpha float32 [4] there"""
+    pixels, c = _rows(first, what)
+    dev = first.device
+    if xs is not None:
+        if not isinstance(xs, (list, tuple)) or len(xs) != 4:
+            raise ValueError('%s: exactly four maps' % name)
+        for i, x in enumerate(xs):
+            _require_cuda_f32(x, 'xs[%d]' % i)
+            if tuple(x.shape) != tuple(first.shape) or x.device != dev:
+                raise ValueError('%s: xs[%d] %s on %s, expected %s on %s' % (name, i, tuple(x.shape), x.device, tuple(first.shape), dev))
+    _bn_vec(alpha, 4, dev, 'alpha')
+    return pixels, c, dev
+
+
+def wsum_forward(xs, alpha, out=None):
+    """The reference's WeightedSum of four maps (yr_wsum_forward): xs four float32 tensors [..., C] of one shape, alpha float32 [4] on
+    their device -> y = ((alpha[0] xs[0] + alpha[1] xs[1]) + alpha[2] xs[2]) + alpha[3] xs[3], the float32 bits of YR_OP_WSUM.  One launch."""
+    if not isinstance(xs, (list, tuple)) or len(xs) != 4:
+        raise ValueError('wsum_forward: exactly four maps')
+    pixels, c, dev = _wsum_args('wsum_forward', xs[0], 'xs[0]', xs, alpha)
+    out = _out_like(out, tuple(xs[0].shape), dev, 'wsum_forward')
+    with torch.cuda.device(dev):
+        check(lib().yr_wsum_forward(_ptr(xs[0]), c, _ptr(xs[1]), c, _ptr(xs[2]), c, _ptr(xs[3]), c, _ptr(alpha), pixels, c, _ptr(out), c, stream_ptr(dev)))
+    return out
+
+
+def wsum_backward(dy, xs, alpha, need=(True, True, True, True), need_alpha=True, out=None, workspace=None):
+    """The gradients of ``wsum_forward`` (yr_wsum_backward): dy [..., C]; xs the forward's four maps (None is allowed with
+    need_alpha=False: they are not read then); alpha [4] -> (dxs, dalpha): dxs[i] = alpha[i] * dy for the i with need[i], None for the
+    others; dalpha[i] = sum(dy * xs[i]) in a fixed order (no atomics: the same call gives the same bytes), None with need_alpha=False.
+    out: a sequence of four tensors or Nones to receive the dxs; workspace: a uint8 tensor of at least wsum_workspace_bytes(pixels, C)
+    bytes (its contents do not matter).  Defaults: fresh ones.  Two launches with need_alpha, one without, none when nothing is needed."""
+    need = tuple(bool(v) for v in need)
+    if len(need) != 4:
+        raise ValueError('wsum_backward: need has four flags')
+    if xs is None and need_alpha:
+        raise ValueError('wsum_backward: d alpha needs the four maps')
+    pixels, c, dev = _wsum_args('wsum_backward', dy, 'dy', xs if need_alpha else None, alpha)
+    if out is None:
+        out = (None,) * 4
+    if len(out) != 4 or any(o is not None and not n for o, n in zip(out, need)):
+        raise ValueError('wsum_backward: out is a sequence of four, None where need is False')
+    dxs = [_out_like(o, tuple(dy.shape), dev, 'wsum_backward') if n else None for o, n in zip(out, need)]
+    dalpha = ws = None
+    if need_alpha:
+        nbytes = wsum_workspace_bytes(pixels, c)
+        if nbytes == 0:
+            raise ValueError('wsum_backward: %d pixels of %d channels are outside the contract' % (pixels, c))
+        ws = _workspace_arg(workspace, nbytes, dev, 'wsum_backward')
+        dalpha = torch.empty((4,), dtype=torch.float32, device=dev)
+    xp = [_ptr(x) for x in xs] if need_alpha else [None] * 4
+    with torch.cuda.device(dev):
+        check(lib().yr_wsum_backward(_ptr(dy), c, xp[0], c, xp[1], c, xp[2], c, xp[3], c, _ptr(alpha), pixels, c,
+                                     _ptr(dxs[0]), c, _ptr(dxs[1]), c, _ptr(dxs[2]), c, _ptr(dxs[3]), c, _ptr(dalpha),
+                                     _ptr(ws), ws.numel() if ws is not None else 0, stream_ptr(dev)))
+    return dxs, dalpha
 
 
 VOC_MAX_ROWS, VOC_MAX_GT = 4096, 512    # YR_VOC_MAX_ROWS, YR_VOC_MAX_GT of include/yoloret_hip.h
