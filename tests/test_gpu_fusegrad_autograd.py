@@ -8,7 +8,8 @@ float64 on the same inputs.  Every comparison prints its figures before it asser
 
 Not here: the agreement of rfcr_module(training=False) with the shipped inference plan on the model's own backbone taps.  A sub-model
 whose outputs are the taps, or the three concatenations, does not compile (the plan compiler accepts only outputs produced by a 1x1
-convolution), and the compiler is not changed for a test."""
+convolution), and the compiler is not changed for a test.  tests/test_gpu_layers_oracle.py compares it with the oracle's RFCR module
+on the oracle's taps instead, which needs no plan."""
 import itertools
 
 import numpy as np
