@@ -649,13 +649,24 @@ def test_autotune_candidate_mirror_matches_the_library():
     assert pairs('chained') == U.AUTOTUNE_MBH_CHAINED
     segs = re.search(r'static const int segs_list\[\] = \{(.*?)\};', src, re.S).group(1)
     assert [int(v) for v in segs.split(',')] == U.AUTOTUNE_MBR_SEGS
+    # the counts follow from the lists of tile shapes (X-macros: one X(...) per shape), which is what is counted here
+    def shapes(text, name):
+        body = re.search(r'#define %s\(X\)((?:.*\\\n)*.*)\n' % name, text).group(1)
+        return len(re.findall(r'\bX\(', body))
+
     pw = open(os.path.join(csrc, 'pointwise.hip')).read()
-    assert int(re.search(r'int yr_pointwise_num_cfgs\(int dtype\) \{ return dtype == YR_F32 \? (\d+) : yr_pwh_num_cfgs\(\); \}', pw).group(1)) == U.PW_NUM_CFGS[0]
+    pc = open(os.path.join(csrc, 'pw_common.h')).read()
+    assert re.search(r'int yr_pointwise_num_cfgs\(int dtype\) \{ return dtype == YR_F32 \? PW_NCFG : yr_pwh_num_cfgs\(\); \}', pw)
+    assert 'static const PwCfg pw_cfgs[] = {PW_LDS_SHAPES(PW_CFG_LDS) PW_DIRECT_SHAPES(PW_CFG_DIRECT)};' in pw
+    assert 'constexpr int PW_NCFG = sizeof(pw_cfgs) / sizeof(pw_cfgs[0]);' in pw
+    assert shapes(pc, 'PW_LDS_SHAPES') == 14 and shapes(pc, 'PW_LDS_SHAPES') + shapes(pc, 'PW_DIRECT_SHAPES') == U.PW_NUM_CFGS[0]
     ph = open(os.path.join(csrc, 'pointwise_h.hip')).read()
     assert re.search(r'int yr_pwh_num_cfgs\(\) \{ return PWH_NCFG \+ PWH_NWALK \+ PWH_NSQ; \}', ph)
-    ncfg = len(re.findall(r'\{\s*\d+\s*,\s*\d+\s*\}', re.search(r'static const PwhCfg pwh_cfgs\[\] = \{(.*?)\};', ph, re.S).group(1)))
-    nwalk = int(re.search(r'constexpr int PWH_NWALK = (\d+);', ph).group(1))
-    nsq = int(re.search(r'constexpr int PWH_NSQ = (\d+);', ph).group(1))
+    assert 'static const PwhCfg pwh_cfgs[] = {PWH_DIRECT_SHAPES(PWH_CFG)};' in ph and 'constexpr int PWH_NCFG = sizeof(pwh_cfgs) / sizeof(pwh_cfgs[0]);' in ph
+    assert 'constexpr int PWH_NWALK = 0 PWH_WALK_SHAPES(PW_COUNT) PWH_LDS_SHAPES(PW_COUNT);' in ph and 'constexpr int PWH_NSQ = 2 * PWH_NVARIANT;' in ph
+    ncfg = shapes(ph, 'PWH_DIRECT_SHAPES')
+    nwalk = shapes(ph, 'PWH_WALK_SHAPES') + shapes(ph, 'PWH_LDS_SHAPES')
+    nsq = 2 * int(re.search(r'constexpr int PWH_NVARIANT = (\d+);', ph).group(1))
     assert ncfg + nwalk + nsq == U.PW_NUM_CFGS[1] == U.PW_NUM_CFGS[2]
     # ... and the tuner skips exactly the forms the mirror skips
     assert 'if (h->ops[i].dtype == YR_F32 && (h->ops[i].se_reduced & YR_PWF_STATIONARY)) continue;' in src

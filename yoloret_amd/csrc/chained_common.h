@@ -66,27 +66,11 @@ static inline int ch_row_segments(int Ho, int walks, int nw, int target_waves, i
 }
 
 #ifdef __HIPCC__
-// ---- THE LAUNCH TAIL of a template launcher: note the kernel's name (formatted once per instantiation: name_fmt's arguments are
-// its template parameters), raise the kernel's dynamic LDS limit where the instantiation asks for more than 48 KB - lds_max, the
-// most any of its launches takes; once per device: a process that drives several GPUs needs the attribute on each -, launch, check.
+// ---- THE LAUNCH TAIL of a template launcher is yr_launch (yr_common.h); here with the kernel's name formatted once per instantiation
+// from name_fmt, whose arguments are its template parameters.
 template <auto KERN, class Args, class... NameArgs>
 static int ch_launch(dim3 grid, dim3 block, size_t lds, size_t lds_max, hipStream_t s, const Args& a, const char* name_fmt, NameArgs... name_args) {
-    static char nm[64];
-    static const int nm_len = snprintf(nm, sizeof(nm), name_fmt, name_args...);
-    (void)nm_len;
-    yr_note_kernel(nm);
-    if (lds_max > 48 * 1024) {
-        static bool attr_set_dev[64] = {};
-        int cur_dev = 0;
-        (void)hipGetDevice(&cur_dev);
-        bool& attr_set = attr_set_dev[cur_dev & 63];
-        if (!attr_set) {
-            YR_CHECK_HIP(hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            attr_set = true;
-        }
-    }
-    hipLaunchKernelGGL(KERN, grid, block, lds, s, a);
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+    static const yr_kname nm = yr_kname_fmt(name_fmt, name_args...);
+    return yr_launch<KERN>(nm.s, grid, block, lds, lds_max, s, a);
 }
 #endif

@@ -137,7 +137,7 @@ __device__ __forceinline__ void head_finish(const HeadArgs& h, const HeadRegion&
                 const int nl = c * 16 + g * 4;
                 const f32x4 sc = *reinterpret_cast<const f32x4*>(ss + nl);
                 const f32x4 sh = *reinterpret_cast<const f32x4*>(ss + BN + nl);
-                f32x4 v = __builtin_elementwise_fma(ac1[c][p], (f32x4){0.00048828125f, 0.00048828125f, 0.00048828125f, 0.00048828125f}, acc[c][p]);
+                f32x4 v = yr_split_join(acc[c][p], ac1[c][p]);
                 if (use_pre) v += pq[p][c];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = __builtin_fmaf(v[r], sc[r], sh[r]);
@@ -263,11 +263,7 @@ __global__ __launch_bounds__(256, 2) void head_kernel(HeadArgs h) {
     const int tid = threadIdx.x;
     const HeadRegion R = head_region(h, BN);
     const int kp = a.S.kp;
-    if (tid < BN) {
-        const int n = R.n0 + tid < a.N ? R.n0 + tid : a.N - 1;
-        ss[tid] = a.scale ? a.scale[n] : 1.f;
-        ss[BN + tid] = a.shift ? a.shift[n] : 0.f;
-    }
+    pw_bn_to_lds(a.scale, a.shift, a.N, R.n0, BN, tid, ss);
     const int lr = tid / PWS_KQ;
     constexpr int MODE = SIMPLE ? 2 : 0;
     const bool gated = SIMPLE && a.gate != nullptr;
@@ -326,11 +322,7 @@ __global__ __launch_bounds__(256, 2) void head2_kernel(HeadArgs h) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const HeadRegion R = head_region(h, BN);
-    if (tid < BN) {
-        const int n = R.n0 + tid < a.N ? R.n0 + tid : a.N - 1;
-        ss[tid] = a.scale ? a.scale[n] : 1.f;
-        ss[BN + tid] = a.shift ? a.shift[n] : 0.f;
-    }
+    pw_bn_to_lds(a.scale, a.shift, a.N, R.n0, BN, tid, ss);
     const bool gated = a.gate != nullptr;
     if (gated)
         for (int k = tid; k < 512; k += NTH) gl[k] = k < a.S.s[0].c ? a.gate[(size_t)R.b * a.gate_ld + k] : 0.f;

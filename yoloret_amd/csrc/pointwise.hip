@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256) void pwd_kernel(PwArgs a) {
         const int kraw = chunk * 16 + kl;
 #pragma unroll
         for (int p = 0; p < PT; ++p) row[p].issue(a, kraw, kp, F.x[p], F.gt[MODE == 2 ? p : 0], F.cv[p]);
-        const int k = kraw < kp ? kraw : kp - 4;  // the k tail of the weights meets zeroed activations
+        const int k = pw_kclamp<4>(kraw, kp);  // the k tail of the weights meets zeroed activations
 #pragma unroll
         for (int c = 0; c < CT; ++c) F.w[c] = *reinterpret_cast<const float4*>(brow[c] + k);
     };
@@ -134,26 +134,43 @@ __global__ __launch_bounds__(256) void pwd_kernel(PwArgs a) {
 
 template <int PT, int CT>
 static int launch_direct(const PwArgs& a, hipStream_t s) {
-    constexpr int BM = 64 * PT, BN = 16 * CT;
     constexpr int D = PT * CT <= 2 ? 4 : (PT * CT <= 6 ? 3 : 2);
-    dim3 grid((unsigned)((a.M + BM - 1) / BM) * (unsigned)((a.N + BN - 1) / BN));
-    const int mode = (a.S.n == 1 && a.S.s[0].xform == YR_X_IDENTITY) ? (a.gate ? 2 : 1) : 0;
-    if (mode == 0 && a.gate) { yr_set_error("pointwise: an SE gate needs one identity source"); return YR_ERR_ARG; }
-    static char nm[3][48];
-    static const int nm_len = snprintf(nm[0], sizeof(nm[0]), "pwd_kernel<%d,%d,%d,0>", PT, CT, D) +
-                              snprintf(nm[1], sizeof(nm[1]), "pwd_kernel<%d,%d,%d,1>", PT, CT, D) +
-                              snprintf(nm[2], sizeof(nm[2]), "pwd_kernel<%d,%d,%d,2>", PT, CT, D);
-    (void)nm_len;
-    yr_note_kernel(nm[mode]);
-    if (mode == 1) hipLaunchKernelGGL((pwd_kernel<PT, CT, D, 1>), grid, dim3(256), 0, s, a);
-    else if (mode == 2) hipLaunchKernelGGL((pwd_kernel<PT, CT, D, 2>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((pwd_kernel<PT, CT, D, 0>), grid, dim3(256), 0, s, a);
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+    int mode;
+    if (int rc = pw_mode(a, &mode)) return rc;
+#define PWD_GO(MODE) YR_LAUNCH((pwd_kernel<PT, CT, D, MODE>), pw_grid(a, 64 * PT, 16 * CT), dim3(256), 0, 0, s, ("pwd_kernel<%d,%d,%d,%d>", PT, CT, D, MODE), a)
+    return PW_BY_MODE(mode, PWD_GO);
+#undef PWD_GO
 }
 
-template <int SHAPE>
-static int launch_lds(const PwArgs& a, hipStream_t s) { return yr_pw_launch_lds(SHAPE, a, s); }
+// ---- tile selection.  Candidates (BM x BN), in the order of the tuner's index: the LDS-staged shapes (launched through
+// yr_pw_launch_lds / yr_pw_launch_split by index), then the direct ones.
+struct PwCfg { int bm, bn; int (*direct)(const PwArgs&, hipStream_t); };
+#define PW_CFG_LDS(PT, CT, WM, WN) {16 * PT * WM, 16 * CT * WN, nullptr},
+#define PW_CFG_DIRECT(PT, CT) {64 * PT, 16 * CT, launch_direct<PT, CT>},
+static const PwCfg pw_cfgs[] = {PW_LDS_SHAPES(PW_CFG_LDS) PW_DIRECT_SHAPES(PW_CFG_DIRECT)};
+constexpr int PW_NCFG = sizeof(pw_cfgs) / sizeof(pw_cfgs[0]);
+static int launch_cfg_index(int i, const PwArgs& a, hipStream_t s) { return i < PW_NLDS ? yr_pw_launch_lds(i, a, s) : pw_cfgs[i].direct(a, s); }
+
+// The heuristic's pick among the LDS-staged shapes, a pure function of the GEMM's extents.  Big-M layers take 128-row tiles, layers
+// with few pixels (13x13 / 26x26 maps) take 64-row tiles and, if still short of ~2 workgroups per CU, narrower cout tiles - these
+// layers are latency/occupancy-bound, not bandwidth-bound.  Cost model (seconds, rough): activations re-read once per cout tile
+// (mostly from L2/MALL), MFMA work on the padded cout width, and a penalty when the grid cannot fill the chip.
+static int pw_pick_shape(int M, int N, int kp) {
+    const double Md = (double)M, Kd = (double)kp;
+    auto cost = [&](const PwCfg& c) {
+        const double ntn = (double)((N + c.bn - 1) / c.bn), npad = ntn * c.bn;
+        const double nblk = (double)((M + c.bm - 1) / c.bm) * ntn;
+        const double t_mem = (Md * Kd * 4.0 * (1.0 + 0.3 * (ntn - 1.0)) + Md * N * 4.0) / 4.0e12;
+        const double t_cmp = 2.0 * Md * npad * Kd / (c.bm >= 128 ? 60.0e12 : 45.0e12);
+        const double fill = nblk < 512.0 ? 512.0 / nblk : 1.0;
+        return (t_mem + t_cmp) * fill;
+    };
+    int best = 0;
+    double bc = cost(pw_cfgs[0]);
+    for (int i = 1; i < PW_NLDS; ++i)
+        if (cost(pw_cfgs[i]) < bc) { bc = cost(pw_cfgs[i]); best = i; }
+    return best;
+}
 
 int yr_launch_pointwise(const yr_op& op_in, int batch, hipStream_t s) {
     PwArgs a;
@@ -228,31 +245,11 @@ int yr_launch_pointwise(const yr_op& op_in, int batch, hipStream_t s) {
     YR_REQUIRE(M > 0 && M < (1ll << 31), "pointwise: pixel count %lld out of range", M);
     a.M = (int)M;
     a.out_ld = op.out_ld; a.res_ld = op.res_ld; a.gate_ld = op.gate_ld; a.act = op.act;
-    // ---- tile selection.  Candidates (BM x BN); big-M layers take 128-row tiles, layers with few
-    // pixels (13x13 / 26x26 maps) take 64-row tiles and, if still short of ~2 workgroups per CU,
-    // narrower cout tiles - these layers are latency/occupancy-bound, not bandwidth-bound.
-    struct Cfg { int bm, bn; int (*fn)(const PwArgs&, hipStream_t); };
-    static const Cfg cfgs[] = {{256, 16, launch_lds<0>}, {128, 32, launch_lds<1>}, {128, 48, launch_lds<2>},
-                               {128, 64, launch_lds<3>}, {128, 80, launch_lds<4>}, {128, 96, launch_lds<5>},
-                               {128, 128, launch_lds<6>},
-                               {64, 16, launch_lds<7>}, {64, 32, launch_lds<8>}, {64, 48, launch_lds<9>},
-                               {64, 64, launch_lds<10>}, {64, 80, launch_lds<11>}, {64, 96, launch_lds<12>},
-                               {64, 128, launch_lds<13>},
-                               // direct (LDS-free) variants, BM = 64*PT, BN = 16*CT
-                               {64, 16, launch_direct<1, 1>}, {64, 32, launch_direct<1, 2>}, {64, 48, launch_direct<1, 3>},
-                               {64, 64, launch_direct<1, 4>}, {64, 80, launch_direct<1, 5>}, {64, 96, launch_direct<1, 6>},
-                               {64, 128, launch_direct<1, 8>},
-                               {128, 32, launch_direct<2, 2>}, {128, 48, launch_direct<2, 3>}, {128, 64, launch_direct<2, 4>},
-                               {128, 80, launch_direct<2, 5>}, {128, 96, launch_direct<2, 6>},
-                               {256, 32, launch_direct<4, 2>}, {256, 48, launch_direct<4, 3>}, {256, 64, launch_direct<4, 4>}};
     if (narrow && (op.se_reduced & YR_PWF_KSPLIT) && a.S.kp >= 2 * 32 && a.dw_w == nullptr) return yr_pwh_launch_ksplit(op.dtype, a, s);   // (the plan asks for the k-split form)
     if (narrow) return yr_pw_launch_h(op.dtype, op.k - 1, a, s);   // bf16 / f16: pointwise_h.hip (its own tile table)
-    constexpr int NLDS = 14;  // the first NLDS entries are the LDS-staged kernel (the heuristic below only ranks those)
-    constexpr int NCFG = sizeof(cfgs) / sizeof(cfgs[0]);
-    const int N = op.cout;
     // autotuned choice (yr_autotune stores the fastest shape per op and batch): op.k = 1 + index
     if (dw) {  // LDS-staged kernel only; shapes it is not built for fall back inside yr_pw_launch_lds
-        const int shape = (op.k >= 1 && op.k <= NLDS) ? op.k - 1 : -1;
+        const int shape = (op.k >= 1 && op.k <= PW_NLDS) ? op.k - 1 : -1;
         return yr_pw_launch_lds(shape, a, s);
     }
     // The SPLIT form (pointwise_split.hip): every float32 conv at least 16 channels deep without a depthwise-folded source - by
@@ -273,34 +270,19 @@ int yr_launch_pointwise(const yr_op& op_in, int batch, hipStream_t s) {
         return yr_pw_launch_stream(a, s);
     }
     if (split && (op.se_reduced & YR_PWF_KSPLIT) && a.S.kp >= 2 * 32) return yr_pw_launch_ksplit(a, s);
-    if (split && op.k >= 1 && op.k <= NCFG) return yr_pw_launch_split((op.k - 1) % NLDS, a, s);
-    if (op.k >= 1 && op.k <= NCFG) return cfgs[op.k - 1].fn(a, s);
+    if (split && op.k >= 1 && op.k <= PW_NCFG) return yr_pw_launch_split((op.k - 1) % PW_NLDS, a, s);
+    if (op.k >= 1 && op.k <= PW_NCFG) return launch_cfg_index(op.k - 1, a, s);
     // tuning override: YR_PW_CFG="BMxBN" forces one tile shape for every layer (experiments only)
     static const char* force = getenv("YR_PW_CFG");
     if (force) {
         int bm = 0, bn = 0;
         if (sscanf(force, "%dx%d", &bm, &bn) == 2)
-            for (int i = 0; i < NCFG; ++i)
-                if (cfgs[i].bm == bm && cfgs[i].bn == bn) return cfgs[i].fn(a, s);
+            for (int i = 0; i < PW_NCFG; ++i)
+                if (pw_cfgs[i].bm == bm && pw_cfgs[i].bn == bn) return launch_cfg_index(i, a, s);
     }
-    // cost model (seconds, rough): activations re-read once per cout tile (mostly from L2/MALL),
-    // MFMA work on the padded cout width, and a penalty when the grid cannot fill the chip.
-    const double Md = (double)a.M, Kd = (double)a.S.kp;
-    auto cost = [&](const Cfg& c) {
-        const double ntn = (double)((N + c.bn - 1) / c.bn), npad = ntn * c.bn;
-        const double nblk = (double)((a.M + c.bm - 1) / c.bm) * ntn;
-        const double t_mem = (Md * Kd * 4.0 * (1.0 + 0.3 * (ntn - 1.0)) + Md * N * 4.0) / 4.0e12;
-        const double t_cmp = 2.0 * Md * npad * Kd / (c.bm >= 128 ? 60.0e12 : 45.0e12);
-        const double fill = nblk < 512.0 ? 512.0 / nblk : 1.0;
-        return (t_mem + t_cmp) * fill;
-    };
-    const Cfg* best = &cfgs[0];
-    double bc = cost(cfgs[0]);
-    for (int i = 1; i < NLDS; ++i)
-        if (cost(cfgs[i]) < bc) { bc = cost(cfgs[i]); best = &cfgs[i]; }
-    if (split) return yr_pw_launch_split((int)(best - cfgs), a, s);
-    return best->fn(a, s);
+    const int best = pw_pick_shape(a.M, op.cout, a.S.kp);
+    return split ? yr_pw_launch_split(best, a, s) : yr_pw_launch_lds(best, a, s);
 }
 
 // number of tile shapes yr_launch_pointwise can be forced to through op.k (1-based) for ops of this dtype
-int yr_pointwise_num_cfgs(int dtype) { return dtype == YR_F32 ? 29 : yr_pwh_num_cfgs(); }
+int yr_pointwise_num_cfgs(int dtype) { return dtype == YR_F32 ? PW_NCFG : yr_pwh_num_cfgs(); }

@@ -39,6 +39,7 @@ __global__ __launch_bounds__(256) void pwh_kernel(PwArgs a) {
 #pragma unroll
     for (int t = 0; t < CT; ++t) {
         // MFMA row li of tile t <-> cout: see the header (lane group g ends up owning couts 8g..8g+7 of the pair)
+        // (also in pwhp_kernel, pwhl_kernel, pwkh_kernel and mbh.hip: sharing it as a function changes the code of 44 kernels)
         const int n = n0 + (t >> 1) * 32 + 8 * (li >> 2) + 4 * (t & 1) + (li & 3);
         brow[t] = reinterpret_cast<const T*>(a.wt) + (size_t)(n < a.N ? n : 0) * kp;  // rows beyond N feed couts that are never stored
     }
@@ -54,7 +55,7 @@ __global__ __launch_bounds__(256) void pwh_kernel(PwArgs a) {
 #pragma unroll
         for (int p = 0; p < PT; ++p)
             row[p].template issue<POOLS>(a, kraw, kp, F.x[p], F.g0[MODE == 2 ? p : 0], F.g1[MODE == 2 ? p : 0], F.cv[p]);
-        const int k = kraw < kp ? kraw : kp - 8;  // the k tail of the weights meets zeroed activations
+        const int k = pw_kclamp<8>(kraw, kp);  // the k tail of the weights meets zeroed activations
 #pragma unroll
         for (int t = 0; t < CT; ++t) F.w[t] = *reinterpret_cast<const pwh_u4*>(brow[t] + k);
     };
@@ -150,7 +151,7 @@ __global__ __launch_bounds__(256) void pwhp_kernel(PwArgs a, int tiles_per_wg) {
 #pragma unroll
         for (int ch = 0; ch < NCH; ++ch) {
             const int kraw = ch * 32 + kl;
-            wf[ch][t] = *reinterpret_cast<const pwh_u4*>(brow + (kraw < kp ? kraw : kp - 8));
+            wf[ch][t] = *reinterpret_cast<const pwh_u4*>(brow + pw_kclamp<8>(kraw, kp));
         }
     }
     float sc[CP][8], sh[CP][8];
@@ -256,7 +257,7 @@ __global__ __launch_bounds__(256, 3) void pwhl_kernel(PwArgs a) {
     };
     auto fetch = [&](int chunk, Stage& R) __attribute__((always_inline)) {
         const int kraw = chunk * 32 + lg * 8;
-        const int k = kraw < kp ? kraw : kp - 8;   // the k tail of the weights meets zeroed activations
+        const int k = pw_kclamp<8>(kraw, kp);   // the k tail of the weights meets zeroed activations
 #pragma unroll
         for (int h = 0; h < NWH; ++h) R.w[h] = *reinterpret_cast<const pwh_u4*>(wrow[h] + k);
 #pragma unroll
@@ -315,31 +316,15 @@ __global__ __launch_bounds__(256, 3) void pwhl_kernel(PwArgs a) {
     }
 }
 
-template <class T, int PT, int CP>
-static int launch_h(const PwArgs& a, hipStream_t s);
-
 template <class T, int PT, int CT>
 static int launch_lds(const PwArgs& a, hipStream_t s) {
     if (a.dw_w) { yr_set_error("pointwise: the depthwise-folded source is a float32 feature"); return YR_ERR_ARG; }
-    constexpr int BM = 32 * PT, BN = 32 * CT;
-    const int mode = (a.S.n == 1 && a.S.s[0].xform == YR_X_IDENTITY) ? (a.gate ? 2 : 1) : 0;
-    if (mode == 0 && a.gate) { yr_set_error("pointwise: an SE gate needs one identity source"); return YR_ERR_ARG; }
-    bool pooled = false;
-    for (int i = 0; i < YR_MAX_SRC; ++i) pooled |= a.S.s[i].xform == YR_X_MAXPOOL2 || a.S.s[i].xform == YR_X_MAXPOOL4;
-    dim3 grid((unsigned)((a.M + BM - 1) / BM) * (unsigned)((a.N + BN - 1) / BN));
-    static char nm[4][48];   // spelled like the symbols: element type, PT, CT, MODE, POOLS
-    static const int nm_len = snprintf(nm[0], sizeof(nm[0]), "pwhl_kernel<%s,%d,%d,0,0>", yr_dtype_name(yr_elem<T>::dtype), PT, CT) +
-                              snprintf(nm[1], sizeof(nm[1]), "pwhl_kernel<%s,%d,%d,1,0>", yr_dtype_name(yr_elem<T>::dtype), PT, CT) +
-                              snprintf(nm[2], sizeof(nm[2]), "pwhl_kernel<%s,%d,%d,2,0>", yr_dtype_name(yr_elem<T>::dtype), PT, CT) +
-                              snprintf(nm[3], sizeof(nm[3]), "pwhl_kernel<%s,%d,%d,0,1>", yr_dtype_name(yr_elem<T>::dtype), PT, CT);
-    (void)nm_len;
-    yr_note_kernel(nm[mode == 0 && pooled ? 3 : mode]);
-    if (mode == 1) hipLaunchKernelGGL((pwhl_kernel<T, PT, CT, 1, false>), grid, dim3(256), 0, s, a);
-    else if (mode == 2) hipLaunchKernelGGL((pwhl_kernel<T, PT, CT, 2, false>), grid, dim3(256), 0, s, a);
-    else if (pooled) hipLaunchKernelGGL((pwhl_kernel<T, PT, CT, 0, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((pwhl_kernel<T, PT, CT, 0, false>), grid, dim3(256), 0, s, a);
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+    int mode;
+    if (int rc = pw_mode(a, &mode)) return rc;
+    // (names spelled like the symbols: element type, PT, CT, MODE, POOLS)
+#define PWHL_GO(MODE, POOLS) YR_LAUNCH((pwhl_kernel<T, PT, CT, MODE, POOLS>), pw_grid(a, 32 * PT, 32 * CT), dim3(256), 0, 0, s, ("pwhl_kernel<%s,%d,%d,%d,%d>", yr_dtype_name(yr_elem<T>::dtype), PT, CT, MODE, POOLS), a)
+    return mode == 1 ? PWHL_GO(1, 0) : mode == 2 ? PWHL_GO(2, 0) : pw_any_pooled(a.S) ? PWHL_GO(0, 1) : PWHL_GO(0, 0);
+#undef PWHL_GO
 }
 
 template <class T, int PT, int CP, int NCH>
@@ -350,57 +335,28 @@ static int launch_hp(const PwArgs& a, int mode, hipStream_t s) {
     int per = (ntm + 2047) / 2048;
     if (per < 4) per = 4;
     const int wgs = (ntm + per - 1) / per;
-    static char nm[2][48];
-    static const int nm_len = snprintf(nm[0], sizeof(nm[0]), "pwhp_kernel<%s,%d,%d,%d,1>", yr_dtype_name(yr_elem<T>::dtype), PT, CP, NCH) +
-                              snprintf(nm[1], sizeof(nm[1]), "pwhp_kernel<%s,%d,%d,%d,2>", yr_dtype_name(yr_elem<T>::dtype), PT, CP, NCH);
-    (void)nm_len;
-    yr_note_kernel(nm[mode - 1]);
     const dim3 grid((unsigned)wgs, (unsigned)ntn);
-    if (mode == 1) hipLaunchKernelGGL((pwhp_kernel<T, PT, CP, NCH, 1>), grid, dim3(256), 0, s, a, per);
-    else hipLaunchKernelGGL((pwhp_kernel<T, PT, CP, NCH, 2>), grid, dim3(256), 0, s, a, per);
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+#define PWHP_GO(MODE) YR_LAUNCH((pwhp_kernel<T, PT, CP, NCH, MODE>), grid, dim3(256), 0, 0, s, ("pwhp_kernel<%s,%d,%d,%d,%d>", yr_dtype_name(yr_elem<T>::dtype), PT, CP, NCH, MODE), a, per)
+    return mode == 1 ? PWHP_GO(1) : PWHP_GO(2);
+#undef PWHP_GO
 }
 
 template <class T, int PT, int CP>
 static int launch_h(const PwArgs& a, hipStream_t s) {
-    constexpr int BM = 64 * PT, BN = 32 * CP;
     // chunks of loads in flight; four pixel tiles per wave keep two (three spilled 464-544 bytes per lane in the f16 gather form)
     constexpr int D = PT >= 4 ? 2 : (PT + 2 * CP <= 4 ? 4 : (PT + 2 * CP <= 8 ? 3 : 2));
-    dim3 grid((unsigned)((a.M + BM - 1) / BM) * (unsigned)((a.N + BN - 1) / BN));
-    const int mode = (a.S.n == 1 && a.S.s[0].xform == YR_X_IDENTITY) ? (a.gate ? 2 : 1) : 0;
-    if (mode == 0 && a.gate) { yr_set_error("pointwise: an SE gate needs one identity source"); return YR_ERR_ARG; }
-    static char nm[3][48];
-    static const int nm_len = snprintf(nm[0], sizeof(nm[0]), "pwh_kernel<%s,%d,%d,%d,0>", yr_dtype_name(yr_elem<T>::dtype), PT, CP, D) +
-                              snprintf(nm[1], sizeof(nm[1]), "pwh_kernel<%s,%d,%d,%d,1>", yr_dtype_name(yr_elem<T>::dtype), PT, CP, D) +
-                              snprintf(nm[2], sizeof(nm[2]), "pwh_kernel<%s,%d,%d,%d,2>", yr_dtype_name(yr_elem<T>::dtype), PT, CP, D);
-    (void)nm_len;
-    yr_note_kernel(nm[mode]);
-    if (mode == 1) hipLaunchKernelGGL((pwh_kernel<T, PT, CP, D, 1>), grid, dim3(256), 0, s, a);
-    else if (mode == 2) hipLaunchKernelGGL((pwh_kernel<T, PT, CP, D, 2>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((pwh_kernel<T, PT, CP, D, 0>), grid, dim3(256), 0, s, a);
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+    int mode;
+    if (int rc = pw_mode(a, &mode)) return rc;
+#define PWH_GO(MODE) YR_LAUNCH((pwh_kernel<T, PT, CP, D, MODE>), pw_grid(a, 64 * PT, 32 * CP), dim3(256), 0, 0, s, ("pwh_kernel<%s,%d,%d,%d,%d>", yr_dtype_name(yr_elem<T>::dtype), PT, CP, D, MODE), a)
+    return PW_BY_MODE(mode, PWH_GO);
+#undef PWH_GO
 }
 
-struct PwhCfg { int bm, bn; };
-static const PwhCfg pwh_cfgs[] = {{64, 32}, {64, 64}, {64, 96}, {64, 128},
-                                  {128, 32}, {128, 64}, {128, 96}, {128, 128}, {256, 32}, {256, 64}};
-constexpr int PWH_NCFG = sizeof(pwh_cfgs) / sizeof(pwh_cfgs[0]);
-// + the small-K walking form (pwhp_kernel) in four shapes; where it does not apply (more than 128 k, gathered sources)
-// these indices run the plain kernel of the same tile shape, so every index is valid for every op
-constexpr int PWH_NWALK = 8;   // ... and the LDS-tiled form (pwhl_kernel) in four shapes
-// ... and the activation-stationary form (pointwise_hs.hip, k <= 256) and the all-couts k-streaming form (pointwise_hq.hip)
-// in four variants each as the last indices; ops they do not take run the 128 x 64 LDS-tiled shape
-constexpr int PWH_NSQ = 8;
-int yr_pwh_num_cfgs() { return PWH_NCFG + PWH_NWALK + PWH_NSQ; }
-
-template <class T, int PT, int CP>
-static int launch_h(const PwArgs& a, hipStream_t s);
-
+// the small-K walking form (pwhp_kernel); where it does not apply (more than 128 k, gathered sources) the plain kernel of the same
+// tile shape runs, so every index is valid for every op
 template <class T, int PT, int CP>
 static int launch_walk(const PwArgs& a, hipStream_t s) {
-    const int mode = (a.S.n == 1 && a.S.s[0].xform == YR_X_IDENTITY) ? (a.gate ? 2 : 1) : 0;
+    const int mode = pw_mode_of(a);
     const int nch = (a.S.kp + 31) >> 5;
     if (mode == 0 || nch > 4 || a.dw_w != nullptr) return launch_h<T, PT, CP>(a, s);
     if (nch <= 1) return launch_hp<T, PT, CP, 1>(a, mode, s);
@@ -408,37 +364,38 @@ static int launch_walk(const PwArgs& a, hipStream_t s) {
     return launch_hp<T, PT, CP, 4>(a, mode, s);
 }
 
+// ---- THE TILE SHAPES of the 16-bit kernels, index = position in the lists taken one after the other (the tuner's op.k - 1):
+// the direct kernel, X(PT, CP, launcher): BM = 64 PT, BN = 32 CP - the shapes the heuristic ranks (the direct kernel of the
+// 128 x 128 shape spilled 272 bytes per lane: that index runs its LDS-tiled twin, launch_lds<T, 2, 4>);
+#define PWH_DIRECT_SHAPES(X)                                                                                              \
+    X(1, 1, launch_h) X(1, 2, launch_h) X(1, 3, launch_h) X(1, 4, launch_h) X(2, 1, launch_h) X(2, 2, launch_h) X(2, 3, launch_h) \
+    X(2, 4, launch_lds) X(4, 1, launch_h) X(4, 2, launch_h)
+// the small-K walking form in four of those shapes, and the LDS-tiled form (pwhl_kernel), X(PT, CT): BM = 32 PT, BN = 32 CT;
+#define PWH_WALK_SHAPES(X) X(1, 1) X(2, 1) X(1, 2) X(2, 2)
+#define PWH_LDS_SHAPES(X) X(4, 4) X(2, 4) X(4, 2) X(2, 2)
+// then the activation-stationary form (pointwise_hs.hip, k <= 256) and the all-couts k-streaming form (pointwise_hq.hip) in
+// PWH_NVARIANT variants each; ops they do not take run the 128 x 64 LDS-tiled shape
+constexpr int PWH_NVARIANT = 4;
+struct PwhCfg { int bm, bn; };
+#define PWH_CFG(PT, CP, FN) {64 * PT, 32 * CP},
+static const PwhCfg pwh_cfgs[] = {PWH_DIRECT_SHAPES(PWH_CFG)};
+constexpr int PWH_NCFG = sizeof(pwh_cfgs) / sizeof(pwh_cfgs[0]);
+constexpr int PWH_NWALK = 0 PWH_WALK_SHAPES(PW_COUNT) PWH_LDS_SHAPES(PW_COUNT);
+constexpr int PWH_NSQ = 2 * PWH_NVARIANT;
+int yr_pwh_num_cfgs() { return PWH_NCFG + PWH_NWALK + PWH_NSQ; }
+
 template <class T>
 static int launch_h_cfg(int cfg, const PwArgs& a, hipStream_t s) {
-    switch (cfg) {
-        case 0: return launch_h<T, 1, 1>(a, s);
-        case 1: return launch_h<T, 1, 2>(a, s);
-        case 2: return launch_h<T, 1, 3>(a, s);
-        case 3: return launch_h<T, 1, 4>(a, s);
-        case 4: return launch_h<T, 2, 1>(a, s);
-        case 5: return launch_h<T, 2, 2>(a, s);
-        case 6: return launch_h<T, 2, 3>(a, s);
-        case 7: return launch_lds<T, 2, 4>(a, s);   // (the direct kernel of this 128 x 128 shape spilled 272 bytes per lane: its LDS-tiled twin)
-        case 8: return launch_h<T, 4, 1>(a, s);
-        case 9: return launch_h<T, 4, 2>(a, s);
-        case 10: return launch_walk<T, 1, 1>(a, s);
-        case 11: return launch_walk<T, 2, 1>(a, s);
-        case 12: return launch_walk<T, 1, 2>(a, s);
-        case 13: return launch_walk<T, 2, 2>(a, s);
-        case 14: return launch_lds<T, 4, 4>(a, s);
-        case 15: return launch_lds<T, 2, 4>(a, s);
-        case 16: return launch_lds<T, 4, 2>(a, s);
-        case 17: return launch_lds<T, 2, 2>(a, s);
-        case 18: case 19: case 20: case 21: {
-            const int rc = yr_pwhs_launch(yr_elem<T>::dtype, cfg - 18, a, s);
-            return rc == YR_NOT_TAKEN ? launch_lds<T, 4, 2>(a, s) : rc;
-        }
-        case 22: case 23: case 24: case 25: {
-            const int rc = yr_pwhq_launch(yr_elem<T>::dtype, cfg - 22, a, s);
-            return rc == YR_NOT_TAKEN ? launch_lds<T, 4, 2>(a, s) : rc;
-        }
-        default: yr_set_error("pointwise: 16-bit tile shape %d out of range", cfg); return YR_ERR_ARG;
-    }
+    typedef int (*Fn)(const PwArgs&, hipStream_t);
+#define PWH_FN_H(PT, CP, FN) FN<T, PT, CP>,
+#define PWH_FN_W(PT, CP) launch_walk<T, PT, CP>,
+#define PWH_FN_L(PT, CT) launch_lds<T, PT, CT>,
+    static const Fn fns[] = {PWH_DIRECT_SHAPES(PWH_FN_H) PWH_WALK_SHAPES(PWH_FN_W) PWH_LDS_SHAPES(PWH_FN_L)};
+    if (cfg >= 0 && cfg < PWH_NCFG + PWH_NWALK) return fns[cfg](a, s);
+    YR_REQUIRE(cfg >= 0 && cfg < PWH_NCFG + PWH_NWALK + PWH_NSQ, "pointwise: 16-bit tile shape %d out of range", cfg);
+    const int v = cfg - (PWH_NCFG + PWH_NWALK);
+    const int rc = v < PWH_NVARIANT ? yr_pwhs_launch(yr_elem<T>::dtype, v, a, s) : yr_pwhq_launch(yr_elem<T>::dtype, v - PWH_NVARIANT, a, s);
+    return rc == YR_NOT_TAKEN ? launch_lds<T, 4, 2>(a, s) : rc;
 }
 
 // The K-SPLIT form for the passes of one or two images (YR_PWF_KSPLIT on a POINTWISE op, set by the compiler's 'latency' variant of
@@ -475,7 +432,7 @@ __global__ __launch_bounds__(256) void pwkh_kernel(PwArgs a) {
                 constexpr int j = decltype(J)::value;
                 const int kraw = (c0 + 4 * j) * 32 + g * 8;       // (beyond kp for a dead chunk: clamped addresses, cv = 0)
                 row.template issue<POOLS>(a, kraw, kp, x[j], g0[j], g1[j], cv[j]);
-                const int k = kraw < kp ? kraw : kp - 8;
+                const int k = pw_kclamp<8>(kraw, kp);
                 w[j][0] = *reinterpret_cast<const pwh_u4*>(brow[0] + k);
                 w[j][1] = *reinterpret_cast<const pwh_u4*>(brow[1] + k);
             });
@@ -510,47 +467,35 @@ __global__ __launch_bounds__(256) void pwkh_kernel(PwArgs a) {
 
 template <class T>
 static int launch_ksplit_t(const PwArgs& a, hipStream_t s) {
-    const int mode = (a.S.n == 1 && a.S.s[0].xform == YR_X_IDENTITY) ? (a.gate ? 2 : 1) : 0;
-    if (mode == 0 && a.gate) { yr_set_error("pointwise: an SE gate needs one identity source"); return YR_ERR_ARG; }
-    dim3 grid((unsigned)((a.M + 15) / 16) * (unsigned)((a.N + 31) / 32));
-    static char nm[3][40];
-    static const int nm_len = snprintf(nm[0], sizeof(nm[0]), "pwkh_kernel<%s,0>", yr_dtype_name(yr_elem<T>::dtype)) +
-                              snprintf(nm[1], sizeof(nm[1]), "pwkh_kernel<%s,1>", yr_dtype_name(yr_elem<T>::dtype)) +
-                              snprintf(nm[2], sizeof(nm[2]), "pwkh_kernel<%s,2>", yr_dtype_name(yr_elem<T>::dtype));
-    (void)nm_len;
-    yr_note_kernel(nm[mode]);
-    if (mode == 1) hipLaunchKernelGGL((pwkh_kernel<T, 1>), grid, dim3(256), 0, s, a);
-    else if (mode == 2) hipLaunchKernelGGL((pwkh_kernel<T, 2>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((pwkh_kernel<T, 0>), grid, dim3(256), 0, s, a);
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+    int mode;
+    if (int rc = pw_mode(a, &mode)) return rc;
+#define PWKH_GO(MODE) YR_LAUNCH((pwkh_kernel<T, MODE>), pw_grid(a, 16, 32), dim3(256), 0, 0, s, ("pwkh_kernel<%s,%d>", yr_dtype_name(yr_elem<T>::dtype), MODE), a)
+    return PW_BY_MODE(mode, PWKH_GO);
+#undef PWKH_GO
 }
-int yr_pwh_launch_ksplit(int dtype, const PwArgs& a, hipStream_t s) {
-    if (dtype == YR_BF16) return launch_ksplit_t<yr_bf16>(a, s);
-    if (dtype == YR_F16) return launch_ksplit_t<yr_f16>(a, s);
-    yr_set_error("pointwise: dtype %d is not a 16-bit type", dtype);
-    return YR_ERR_ARG;
-}
+int yr_pwh_launch_ksplit(int dtype, const PwArgs& a, hipStream_t s) { return PWH_BY_DTYPE(dtype, pwh_bad_dtype(dtype), launch_ksplit_t, a, s); }
 
 // 16-bit ops: a filled PwArgs (yr_launch_pointwise did the argument checks that do not depend on the element type);
 // cfg = op.k - 1 (autotuned tile shape) or -1: heuristic.
-int yr_pw_launch_h(int dtype, int cfg, const PwArgs& a, hipStream_t s) {
-    if (cfg < 0 || cfg >= PWH_NCFG + PWH_NWALK + PWH_NSQ) {
-        // heuristic: the widest cout tile that still yields ~2 workgroups per CU, 128-row tiles when pixels abound
-        const double Md = (double)a.M;
-        double best = 1e30;
-        for (int i = 0; i < PWH_NCFG; ++i) {
-            const PwhCfg& c = pwh_cfgs[i];
-            const double ntn = (double)((a.N + c.bn - 1) / c.bn), nblk = (double)((a.M + c.bm - 1) / c.bm) * ntn;
-            const double t_mem = Md * a.S.kp * 2.0 * (1.0 + 0.25 * (ntn - 1.0)) + Md * a.N * 2.0 + nblk * c.bn * a.S.kp * 2.0 * 0.25;
-            const double fill = nblk < 512.0 ? 512.0 / nblk : 1.0;
-            const double regs = (c.bm / 64) * (c.bn / 16) > 16 ? 1.3 : 1.0;
-            const double cost = t_mem * fill * regs;
-            if (cost < best) { best = cost; cfg = i; }
-        }
+// the heuristic's pick among the direct shapes, a pure function of the GEMM's extents: the widest cout tile that still yields ~2
+// workgroups per CU, 128-row tiles when pixels abound
+static int pwh_pick_cfg(int M, int N, int kp) {
+    const double Md = (double)M;
+    double best = 1e30;
+    int cfg = -1;
+    for (int i = 0; i < PWH_NCFG; ++i) {
+        const PwhCfg& c = pwh_cfgs[i];
+        const double ntn = (double)((N + c.bn - 1) / c.bn), nblk = (double)((M + c.bm - 1) / c.bm) * ntn;
+        const double t_mem = Md * kp * 2.0 * (1.0 + 0.25 * (ntn - 1.0)) + Md * N * 2.0 + nblk * c.bn * kp * 2.0 * 0.25;
+        const double fill = nblk < 512.0 ? 512.0 / nblk : 1.0;
+        const double regs = (c.bm / 64) * (c.bn / 16) > 16 ? 1.3 : 1.0;
+        const double cost = t_mem * fill * regs;
+        if (cost < best) { best = cost; cfg = i; }
     }
-    if (dtype == YR_BF16) return launch_h_cfg<yr_bf16>(cfg, a, s);
-    if (dtype == YR_F16) return launch_h_cfg<yr_f16>(cfg, a, s);
-    yr_set_error("pointwise: dtype %d is not a 16-bit type", dtype);
-    return YR_ERR_ARG;
+    return cfg;
+}
+
+int yr_pw_launch_h(int dtype, int cfg, const PwArgs& a, hipStream_t s) {
+    if (cfg < 0 || cfg >= PWH_NCFG + PWH_NWALK + PWH_NSQ) cfg = pwh_pick_cfg(a.M, a.N, a.S.kp);
+    return PWH_BY_DTYPE(dtype, pwh_bad_dtype(dtype), launch_h_cfg, cfg, a, s);
 }

@@ -53,7 +53,7 @@ __global__ __launch_bounds__(256, 2) void pwhq_kernel(PwArgs a, int nsplit, unsi
     }
     auto wfetch = [&](int step, pwh_u4 (&R)[CP]) __attribute__((always_inline)) {
         const int kraw = step * 64 + lk;
-        const int k = kraw < kp ? kraw : kp - 8;   // the k tail of the weights meets zeroed activations
+        const int k = pw_kclamp<8>(kraw, kp);   // the k tail of the weights meets zeroed activations
 #pragma unroll
         for (int c = 0; c < CP; ++c) R[c] = *reinterpret_cast<const pwh_u4*>(wrow[c] + k);
     };
@@ -132,19 +132,11 @@ template <class T, int PT, int CP>
 static int launch_q(const PwArgs& a, int mode, hipStream_t s) {
     constexpr int BM = 64 * PT;
     const int ntm = (a.M + BM - 1) / BM, nsplit = (a.N + 32 * CP - 1) / (32 * CP);
-    static char nm[3][48];
-    static const int nm_len = snprintf(nm[0], sizeof(nm[0]), "pwhq_kernel<%s,%d,%d,0>", yr_dtype_name(yr_elem<T>::dtype), PT, CP) +
-                              snprintf(nm[1], sizeof(nm[1]), "pwhq_kernel<%s,%d,%d,1>", yr_dtype_name(yr_elem<T>::dtype), PT, CP) +
-                              snprintf(nm[2], sizeof(nm[2]), "pwhq_kernel<%s,%d,%d,2>", yr_dtype_name(yr_elem<T>::dtype), PT, CP);
-    (void)nm_len;
-    yr_note_kernel(nm[mode]);
     const dim3 grid((unsigned)ntm * (unsigned)nsplit);
     const unsigned ob = pwh_out_bytes(a);
-    if (mode == 1) hipLaunchKernelGGL((pwhq_kernel<T, PT, CP, 1>), grid, dim3(256), 0, s, a, nsplit, ob);
-    else if (mode == 2) hipLaunchKernelGGL((pwhq_kernel<T, PT, CP, 2>), grid, dim3(256), 0, s, a, nsplit, ob);
-    else hipLaunchKernelGGL((pwhq_kernel<T, PT, CP, 0>), grid, dim3(256), 0, s, a, nsplit, ob);
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+#define PWHQ_GO(MODE) YR_LAUNCH((pwhq_kernel<T, PT, CP, MODE>), grid, dim3(256), 0, 0, s, ("pwhq_kernel<%s,%d,%d,%d>", yr_dtype_name(yr_elem<T>::dtype), PT, CP, MODE), a, nsplit, ob)
+    return PW_BY_MODE(mode, PWHQ_GO);
+#undef PWHQ_GO
 }
 
 // pairs per workgroup: all of N when that is at most `cap` pairs, else equal parts of at most `cap`
@@ -167,13 +159,13 @@ static int launch_q_pt(const PwArgs& a, int mode, int cap, hipStream_t s) {
 // variant: 0 = one pixel tile per wave, up to 256 couts per workgroup; 1 = two pixel tiles, up to 160 couts; 2 / 3 = the same
 // with up to 128 / 96 couts (more workgroups on the small maps, the activations read once per cout range - from L2).
 // Returns YR_NOT_TAKEN (no launch, no error text) when the form does not take the op: the caller falls back; real errors propagate.
-int yr_pwhq_launch(int dtype, int variant, const PwArgs& a, hipStream_t s) {
-    const int mode = (a.S.n == 1 && a.S.s[0].xform == YR_X_IDENTITY) ? (a.gate ? 2 : 1) : 0;
-    if (a.dw_w != nullptr || (mode == 0 && a.gate) || !pwh_out_fits_rsrc(a)) return YR_NOT_TAKEN;
-    for (int i = 0; i < YR_MAX_SRC; ++i)
-        if (a.S.s[i].xform == YR_X_MAXPOOL2 || a.S.s[i].xform == YR_X_MAXPOOL4) return YR_NOT_TAKEN;
+template <class T>
+static int launch_q_variant(int variant, const PwArgs& a, int mode, hipStream_t s) {
     const int cap = (variant & 1) ? (variant >= 2 ? 3 : 5) : (variant >= 2 ? 4 : 8);
-    if (dtype == YR_BF16) return (variant & 1) ? launch_q_pt<yr_bf16, 2>(a, mode, cap, s) : launch_q_pt<yr_bf16, 1>(a, mode, cap, s);
-    if (dtype == YR_F16) return (variant & 1) ? launch_q_pt<yr_f16, 2>(a, mode, cap, s) : launch_q_pt<yr_f16, 1>(a, mode, cap, s);
-    return YR_NOT_TAKEN;
+    return (variant & 1) ? launch_q_pt<T, 2>(a, mode, cap, s) : launch_q_pt<T, 1>(a, mode, cap, s);
+}
+int yr_pwhq_launch(int dtype, int variant, const PwArgs& a, hipStream_t s) {
+    const int mode = pw_mode_of(a);
+    if (a.dw_w != nullptr || (mode == 0 && a.gate) || !pwh_out_fits_rsrc(a) || pw_any_pooled(a.S)) return YR_NOT_TAKEN;
+    return PWH_BY_DTYPE(dtype, YR_NOT_TAKEN, launch_q_variant, variant, a, mode, s);
 }

@@ -210,29 +210,18 @@ static int launch_s(const PwArgs& a, int mode, int target_wgs, hipStream_t s) {
     const int per = (npairs + nsplit - 1) / nsplit;
     nsplit = (npairs + per - 1) / per;
     const bool plain = !a.pre && !a.res && !a.pool && (a.act == YR_ACT_NONE || a.act == YR_ACT_RELU6);
-    const int form = !plain ? 0 : (a.act == YR_ACT_RELU6 ? 2 : 1);   // generic | plain | plain + ReLU6: the last two template arguments
-    static char nm[3][3][56];
-    static bool named = false;
-    if (!named) {
-        for (int m = 0; m < 3; ++m)
-            for (int f = 0; f < 3; ++f)
-                snprintf(nm[m][f], sizeof(nm[m][f]), "pwhs_kernel<%s,%d,%d,%d,%d,%d>", yr_dtype_name(yr_elem<T>::dtype), PT, NCH, m, f > 0, f > 1);
-        named = true;
-    }
-    yr_note_kernel(nm[mode][form]);
+    const bool clamp = plain && a.act == YR_ACT_RELU6;   // generic | plain | plain + ReLU6: the last two template arguments
     const dim3 grid((unsigned)ntm * (unsigned)nsplit);
     const unsigned ob = pwh_out_bytes(a);
-#define PWHS_GO(MODE, PLAIN, CLAMP) hipLaunchKernelGGL((pwhs_kernel<T, PT, NCH, MODE, PLAIN, CLAMP>), grid, dim3(256), 0, s, a, per, nsplit, ob)
-    if (plain && a.act == YR_ACT_RELU6) {
-        if (mode == 1) PWHS_GO(1, true, true); else if (mode == 2) PWHS_GO(2, true, true); else PWHS_GO(0, true, true);
-    } else if (plain) {
-        if (mode == 1) PWHS_GO(1, true, false); else if (mode == 2) PWHS_GO(2, true, false); else PWHS_GO(0, true, false);
-    } else {
-        if (mode == 1) PWHS_GO(1, false, false); else if (mode == 2) PWHS_GO(2, false, false); else PWHS_GO(0, false, false);
-    }
+#define PWHS_GO(MODE, PLAIN, CLAMP) YR_LAUNCH((pwhs_kernel<T, PT, NCH, MODE, PLAIN, CLAMP>), grid, dim3(256), 0, 0, s, ("pwhs_kernel<%s,%d,%d,%d,%d,%d>", yr_dtype_name(yr_elem<T>::dtype), PT, NCH, MODE, PLAIN, CLAMP), a, per, nsplit, ob)
+#define PWHS_RELU6(MODE) PWHS_GO(MODE, 1, 1)
+#define PWHS_PLAIN(MODE) PWHS_GO(MODE, 1, 0)
+#define PWHS_GENERIC(MODE) PWHS_GO(MODE, 0, 0)
+    return clamp ? PW_BY_MODE(mode, PWHS_RELU6) : plain ? PW_BY_MODE(mode, PWHS_PLAIN) : PW_BY_MODE(mode, PWHS_GENERIC);
 #undef PWHS_GO
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+#undef PWHS_RELU6
+#undef PWHS_PLAIN
+#undef PWHS_GENERIC
 }
 
 template <class T, int PT>
@@ -249,13 +238,13 @@ static int launch_s_pt(const PwArgs& a, int mode, int target_wgs, hipStream_t s)
 // variant: 0 / 1 = one / two pixel tiles per wave with ~512 workgroups wanted, 2 / 3 = the same with ~1280.
 // Returns YR_NOT_TAKEN (pw_common.h: positive, distinct from every yr_status error; no launch, no error text) when the form
 // does not take the op: the caller falls back.  Real argument errors keep their negative codes and are propagated.
-int yr_pwhs_launch(int dtype, int variant, const PwArgs& a, hipStream_t s) {
-    const int mode = (a.S.n == 1 && a.S.s[0].xform == YR_X_IDENTITY) ? (a.gate ? 2 : 1) : 0;
-    if (a.S.kp > 256 || a.dw_w != nullptr || (mode == 0 && a.gate) || !pwh_out_fits_rsrc(a)) return YR_NOT_TAKEN;
-    for (int i = 0; i < YR_MAX_SRC; ++i)
-        if (a.S.s[i].xform == YR_X_MAXPOOL2 || a.S.s[i].xform == YR_X_MAXPOOL4) return YR_NOT_TAKEN;
+template <class T>
+static int launch_s_variant(int variant, const PwArgs& a, int mode, hipStream_t s) {
     const int target = variant >= 2 ? 1280 : 512;
-    if (dtype == YR_BF16) return (variant & 1) ? launch_s_pt<yr_bf16, 2>(a, mode, target, s) : launch_s_pt<yr_bf16, 1>(a, mode, target, s);
-    if (dtype == YR_F16) return (variant & 1) ? launch_s_pt<yr_f16, 2>(a, mode, target, s) : launch_s_pt<yr_f16, 1>(a, mode, target, s);
-    return YR_NOT_TAKEN;
+    return (variant & 1) ? launch_s_pt<T, 2>(a, mode, target, s) : launch_s_pt<T, 1>(a, mode, target, s);
+}
+int yr_pwhs_launch(int dtype, int variant, const PwArgs& a, hipStream_t s) {
+    const int mode = pw_mode_of(a);
+    if (a.S.kp > 256 || a.dw_w != nullptr || (mode == 0 && a.gate) || !pwh_out_fits_rsrc(a) || pw_any_pooled(a.S)) return YR_NOT_TAKEN;
+    return PWH_BY_DTYPE(dtype, YR_NOT_TAKEN, launch_s_variant, variant, a, mode, s);
 }

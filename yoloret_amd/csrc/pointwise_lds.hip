@@ -59,6 +59,7 @@ __global__ __launch_bounds__(256, DW ? 3 : pw_min_blocks(PT, CT, SIMPLE)) void p
 
     // the tile's BatchNorm scale / shift go to LDS now (behind the k loop's barriers by the time they are read):
     // fetched in the epilogue they would cost every tile an L2 round trip with nothing left to hide it
+    // (also pw_bn_to_lds in pw_common.h: calling it here changes the code of the 14 gathering instantiations of this kernel)
     if (tid < BN) {
         const int n = n0 + tid < a.N ? n0 + tid : a.N - 1;
         ss[tid] = a.scale ? a.scale[n] : 1.f;
@@ -113,7 +114,7 @@ __global__ __launch_bounds__(256, DW ? 3 : pw_min_blocks(PT, CT, SIMPLE)) void p
         };
         auto fetch = [&](int k0, Regs& R) __attribute__((always_inline)) {
             const int kraw = k0 + kq * 4;
-            const int k = kraw < kp ? kraw : kp - 4;
+            const int k = pw_kclamp<4>(kraw, kp);
             pw_unroll<A_PASSES>([&](auto P) __attribute__((always_inline)) {
                 constexpr int p = decltype(P)::value;
                 if constexpr (DW) row[p].issue(a, kraw, kp, R.ra[p], R.cv[p]);
@@ -136,7 +137,7 @@ __global__ __launch_bounds__(256, DW ? 3 : pw_min_blocks(PT, CT, SIMPLE)) void p
                 float4 v;
                 if constexpr (DW) {
                     const int kraw = k0 + kq * 4;
-                    v = row[p].finish(a, R.ra[p], R.cv[p], dwl, kp, kraw < kp ? kraw : kp - 4);
+                    v = row[p].finish(a, R.ra[p], R.cv[p], dwl, kp, pw_kclamp<4>(kraw, kp));
                 } else {
                     v = gated ? pw_finish<2>(R.ra[p][0], R.rg[p], R.cv[p]) : pw_finish<1>(R.ra[p][0], R.rg[p], R.cv[p]);
                 }
@@ -217,52 +218,26 @@ __global__ __launch_bounds__(256, DW ? 3 : pw_min_blocks(PT, CT, SIMPLE)) void p
 template <int PT, int CT, int WM, int WN>
 static int launch_cfg(const PwArgs& a, hipStream_t s) {
     constexpr int BM = 16 * PT * WM, BN = 16 * CT * WN;
-    dim3 grid((unsigned)((a.M + BM - 1) / BM) * (unsigned)((a.N + BN - 1) / BN));
+    // (names spelled like the symbols: SIMPLE, DW)
+#define PW_GO(SIMPLE, DW, lds) YR_LAUNCH((pw_kernel<PT, CT, WM, WN, SIMPLE, DW>), pw_grid(a, BM, BN), dim3(256), lds, 0, s, ("pw_kernel<%d,%d,%d,%d,%d,%d>", PT, CT, WM, WN, SIMPLE, DW), a)
     if (a.dw_w != nullptr) {  // depthwise-folded source: built for the 64-row shapes with 3..8 cout tiles
         if constexpr (PT == 1 && WM == 4 && CT >= 3) {
-            static char dnm[48];
-            static const int dnm_len = snprintf(dnm, sizeof(dnm), "pw_kernel<%d,%d,%d,%d,1,1>", PT, CT, WM, WN);   // (spelled like the symbol: SIMPLE, DW)
-            (void)dnm_len;
-            yr_note_kernel(dnm);
-            hipLaunchKernelGGL((pw_kernel<PT, CT, WM, WN, true, true>), grid, dim3(256), (size_t)11 * a.S.kp * sizeof(float), s, a);
-            YR_LAUNCH_CHECK();
-            return YR_OK;
+            return PW_GO(1, 1, (size_t)11 * a.S.kp * sizeof(float));
         } else {
             yr_set_error("pointwise: no depthwise-folded kernel for tile shape %dx%d", BM, BN);
             return YR_ERR_ARG;
         }
     }
-    const bool simple = a.S.n == 1 && a.S.s[0].xform == YR_X_IDENTITY;
-    static char nm[2][48];
-    static const int nm_len = snprintf(nm[0], sizeof(nm[0]), "pw_kernel<%d,%d,%d,%d,0,0>", PT, CT, WM, WN) +
-                              snprintf(nm[1], sizeof(nm[1]), "pw_kernel<%d,%d,%d,%d,1,0>", PT, CT, WM, WN);
-    (void)nm_len;
-    yr_note_kernel(nm[simple ? 1 : 0]);
-    if (simple) hipLaunchKernelGGL((pw_kernel<PT, CT, WM, WN, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((pw_kernel<PT, CT, WM, WN, false>), grid, dim3(256), 0, s, a);
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+    return pw_mode_of(a) != 0 ? PW_GO(1, 0, 0) : PW_GO(0, 0, 0);
+#undef PW_GO
 }
 
 int yr_pw_launch_lds(int shape, const PwArgs& a, hipStream_t s) {
-    if (a.dw_w != nullptr && (shape < 9 || shape > 13)) {  // any other request: the narrowest built shape that covers N
-        shape = a.N <= 48 ? 9 : a.N <= 64 ? 10 : a.N <= 80 ? 11 : a.N <= 96 ? 12 : 13;
-    }
-    switch (shape) {
-        case 0: return launch_cfg<4, 1, 4, 1>(a, s);
-        case 1: return launch_cfg<2, 2, 4, 1>(a, s);
-        case 2: return launch_cfg<2, 3, 4, 1>(a, s);
-        case 3: return launch_cfg<4, 2, 2, 2>(a, s);
-        case 4: return launch_cfg<2, 5, 4, 1>(a, s);
-        case 5: return launch_cfg<4, 3, 2, 2>(a, s);
-        case 6: return launch_cfg<4, 4, 2, 2>(a, s);
-        case 7: return launch_cfg<1, 1, 4, 1>(a, s);
-        case 8: return launch_cfg<1, 2, 4, 1>(a, s);
-        case 9: return launch_cfg<1, 3, 4, 1>(a, s);
-        case 10: return launch_cfg<1, 4, 4, 1>(a, s);
-        case 11: return launch_cfg<1, 5, 4, 1>(a, s);
-        case 12: return launch_cfg<1, 6, 4, 1>(a, s);
-        case 13: return launch_cfg<1, 8, 4, 1>(a, s);
-        default: yr_set_error("pointwise: LDS shape %d out of range", shape); return YR_ERR_ARG;
-    }
+    if (a.dw_w != nullptr) shape = pw_dw_shape(shape, a.N);
+    typedef int (*Fn)(const PwArgs&, hipStream_t);
+#define PW_FN(PT, CT, WM, WN) launch_cfg<PT, CT, WM, WN>,
+    static const Fn fns[] = {PW_LDS_SHAPES(PW_FN)};
+#undef PW_FN
+    YR_REQUIRE(shape >= 0 && shape < PW_NLDS, "pointwise: LDS shape %d out of range", shape);
+    return fns[shape](a, s);
 }

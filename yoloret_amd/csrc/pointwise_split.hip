@@ -53,11 +53,7 @@ __global__ __launch_bounds__(256, pws_min_blocks(PT, CT)) void pws_kernel(PwArgs
 
     // the tile's BatchNorm scale / shift go to LDS now (behind the k loop's barriers by the time they are read):
     // fetched in the epilogue they would cost every tile an L2 round trip with nothing left to hide it
-    if (tid < BN) {
-        const int n = n0 + tid < a.N ? n0 + tid : a.N - 1;
-        ss[tid] = a.scale ? a.scale[n] : 1.f;
-        ss[BN + tid] = a.shift ? a.shift[n] : 0.f;
-    }
+    pw_bn_to_lds(a.scale, a.shift, a.N, n0, BN, tid, ss);
 
     // loader mapping: quad kq of row lr (+64 per pass)
     const int lr = tid / PWS_KQ;
@@ -97,7 +93,7 @@ __global__ __launch_bounds__(256, pws_min_blocks(PT, CT)) void pws_kernel(PwArgs
         const f32x4 sh = *reinterpret_cast<const f32x4*>(ss + BN + nl);
 #pragma unroll
         for (int p = 0; p < PT; ++p)
-            pw_finish_quad(a, __builtin_elementwise_fma(ac1[c][p], (f32x4){0.00048828125f, 0.00048828125f, 0.00048828125f, 0.00048828125f}, acc[c][p]), sc, sh, m0 + (wm * PT + p) * 16 + li, n0 + nl, li, vec_out, vec_res, vec_pre);
+            pw_finish_quad(a, yr_split_join(acc[c][p], ac1[c][p]), sc, sh, m0 + (wm * PT + p) * 16 + li, n0 + nl, li, vec_out, vec_res, vec_pre);
     }
 }
 
@@ -105,21 +101,10 @@ __global__ __launch_bounds__(256, pws_min_blocks(PT, CT)) void pws_kernel(PwArgs
 
 template <int PT, int CT, int WM, int WN>
 static int launch_split_cfg(const PwArgs& a, hipStream_t s) {
-    constexpr int BM = 16 * PT * WM, BN = 16 * CT * WN;
-    dim3 grid((unsigned)((a.M + BM - 1) / BM) * (unsigned)((a.N + BN - 1) / BN));
-    const bool simple = a.S.n == 1 && a.S.s[0].xform == YR_X_IDENTITY;
-    static char nm[2][48];
-    static const int nm_len = snprintf(nm[0], sizeof(nm[0]), "pws_kernel<%d,%d,%d,%d,0>", PT, CT, WM, WN) +
-                              snprintf(nm[1], sizeof(nm[1]), "pws_kernel<%d,%d,%d,%d,1>", PT, CT, WM, WN);
-    (void)nm_len;
-    yr_note_kernel(nm[simple ? 1 : 0]);
-    bool pooled = false;
-    for (int i = 0; i < a.S.n; ++i) pooled |= a.S.s[i].xform == YR_X_MAXPOOL2 || a.S.s[i].xform == YR_X_MAXPOOL4;
-    if (simple) hipLaunchKernelGGL((pws_kernel<PT, CT, WM, WN, true>), grid, dim3(256), 0, s, a);
-    else if (pooled) hipLaunchKernelGGL((pws_kernel<PT, CT, WM, WN, false, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((pws_kernel<PT, CT, WM, WN, false>), grid, dim3(256), 0, s, a);
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+    // (the pooled instantiation reports the gathering form's name: SIMPLE is all a name carries)
+#define PWS_GO(SIMPLE, POOLED) YR_LAUNCH((pws_kernel<PT, CT, WM, WN, SIMPLE, POOLED>), pw_grid(a, 16 * PT * WM, 16 * CT * WN), dim3(256), 0, 0, s, ("pws_kernel<%d,%d,%d,%d,%d>", PT, CT, WM, WN, SIMPLE), a)
+    return pw_mode_of(a) != 0 ? PWS_GO(1, 0) : pw_any_pooled(a.S) ? PWS_GO(0, 1) : PWS_GO(0, 0);
+#undef PWS_GO
 }
 
 // The K-SPLIT form (round 5, the passes of one or two images: YR_PWF_KSPLIT on a POINTWISE op, set by the compiler's 'nohead_k'
@@ -171,7 +156,7 @@ __global__ __launch_bounds__(256) void pwk_kernel(PwArgs a) {
                     constexpr int q = decltype(Q)::value;
                     const int kraw = (c0 + 4 * j) * PWS_BK + g * 8 + q * 4;     // (beyond kp for a dead chunk: clamped addresses, cv = 0)
                     row.template issue<POOLS>(a, kraw, kp, xa[j][q], xg[j][q], cv[j][q]);
-                    wb[j][q] = *reinterpret_cast<const float4*>(brow + (kraw < kp ? kraw : kp - 4));
+                    wb[j][q] = *reinterpret_cast<const float4*>(brow + pw_kclamp<4>(kraw, kp));
                 });
             });
             pw_unroll<PWK_G>([&](auto J) __attribute__((always_inline)) {
@@ -210,36 +195,21 @@ __global__ __launch_bounds__(256) void pwk_kernel(PwArgs a) {
 #pragma unroll
     for (int w = 0; w < 3; ++w) { acc += red[w][0][lane]; ac1 += red[w][1][lane]; }    // (in wave order: the result does not depend on timing)
     const f32x4 sc = {scq[0], scq[1], scq[2], scq[3]}, sh = {shq[0], shq[1], shq[2], shq[3]};
-    pw_finish_quad(a, __builtin_elementwise_fma(ac1, (f32x4){0.00048828125f, 0.00048828125f, 0.00048828125f, 0.00048828125f}, acc), sc, sh, m0 + li, n0 + g * 4, li,
+    pw_finish_quad(a, yr_split_join(acc, ac1), sc, sh, m0 + li, n0 + g * 4, li,
                    (a.out_ld & 3) == 0, (a.res_ld & 3) == 0, (a.pre_ld & 3) == 0);
 }
 
 int yr_pw_launch_ksplit(const PwArgs& a, hipStream_t s) {
-    dim3 grid((unsigned)((a.M + 15) / 16) * (unsigned)((a.N + 15) / 16));
-    const bool simple = a.S.n == 1 && a.S.s[0].xform == YR_X_IDENTITY;
-    yr_note_kernel(simple ? "pwk_kernel<1>" : "pwk_kernel<0>");
-    if (simple) hipLaunchKernelGGL((pwk_kernel<true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((pwk_kernel<false>), grid, dim3(256), 0, s, a);
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+#define PWK_GO(SIMPLE) YR_LAUNCH((pwk_kernel<SIMPLE>), pw_grid(a, 16, 16), dim3(256), 0, 0, s, ("pwk_kernel<%d>", SIMPLE), a)
+    return pw_mode_of(a) != 0 ? PWK_GO(1) : PWK_GO(0);
+#undef PWK_GO
 }
 
 int yr_pw_launch_split(int shape, const PwArgs& a, hipStream_t s) {
-    switch (shape) {
-        case 0: return launch_split_cfg<4, 1, 4, 1>(a, s);
-        case 1: return launch_split_cfg<2, 2, 4, 1>(a, s);
-        case 2: return launch_split_cfg<2, 3, 4, 1>(a, s);
-        case 3: return launch_split_cfg<4, 2, 2, 2>(a, s);
-        case 4: return launch_split_cfg<2, 5, 4, 1>(a, s);
-        case 5: return launch_split_cfg<4, 3, 2, 2>(a, s);
-        case 6: return launch_split_cfg<4, 4, 2, 2>(a, s);
-        case 7: return launch_split_cfg<1, 1, 4, 1>(a, s);
-        case 8: return launch_split_cfg<1, 2, 4, 1>(a, s);
-        case 9: return launch_split_cfg<1, 3, 4, 1>(a, s);
-        case 10: return launch_split_cfg<1, 4, 4, 1>(a, s);
-        case 11: return launch_split_cfg<1, 5, 4, 1>(a, s);
-        case 12: return launch_split_cfg<1, 6, 4, 1>(a, s);
-        case 13: return launch_split_cfg<1, 8, 4, 1>(a, s);
-        default: yr_set_error("pointwise (split form): shape %d out of range", shape); return YR_ERR_ARG;
-    }
+    typedef int (*Fn)(const PwArgs&, hipStream_t);
+#define PWS_FN(PT, CT, WM, WN) launch_split_cfg<PT, CT, WM, WN>,
+    static const Fn fns[] = {PW_LDS_SHAPES(PWS_FN)};
+#undef PWS_FN
+    YR_REQUIRE(shape >= 0 && shape < PW_NLDS, "pointwise (split form): shape %d out of range", shape);
+    return fns[shape](a, s);
 }

@@ -297,8 +297,7 @@ __global__ __launch_bounds__(64 * pwt_waves(NK, ROWS, MODE)) void pwt_kernel(PwA
 
 template <int NK, int ROWS>
 static int launch_pwt(const PwArgs& a, PwtArgs& x, hipStream_t s) {
-    const bool simple = a.S.n == 1 && a.S.s[0].xform == YR_X_IDENTITY;
-    const int mode = !simple ? 0 : a.gate != nullptr ? 2 : 1;
+    const int mode = pw_mode_of(a);
     const int NW = pwt_waves(NK, ROWS, mode);
     x.ntiles = (a.M + 16 * ROWS - 1) / (16 * ROWS);
     // parts: the run of cout tiles of a workgroup must fit LDS (every part fetches the pixels again - from the L2)
@@ -313,30 +312,10 @@ static int launch_pwt(const PwArgs& a, PwtArgs& x, hipStream_t s) {
     if (x.nwg > cus) x.nwg = cus;
     const size_t lds = (size_t)((x.T + cs - 1) / cs) * (NK * 2048 + 128);
     YR_REQUIRE(lds <= 160 * 1024 && (x.T + cs - 1) / cs <= 32, "pointwise (pixel-stationary form): %d tiles of %d chunks do not fit LDS", x.T, NK);
-    static char nm[3][40];
-    static const int nm_len = snprintf(nm[0], sizeof(nm[0]), "pwt_kernel<%d,%d,0>", NK, ROWS) + snprintf(nm[1], sizeof(nm[1]), "pwt_kernel<%d,%d,1>", NK, ROWS) +
-                              snprintf(nm[2], sizeof(nm[2]), "pwt_kernel<%d,%d,2>", NK, ROWS);
-    (void)nm_len;
-    yr_note_kernel(nm[mode]);
     const dim3 grid((unsigned)(x.nwg * cs));
-#define PWT_GO(MD)                                                                                                         \
-    {                                                                                                                      \
-        auto kern = pwt_kernel<NK, ROWS, MD>;                                                                              \
-        static bool attr_set[64] = {};                                                                                     \
-        int dev = 0;                                                                                                       \
-        (void)hipGetDevice(&dev);                                                                                          \
-        if (!attr_set[dev & 63]) {                                                                                         \
-            YR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));  \
-            attr_set[dev & 63] = true;                                                                                     \
-        }                                                                                                                  \
-        hipLaunchKernelGGL(kern, grid, dim3(64 * pwt_waves(NK, ROWS, MD)), lds, s, a, x);                                 \
-    }
-    if (mode == 0) PWT_GO(0)
-    else if (mode == 1) PWT_GO(1)
-    else PWT_GO(2)
+#define PWT_GO(MD) YR_LAUNCH((pwt_kernel<NK, ROWS, MD>), grid, dim3(64 * pwt_waves(NK, ROWS, MD)), lds, 160 * 1024, s, ("pwt_kernel<%d,%d,%d>", NK, ROWS, MD), a, x)
+    return mode == 0 ? PWT_GO(0) : mode == 1 ? PWT_GO(1) : PWT_GO(2);
 #undef PWT_GO
-    YR_LAUNCH_CHECK();
-    return YR_OK;
 }
 
 // chunk counts the form is built for (a k space in between runs the next one: its planes are padded with zero chunks by the compiler)
@@ -353,13 +332,12 @@ static int pwt_launch_images(const PwArgs& a, hipStream_t s) {
     YR_REQUIRE(nk > 0, "pointwise (pixel-stationary form): a k space of %d channels is beyond 16 chunks", a.S.kp);
     YR_REQUIRE(a.dw_w == nullptr && a.pre == nullptr && a.res == nullptr, "pointwise (pixel-stationary form): no depthwise-folded source, addend or residual");
     YR_REQUIRE(a.act == YR_ACT_NONE || a.act == YR_ACT_RELU6, "pointwise (pixel-stationary form): activation %d (none and ReLU6 only)", a.act);
-    for (int i = 0; i < a.S.n; ++i)
-        YR_REQUIRE(a.S.s[i].xform != YR_X_MAXPOOL2 && a.S.s[i].xform != YR_X_MAXPOOL4, "pointwise (pixel-stationary form): no pooled source");
+    YR_REQUIRE(!pw_any_pooled(a.S), "pointwise (pixel-stationary form): no pooled source");
     PwtArgs x;
     x.TA = (a.N + 15) / 16;
     x.planes = a.wt; x.T = x.TA + (a.out2 ? (a.N2 + 15) / 16 : 0);
     x.quad = a.pool || (a.out2 && a.pool2);
-    if (a.out2) YR_REQUIRE(a.S.n == 1 && a.S.s[0].xform == YR_X_IDENTITY, "pointwise (pixel-stationary form): two outputs need a single identity source");
+    if (a.out2) YR_REQUIRE(pw_mode_of(a) != 0, "pointwise (pixel-stationary form): two outputs need a single identity source");
     if (a.out2) YR_REQUIRE(a.act2 == YR_ACT_NONE || a.act2 == YR_ACT_RELU6, "pointwise (pixel-stationary form): activation %d of the second output", a.act2);
     if (x.quad) YR_REQUIRE(a.H % 2 == 0 && a.W % 2 == 0, "pointwise (pixel-stationary form): a pooled output needs an even map");
     x.plane_bytes = (unsigned)x.T * (unsigned)nk * 2048u;

@@ -1,4 +1,12 @@
-// Shared by pointwise.hip (direct kernel + dispatcher) and pointwise_lds.hip (LDS-staged kernel).
+// What the pointwise (1x1 conv) family shares, each rule stated once - float32: pointwise.hip (direct kernel + dispatcher),
+// pointwise_lds.hip (LDS-staged kernel), pointwise_split.hip / pointwise_stream.hip through pws_common.h; 16-bit: pointwise_h.hip,
+// pointwise_hs.hip, pointwise_hq.hip through pwh_common.h; headblock.hip on top.
+//   device: PwArgs, the epilogue of an accumulator quad (pw_finish_quad and its loads), the activation row objects PwRow / PwDwRow
+//           with their gathers (pw_source_row: xform -> source pixel; PW_PICK: the four-way pick of a per-source field), the k-tail
+//           clamp pw_kclamp, the 2 x 2 maximum across lanes pw_pool4, the BatchNorm rows of a tile to LDS pw_bn_to_lds;
+//   host:   pw_mode_of / pw_mode (the source mode of an op and the gate error), pw_any_pooled, pw_grid, PW_BY_MODE (one launch per
+//           source mode, each instantiation stated once: YR_LAUNCH in yr_common.h), the lists of tile shapes PW_LDS_SHAPES /
+//           PW_DIRECT_SHAPES from which the dispatchers, the heuristic's table and the shape counts are generated.
 #pragma once
 #include <type_traits>
 #include <utility>
@@ -66,11 +74,26 @@ __device__ __forceinline__ int pw_pixel_of_row(const PwArgs& a, int m) {
 
 // MaxPooling2D(2) of the finished (BN + activation) values across the four lanes of a pooling window; lane
 // (row & 3) == 0 then owns the result, which goes to pooled pixel row >> 2.
-__device__ __forceinline__ void pw_pool4(float (&v)[4]) {
+template <int N>
+__device__ __forceinline__ void pw_pool4(float (&v)[N]) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
+    for (int r = 0; r < N; ++r) {
         v[r] = fmaxf(v[r], __shfl_xor(v[r], 1));
         v[r] = fmaxf(v[r], __shfl_xor(v[r], 2));
+    }
+}
+
+// The k tail: a vector of V channels at raw k beyond the padded k space re-reads the last one (the activations it meets are zeroed).
+template <int V>
+__device__ __forceinline__ int pw_kclamp(int kraw, int kp) { return kraw < kp ? kraw : kp - V; }
+
+// The tile's BatchNorm scale | shift of couts n0 .. n0 + BN - 1 to LDS, ss[2 BN] (couts beyond N repeat the last one; a null
+// vector: 1 / 0): fetched in the epilogue they would cost every tile an L2 round trip with nothing left to hide it.
+__device__ __forceinline__ void pw_bn_to_lds(const float* scale, const float* shift, int N, int n0, int BN, int tid, float* ss) {
+    if (tid < BN) {
+        const int n = n0 + tid < N ? n0 + tid : N - 1;
+        ss[tid] = scale ? scale[n] : 1.f;
+        ss[BN + tid] = shift ? shift[n] : 0.f;
     }
 }
 
@@ -148,20 +171,28 @@ __device__ __forceinline__ void pw_finish_quad(const PwArgs& a, const f32x4& acc
 // loads of two array slots into ONE load with a selected address, which pins the array in scratch memory and puts
 // a scratch round trip in front of every activation load.
 static_assert(YR_MAX_SRC == 4, "PwRow spells out four sources");
+// row of source d (elements of type E behind the type-erased pointer) that conv pixel (b, y, x) reads: the xform folded in
+template <class E>
+__device__ __forceinline__ const E* pw_source_row(const DSrc& d, int b, int y, int x) {
+    int sy = y, sx = x;
+    if (d.xform == YR_X_UP2) { sy = y >> 1; sx = x >> 1; }
+    else if (d.xform == YR_X_MAXPOOL2) { sy = y * 2; sx = x * 2; }
+    else if (d.xform == YR_X_MAXPOOL4) { sy = y * 4; sx = x * 4; }
+    return reinterpret_cast<const E*>(d.ptr) + ((size_t)(b * d.h + sy) * d.w + sx) * d.ld;
+}
+// a per-source int picked by the k segment (at1 .. at3: k lies at or beyond source 1 .. 3): every candidate is first made an opaque
+// VALUE (readfirstlane) - a select between two loads of kernel-argument fields is otherwise folded into ONE load from a selected
+// address, a per-lane global load of the argument block
+#define PW_PICK(name, e0, e1, e2, e3)                                                                   \
+    const int name##0 = __builtin_amdgcn_readfirstlane(e0), name##1 = __builtin_amdgcn_readfirstlane(e1), \
+              name##2 = __builtin_amdgcn_readfirstlane(e2), name##3 = __builtin_amdgcn_readfirstlane(e3); \
+    const int name = at3 ? name##3 : at2 ? name##2 : at1 ? name##1 : name##0;
 template <int MODE>
 struct PwRow {
     const float* arow;               // MODE != 0: the pixel's contiguous row
     const float* grow;               // MODE == 2: SE gate row of the pixel's image
     const float *s0, *s1, *s2, *s3;  // MODE == 0: per-source row pointer (xform folded in)
     bool valid;
-
-    static __device__ __forceinline__ const float* source_row(const DSrc& d, int b, int y, int x) {
-        int sy = y, sx = x;
-        if (d.xform == YR_X_UP2) { sy = y >> 1; sx = x >> 1; }
-        else if (d.xform == YR_X_MAXPOOL2) { sy = y * 2; sx = x * 2; }
-        else if (d.xform == YR_X_MAXPOOL4) { sy = y * 4; sx = x * 4; }
-        return d.ptr + ((size_t)(b * d.h + sy) * d.w + sx) * d.ld;
-    }
 
     __device__ __forceinline__ void init(const PwArgs& a, int m) {
         valid = m < a.M;
@@ -175,10 +206,10 @@ struct PwRow {
         } else {
             const int rem = mm - b * hw;
             const int y = rem / a.W, x = rem - y * a.W;
-            s0 = source_row(a.S.s[0], b, y, x) - a.S.s[0].kbase;  // pre-offset: channel k of the conv is s_i[k]
-            s1 = source_row(a.S.s[1], b, y, x) - a.S.s[1].kbase;
-            s2 = source_row(a.S.s[2], b, y, x) - a.S.s[2].kbase;
-            s3 = source_row(a.S.s[3], b, y, x) - a.S.s[3].kbase;
+            s0 = pw_source_row<float>(a.S.s[0], b, y, x) - a.S.s[0].kbase;  // pre-offset: channel k of the conv is s_i[k]
+            s1 = pw_source_row<float>(a.S.s[1], b, y, x) - a.S.s[1].kbase;
+            s2 = pw_source_row<float>(a.S.s[2], b, y, x) - a.S.s[2].kbase;
+            s3 = pw_source_row<float>(a.S.s[3], b, y, x) - a.S.s[3].kbase;
         }
     }
 
@@ -190,10 +221,10 @@ struct PwRow {
         if (MODE != 0) {
             arow = a.S.s[0].ptr + ((size_t)(b * a.H + y) * a.W + x) * a.S.s[0].ld;
         } else {
-            s0 = source_row(a.S.s[0], b, y, x) - a.S.s[0].kbase;
-            s1 = source_row(a.S.s[1], b, y, x) - a.S.s[1].kbase;
-            s2 = source_row(a.S.s[2], b, y, x) - a.S.s[2].kbase;
-            s3 = source_row(a.S.s[3], b, y, x) - a.S.s[3].kbase;
+            s0 = pw_source_row<float>(a.S.s[0], b, y, x) - a.S.s[0].kbase;
+            s1 = pw_source_row<float>(a.S.s[1], b, y, x) - a.S.s[1].kbase;
+            s2 = pw_source_row<float>(a.S.s[2], b, y, x) - a.S.s[2].kbase;
+            s3 = pw_source_row<float>(a.S.s[3], b, y, x) - a.S.s[3].kbase;
         }
     }
 
@@ -207,7 +238,7 @@ struct PwRow {
     // TAPS: how many taps of a 4 x 4 window are in flight at once (1: one after the other)
     template <bool POOLS = true, int TAPS = 1>
     __device__ __forceinline__ void issue(const PwArgs& a, int kraw, int kp, float4& v, float4& gt, int& cv) const {
-        const int k = kraw < kp ? kraw : kp - 4;
+        const int k = pw_kclamp<4>(kraw, kp);
         int cvalid;
         if (MODE != 0) {
             v = *reinterpret_cast<const float4*>(arow + k);
@@ -218,17 +249,13 @@ struct PwRow {
             // per lane is first made an opaque VALUE (empty asm / readfirstlane): a select between two loads (of
             // stack slots or of kernel-argument fields) is otherwise folded into ONE load from a selected address -
             // scratch traffic for the pointers, a per-lane global load of the argument block for the fields.
-            const bool g1 = k >= a.S.s[1].kbase, g2 = k >= a.S.s[2].kbase, g3 = k >= a.S.s[3].kbase;
+            const bool at1 = k >= a.S.s[1].kbase, at2 = k >= a.S.s[2].kbase, at3 = k >= a.S.s[3].kbase;
             const float *p0 = s0, *p1 = s1, *p2 = s2, *p3 = s3;  // pre-offset by -kbase (init)
             asm("" : "+v"(p0));
             asm("" : "+v"(p1));
             asm("" : "+v"(p2));
             asm("" : "+v"(p3));
-            const float* rp = g3 ? p3 : g2 ? p2 : g1 ? p1 : p0;
-#define PW_PICK(name, e0, e1, e2, e3)                                                                   \
-    const int name##0 = __builtin_amdgcn_readfirstlane(e0), name##1 = __builtin_amdgcn_readfirstlane(e1), \
-              name##2 = __builtin_amdgcn_readfirstlane(e2), name##3 = __builtin_amdgcn_readfirstlane(e3); \
-    const int name = g3 ? name##3 : g2 ? name##2 : g1 ? name##1 : name##0;
+            const float* rp = at3 ? p3 : at2 ? p2 : at1 ? p1 : p0;
             PW_PICK(kend, a.S.s[0].kbase + a.S.s[0].c, a.S.s[1].kbase + a.S.s[1].c, a.S.s[2].kbase + a.S.s[2].c,
                     a.S.s[3].kbase + a.S.s[3].c)
             cvalid = kend - k;
@@ -243,7 +270,6 @@ struct PwRow {
                 PW_PICK(sldp, a.S.s[0].ld, a.S.s[1].ld, a.S.s[2].ld, a.S.s[3].ld)
                 xf = xfp; sw = swp; sld = sldp;
             }
-#undef PW_PICK
             if (!POOLS) {
             } else if (xf == YR_X_MAXPOOL2) {  // pooled sources are reduced here (the only path that waits at issue):
                 // the three other taps are issued together - ONE round trip, not one per tap (sld % 4 == 0)
@@ -313,7 +339,7 @@ struct PwDwRow {
     }
 
     __device__ __forceinline__ void issue(const PwArgs& a, int kraw, int kp, float4 (&v)[9], int& cv) const {
-        const int k = kraw < kp ? kraw : kp - 4;
+        const int k = pw_kclamp<4>(kraw, kp);
 #pragma unroll
         for (int t = 0; t < 9; ++t) v[t] = *reinterpret_cast<const float4*>(img + off[t] + k);
         cv = (valid && kraw < kp) ? a.S.s[0].c - k : 0;
@@ -352,8 +378,44 @@ __device__ __forceinline__ float4 pw_finish(float4 v, const float4& gt, int cval
     return v;
 }
 
-// LDS-staged kernel, tile shape index 0..13: (BM x BN) = 256x16, 128x32, 128x48, 128x64, 128x80, 128x96, 128x128,
-// 64x16, 64x32, 64x48, 64x64, 64x80, 64x96, 64x128
+// ---- host side: what every launcher of the family asks of an op ----------------------------------------------------
+// The source mode (MODE of PwRow / PwhRow): 1 = one identity source, 2 = the same with an SE gate, 0 = the generic gather.
+// `simple` is mode != 0.  pw_mode also refuses the gate on a gathered source; the forms that fall back instead ask pw_mode_of.
+static inline int pw_mode_of(const PwArgs& a) { return (a.S.n == 1 && a.S.s[0].xform == YR_X_IDENTITY) ? (a.gate ? 2 : 1) : 0; }
+static inline int pw_mode(const PwArgs& a, int* mode) {
+    *mode = pw_mode_of(a);
+    YR_REQUIRE(*mode != 0 || !a.gate, "pointwise: an SE gate needs one identity source");
+    return YR_OK;
+}
+// a source is read through a 2 x 2 or 4 x 4 maximum (unused slots repeat source 0: yr_make_srcset)
+static inline bool pw_any_pooled(const DSrcSet& S) {
+    bool pooled = false;
+    for (int i = 0; i < YR_MAX_SRC; ++i) pooled |= S.s[i].xform == YR_X_MAXPOOL2 || S.s[i].xform == YR_X_MAXPOOL4;
+    return pooled;
+}
+// one workgroup per BM x BN output tile, cout tile fastest (the kernels undo the 1-D index: yr_xcd_swizzle)
+static inline dim3 pw_grid(const PwArgs& a, int BM, int BN) { return dim3((unsigned)((a.M + BM - 1) / BM) * (unsigned)((a.N + BN - 1) / BN)); }
+// GO(MODE) for the op's source mode: a launcher defines GO as the YR_LAUNCH of its kernel with MODE among the template arguments
+#define PW_BY_MODE(mode, GO) ((mode) == 1 ? GO(1) : (mode) == 2 ? GO(2) : GO(0))
+
+// ---- THE TILE SHAPES of the float32 kernels, index = position in the list (the tuner's op.k - 1).
+// LDS-staged kernels (pw_kernel, pws_kernel), X(PT, CT, WM, WN): BM = 16 PT WM rows x BN = 16 CT WN couts -
+//   256x16, 128x32, 128x48, 128x64, 128x80, 128x96, 128x128, 64x16, 64x32, 64x48, 64x64, 64x80, 64x96, 64x128
+#define PW_LDS_SHAPES(X)                                                                                   \
+    X(4, 1, 4, 1) X(2, 2, 4, 1) X(2, 3, 4, 1) X(4, 2, 2, 2) X(2, 5, 4, 1) X(4, 3, 2, 2) X(4, 4, 2, 2)      \
+    X(1, 1, 4, 1) X(1, 2, 4, 1) X(1, 3, 4, 1) X(1, 4, 4, 1) X(1, 5, 4, 1) X(1, 6, 4, 1) X(1, 8, 4, 1)
+// ... then the direct (LDS-free) kernel pwd_kernel, X(PT, CT): BM = 64 PT, BN = 16 CT
+#define PW_DIRECT_SHAPES(X)                                                                                \
+    X(1, 1) X(1, 2) X(1, 3) X(1, 4) X(1, 5) X(1, 6) X(1, 8) X(2, 2) X(2, 3) X(2, 4) X(2, 5) X(2, 6) X(4, 2) X(4, 3) X(4, 4)
+#define PW_COUNT(...) +1
+constexpr int PW_NLDS = 0 PW_LDS_SHAPES(PW_COUNT);   // the first PW_NLDS indices are the LDS-staged shapes (the heuristic ranks only those)
+// a depthwise-folded source (YR_X_DW3) is built for the 64-row shapes with 3 .. 8 cout tiles, indices 9 .. 13; any other request
+// takes the narrowest of them that covers N
+static inline int pw_dw_shape(int shape, int N) {
+    return (shape >= 9 && shape <= 13) ? shape : N <= 48 ? 9 : N <= 64 ? 10 : N <= 80 ? 11 : N <= 96 ? 12 : 13;
+}
+
+// LDS-staged kernel, tile shape index 0 .. PW_NLDS - 1 (PW_LDS_SHAPES)
 int yr_pw_launch_lds(int shape, const PwArgs& a, hipStream_t s);
 // the same tile shapes on the 16-bit matrix pipe with float32-grade operands (pointwise_split.hip: two float16 planes per operand)
 int yr_pw_launch_split(int shape, const PwArgs& a, hipStream_t s);

@@ -1,8 +1,17 @@
 // 16-bit pointwise GEMM: what pointwise_h.hip (direct / walking / LDS-tiled forms) and pointwise_hs.hip / pointwise_hq.hip
-// (activation-stationary and all-couts k-streaming forms) share - operand types, the MFMA wrapper, the activation row
-// object with its gathers, the accumulator-octet epilogue.
+// (activation-stationary and all-couts k-streaming forms) share on top of pw_common.h (source mode, pooled predicate, grid, launch
+// tail) - operand types, the MFMA wrapper, the activation row object with its gathers, the accumulator-octet epilogue, the
+// bf16 / f16 dispatch of a launcher template (PWH_BY_DTYPE).
 #pragma once
 #include "pw_common.h"
+
+// fn<yr_bf16 | yr_f16>(args...) by the op's 16-bit element type; any other dtype: `other` (pwh_bad_dtype, or YR_NOT_TAKEN in the
+// forms that fall back)
+#define PWH_BY_DTYPE(dt, other, fn, ...) ((dt) == YR_BF16 ? fn<yr_bf16>(__VA_ARGS__) : (dt) == YR_F16 ? fn<yr_f16>(__VA_ARGS__) : (other))
+static inline int pwh_bad_dtype(int dtype) {
+    yr_set_error("pointwise: dtype %d is not a 16-bit type", dtype);
+    return YR_ERR_ARG;
+}
 
 template <class T> using pwh_v8 = T __attribute__((ext_vector_type(8)));
 typedef float pwh_f8 __attribute__((ext_vector_type(8)));
@@ -47,14 +56,6 @@ struct PwhRow {
     const T *s0, *s1, *s2, *s3;   // MODE == 0: per-source row pointer (xform folded in), pre-offset by -kbase
     bool valid;
 
-    static __device__ __forceinline__ const T* source_row(const DSrc& d, int b, int y, int x) {
-        int sy = y, sx = x;
-        if (d.xform == YR_X_UP2) { sy = y >> 1; sx = x >> 1; }
-        else if (d.xform == YR_X_MAXPOOL2) { sy = y * 2; sx = x * 2; }
-        else if (d.xform == YR_X_MAXPOOL4) { sy = y * 4; sx = x * 4; }
-        return reinterpret_cast<const T*>(d.ptr) + ((size_t)(b * d.h + sy) * d.w + sx) * d.ld;
-    }
-
     __device__ __forceinline__ void init(const PwArgs& a, int m) {
         valid = m < a.M;
         const int mm = pw_pixel_of_row(a, valid ? m : 0);
@@ -67,10 +68,10 @@ struct PwhRow {
         } else {
             const int rem = mm - b * hw;
             const int y = rem / a.W, x = rem - y * a.W;
-            s0 = source_row(a.S.s[0], b, y, x) - a.S.s[0].kbase;
-            s1 = source_row(a.S.s[1], b, y, x) - a.S.s[1].kbase;
-            s2 = source_row(a.S.s[2], b, y, x) - a.S.s[2].kbase;
-            s3 = source_row(a.S.s[3], b, y, x) - a.S.s[3].kbase;
+            s0 = pw_source_row<T>(a.S.s[0], b, y, x) - a.S.s[0].kbase;
+            s1 = pw_source_row<T>(a.S.s[1], b, y, x) - a.S.s[1].kbase;
+            s2 = pw_source_row<T>(a.S.s[2], b, y, x) - a.S.s[2].kbase;
+            s3 = pw_source_row<T>(a.S.s[3], b, y, x) - a.S.s[3].kbase;
         }
     }
 
@@ -79,7 +80,7 @@ struct PwhRow {
     // reads a loaded register and the main load is unconditional (see pw_common.h for why).
     template <bool POOLS = true>
     __device__ __forceinline__ void issue(const PwArgs& a, int kraw, int kp, pwh_u4& v, float4& g0, float4& g1, int& cv) const {
-        const int k = kraw < kp ? kraw : kp - 8;
+        const int k = pw_kclamp<8>(kraw, kp);
         int cvalid;
         if (MODE != 0) {
             v = *reinterpret_cast<const pwh_u4*>(arow + k);
@@ -89,26 +90,22 @@ struct PwhRow {
                 g1 = *reinterpret_cast<const float4*>(grow + k + 4);
             }
         } else {
-            const bool q1 = k >= a.S.s[1].kbase, q2 = k >= a.S.s[2].kbase, q3 = k >= a.S.s[3].kbase;
+            const bool at1 = k >= a.S.s[1].kbase, at2 = k >= a.S.s[2].kbase, at3 = k >= a.S.s[3].kbase;
             const T *p0 = s0, *p1 = s1, *p2 = s2, *p3 = s3;
             asm("" : "+v"(p0));
             asm("" : "+v"(p1));
             asm("" : "+v"(p2));
             asm("" : "+v"(p3));
-            const T* rp = q3 ? p3 : q2 ? p2 : q1 ? p1 : p0;
-#define PWH_PICK(name, e0, e1, e2, e3)                                                                  \
-    const int name##0 = __builtin_amdgcn_readfirstlane(e0), name##1 = __builtin_amdgcn_readfirstlane(e1), \
-              name##2 = __builtin_amdgcn_readfirstlane(e2), name##3 = __builtin_amdgcn_readfirstlane(e3); \
-    const int name = q3 ? name##3 : q2 ? name##2 : q1 ? name##1 : name##0;
-            PWH_PICK(kend, a.S.s[0].kbase + a.S.s[0].c, a.S.s[1].kbase + a.S.s[1].c, a.S.s[2].kbase + a.S.s[2].c,
-                     a.S.s[3].kbase + a.S.s[3].c)
+            const T* rp = at3 ? p3 : at2 ? p2 : at1 ? p1 : p0;
+            PW_PICK(kend, a.S.s[0].kbase + a.S.s[0].c, a.S.s[1].kbase + a.S.s[1].c, a.S.s[2].kbase + a.S.s[2].c,
+                    a.S.s[3].kbase + a.S.s[3].c)
             cvalid = kend - k;
             const pwh_gu4* q = (const pwh_gu4*)(rp + k);
             v = q[0];
             if (POOLS) {
-                PWH_PICK(xf, a.S.s[0].xform, a.S.s[1].xform, a.S.s[2].xform, a.S.s[3].xform)
-                PWH_PICK(sw, a.S.s[0].w, a.S.s[1].w, a.S.s[2].w, a.S.s[3].w)
-                PWH_PICK(sld, a.S.s[0].ld, a.S.s[1].ld, a.S.s[2].ld, a.S.s[3].ld)
+                PW_PICK(xf, a.S.s[0].xform, a.S.s[1].xform, a.S.s[2].xform, a.S.s[3].xform)
+                PW_PICK(sw, a.S.s[0].w, a.S.s[1].w, a.S.s[2].w, a.S.s[3].w)
+                PW_PICK(sld, a.S.s[0].ld, a.S.s[1].ld, a.S.s[2].ld, a.S.s[3].ld)
                 if (xf == YR_X_MAXPOOL2) {  // the three other taps are issued together (sld % 8 == 0: whole 16-byte steps)
                     const pwh_u4 v1 = q[sld >> 3], v2 = q[((size_t)sw * sld) >> 3], v3 = q[(((size_t)sw + 1) * sld) >> 3];
                     v = pwh_max<T>(pwh_max<T>(v, v1), pwh_max<T>(v2, v3));
@@ -117,7 +114,6 @@ struct PwhRow {
                         for (int dx = 0; dx < 4; ++dx) v = pwh_max<T>(v, q[(((size_t)dy * sw + dx) * sld) >> 3]);
                 }
             }
-#undef PWH_PICK
         }
         cv = (valid && kraw < kp) ? cvalid : 0;
     }
@@ -178,11 +174,7 @@ __device__ __forceinline__ void pwh_finish_oct(const PwArgs& a, const f32x4& lo,
     int orow = m;
     bool keep = m < a.M && cnt > 0;
     if (a.pool) {  // uniform: MaxPooling2D(2) across the 4 adjacent lanes of a window
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            v[r] = fmaxf(v[r], __shfl_xor(v[r], 1));
-            v[r] = fmaxf(v[r], __shfl_xor(v[r], 2));
-        }
+        pw_pool4(v);
         keep = keep && (li & 3) == 0;
         orow = m >> 2;
     }
@@ -288,11 +280,7 @@ __device__ __forceinline__ void pwh_finish_oct_b(const PwArgs& a, yr_rsrc out, c
     int orow = m;
     bool keep = m < a.M && cnt > 0;
     if (a.pool) {  // uniform
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            v[r] = fmaxf(v[r], __shfl_xor(v[r], 1));
-            v[r] = fmaxf(v[r], __shfl_xor(v[r], 2));
-        }
+        pw_pool4(v);
         keep = keep && (li & 3) == 0;
         orow = m >> 2;
     }

@@ -1,6 +1,8 @@
 // The k loop of the SPLIT pointwise GEMM (float32 operands as two float16 planes on v_mfma_f32_16x16x32_f16; see
 // pointwise_split.hip for the arithmetic), shared by pws_kernel and the head-block kernel (headblock.hip): global fetch through
 // PwRow (gathers, concat, up-sampling, pooling, SE gate) -> planes cut on the way into LDS -> fragments -> three MFMAs per tile.
+// The rules it shares with the rest of the pointwise family are stated in pw_common.h (k-tail clamp pw_kclamp, BatchNorm rows to LDS
+// pw_bn_to_lds, source mode, grid, launch tail) and yr_common.h (yr_cut2, the 2^-11 join yr_split_join).
 #pragma once
 #include <type_traits>
 
@@ -66,7 +68,7 @@ __device__ __forceinline__ void pws_k_loop(const PwArgs& a, PwRow<MODE> (&row)[A
         };
         auto fetch = [&](int k0, Regs& R) __attribute__((always_inline)) {
             const int kraw = k0 + kq * 4;
-            const int k = kraw < kp ? kraw : kp - 4;
+            const int k = pw_kclamp<4>(kraw, kp);
             pw_unroll<A_PASSES>([&](auto P) __attribute__((always_inline)) {
                 constexpr int p = decltype(P)::value;
                 row[p].template issue<POOLS, TAPS>(a, kraw, kp, R.ra[p][0], R.rg[p], R.cv[p]);

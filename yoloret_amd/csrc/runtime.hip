@@ -392,6 +392,20 @@ extern "C" int yr_set_tuning(yr_handle* h, int batch, const int32_t* cfg, int n)
     return YR_OK;
 }
 
+// How a tuned value (an entry of a tuning table, the tuner's best so far) is merged into op.k - for every kind that is tuned.
+static void apply_tuning(yr_op& op, int cfg) {
+    if (op.kind == YR_OP_POINTWISE) {
+        op.k = cfg;   // 1 + tile shape index, 0: the heuristic
+    } else if (op.kind == YR_OP_MBH || op.kind == YR_OP_MBX) {   // the tuned output tile (YR_MBH_TH_MASK | YR_MBH_TW_MASK) rides in the upper bytes of k
+        op.k = (op.k & YR_MBH_K_MASK) | cfg;
+    } else if (op.kind == YR_OP_MBR || op.kind == YR_OP_MBE) {   // (YR_MBR_NW_MASK | YR_MBR_SEGS_MASK: the tuned walk geometry)
+        if (cfg == 0 || (op.k & YR_MBR_STREAM)) return;          // (the weight-streaming form: its geometry is the plan's)
+        // the SPLIT form's fragments are packed for the plan's nw (compiler.mbs_pack): only the row segments are tunable there
+        if (op.k & YR_MBR_SPLIT) op.k = (op.k & (YR_MBR_FORM_MASK | YR_MBR_NW_MASK)) | (cfg & YR_MBR_SEGS_MASK);
+        else op.k = (op.k & YR_MBR_FORM_MASK) | cfg;
+    }
+}
+
 static int resolve_op(const yr_handle* h, size_t i, int batch, float* const ext[4], char* ws, yr_op* out) {
     yr_op op = h->ops[i];
     auto bufptr = [&](int32_t b) -> void* {
@@ -410,20 +424,9 @@ static int resolve_op(const yr_handle* h, size_t i, int batch, float* const ext[
     op.wgt = wptr(op.wgt_off); op.scale = wptr(op.scale_off); op.shift = wptr(op.shift_off);
     op.wgt2 = wptr(op.wgt2_off); op.b1 = wptr(op.b1_off); op.b2 = wptr(op.b2_off);
     if (op.out == nullptr) { yr_set_error("op %zu writes a null external buffer", i); return YR_ERR_ARG; }
-    if (op.kind == YR_OP_POINTWISE) {
-        auto it = h->tuned.find(batch);
-        op.k = it != h->tuned.end() ? it->second[i] : 0;
-    } else if (op.kind == YR_OP_MBH || op.kind == YR_OP_MBX) {   // the tuned output tile (YR_MBH_TH_MASK | YR_MBH_TW_MASK) rides in the upper bytes of k
-        auto it = h->tuned.find(batch);
-        if (it != h->tuned.end()) op.k = (op.k & YR_MBH_K_MASK) | it->second[i];
-    } else if (op.kind == YR_OP_MBR || op.kind == YR_OP_MBE) {   // (YR_MBR_NW_MASK | YR_MBR_SEGS_MASK: the tuned walk geometry)
-        auto it = h->tuned.find(batch);
-        if (it != h->tuned.end() && it->second[i] != 0 && !(op.k & YR_MBR_STREAM)) {   // (the weight-streaming form: its geometry is the plan's)
-            // the SPLIT form's fragments are packed for the plan's nw (compiler.mbs_pack): only the row segments are tunable there
-            if (op.k & YR_MBR_SPLIT) op.k = (op.k & (YR_MBR_FORM_MASK | YR_MBR_NW_MASK)) | (it->second[i] & YR_MBR_SEGS_MASK);
-            else op.k = (op.k & YR_MBR_FORM_MASK) | it->second[i];
-        }
-    }
+    auto it = h->tuned.find(batch);
+    if (it != h->tuned.end()) apply_tuning(op, it->second[i]);
+    else if (op.kind == YR_OP_POINTWISE) op.k = 0;   // an untuned batch: the heuristic (a block keeps the plan's geometry)
     *out = op;
     return YR_OK;
 }
@@ -653,10 +656,7 @@ extern "C" int yr_autotune(yr_handle* h, const float* images, int batch, float* 
             if (have_prev) {
                 rc = resolve_op(h, i - 1, batch, ext, static_cast<char*>(workspace), &prev);
                 if (rc) break;
-                if (h->ops[i - 1].kind == YR_OP_POINTWISE) prev.k = best[i - 1];
-                else if (prev.kind == YR_OP_MBR && (prev.k & YR_MBR_STREAM)) {}
-                else if (best[i - 1] != 0 && (prev.k & YR_MBR_SPLIT)) prev.k = (prev.k & (YR_MBR_FORM_MASK | YR_MBR_NW_MASK)) | (best[i - 1] & YR_MBR_SEGS_MASK);
-                else if (best[i - 1] != 0) prev.k = (prev.k & YR_MBR_FORM_MASK) | best[i - 1];
+                apply_tuning(prev, best[i - 1]);
             }
             static const int segs_list[] = {0, 1, 2, 3, 4, 6, 8, 13, 18, 26};   // (13 .. 26: the few-image passes, where a strip's walk is the whole launch)
             const int base = op.k & (YR_MBR_FORM_MASK | YR_MBR_NW_MASK);     // 3 | nw: the workgroup shape the plan asks for
@@ -707,7 +707,7 @@ extern "C" int yr_autotune(yr_handle* h, const float* images, int batch, float* 
         if (i > 0 && !output_aliases_inputs_of(h, i, i - 1)) {
             rc = resolve_op(h, i - 1, batch, ext, static_cast<char*>(workspace), &prev);
             if (rc) break;
-            if (h->ops[i - 1].kind == YR_OP_POINTWISE) prev.k = best[i - 1];
+            if (prev.kind == YR_OP_POINTWISE) apply_tuning(prev, best[i - 1]);   // (a block in front of a pointwise op runs in the plan's geometry here, as it always has)
             have_prev = true;
         }
         auto time_in_context = [&](int c, float* ms) -> int {

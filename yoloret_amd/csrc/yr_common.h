@@ -30,6 +30,48 @@ void yr_note_kernel(const char* name);
 
 #define YR_LAUNCH_CHECK() YR_CHECK_HIP(hipGetLastError())
 
+#ifdef __HIPCC__
+// ---- THE LAUNCH TAIL of a template launcher: note the kernel's name, raise the kernel's dynamic LDS limit where the instantiation
+// asks for more than 48 KB - lds_max, the most any of its launches takes; once per device: a process that drives several GPUs needs
+// the attribute on each -, launch, check.
+template <auto KERN, class... KArgs>
+static int yr_launch(const char* name, dim3 grid, dim3 block, size_t lds, size_t lds_max, hipStream_t s, const KArgs&... kargs) {
+    yr_note_kernel(name);
+    if (lds_max > 48 * 1024) {
+        static bool attr_set_dev[64] = {};
+        int cur_dev = 0;
+        (void)hipGetDevice(&cur_dev);
+        bool& attr_set = attr_set_dev[cur_dev & 63];
+        if (!attr_set) {
+            YR_CHECK_HIP(hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+            attr_set = true;
+        }
+    }
+    hipLaunchKernelGGL(KERN, grid, block, lds, s, kargs...);
+    YR_LAUNCH_CHECK();
+    return YR_OK;
+}
+// ... and the name, spelled like the symbol and formatted ONCE per instantiation (a static of the launcher's instantiation):
+// YR_LAUNCH((kernel<args>), grid, block, lds, lds_max, stream, ("kernel<%d,%d>", args), kernel arguments...) is one launch of one
+// instantiation; a launcher that picks among instantiations wraps it in a macro of its own and states each one once (PW_BY_MODE).
+struct yr_kname { char s[64]; };
+static inline yr_kname yr_kname_fmt(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+static inline yr_kname yr_kname_fmt(const char* fmt, ...) {
+    yr_kname n;
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(n.s, sizeof(n.s), fmt, ap);
+    va_end(ap);
+    return n;
+}
+#define YR_UNPAREN(...) __VA_ARGS__
+#define YR_LAUNCH(KERN, grid, block, lds, lds_max, s, NAME, ...)                                   \
+    ([&]() -> int {                                                                                \
+        static const yr_kname nm_ = yr_kname_fmt NAME;                                             \
+        return yr_launch<YR_UNPAREN KERN>(nm_.s, grid, block, lds, lds_max, s, __VA_ARGS__);       \
+    }())
+#endif
+
 // per-kind launchers (defined in the .hip files); `op` holds device pointers.
 int yr_launch_stem(const yr_op& op, int batch, hipStream_t s);
 int yr_launch_pointwise(const yr_op& op, int batch, hipStream_t s);
@@ -192,6 +234,13 @@ __device__ __forceinline__ void yr_cut2(float x0, float x1, unsigned& h, unsigne
     //  plane (logit errors of 5e-4: the h plane alone).  A VALU or LDS consumer needs no wait: tools/cut_probe.hip.)
     asm("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(m) : "v"(h), "s"(c), "v"(xs[0]));
     asm("v_fma_mixhi_f16 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\ts_nop 1" : "+v"(m) : "v"(h), "s"(c), "v"(xs[1]));
+}
+
+// The join of a SPLIT form's two accumulators: acc holds the h h' products, ac1 the h m' + m h' ones, which weigh 2^-11.  An FMA by
+// name: the library is built without contraction.
+typedef float yr_f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ yr_f32x4 yr_split_join(yr_f32x4 acc, yr_f32x4 ac1) {
+    return __builtin_elementwise_fma(ac1, (yr_f32x4){0.00048828125f, 0.00048828125f, 0.00048828125f, 0.00048828125f}, acc);
 }
 
 // A buffer descriptor over `bytes` bytes at `base` (wave-uniform; raw, no swizzle) for the raw_buffer loads and stores, and the
