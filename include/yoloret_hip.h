@@ -899,6 +899,48 @@ int yr_wsum_backward(const float* dy, int dy_ld, const float* x0, int x0_ld, con
                      float* dx3 /*or null*/, int dx3_ld, float* dalpha /*device [4], or null*/,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the squeeze-excite block, forward and backward (yolo3/efficientnet.py:406-438: reduce_mean over the map, the 1x1 convolution
+ * <name>_se_reduce with bias, Swish, the 1x1 convolution <name>_se_expand with bias, sigmoid, Multiply; every MBConv of the EfficientNet
+ * backbones and of the six head blocks, yolo3/model.py:91-115, runs one with se_ratio 0.25); added under ABI 9 (additive).
+ * csrc/segrad.hip has the kernels' forms, tests/segrad_ref.py is the definition (the reference's backward is TensorFlow's tape: its
+ * rules for reduce_mean, Conv2D + bias, x sigmoid(x), sigmoid and Multiply, restated).  The conventions of the entries above hold:
+ * float32, maps [B][H][W][ld] with C <= ld channels taken (pad columns neither read nor written), 4-byte alignment, no float atomics,
+ * nothing read before the call wrote it, every named output element written and nothing else, the same call gives the same bytes.
+ * x, y, dy, dx are maps, N = H * W pixels an image; w1 [C][R] (the Keras kernel [1,1,C,R]), b1 [R], w2 [R][C], b2 [C], m [B][C],
+ * z1 [B][R], g [B][C], dw1, db1, dw2, db2 (the shapes of w1, b1, w2, b2) are dense.  B, H, W >= 1, B * H * W < 2^40, 1 <= C <= 4096,
+ * 1 <= R <= 1024; the workspace (device, 16-byte aligned, yr_se_workspace_bytes(B, H * W, C, R) bytes: enough for either call) may hold
+ * anything before the call.  YR_ERR_ARG, nothing written, for anything else, a null pointer where none is allowed, a leading dimension
+ * below C, byte offsets beyond 2^63, a short or misaligned workspace, some but not all of dw1, db1, dw2, db2.  Every operation is one
+ * IEEE float32 operation in this order, nothing contracted (the only fused multiply-adds are those inside the pinned exp of sigmoid):
+ *   forward   S[b][c] = sum_p x[b][p][c];  m = S / (float)N;  z1[b][r] = b1[r] + sum_c m[b][c] * w1[c][r];  h = z1 * sigmoid(z1)
+ *             (YR_ACT_SWISH of the forward kernels);  z2[b][c] = b2[c] + sum_r h[b][r] * w2[r][c];  g = sigmoid(z2);  y = x * g[b][c].
+ *             Writes y, m, z1, g.  3 launches.
+ *   backward  takes dy, x, w1, w2 and the forward's m, z1, g; h is recomputed from z1 by the forward's operations (the same bits).
+ *             dg[b][c] = sum_p dy[b][p][c] * x[b][p][c] (each term one rounded product, added by one rounded addition);  t = 1.0f - g;
+ *             u = g * t;  dz2 = dg * u;  dh[b][r] = sum_c dz2[b][c] * w2[r][c];  dz1 = dh * (sg * (1.0f + z1 * (1.0f - sg))),
+ *             sg = sigmoid(z1) (the Swish rule of yr_bn_act_backward);  dm[b][c] = sum_r dz1[b][r] * w1[c][r];  q = dm / (float)N;
+ *             dx = dy * g[b][c] + q[b][c] (a rounded product, then a rounded addition);  db2[c] = sum_b dz2[b][c];
+ *             dw2[r][c] = sum_b h[b][r] * dz2[b][c];  db1[r] = sum_b dz1[b][r];  dw1[c][r] = sum_b m[b][c] * dz1[b][r] - every sum
+ *             over the batch in increasing b, the first term image 0's own.  dx may be null: not computed, its map pass not launched.
+ *             dw1, db1, dw2, db2 are all given or all null: when null the batch sums are not computed.  4 launches, 3 with dx or the
+ *             parameters alone, none with neither.
+ * The orders of the sums.  A sum over the pixels has two stages: stage 1 gives every workgroup a contiguous range of
+ * yr_se_chunk(B, H * W, C) pixels of ONE image (a function of H * W and C only: an image alone is summed as inside a batch) and writes
+ * one [C] slab per range; within a range the pixels are dealt to PP = 256 / Cb lanes a channel in turn (Cb = ceil(C / ceil(C / 64))),
+ * a lane adds its terms in pixel order from +0, the lanes are added in order from +0; stage 2 adds an image's slabs in index order from
+ * +0.  The sums of the two 1x1 convolutions and of their backward are plain products and sums in the orders csrc/segrad.hip's header
+ * gives (`fc`: slices of the inputs in order, then bias + the slices in order; `fct`: 64 interleaved lane sums folded by halves).
+ * The two size entries return 0 for sizes the calls refuse. */
+long long yr_se_chunk(int B, long long N, int C);
+size_t    yr_se_workspace_bytes(int B, long long N, int C, int R);
+int yr_se_forward(const float* x, int x_ld, const float* w1 /*[C][R]*/, const float* b1 /*[R]*/, const float* w2 /*[R][C]*/,
+                  const float* b2 /*[C]*/, int B, int H, int W, int C, int R, float* y, int y_ld, float* m /*[B][C]*/,
+                  float* z1 /*[B][R]*/, float* g /*[B][C]*/, void* workspace, size_t workspace_bytes, void* stream);
+int yr_se_backward(const float* dy, int dy_ld, const float* x, int x_ld, const float* w1, const float* w2, const float* m,
+                   const float* z1, const float* g, int B, int H, int W, int C, int R, float* dx /*or null*/, int dx_ld,
+                   float* dw1 /*[C][R]*/, float* db1 /*[R]*/, float* dw2 /*[R][C]*/, float* db2 /*[C]; all four or none*/,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,9 @@ convolutions, depthwise convolutions and frozen BatchNorm + activation on top of
     weighted_sum(xs, alpha)                 the reference's WeightedSum of four maps, alpha float32 [4], differentiable in all five
     concat(xs)                              Keras Concatenate() over the channels
     rfcr_module(b1, b2, b3, b4, params, training=True), rfcr_parameters(model, device)   the RFCR module (model.py:146-168) of these
+    squeeze_excite(x, w1, b1, w2, b2)       the squeeze-excite block (efficientnet.py:406-438; csrc/segrad.hip): x [B, H, W, C], w1 [C, R],
+                                            b1 [R], w2 [R, C], b2 [C] -> x * sigmoid(swish(mean(x) w1 + b1) w2 + b2), differentiable in all five
+    head_block(x, params, training=True), head_block_parameters(model, name, device)   a head block (model.py:91-115) of these
 
 Written the way ``_YoloLossFunction`` of yolo3/model.py is: forward and backward are calls of the C entries, only what backward needs
 is saved, a gradient is computed only for an input that requires one (the others are None and their kernel is not launched).  float32
@@ -163,6 +166,26 @@ class _WeightedSum(torch.autograd.Function):
         return (dalpha,) + tuple(dxs)
 
 
+class _SqueezeExcite(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2):
+        b, h, w, c = x.shape
+        y, m, z1, g = rt.se_forward(x, w1, b1, w2, b2, workspace=_workspace(x.device, rt.se_workspace_bytes(b, h * w, c, w1.shape[1])))
+        ctx.save_for_backward(x, w1, w2, m, z1, g)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w1, w2, m, z1, g = ctx.saved_tensors
+        need_dx, need_params = ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:])
+        if not (need_dx or need_params):
+            return (None,) * 5
+        b, h, w, c = x.shape
+        dx, dw1, db1, dw2, db2 = rt.se_backward(_f32(dy), x, w1, w2, m, z1, g, need_dx=need_dx, need_params=need_params,
+                                                workspace=_workspace(x.device, rt.se_workspace_bytes(b, h * w, c, w1.shape[1])))
+        return (dx,) + tuple(gr if need else None for gr, need in zip((dw1, db1, dw2, db2), ctx.needs_input_grad[1:]))
+
+
 class _Concat(torch.autograd.Function):
     @staticmethod
     def forward(ctx, *xs):
@@ -251,6 +274,15 @@ def concat(xs):
     return _Concat.apply(*xs)
 
 
+def squeeze_excite(x, w1, b1, w2, b2):
+    """The squeeze-excite block (efficientnet.py:406-438): x [B, H, W, C]; w1 [C, R] and b1 [R], the Keras <name>_se_reduce kernel
+    [1, 1, C, R] reshaped and its bias; w2 [R, C] and b2 [C], <name>_se_expand -> x * g, g = sigmoid(swish(mean_hw(x) w1 + b1) w2 + b2),
+    differentiable in all five (``runtime.se_backward``).  Only x, w1, w2 and the three small tensors of the forward (the mean, the
+    reduced pre-activation and the gate) are saved; when no parameter requires a gradient the batch sums are skipped, when x does not,
+    the pass over the map that writes its gradient."""
+    return _SqueezeExcite.apply(x.contiguous(), w1.contiguous(), b1.contiguous(), w2.contiguous(), b2.contiguous())
+
+
 RFCR_BN_MOMENTUM, RFCR_BN_EPS = 0.99, 1e-3      # tf.keras.layers.BatchNormalization() as model.py:24,29 calls it: the Keras defaults
 RFCR_CONVS = ('rfcr_b1c', 'rfcr_b2c', 'rfcr_b3c', 'rfcr_b4c')
 RFCR_BNS = ('rfcr_sep_dw_BN', 'rfcr_sep_pw_BN')
@@ -305,3 +337,73 @@ def rfcr_module(b1, b2, b3, b4, params, training=True):
     bc = bn_relu6(depthwise(bc, p['rfcr_sep_dw'], 1, 'same'), RFCR_BNS[0])
     bc = bn_relu6(linear1x1(bc, p['rfcr_sep_pw']), RFCR_BNS[1])
     return concat([b1, maxpool(bc, 2)]), concat([b2, bc]), concat([b3, upsample2(bc)])
+
+
+HEAD_BLOCKS = ('td1', 'td2', 'td3', 'bu3', 'bu2', 'bu1')
+HEAD_BN_MOMENTUM, HEAD_BN_EPS = 0.99, 1e-3      # efficientnet.py's get_model_params defaults (batch_norm_momentum, batch_norm_epsilon)
+HEAD_CONVS = ('_conv', '_mb_project', '_y')
+HEAD_BNS = ('_conv_BN', '_mb_dw_BN', '_mb_project_BN')
+
+
+def head_block_parameters(model, name, device):
+    """The parameters of ``model``'s head block ``name`` (one of 'td1', 'td2', 'td3', 'bu3', 'bu2', 'bu1': ``yolov3_body``'s
+    make_last_layers_efficientnet_lite, model.py:91-115) as float32 tensors on ``device``, in the layouts the operators take ->
+    {key: tensor}, the keys without the block's name:
+        '_conv', '_mb_project', '_y'      Keras [1, 1, cin, cout] -> wt [cout, round_up(cin, 4)], pad columns 0
+        '_mb_dw'                          Keras [3, 3, F, 1] -> [9, F]
+        '_mb_se_reduce', '_mb_se_expand'  Keras [1, 1, F, R] -> [F, R] and [1, 1, R, F] -> [R, F]; '<se>/bias' [R] and [F]
+        '<bn>/gamma', '<bn>/beta', '<bn>/moving_mean', '<bn>/moving_variance' for <bn> in '_conv_BN', '_mb_dw_BN', '_mb_project_BN'
+    and 'name', the block's name (a string).  The top-down blocks 'td1' .. 'td3' have no '_y': with the PANet pass ``yolov3_body``
+    discards their y convolutions (model.py:240-241) and the model holds no such layer.  ``requires_grad`` is set on everything the reference trains (train.py:150-171 trains
+    all that lies behind the backbone); the moving statistics take no gradient: ``head_block(training=True)`` updates them in place."""
+    if name not in HEAD_BLOCKS:
+        raise ValueError('head_block_parameters: name must be one of %s, not %r' % (', '.join(HEAD_BLOCKS), name))
+    host = model.get_weights()
+    if host is None:
+        raise ValueError('head_block_parameters: the model has no weights (set_weights / load_weights)')
+
+    def dev(a, grad=True):
+        return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(device).requires_grad_(grad)
+    out = {'name': name}
+    for conv in HEAD_CONVS:
+        if conv == '_y' and name + '_y/kernel' not in host:      # a top-down block: yolov3_body discards its y (model.py:240-241)
+            continue
+        k = np.asarray(host[name + conv + '/kernel'], np.float32)
+        cin, cout = k.shape[-2], k.shape[-1]
+        wt = np.zeros((cout, (cin + 3) // 4 * 4), np.float32)
+        wt[:, :cin] = k.reshape(cin, cout).T
+        out[conv] = dev(wt)
+    dw = np.asarray(host[name + '_mb_dw/depthwise_kernel'], np.float32)
+    out['_mb_dw'] = dev(dw.reshape(dw.shape[0] * dw.shape[1], -1))
+    for se in ('_mb_se_reduce', '_mb_se_expand'):
+        k = np.asarray(host[name + se + '/kernel'], np.float32)
+        out[se] = dev(k.reshape(k.shape[-2], k.shape[-1]))
+        out[se + '/bias'] = dev(np.asarray(host[name + se + '/bias'], np.float32).reshape(-1))
+    for bn in HEAD_BNS:
+        for p, grad in (('gamma', True), ('beta', True), ('moving_mean', False), ('moving_variance', False)):
+            out['%s/%s' % (bn, p)] = dev(np.asarray(host['%s%s/%s' % (name, bn, p)], np.float32).reshape(-1), grad)
+    return out
+
+
+def head_block(x, params, training=True):
+    """A head block (model.py:91-115, make_last_layers_efficientnet_lite) on x [B, H, W, cin]; params: ``head_block_parameters``'
+    dictionary -> (x_out, y): the 1x1 convolution to F channels + BatchNorm + ReLU6; the MBConv with expand ratio 1 - depthwise 3 x 3
+    + BatchNorm + Swish, ``squeeze_excite``, the 1x1 projection to O channels + BatchNorm, no residual because F != O -; and
+    y = the 1x1 convolution '_y' of x_out (None for a top-down block, whose parameters hold no '_y').  training: the three BatchNorms run on the statistics of the batch and update their moving
+    statistics in place (``batchnorm_act``, momentum 0.99, eps 1e-3); otherwise they are folded (``fold_batchnorm`` +
+    ``frozen_bn_act``: no gradient for gamma and beta, one host synchronisation per BatchNorm).
+    The 1x1 operators take cin, cout <= 256 today, so 'bu3' (its input is td3's output, F = 128) runs for every model and 'td3'
+    where its concatenated input is at most 256 wide (MobileNetV2 x0.75: 128 + 24 + 96 = 248); the wider blocks raise
+    ``linear_forward``'s own error.  Lifting that cap is the linear entries' business, not this module's."""
+    p = params
+
+    def bn_act(z, bn, act):
+        stats = [p['%s/%s' % (bn, k)] for k in ('gamma', 'beta', 'moving_mean', 'moving_variance')]
+        if training:
+            return batchnorm_act(z, *stats, momentum=HEAD_BN_MOMENTUM, eps=HEAD_BN_EPS, act=act)
+        return frozen_bn_act(z, *fold_batchnorm(*stats, eps=HEAD_BN_EPS), act=act)
+    t = bn_act(linear1x1(x, p['_conv']), '_conv_BN', 'relu6')
+    t = bn_act(depthwise(t, p['_mb_dw'], 1, 'same'), '_mb_dw_BN', 'swish')
+    t = squeeze_excite(t, p['_mb_se_reduce'], p['_mb_se_reduce/bias'], p['_mb_se_expand'], p['_mb_se_expand/bias'])
+    x_out = bn_act(linear1x1(t, p['_mb_project']), '_mb_project_BN', None)
+    return x_out, (linear1x1(x_out, p['_y']) if '_y' in p else None)

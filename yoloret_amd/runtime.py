@@ -139,7 +139,8 @@ EXPORTS = ['yr_jpeg_workspace_bytes', 'yr_jpeg_roundtrip_batch', 'yr_augment_geo
            'yr_bn_act_forward', 'yr_bn_act_backward',
            'yr_bn_train_chunk', 'yr_bn_train_workspace_bytes', 'yr_bn_train_forward', 'yr_bn_train_backward',
            'yr_maxpool_forward', 'yr_maxpool_backward', 'yr_upsample2_forward', 'yr_upsample2_backward',
-           'yr_wsum_chunk', 'yr_wsum_workspace_bytes', 'yr_wsum_forward', 'yr_wsum_backward']
+           'yr_wsum_chunk', 'yr_wsum_workspace_bytes', 'yr_wsum_forward', 'yr_wsum_backward',
+           'yr_se_chunk', 'yr_se_workspace_bytes', 'yr_se_forward', 'yr_se_backward']
 
 _lib = None
 
@@ -263,6 +264,14 @@ def lib():
                                                                           ctypes.c_void_p]
         L.yr_wsum_backward.argtypes = [ctypes.c_void_p, ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int] + \
             [ctypes.c_void_p, ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        L.yr_se_chunk.restype = ctypes.c_longlong
+        L.yr_se_chunk.argtypes = [ctypes.c_int, ctypes.c_longlong, ctypes.c_int]
+        L.yr_se_workspace_bytes.restype = ctypes.c_size_t
+        L.yr_se_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_int]
+        L.yr_se_forward.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_int] + \
+            [ctypes.c_void_p] * 4 + [ctypes.c_size_t, ctypes.c_void_p]
+        L.yr_se_backward.argtypes = [ctypes.c_void_p, ctypes.c_int] * 2 + [ctypes.c_void_p] * 5 + [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_int] + \
+            [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p]
         if L.yr_abi_version() != ABI_VERSION:
             raise YoloretHipError('libyoloret_hip.so ABI version mismatch')
         L.yr_abi_sizeof.argtypes = [ctypes.c_int]
@@ -946,6 +955,88 @@ def wsum_backward(dy, xs, alpha, need=(True, True, True, True), need_alpha=True,
                                      _ptr(dxs[0]), c, _ptr(dxs[1]), c, _ptr(dxs[2]), c, _ptr(dxs[3]), c, _ptr(dalpha),
                                      _ptr(ws), ws.numel() if ws is not None else 0, stream_ptr(dev)))
     return dxs, dalpha
+
+
+# ----------------------------------------------------------------------------- the squeeze-excite block (csrc/segrad.hip)
+def se_chunk(b, n, c):
+    """Pixels of one image per workgroup of the first stage of ``se_forward``'s and ``se_backward``'s sums over the map: a function of
+    n = H * W and c only (b is checked: b * n < 2^40); 0: refused sizes."""
+    return int(lib().yr_se_chunk(int(b), int(n), int(c)))
+
+
+def se_workspace_bytes(b, n, c, r):
+    """Bytes of workspace that ``se_forward`` and ``se_backward`` need (the same for both; 0: refused sizes)."""
+    return int(lib().yr_se_workspace_bytes(int(b), int(n), int(c), int(r)))
+
+
+def _se_args(name, x, w1, w2):
+    """-> (b, h, w, c, r, device) of the map x [B, H, W, C] and the kernels w1 [C, R], w2 [R, C] there"""
+    b, h, w, c = _dw_map(x, 'x')
+    dev = x.device
+    for t, what in ((w1, 'w1'), (w2, 'w2')):
+        _require_cuda_f32(t, what)
+    if w1.dim() != 2 or w1.shape[0] != c or tuple(w2.shape) != (w1.shape[1], c) or w1.device != dev or w2.device != dev:
+        raise ValueError('%s: w1 %s and w2 %s, expected (%d, R) and (R, %d) on %s' % (name, tuple(w1.shape), tuple(w2.shape), c, c, dev))
+    return b, h, w, c, int(w1.shape[1]), dev
+
+
+def _se_workspace(workspace, b, n, c, r, dev, name):
+    need = se_workspace_bytes(b, n, c, r)
+    if need == 0:
+        raise ValueError('%s: %d images of %d pixels, C = %d, R = %d are outside the contract' % (name, b, n, c, r))
+    return _workspace_arg(workspace, need, dev, name)
+
+
+def _se_mat(t, shape, dev, name):
+    _require_cuda_f32(t, name)
+    if tuple(t.shape) != tuple(shape) or t.device != dev:
+        raise ValueError('%s has shape %s on %s, expected %s on %s' % (name, tuple(t.shape), t.device, tuple(shape), dev))
+
+
+def se_forward(x, w1, b1, w2, b2, out=None, workspace=None):
+    """The squeeze-excite block (yr_se_forward): x [B, H, W, C] float32, w1 [C, R] and b1 [R] (the Keras <name>_se_reduce kernel
+    [1, 1, C, R] reshaped, and its bias), w2 [R, C] and b2 [C] (<name>_se_expand) -> (y, m, z1, g): m [B, C] the mean over the map,
+    z1 [B, R] = b1 + m w1, g [B, C] = sigmoid(b2 + swish(z1) w2), y = x * g; m, z1 and g are what ``se_backward`` needs.  workspace: a
+    uint8 tensor of at least se_workspace_bytes(B, H * W, C, R) bytes (its contents do not matter); default: a fresh one.  Three launches."""
+    b, h, w, c, r, dev = _se_args('se_forward', x, w1, w2)
+    _bn_vec(b1, r, dev, 'b1')
+    _bn_vec(b2, c, dev, 'b2')
+    out = _out_like(out, (b, h, w, c), dev, 'se_forward')
+    ws = _se_workspace(workspace, b, h * w, c, r, dev, 'se_forward')
+    m = torch.empty((b, c), dtype=torch.float32, device=dev)
+    z1 = torch.empty((b, r), dtype=torch.float32, device=dev)
+    g = torch.empty((b, c), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().yr_se_forward(_ptr(x), c, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), b, h, w, c, r, _ptr(out), c, _ptr(m), _ptr(z1), _ptr(g),
+                                  _ptr(ws), ws.numel(), stream_ptr(dev)))
+    return out, m, z1, g
+
+
+def se_backward(dy, x, w1, w2, m, z1, g, need_dx=True, need_params=True, out=None, workspace=None):
+    """The gradients of ``se_forward`` (yr_se_backward): dy and x [B, H, W, C], w1 [C, R], w2 [R, C], and m, z1, g as the forward
+    returned them -> (dx, dw1, db1, dw2, db2): dx of x's shape (None with need_dx=False: its pass over the map is not launched), the
+    four parameter gradients in the parameters' shapes, summed over the batch in image order (all None with need_params=False: the
+    batch sums are not computed).  The other outputs keep their bits either way; no atomics: the same call gives the same bytes.
+    out: a tensor to receive dx; workspace: as ``se_forward``'s.  Four launches, three with need_dx or need_params alone, none with
+    neither."""
+    b, h, w, c, r, dev = _se_args('se_backward', x, w1, w2)
+    _se_mat(dy, (b, h, w, c), dev, 'dy')
+    _se_mat(m, (b, c), dev, 'm')
+    _se_mat(z1, (b, r), dev, 'z1')
+    _se_mat(g, (b, c), dev, 'g')
+    if need_dx:
+        out = _out_like(out, (b, h, w, c), dev, 'se_backward')
+    elif out is not None:
+        raise ValueError('se_backward: out given with need_dx=False')
+    ws = _se_workspace(workspace, b, h * w, c, r, dev, 'se_backward')
+    dw1 = db1 = dw2 = db2 = None
+    if need_params:
+        dw1, db1 = torch.empty((c, r), dtype=torch.float32, device=dev), torch.empty((r,), dtype=torch.float32, device=dev)
+        dw2, db2 = torch.empty((r, c), dtype=torch.float32, device=dev), torch.empty((c,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().yr_se_backward(_ptr(dy), c, _ptr(x), c, _ptr(w1), _ptr(w2), _ptr(m), _ptr(z1), _ptr(g), b, h, w, c, r, _ptr(out), c,
+                                   _ptr(dw1), _ptr(db1), _ptr(dw2), _ptr(db2), _ptr(ws), ws.numel(), stream_ptr(dev)))
+    return out, dw1, db1, dw2, db2
 
 
 VOC_MAX_ROWS, VOC_MAX_GT = 4096, 512    # YR_VOC_MAX_ROWS, YR_VOC_MAX_GT of include/yoloret_hip.h
