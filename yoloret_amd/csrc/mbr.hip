@@ -16,7 +16,8 @@
 //     taps are the last three rows of the walk, kept in registers (a ring of two rows + the new one).  The depthwise
 //     result (BN shift as the first addend, v_med3) is used AS IS as the B operand of the projection MFMAs.
 //   * the A operands (expand and project weights of the wave's expanded-channel tiles) are STATIONARY in registers for the
-//     whole walk; only the nine depthwise taps per tile come from a small LDS table.
+//     whole walk; only the nine depthwise taps per tile come from a small LDS table.  (Split form, stride 2, two cout tiles: the
+//     projection's plane fragments, used in one row of four, are read from LDS too - 49 registers less, three waves per SIMD.)
 //   * the NW waves of a workgroup share one strip and split the expanded channels (tiles of 16); their partial projections
 //     of an output row meet in LDS (one barrier per output row, two buffers), the wave that finishes a cout tile adds the
 //     BN shift and the residual and stores 16 bytes per lane.
@@ -44,11 +45,19 @@ struct MbrArgs {
     int H, W, Ho, Wo, ld_in, ld_out, pad_t, pad_l, strips, segs, seg_rows;
 };
 
-template <int CIN, int CEXP, int COUT, int S, int NW, bool RES, int NT, bool SP>
+// 1 KB slots of ONE of the two buffers in which the waves' partial projections of an output row meet: every wave's TO tiles; where plane
+// fragments live in LDS too (PL > 0), without the slot of the wave that finishes the tile - that room is what lets the fragments in
+static constexpr __host__ __device__ int mbr_red_slots(int nw, int to, int pl) { return nw == 1 ? 0 : pl > 0 ? to * (nw - 1) : nw * to; }
+
+template <int CIN, int CEXP, int COUT, int S, int NW, bool RES, int NT, bool SP, int PL>
 __device__ __forceinline__ void mbr_body(const MbrArgs& a, const int t0, const int w, float* lds) {
     constexpr int T = CEXP / 16, TO = (COUT + 15) / 16, NMAIN = CIN / 16, TAIL = CIN % 16, KE = NMAIN * 4 + TAIL / 4;
     constexpr int NREG = KE + 4 * TO, NOUT = 14 / S;
     constexpr int NKE = (CIN + 31) / 32, NP = (NT + 1) / 2;   // SP: K = 32 steps of the expand conv, tile pairs of this wave
+    // SP: the wave's projection plane fragments f = (q TO + t) 2 + plane: the first NFR stay in registers, the last NFL are read from LDS
+    // where they are used (PL > 0, stride 2: the projection runs once per four input rows; the registers are wanted by the other three)
+    constexpr int NFRAG = NP * TO * 2, NFL = SP ? (PL < NFRAG ? PL : NFRAG) : 0, NFR = NFRAG - NFL;
+    static_assert(PL == 0 || (SP && S == 2), "projection planes from LDS: the stride-2 split form only");
     static_assert(TAIL == 0 || TAIL == 8, "block input width must be 16 n or 16 n + 8");
     static_assert(CEXP % 16 == 0 && COUT % 4 == 0, "widths");
     typedef unsigned u4 __attribute__((ext_vector_type(4)));
@@ -72,6 +81,8 @@ __device__ __forceinline__ void mbr_body(const MbrArgs& a, const int t0, const i
     float we[SP ? 1 : NT][SP ? 1 : KE], wp[SP ? 1 : NT][TO][4];
     v4u weh[SP ? NT : 1][NKE], wem[SP ? NT : 1][NKE], wph[SP ? NP : 1][TO], wpm[SP ? NP : 1][TO];
     v4f se[NT];
+    // LDS: the depthwise table | red [2][mbr_red_slots][64] x 16 bytes | the waves' plane fragments [NW][PL][64] x 16 bytes, a lane's at its own index
+    v4u* const pll = reinterpret_cast<v4u*>(lds + T * MBR_TAB + 2 * mbr_red_slots(NW, TO, PL) * 64 * 4) + w * PL * 64 + lane;   // fragment f >= NFR: pll[(f - NFR) * 64]
     if constexpr (!SP) {
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
@@ -99,8 +110,10 @@ __device__ __forceinline__ void mbr_body(const MbrArgs& a, const int t0, const i
         for (int q = 0; q < NP; ++q)
 #pragma unroll
             for (int t = 0; t < TO; ++t) {
-                wph[q][t] = pp[(((size_t)(pair0 + q) * TO + t) * 2 + 0) * 64 + lane];
-                wpm[q][t] = pp[(((size_t)(pair0 + q) * TO + t) * 2 + 1) * 64 + lane];
+                const int f = (q * TO + t) * 2;
+                const v4u h = pp[(((size_t)(pair0 + q) * TO + t) * 2 + 0) * 64 + lane], m = pp[(((size_t)(pair0 + q) * TO + t) * 2 + 1) * 64 + lane];
+                if (f < NFR) wph[q][t] = h; else pll[(f - NFR) * 64] = h;
+                if (f + 1 < NFR) wpm[q][t] = m; else pll[(f + 1 - NFR) * 64] = m;
             }
     }
 #pragma unroll
@@ -108,7 +121,7 @@ __device__ __forceinline__ void mbr_body(const MbrArgs& a, const int t0, const i
     // ---- the depthwise table of all tiles -> LDS
     float* tab = lds;
     for (int i = threadIdx.x; i < T * MBR_TAB; i += 64 * NW) tab[i] = a.wt[i];
-    v4f* red = reinterpret_cast<v4f*>(lds + T * MBR_TAB);   // [2][NW][TO][64]
+    v4f* red = reinterpret_cast<v4f*>(lds + T * MBR_TAB);   // [2][NW][TO][64] (PL > 0: [2][TO][NW - 1][64])
     __syncthreads();
 
     // Every global access of the walk is UNCONDITIONAL, through buffer descriptors (dead lanes pass an offset beyond
@@ -236,9 +249,11 @@ __device__ __forceinline__ void mbr_body(const MbrArgs& a, const int t0, const i
             mbs_split8(v, bh, bm);
 #pragma unroll
             for (int t = 0; t < TO; ++t) {
-                P[t] = mbs_mfma(wph[q][t], bh, P[t]);
-                P1[t] = mbs_mfma(wph[q][t], bm, P1[t]);
-                P1[t] = mbs_mfma(wpm[q][t], bh, P1[t]);
+                const int f = (q * TO + t) * 2;   // (a constant once unrolled: a register or one 16-byte LDS read at the lane's own index)
+                const v4u ah = f < NFR ? wph[q][t] : pll[(f - NFR) * 64], am = f + 1 < NFR ? wpm[q][t] : pll[(f + 1 - NFR) * 64];
+                P[t] = mbs_mfma(ah, bh, P[t]);
+                P1[t] = mbs_mfma(ah, bm, P1[t]);
+                P1[t] = mbs_mfma(am, bh, P1[t]);
             }
         };
         if constexpr (S == 2 && PH != 0) {
@@ -311,17 +326,34 @@ __device__ __forceinline__ void mbr_body(const MbrArgs& a, const int t0, const i
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, v), osrc, flive[t] && rlive ? opix + (16u * t + 4u * mg) * 4u : YR_DEAD, 0, 0);
                 }
             } else {
-                v4f* rb = red + buf * (NW * TO * 64);
+                v4f* rb = red + buf * (mbr_red_slots(NW, TO, PL) * 64);
+                if constexpr (PL == 0) {
 #pragma unroll
-                for (int t = 0; t < TO; ++t) rb[(w * TO + t) * 64 + lane] = P[t];
+                    for (int t = 0; t < TO; ++t) rb[(w * TO + t) * 64 + lane] = P[t];
+                } else {   // PL > 0: [TO][NW - 1] - the wave that finishes tile t (t % NW) keeps its own partial sums in registers, the others take its place in turn
+#pragma unroll
+                    for (int t = 0; t < TO; ++t)
+                        if (w != t % NW) rb[(t * (NW - 1) + w - (w > t % NW)) * 64 + lane] = P[t];   // (wave-uniform)
+                }
                 __syncthreads();
 #pragma unroll
                 for (int tt = 0; tt < NF; ++tt) {
                     const int t = w + tt * NW;
                     v4f v = fsh[tt];
                     if (t < TO) {   // (wave-uniform; LDS reads only - the store below stays unconditional)
+                        if constexpr (PL == 0) {
 #pragma unroll
-                        for (int ww = 0; ww < NW; ++ww) v += rb[(ww * TO + t) * 64 + lane];
+                            for (int ww = 0; ww < NW; ++ww) v += rb[(ww * TO + t) * 64 + lane];
+                        } else {   // the same sum in the same order, this wave's own addend from its registers
+                            v4f own = P[0];
+#pragma unroll
+                            for (int t2 = 1; t2 < TO; ++t2) own = t2 == t ? P[t2] : own;
+#pragma unroll
+                            for (int ww = 0; ww < NW; ++ww) {
+                                if (ww == w) v += own;
+                                else v += rb[(t * (NW - 1) + ww - (ww > w)) * 64 + lane];
+                            }
+                        }
                     }
                     if (RES) v += fres[tt];   // last: the residual load issued at the row's start is waited for only here
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, v), osrc, flive[tt] && rlive ? opix + (16u * t + 4u * mg) * 4u : YR_DEAD, 0, 0);
@@ -362,36 +394,44 @@ __device__ __forceinline__ void mbr_body(const MbrArgs& a, const int t0, const i
     }
 }
 
-template <int CIN, int CEXP, int COUT, int S, int NW, bool RES, bool SP, int MW>
+template <int CIN, int CEXP, int COUT, int S, int NW, bool RES, bool SP, int MW, int PL>
 __global__ __launch_bounds__(64 * NW, MW) void mbr_kernel(MbrArgs a) {
     constexpr int T = CEXP / 16, NTL = T / NW, R = T % NW, NTH = NTL + (R ? 1 : 0);
     static_assert(NTL >= 1, "more waves than expanded tiles");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if constexpr (R != 0) {
-        if (w < R) { mbr_body<CIN, CEXP, COUT, S, NW, RES, NTH, SP>(a, w * NTH, w, lds); return; }
+        if (w < R) { mbr_body<CIN, CEXP, COUT, S, NW, RES, NTH, SP, PL>(a, w * NTH, w, lds); return; }
     }
-    mbr_body<CIN, CEXP, COUT, S, NW, RES, NTL, SP>(a, R * NTH + (w - R) * NTL, w, lds);
+    mbr_body<CIN, CEXP, COUT, S, NW, RES, NTL, SP, PL>(a, R * NTH + (w - R) * NTL, w, lds);
 }
 
-template <int CIN, int CEXP, int COUT, int S, int NW, bool RES, bool SP = false>
+// MWS, PL (split form): waves per SIMD the instantiation is built for and the projection plane fragments per wave it reads from LDS
+// (MBS_CASE below states both per instantiation, from the compile-time resource report)
+template <int CIN, int CEXP, int COUT, int S, int NW, bool RES, bool SP = false, int MWS = 0, int PL = 0>
 static int launch_mbr(const MbrArgs& a0, int batch, int want_segs, hipStream_t s) {
     MbrArgs a = a0;
     constexpr int T = CEXP / 16, TO = (COUT + 15) / 16, NOUT = 14 / S;
     a.strips = (a.Wo + NOUT - 1) / NOUT;
     // segments: enough workgroups for ~2 generations of the chip's SIMDs, not so many that the 2 halo rows matter; stride 2 walks pairs of output rows
-    a.seg_rows = ch_row_segments(a.Ho, batch * a.strips, NW, 2 * 1024, 6, S == 2, want_segs, &a.segs);
-    const size_t lds = (size_t)T * MBR_TAB * 4 + (NW > 1 ? (size_t)2 * NW * TO * 64 * 16 : 0);
-    // waves per SIMD the register allocator must leave room for, from an estimate of what a wave holds: the stationary
-    // fragments + BN shifts, ring and new row, projection accumulators, two rows of pixel operands, ~44 others
+    // (PL > 0, three waves resident per SIMD: two generations of THOSE - block_1 at 64 images 134 us with four segments, 171 with the two
+    //  the smaller target gives: one full generation and a quarter of a second one)
+    a.seg_rows = ch_row_segments(a.Ho, batch * a.strips, NW, PL > 0 ? 6 * 1024 : 2 * 1024, 6, S == 2, want_segs, &a.segs);
+    constexpr size_t lds = (size_t)T * MBR_TAB * 4 + (size_t)2 * mbr_red_slots(NW, TO, PL) * 64 * 16 + (size_t)NW * PL * 64 * 16;
+    // waves per SIMD the register allocator must leave room for.  Float32-MFMA form: from an estimate of what a wave holds - the
+    // stationary fragments + BN shifts, ring and new row, projection accumulators, two rows of pixel operands, ~44 others.
+    // Split form: MWS, the measured fact (the estimate NTH (8 NKE + 20) + NPH 8 TO + 8 TO + 24 NKE + 60 is 20-40 registers off
+    // either way): three waves per SIMD where the kernel fits 168 registers without scratch - the stride-1 three-wave block as it is,
+    // the stride-2 blocks of up to three waves once PL of their NPH TO 2 projection plane fragments are read from LDS.
     constexpr int NTH = (T + NW - 1) / NW, KE = CIN / 4;
-    constexpr int NKE = (CIN + 31) / 32, NPH = (NTH + 1) / 2;
-    constexpr int EST = SP ? NTH * (8 * NKE + 4 + 12 + 4) + NPH * 8 * TO + 8 * TO + 16 * NKE + 8 * NKE + 60
-                           : NTH * (KE + 4 * TO + 4 + 12) + 4 * TO + 2 * KE + 44;
-    // (SP: measured register counts - the stride-1 three-wave kernels fit 168, the others spill there)
-    constexpr int MW = SP ? (S == 1 && NW <= 3 ? 3 : 2) : EST <= 164 ? 3 : EST <= 250 ? 2 : 1;
+    constexpr int EST = NTH * (KE + 4 * TO + 4 + 12) + 4 * TO + 2 * KE + 44;
+    constexpr int MW = SP ? MWS : EST <= 164 ? 3 : EST <= 250 ? 2 : 1;
+    static_assert(!SP || MWS == 2 || MWS == 3, "split form: state the waves per SIMD");
     static_assert(NW <= 4 * MW, "a workgroup's waves must fit one CU at this register budget");
-    return ch_launch<mbr_kernel<CIN, CEXP, COUT, S, NW, RES, SP, MW>>(dim3((unsigned)(batch * a.strips * a.segs)), dim3(64 * NW), lds, lds, s, a,
+    // the 4 MW / NW workgroups a CU holds at that many waves per SIMD must find their LDS in its 160 KB, or the third wave never arrives
+    // (LDS is handed out in pieces of 1280 bytes on gfx950)
+    static_assert(PL == 0 || (size_t)(4 * MW / NW) * ((lds + 1279) / 1280 * 1280) <= 160 * 1024, "plane fragments in LDS: the workgroups wanted per CU exceed its 160 KB");
+    return ch_launch<mbr_kernel<CIN, CEXP, COUT, S, NW, RES, SP, MW, PL>>(dim3((unsigned)(batch * a.strips * a.segs)), dim3(64 * NW), lds, lds, s, a,
                                                                       "mbr_kernel<%d,%d,%d,%d,%d,%d,%d>", CIN, CEXP, COUT, S, NW, (int)RES, (int)SP);   // (... SP = 1: the split form)
 }
 
@@ -645,19 +685,22 @@ int yr_launch_mbr(const yr_op& op, int batch, hipStream_t s) {
     a.strips = a.segs = a.seg_rows = 0;
     const int nw = (op.k & YR_MBR_NW_MASK) >> YR_MBR_NW_SHIFT;
     if (op.k & YR_MBR_SPLIT) {   // the SPLIT form: wgt holds float16 planes packed for exactly this many waves (compiler.mbs_pack)
-#define MBS_CASE(CIN, CEXP, COUT, S, NW, RES)                                                              \
+        // MW: waves per SIMD; PL: projection plane fragments per wave read from LDS (stride 2; 0: all in registers)
+#define MBS_CASE(CIN, CEXP, COUT, S, NW, RES, MW, PL)                                                      \
     if (in.c == CIN && op.se_reduced == CEXP && op.cout == COUT && op.stride == S && res == RES && nw == NW) \
-        return launch_mbr<CIN, CEXP, COUT, S, NW, RES, true>(a, batch, (op.k & YR_MBR_SEGS_MASK) >> YR_MBR_SEGS_SHIFT, s);
-        MBS_CASE(16, 96, 24, 2, 3, false)
-        MBS_CASE(16, 96, 24, 2, 2, false)     // (block_1 @208: 0.188 ms against 0.195-0.204 with three waves - one partner less at the row barrier)
-        MBS_CASE(24, 144, 24, 1, 3, true)
-        MBS_CASE(24, 144, 24, 2, 3, false)
-        MBS_CASE(24, 144, 48, 2, 3, false)
-        MBS_CASE(48, 288, 48, 1, 6, true)
-        MBS_CASE(48, 288, 72, 1, 6, false)
-        MBS_CASE(24, 144, 32, 2, 3, false)     // MobileNetV2 x1.4 block_1
-        MBS_CASE(32, 192, 32, 1, 4, true)      // x1.4 block_2
-        MBS_CASE(32, 192, 48, 2, 4, false)     // x1.4 block_3
+        return launch_mbr<CIN, CEXP, COUT, S, NW, RES, true, MW, PL>(a, batch, (op.k & YR_MBR_SEGS_MASK) >> YR_MBR_SEGS_SHIFT, s);
+        MBS_CASE(16, 96, 24, 2, 3, false, 3, 0)     // (two tiles a wave: 148 registers with its planes in them - three waves per SIMD before and after round 10)
+        MBS_CASE(16, 96, 24, 2, 2, false, 3, 8)     // (block_1 @208, 64 images, four segments: 134 us against 147 with three waves per strip - one partner less at the row
+                                                    //  barrier; with its planes in registers, 214 of them and two waves per SIMD, it ran at 147 too)
+        MBS_CASE(24, 144, 24, 1, 3, true, 3, 0)
+        MBS_CASE(24, 144, 24, 2, 3, false, 3, 8)    // (block_3 @104: 75.5 -> 67.8 us)
+        MBS_CASE(24, 144, 48, 2, 3, false, 2, 0)    // (three cout tiles: 12 fragments a wave - 54 KB a workgroup with them in LDS, and four workgroups must fit a CU's 160 KB;
+                                                    //  with the 7 that fit, the kernel wants 209 registers and spills 52 bytes at 168: two waves per SIMD, planes in registers)
+        MBS_CASE(48, 288, 48, 1, 6, true, 2, 0)
+        MBS_CASE(48, 288, 72, 1, 6, false, 2, 0)
+        MBS_CASE(24, 144, 32, 2, 3, false, 3, 8)    // MobileNetV2 x1.4 block_1
+        MBS_CASE(32, 192, 32, 1, 4, true, 2, 0)     // x1.4 block_2
+        MBS_CASE(32, 192, 48, 2, 4, false, 2, 0)    // x1.4 block_3
 #undef MBS_CASE
         yr_set_error("mbr (split form): block %d -> %d -> %d stride %d res %d nw %d is not built", in.c, op.se_reduced, op.cout, op.stride, (int)res, nw);
         return YR_ERR_ARG;
