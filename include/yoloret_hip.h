@@ -941,6 +941,37 @@ int yr_se_backward(const float* dy, int dy_ld, const float* x, int x_ld, const f
                    float* dw1 /*[C][R]*/, float* db1 /*[R]*/, float* dw2 /*[R][C]*/, float* db2 /*[C]; all four or none*/,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the 1x1 operators at any width up to 1024 channels on either side: the neck and the heads behind the RFCR module are wider than
+ * yr_linear_forward / _dgrad / _wgrad take (model.py:226-258: td1_conv 216..480 -> 512, td2_conv 424..576 -> 256, td3_conv 248..272 ->
+ * 128, bu1_conv 331 -> 512; model.py:104-111: the projections 512 -> anchors * (classes + 5)), and code/train.py:150-171 trains all of
+ * them.  Added under ABI 9 (additive: the narrow entries are unchanged, their 256-channel refusal included).  csrc/linearwide.hip has
+ * the kernels' forms and the order of every sum.  The argument lists, the conventions (float32, rows row-major over pixels with a
+ * leading dimension in floats, Wt[cout][kp] with kp = round_up(cin, 4) and pad columns never read, 4-byte alignment, no float atomics,
+ * nothing read before the call wrote it, every named output element written and nothing else, the same call gives the same bytes)
+ * and the refusals (YR_ERR_ARG, nothing launched or written: a null pointer, ld below the channels taken, a misaligned pointer, byte
+ * offsets beyond 2^63, a workspace that is short or not 16-byte aligned, sizes outside 1 <= cin, cout <= 1024, 1 <= pixels < 2^40; the forward
+ * and the input gradient, one workgroup per 64 pixels, refuse more than 2^37 - 64 pixels, as the narrow twins do) are those of the
+ * narrow twins.  The narrow widths are accepted as well and give the narrow entries' bytes in all three entries. */
+/* model.py:29,100,111 (a bias-free 1x1 Conv2D): y[p][co] = sum_k x[p][k] * wt[co][k], the activations read once per 256 output
+ * channels.  At cin, cout <= 256 the bytes of yr_linear_forward.  One launch. */
+int yr_linear_wide_forward(const float* x, int x_ld, const float* wt /*[cout][kp]*/, long long pixels, int cin, int cout,
+                           float* y, int y_ld, void* stream);
+/* d loss / d x of that layer (tape.gradient, yolo3/train.py:39): dx[p][ci] = sum_co dy[p][co] * wt[co][ci], dy read once per 256 input
+ * channels.  At cin, cout <= 256 the bytes of yr_linear_dgrad.  One launch. */
+int yr_linear_wide_dgrad(const float* dy, int dy_ld, const float* wt /*[cout][kp]*/, long long pixels, int cin, int cout,
+                         float* dx, int dx_ld, void* stream);
+/* d loss / d Wt of that layer (yolo3/train.py:39): dwt[co][ci] = sum_p dy[p][co] * x[p][ci], two launches like yr_linear_wgrad: stage 1
+ * gives every workgroup a contiguous range of yr_linear_wide_wgrad_chunk(pixels, cin, cout) pixels - the least multiple of 16 that is
+ * at least 64, ceil(cout * kp / (cin + cout)) and ceil(pixels / 1024): a function of its three arguments only - and 128 x 128 channels,
+ * and writes one [cout][kp] slab per range; stage 2 adds the slabs in index order and writes EVERY element of dwt, pad columns as +0.
+ * Where cin and cout are both at most 256 the call IS yr_linear_wgrad - its chunk, its workspace size, its bytes (one 128 x 128 block
+ * gains nothing from the wide stage 1) -, and the two size entries return the narrow ones' values.  They return 0 for sizes the call
+ * refuses. */
+int    yr_linear_wide_wgrad_chunk(long long pixels, int cin, int cout);
+size_t yr_linear_wide_wgrad_workspace_bytes(long long pixels, int cin, int cout);
+int    yr_linear_wide_wgrad(const float* x, int x_ld, const float* dy, int dy_ld, long long pixels, int cin, int cout,
+                            void* workspace /*device*/, size_t workspace_bytes, float* dwt /*[cout][kp]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,8 @@
 convolutions, depthwise convolutions and frozen BatchNorm + activation on top of ``yolov3_features`` trains with ``YoloLoss.call``
 (itself an autograd Function) and ``runtime.adam_step``.
 
-    linear1x1(x, wt)                        x [..., cin], wt [cout, round_up(cin, 4)] (pad columns 0) -> [..., cout]
+    linear1x1(x, wt)                        x [..., cin], wt [cout, round_up(cin, 4)] (pad columns 0) -> [..., cout]; cin, cout <= 256
+    conv1x1(x, wt)                          the same at any width up to 1024 (csrc/linearwide.hip); linear1x1 itself where both are <= 256
     depthwise(x, w, stride=1, padding='same')   x [B, H, W, C], w [k * k, C] (the Keras kernel [k, k, C, 1] reshaped), k in {3, 5}
     frozen_bn_act(z, scale, shift, act)     act in {None, 'relu6', 'swish'}; scale and shift are frozen: they never get a gradient
     batchnorm_act(z, gamma, beta, moving_mean, moving_var, momentum, eps, act)   BatchNorm in training mode (csrc/bntrain.hip): batch
@@ -14,7 +15,10 @@ convolutions, depthwise convolutions and frozen BatchNorm + activation on top of
     rfcr_module(b1, b2, b3, b4, params, training=True), rfcr_parameters(model, device)   the RFCR module (model.py:146-168) of these
     squeeze_excite(x, w1, b1, w2, b2)       the squeeze-excite block (efficientnet.py:406-438; csrc/segrad.hip): x [B, H, W, C], w1 [C, R],
                                             b1 [R], w2 [R, C], b2 [C] -> x * sigmoid(swish(mean(x) w1 + b1) w2 + b2), differentiable in all five
-    head_block(x, params, training=True), head_block_parameters(model, name, device)   a head block (model.py:91-115) of these
+    head_block(x, params, training=True, wide=False), head_block_parameters(model, name, device)   a head block (model.py:91-115) of
+                                            these; wide=True: its 1x1 convolutions through conv1x1
+    detector_neck(b1, b2, b3, b4, params, training=True), neck_parameters(model, device), neck_weights(params)   everything yolov3_body
+                                            runs behind the backbone (model.py:226-340), its parameters, and their way back into the model
 
 Written the way ``_YoloLossFunction`` of yolo3/model.py is: forward and backward are calls of the C entries, only what backward needs
 is saved, a gradient is computed only for an input that requires one (the others are None and their kernel is not launched).  float32
@@ -55,6 +59,25 @@ class _Linear1x1(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             pixels, cin, cout = x.numel() // x.shape[-1], x.shape[-1], wt.shape[0]
             dwt = rt.linear_wgrad(x, dy, workspace=_workspace(x.device, rt.linear_wgrad_workspace_bytes(pixels, cin, cout)))
+        return dx, dwt
+
+
+class _LinearWide(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, wt):
+        ctx.save_for_backward(x, wt)
+        return rt.linear_wide_forward(x, wt)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, wt = ctx.saved_tensors
+        dy = _f32(dy)
+        dx = dwt = None
+        if ctx.needs_input_grad[0]:
+            dx = rt.linear_wide_dgrad(dy, wt, x.shape[-1])
+        if ctx.needs_input_grad[1]:
+            pixels, cin, cout = x.numel() // x.shape[-1], x.shape[-1], wt.shape[0]
+            dwt = rt.linear_wide_wgrad(x, dy, workspace=_workspace(x.device, rt.linear_wide_wgrad_workspace_bytes(pixels, cin, cout)))
         return dx, dwt
 
 
@@ -209,6 +232,15 @@ class _Concat(torch.autograd.Function):
 def linear1x1(x, wt):
     """A bias-free 1x1 convolution, differentiable in x (``runtime.linear_dgrad``) and wt (``runtime.linear_wgrad``: pad columns +0)."""
     return _Linear1x1.apply(x.contiguous(), wt.contiguous())
+
+
+def conv1x1(x, wt):
+    """A bias-free 1x1 convolution of any width up to 1024 channels on either side, differentiable in x and wt.  Where cin and cout are
+    both at most 256 it IS ``linear1x1``: the same entries and the same bytes.  Otherwise the three wide entries
+    (``runtime.linear_wide_forward`` / ``_dgrad`` / ``_wgrad``: pad columns of the weight gradient +0)."""
+    if x.shape[-1] <= 256 and wt.shape[0] <= 256:
+        return linear1x1(x, wt)
+    return _LinearWide.apply(x.contiguous(), wt.contiguous())
 
 
 def depthwise(x, w, stride=1, padding='same'):
@@ -385,25 +417,135 @@ def head_block_parameters(model, name, device):
     return out
 
 
-def head_block(x, params, training=True):
+def head_block(x, params, training=True, wide=False):
     """A head block (model.py:91-115, make_last_layers_efficientnet_lite) on x [B, H, W, cin]; params: ``head_block_parameters``'
     dictionary -> (x_out, y): the 1x1 convolution to F channels + BatchNorm + ReLU6; the MBConv with expand ratio 1 - depthwise 3 x 3
     + BatchNorm + Swish, ``squeeze_excite``, the 1x1 projection to O channels + BatchNorm, no residual because F != O -; and
     y = the 1x1 convolution '_y' of x_out (None for a top-down block, whose parameters hold no '_y').  training: the three BatchNorms run on the statistics of the batch and update their moving
     statistics in place (``batchnorm_act``, momentum 0.99, eps 1e-3); otherwise they are folded (``fold_batchnorm`` +
     ``frozen_bn_act``: no gradient for gamma and beta, one host synchronisation per BatchNorm).
-    The 1x1 operators take cin, cout <= 256 today, so 'bu3' (its input is td3's output, F = 128) runs for every model and 'td3'
-    where its concatenated input is at most 256 wide (MobileNetV2 x0.75: 128 + 24 + 96 = 248); the wider blocks raise
-    ``linear_forward``'s own error.  Lifting that cap is the linear entries' business, not this module's."""
+    wide=False: the 1x1 convolutions are ``linear1x1``, which takes cin, cout <= 256, so 'bu3' (its input is td3's output, F = 128)
+    runs for every model and 'td3' where its concatenated input is at most 256 wide (MobileNetV2 x0.75: 128 + 24 + 96 = 248); the wider
+    blocks raise ``linear_forward``'s own error.  wide=True: they are ``conv1x1`` (up to 1024 channels on either side): every block of
+    every model runs, the narrow ones on the same entries and with the same bytes as before."""
     p = params
+    lin = conv1x1 if wide else linear1x1
 
     def bn_act(z, bn, act):
         stats = [p['%s/%s' % (bn, k)] for k in ('gamma', 'beta', 'moving_mean', 'moving_variance')]
         if training:
             return batchnorm_act(z, *stats, momentum=HEAD_BN_MOMENTUM, eps=HEAD_BN_EPS, act=act)
         return frozen_bn_act(z, *fold_batchnorm(*stats, eps=HEAD_BN_EPS), act=act)
-    t = bn_act(linear1x1(x, p['_conv']), '_conv_BN', 'relu6')
+    t = bn_act(lin(x, p['_conv']), '_conv_BN', 'relu6')
     t = bn_act(depthwise(t, p['_mb_dw'], 1, 'same'), '_mb_dw_BN', 'swish')
     t = squeeze_excite(t, p['_mb_se_reduce'], p['_mb_se_reduce/bias'], p['_mb_se_expand'], p['_mb_se_expand/bias'])
-    x_out = bn_act(linear1x1(t, p['_mb_project']), '_mb_project_BN', None)
-    return x_out, (linear1x1(x_out, p['_y']) if '_y' in p else None)
+    x_out = bn_act(lin(t, p['_mb_project']), '_mb_project_BN', None)
+    return x_out, (lin(x_out, p['_y']) if '_y' in p else None)
+
+
+LINK_CONVS = ('block_20', 'block_24', 'bu3_down', 'bu2_down')
+LINK_BN_MOMENTUM, LINK_BN_EPS = 0.9, 1e-3      # model.py:248-250: BatchNormalization(momentum=0.9), the Keras epsilon
+_BN_LEAVES = (('gamma', True), ('beta', True), ('moving_mean', False), ('moving_variance', False))
+
+
+def _pack_wt(kernel):
+    """Keras [1, 1, cin, cout] -> wt [cout, round_up(cin, 4)], pad columns 0"""
+    k = np.asarray(kernel, np.float32)
+    cin, cout = k.shape[-2], k.shape[-1]
+    wt = np.zeros((cout, (cin + 3) // 4 * 4), np.float32)
+    wt[:, :cin] = k.reshape(cin, cout).T
+    return wt
+
+
+def neck_parameters(model, device):
+    """Everything ``yolov3_body`` holds behind the backbone as float32 tensors on ``device``, in the layouts the operators take ->
+        'rfcr'                       ``rfcr_parameters(model, device)``
+        'td1', 'td2', 'td3', 'bu3', 'bu2', 'bu1'   ``head_block_parameters(model, name, device)``
+        'block_20', 'block_24', 'bu3_down', 'bu2_down'   the link convolutions (model.py:248-250, 283-323): {'_conv': wt [cout,
+                                     round_up(cin, 4)], '_BN/gamma', '_BN/beta', '_BN/moving_mean', '_BN/moving_variance'}
+        'cin'                        {Keras name of every 1x1 convolution: its input channels} (integers, for ``neck_weights``)
+    ``requires_grad`` is set on everything the reference trains (train.py:150-171); the moving statistics take no gradient:
+    ``detector_neck(training=True)`` updates them in place."""
+    host = model.get_weights()
+    if host is None:
+        raise ValueError('neck_parameters: the model has no weights (set_weights / load_weights)')
+
+    def dev(a, grad=True):
+        return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(device).requires_grad_(grad)
+    out = {'rfcr': rfcr_parameters(model, device)}
+    for name in HEAD_BLOCKS:
+        out[name] = head_block_parameters(model, name, device)
+    convs = list(RFCR_CONVS) + ['rfcr_sep_pw'] + [name + c for name in HEAD_BLOCKS for c in HEAD_CONVS if name + c + '/kernel' in host]
+    convs += [name + '_conv' for name in LINK_CONVS]
+    out['cin'] = {c: int(np.shape(host[c + '/kernel'])[-2]) for c in convs}      # the layout rounds a row up to 4: neck_weights needs these
+    for name in LINK_CONVS:
+        link = {'_conv': dev(_pack_wt(host[name + '_conv/kernel']))}
+        for leaf, grad in _BN_LEAVES:
+            link['_BN/' + leaf] = dev(np.asarray(host['%s_BN/%s' % (name, leaf)], np.float32).reshape(-1), grad)
+        out[name] = link
+    return out
+
+
+def detector_neck(b1, b2, b3, b4, params, training=True, num_anchors=3):
+    """Everything ``yolov3_body`` runs behind the backbone (model.py:226-340) on the backbone's taps b1 [B, G, G, .], b2 [B, 2G, 2G, .],
+    b3 [B, 4G, 4G, .] and b4, the already 4x-pooled fourth tap, as ``rfcr_module`` takes them; params: ``neck_parameters``' dictionary
+    -> [y1, y2, y3], the logits [B, G, G, num_anchors, O / num_anchors] of strides 32, 16 and 8.  The order: ``rfcr_module``; the
+    top-down pass td1 -> block_20 -> up-sample + concat -> td2 -> block_24 -> up-sample + concat -> td3 (their y convolutions do not
+    exist: model.py:240-241); the bottom-up pass bu3 -> bu3_down -> max-pool + concat -> bu2 -> bu2_down -> max-pool + concat -> bu1.
+    training: every BatchNorm runs on the statistics of the batch and updates its moving statistics in place (momentum 0.9 in the four
+    link convolutions, model.py:248-250; 0.99 in the head blocks and the RFCR module); otherwise they are folded (no gradient for gamma
+    and beta).  Differentiable in the taps and in every parameter that requires a gradient."""
+    p = params
+
+    def link(x, name):
+        q = p[name]
+        stats = [q['_BN/' + leaf] for leaf, _ in _BN_LEAVES]
+        z = conv1x1(x, q['_conv'])
+        if training:
+            return batchnorm_act(z, *stats, momentum=LINK_BN_MOMENTUM, eps=LINK_BN_EPS, act='relu6')
+        return frozen_bn_act(z, *fold_batchnorm(*stats, eps=LINK_BN_EPS), act='relu6')
+
+    def head(x, name):
+        return head_block(x, p[name], training, wide=True)
+    b1, b2, b3 = rfcr_module(b1, b2, b3, b4, p['rfcr'], training)
+    c1, _ = head(b1, 'td1')
+    c2, _ = head(concat([upsample2(link(c1, 'block_20')), b2]), 'td2')
+    c3, _ = head(concat([upsample2(link(c2, 'block_24')), b3]), 'td3')
+    x, y3 = head(c3, 'bu3')
+    x, y2 = head(concat([maxpool(link(x, 'bu3_down'), 2), c2]), 'bu2')
+    x, y1 = head(concat([maxpool(link(x, 'bu2_down'), 2), c1]), 'bu1')
+    return [y.reshape(y.shape[0], y.shape[1], y.shape[2], num_anchors, y.shape[3] // num_anchors) for y in (y1, y2, y3)]
+
+
+def _unpack_wt(wt, cin):
+    """wt [cout, round_up(cin, 4)] (host) -> Keras [1, 1, cin, cout]"""
+    return np.ascontiguousarray(wt[:, :cin].T).reshape(1, 1, cin, wt.shape[0])
+
+
+def neck_weights(params):
+    """The inverse of ``neck_parameters`` -> {Keras layer name/leaf: float32 ndarray in the layout ``model.get_weights()`` holds it in}, so that
+    ``w = model.get_weights(); w.update(neck_weights(params)); model.set_weights(w)`` ships what was trained.  (The channels a packed
+    1x1 weight's rows take are ``params['cin']``, which ``neck_parameters`` records: the layout itself rounds them up to 4.)  One copy
+    to the host, of all tensors flattened into one: it SYNCHRONISES with the device."""
+    flat = []      # (Keras layer name + leaf in the operators' naming, tensor)
+    for k, v in params['rfcr'].items():
+        flat.append((k, v))
+    for name in HEAD_BLOCKS + LINK_CONVS:
+        flat.extend((name + k, v) for k, v in params[name].items() if isinstance(v, torch.Tensor))
+    host = torch.cat([t.detach().reshape(-1).to(torch.float32) for _, t in flat]).cpu().numpy()
+    arrays, at = {}, 0
+    for key, t in flat:
+        arrays[key] = host[at:at + t.numel()].reshape(tuple(t.shape))
+        at += t.numel()
+    out = {}
+    for key, a in arrays.items():
+        if key in params['cin']:                                  # a 1x1 kernel
+            out[key + '/kernel'] = _unpack_wt(a, params['cin'][key])
+        elif key.endswith('_dw'):                                 # a depthwise kernel [k * k, C] -> [k, k, C], as the model holds it
+            k = int(round(a.shape[0] ** .5))
+            out[key + '/depthwise_kernel'] = a.reshape(k, k, a.shape[1]).copy()
+        elif key.endswith(('_se_reduce', '_se_expand')):          # [cin, cout] -> [1, 1, cin, cout]
+            out[key + '/kernel'] = a.reshape(1, 1, a.shape[0], a.shape[1]).copy()
+        else:                                                     # a bias, alpha, or a BatchNorm's vector: the name is the Keras name
+            out[key] = a.copy()
+    return out

@@ -140,7 +140,8 @@ EXPORTS = ['yr_jpeg_workspace_bytes', 'yr_jpeg_roundtrip_batch', 'yr_augment_geo
            'yr_bn_train_chunk', 'yr_bn_train_workspace_bytes', 'yr_bn_train_forward', 'yr_bn_train_backward',
            'yr_maxpool_forward', 'yr_maxpool_backward', 'yr_upsample2_forward', 'yr_upsample2_backward',
            'yr_wsum_chunk', 'yr_wsum_workspace_bytes', 'yr_wsum_forward', 'yr_wsum_backward',
-           'yr_se_chunk', 'yr_se_workspace_bytes', 'yr_se_forward', 'yr_se_backward']
+           'yr_se_chunk', 'yr_se_workspace_bytes', 'yr_se_forward', 'yr_se_backward',
+           'yr_linear_wide_forward', 'yr_linear_wide_dgrad', 'yr_linear_wide_wgrad_chunk', 'yr_linear_wide_wgrad_workspace_bytes', 'yr_linear_wide_wgrad']
 
 _lib = None
 
@@ -234,6 +235,12 @@ def lib():
         L.yr_adam_step.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_longlong] + [ctypes.c_float] * 4 + [ctypes.c_void_p]
         L.yr_linear_dgrad.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                       ctypes.c_int, ctypes.c_void_p]
+        L.yr_linear_wide_forward.argtypes = L.yr_linear_forward.argtypes
+        L.yr_linear_wide_dgrad.argtypes = L.yr_linear_dgrad.argtypes
+        L.yr_linear_wide_wgrad_chunk.argtypes = L.yr_linear_wgrad_chunk.argtypes
+        L.yr_linear_wide_wgrad_workspace_bytes.restype = ctypes.c_size_t
+        L.yr_linear_wide_wgrad_workspace_bytes.argtypes = L.yr_linear_wgrad_workspace_bytes.argtypes
+        L.yr_linear_wide_wgrad.argtypes = L.yr_linear_wgrad.argtypes
         for entry in (L.yr_depthwise_forward, L.yr_depthwise_dgrad):
             entry.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p] + [ctypes.c_int] * 10 + [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
         L.yr_depthwise_wgrad_chunk.argtypes = [ctypes.c_int] * 5
@@ -619,6 +626,81 @@ def linear_dgrad(dy, wt, cin, out=None):
     out = _out_like(out, tuple(dy.shape[:-1]) + (cin,), dy.device, 'linear_dgrad')
     with torch.cuda.device(dy.device):
         check(lib().yr_linear_dgrad(_ptr(dy), cout, _ptr(wt), pixels, cin, cout, _ptr(out), cin, stream_ptr(dy.device)))
+    return out
+
+
+# ----------------------------------------------------------------------------- 1x1 operators of any width up to 1024 (csrc/linearwide.hip)
+LINEAR_WIDE_MAX = 1024
+
+
+def _linear_wide_wt(wt, name, cin=None):
+    _require_cuda_f32(wt, name)
+    if wt.dim() != 2 or wt.shape[1] % 4 or not 1 <= wt.shape[0] <= LINEAR_WIDE_MAX or (cin is not None and wt.shape[1] != (cin + 3) // 4 * 4):
+        raise ValueError('%s has shape %s, expected [cout, round_up(cin, 4)] with cout <= %d' % (name, tuple(wt.shape), LINEAR_WIDE_MAX))
+
+
+def linear_wide_forward(x, wt, out=None):
+    """``linear_forward`` for 1..1024 channels on either side (yr_linear_wide_forward): x [..., cin] float32, wt [cout, round_up(cin, 4)]
+    -> y [..., cout] = x @ wt[:, :cin].T on the float32 matrix pipe, the activations read once per 256 output channels.  out: a
+    contiguous float32 tensor of that shape on x's device (every element is written); default: a fresh one.  One launch."""
+    pixels, cin = _rows(x, 'x')
+    if not 1 <= cin <= LINEAR_WIDE_MAX:
+        raise ValueError('linear_wide_forward: 1..%d channels, not %d' % (LINEAR_WIDE_MAX, cin))
+    _linear_wide_wt(wt, 'wt', cin)
+    if wt.device != x.device:
+        raise ValueError('linear_wide_forward: wt on %s, x on %s' % (wt.device, x.device))
+    out = _out_like(out, tuple(x.shape[:-1]) + (wt.shape[0],), x.device, 'linear_wide_forward')
+    with torch.cuda.device(x.device):
+        check(lib().yr_linear_wide_forward(_ptr(x), cin, _ptr(wt), pixels, cin, wt.shape[0], _ptr(out), wt.shape[0], stream_ptr(x.device)))
+    return out
+
+
+def linear_wide_dgrad(dy, wt, cin, out=None):
+    """``linear_dgrad`` for 1..1024 channels on either side (yr_linear_wide_dgrad): dy [..., cout] float32, wt [cout, round_up(cin, 4)]
+    -> dx [..., cin] = dy @ wt[:, :cin].  out: a contiguous float32 tensor of that shape on dy's device (every element is written);
+    default: a fresh one.  One launch."""
+    pixels, cout = _rows(dy, 'dy')
+    cin = int(cin)
+    if not (1 <= cin <= LINEAR_WIDE_MAX and 1 <= cout <= LINEAR_WIDE_MAX):
+        raise ValueError('linear_wide_dgrad: 1..%d channels, not %d and %d' % (LINEAR_WIDE_MAX, cin, cout))
+    _linear_wide_wt(wt, 'wt', cin)
+    if wt.device != dy.device or wt.shape[0] != cout:
+        raise ValueError('linear_wide_dgrad: wt %s on %s for dy %s on %s' % (tuple(wt.shape), wt.device, tuple(dy.shape), dy.device))
+    out = _out_like(out, tuple(dy.shape[:-1]) + (cin,), dy.device, 'linear_wide_dgrad')
+    with torch.cuda.device(dy.device):
+        check(lib().yr_linear_wide_dgrad(_ptr(dy), cout, _ptr(wt), pixels, cin, cout, _ptr(out), cin, stream_ptr(dy.device)))
+    return out
+
+
+def linear_wide_wgrad_chunk(pixels, cin, cout):
+    """Pixels per workgroup of the wide gradient's first stage: the least multiple of 16 that is at least 64, cout * round_up(cin, 4) /
+    (cin + cout) and pixels / 1024; where cin and cout are both at most 256 ``linear_wgrad_chunk``'s value (the call is then
+    ``linear_wgrad`` itself) - a function of these three numbers only (0: sizes the call refuses)."""
+    return int(lib().yr_linear_wide_wgrad_chunk(int(pixels), int(cin), int(cout)))
+
+
+def linear_wide_wgrad_workspace_bytes(pixels, cin, cout):
+    return int(lib().yr_linear_wide_wgrad_workspace_bytes(int(pixels), int(cin), int(cout)))
+
+
+def linear_wide_wgrad(x, dy, out=None, workspace=None):
+    """``linear_wgrad`` for 1..1024 channels on either side (yr_linear_wide_wgrad): x [..., cin], dy [..., cout] float32 with the same
+    leading axes -> dwt [cout, round_up(cin, 4)] = dy.T @ x, pad columns +0; no atomics, the same call gives the same bytes (those of
+    ``linear_wgrad`` where cin and cout are both at most 256).  out: a
+    contiguous float32 tensor of that shape on x's device (every element is written); workspace: a uint8 tensor of at least
+    linear_wide_wgrad_workspace_bytes(pixels, cin, cout) bytes there (its contents do not matter).  Defaults: fresh ones.  Two
+    launches."""
+    pixels, cin = _rows(x, 'x')
+    pdy, cout = _rows(dy, 'dy')
+    if pdy != pixels or dy.device != x.device:
+        raise ValueError('linear_wide_wgrad: dy %s on %s for x %s on %s' % (tuple(dy.shape), dy.device, tuple(x.shape), x.device))
+    if not (1 <= cin <= LINEAR_WIDE_MAX and 1 <= cout <= LINEAR_WIDE_MAX):
+        raise ValueError('linear_wide_wgrad: 1..%d channels, not %d and %d' % (LINEAR_WIDE_MAX, cin, cout))
+    dev = x.device
+    out = _out_like(out, (cout, (cin + 3) // 4 * 4), dev, 'linear_wide_wgrad')
+    ws = _workspace_arg(workspace, linear_wide_wgrad_workspace_bytes(pixels, cin, cout), dev, 'linear_wide_wgrad')
+    with torch.cuda.device(dev):
+        check(lib().yr_linear_wide_wgrad(_ptr(x), cin, _ptr(dy), cout, pixels, cin, cout, _ptr(ws), ws.numel(), _ptr(out), stream_ptr(dev)))
     return out
 
 
