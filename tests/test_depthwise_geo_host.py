@@ -48,9 +48,12 @@ def test_mirror_constants_are_the_sources():
     assert [int(r) for r in re.findall(r'case (\d): (?:if constexpr \(K == 3\) )?return launch_dwp_r<T, K, SE, \1>', lds)] == [1, 2, 3, 4, 5, 6]
     assert 'const int wave_cap = K == 5 ? 12 : 16;' in walk and 'int pc = (int)(160 * 1024 / l);' in walk
     assert 'if ((K * ni * a->U + nw - 1) / nw > 10) continue;' in walk
-    assert 'const bool big = (long long)batch * a.Ho * a.Wo * a.C4 >= (1ll << 21);' in dw and G.DW_BIG_LANES == 1 << 21
-    # the instantiations of the plain form outside YR_DW_EXPERIMENT builds
+    assert 'const bool big = lanes >= (1ll << 21);' in dw and G.DW_BIG_LANES == 1 << 21
+    assert 'return dw_pick_plain<T>(op.k, op.stride, (long long)batch * a.Ho * a.Wo * a.C4)(a, s);' in dw          # what `lanes` is
+    # the instantiations of the plain form outside YR_DW_EXPERIMENT builds: the rest of dw_pick_plain, which holds the `big` rule
     tail = dw[dw.index('const bool big ='):]
+    tail = tail[:tail.index('\n}\n')]
+    assert tail.count('return ') == 4
     assert sorted(set(tuple(int(v) for v in m) for m in re.findall(r'launch_dw<(\d), (\d), (\d), (\d), T>', tail))) == sorted(G.DW_INSTANCES)
 
 

@@ -10,9 +10,10 @@
 // stores.  Workgroups are walked in XCD-contiguous order so that vertically adjacent output rows
 // (which share K-S input rows) are processed on the same XCD and hit its L2 (the round-robin
 // default was measured to fetch each input row ~3x from HBM - profiles/r01_pmc_fetch.txt).
-#include "yr_common.h"
+// Here: dw_kernel with its squeeze-excite form and their launches, and the family's dispatcher launch_depthwise_t - which of the three
+// forms takes an op (dw_pick_family), which instantiation of this one (dw_pick_plain), and the hand-off of a 16-bit map to the other two (DwMap, dw_common.h).
+#include "dw_common.h"
 #include "se_tail.h"
-#include <cstdlib>
 
 // T: element type of the input and output maps (float32, or bf16 / f16 storage: widened on load, rounded to nearest
 // on store; the accumulation, BatchNorm and activation are float32 either way).  Weights, scale, shift: float32.
@@ -47,27 +48,27 @@ __device__ __forceinline__ float4 fma4(float4 a, float4 b, float4 c) {
 
 // One 16-byte load = Q quads of channels (float32: 1, 16-bit: 2 - the same bytes in flight per lane, half the lanes:
 // with 8-byte loads the 16-bit form took exactly as long as float32, the kernel is bound by loads issued, not bytes).
+template <class T> using dw_t8 = T __attribute__((ext_vector_type(8)));
+typedef float dw_f8 __attribute__((ext_vector_type(8)));
+template <class T>
+__device__ __forceinline__ void dw_widen8(dw_t8<T> t, float4 (&v)[2]) {
+    const dw_f8 x = __builtin_convertvector(t, dw_f8);
+    v[0] = make_float4(x[0], x[1], x[2], x[3]);
+    v[1] = make_float4(x[4], x[5], x[6], x[7]);
+}
+template <class T>
+__device__ __forceinline__ dw_t8<T> dw_narrow8(float4 a, float4 b) {
+    return __builtin_convertvector((dw_f8){a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}, dw_t8<T>);
+}
 template <class T, int Q>
 __device__ __forceinline__ void dw_load(const T* p, float4 (&v)[Q]) {
-    if constexpr (Q == 1) {
-        v[0] = *reinterpret_cast<const float4*>(p);
-    } else {
-        typedef T t8 __attribute__((ext_vector_type(8)));
-        typedef float f8 __attribute__((ext_vector_type(8)));
-        const f8 x = __builtin_convertvector(*reinterpret_cast<const t8*>(p), f8);
-        v[0] = make_float4(x[0], x[1], x[2], x[3]);
-        v[1] = make_float4(x[4], x[5], x[6], x[7]);
-    }
+    if constexpr (Q == 1) v[0] = *reinterpret_cast<const float4*>(p);
+    else dw_widen8<T>(*reinterpret_cast<const dw_t8<T>*>(p), v);
 }
 template <class T, int Q>
 __device__ __forceinline__ void dw_store(T* p, const float4 (&v)[Q]) {
-    if constexpr (Q == 1) {
-        *reinterpret_cast<float4*>(p) = v[0];
-    } else {
-        typedef T t8 __attribute__((ext_vector_type(8)));
-        typedef float f8 __attribute__((ext_vector_type(8)));
-        *reinterpret_cast<t8*>(p) = __builtin_convertvector((f8){v[0].x, v[0].y, v[0].z, v[0].w, v[1].x, v[1].y, v[1].z, v[1].w}, t8);
-    }
+    if constexpr (Q == 1) *reinterpret_cast<float4*>(p) = v[0];
+    else *reinterpret_cast<dw_t8<T>*>(p) = dw_narrow8<T>(v[0], v[1]);
 }
 
 template <int K, int S, int XT, int YT, class T, bool SE = false>
@@ -169,13 +170,8 @@ __global__ __launch_bounds__(256) void dw_kernel(DwArgs<T> a) {
                 for (int q = 0; q < Q; ++q) v[q] = yr_apply_act4_t<T>(fma4(acc[j][i][q], sc[q], sh[q]), a.act);
                 if (!SE || live) dw_store<T, Q>(op + (size_t)i * a.ld_out, v);
                 if constexpr (SE) {
-                    if constexpr (Q == 2) {   // the mean is that of the STORED (rounded) values
-                        typedef T t8 __attribute__((ext_vector_type(8)));
-                        typedef float f8 __attribute__((ext_vector_type(8)));
-                        const f8 rv = __builtin_convertvector(__builtin_convertvector((f8){v[0].x, v[0].y, v[0].z, v[0].w, v[1].x, v[1].y, v[1].z, v[1].w}, t8), f8);
-                        v[0] = make_float4(rv[0], rv[1], rv[2], rv[3]);
-                        v[1] = make_float4(rv[4], rv[5], rv[6], rv[7]);
-                    }
+                    if constexpr (Q == 2)   // the mean is that of the STORED (rounded) values
+                        dw_widen8<T>(dw_narrow8<T>(v[0], v[1]), v);
                     if (live) {
 #pragma unroll
                         for (int q = 0; q < Q; ++q) { psum[q].x += v[q].x; psum[q].y += v[q].y; psum[q].z += v[q].z; psum[q].w += v[q].w; }
@@ -233,13 +229,7 @@ static int launch_dw_se(DwArgs<T> a, int expect_rows, hipStream_t s) {
     YR_REQUIRE(blocks * a.B < (1ll << 31), "depthwise: grid too large");
     a.se.arrivals = (unsigned)blocks;   // every workgroup of an image arrives once
     a.nblocks = (unsigned)blocks;
-    static char nm[48];
-    static const int nm_len = snprintf(nm, sizeof(nm), "dw_kernel<%d,%d,%d,1,%s,1>", K, S, XT, yr_dtype_name(yr_elem<T>::dtype));
-    (void)nm_len;
-    yr_note_kernel(nm);
-    hipLaunchKernelGGL((dw_kernel<K, S, XT, 1, T, true>), dim3((unsigned)blocks, a.B), dim3(256), 0, s, a);
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+    return YR_LAUNCH((dw_kernel<K, S, XT, 1, T, true>), dim3((unsigned)blocks, a.B), dim3(256), 0, 0, s, ("dw_kernel<%d,%d,%d,1,%s,1>", K, S, XT, yr_dtype_name(yr_elem<T>::dtype)), a);
 }
 
 template <int K, int S, int XT, int YT, class T>
@@ -250,13 +240,34 @@ static int launch_dw(DwArgs<T> a, hipStream_t s) {
     const long long blocks = (a.total + 255) / 256;
     YR_REQUIRE(blocks < (1ll << 31), "depthwise: grid too large");
     a.nblocks = (unsigned)blocks;
-    static char nm[40];
-    static const int nm_len = snprintf(nm, sizeof(nm), "dw_kernel<%d,%d,%d,%d,%s,0>", K, S, XT, YT, yr_dtype_name(yr_elem<T>::dtype));
-    (void)nm_len;
-    yr_note_kernel(nm);
-    hipLaunchKernelGGL((dw_kernel<K, S, XT, YT, T>), dim3((unsigned)blocks), dim3(256), 0, s, a);
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+    return YR_LAUNCH((dw_kernel<K, S, XT, YT, T>), dim3((unsigned)blocks), dim3(256), 0, 0, s, ("dw_kernel<%d,%d,%d,%d,%s,0>", K, S, XT, YT, yr_dtype_name(yr_elem<T>::dtype)), a);
+}
+
+// Which instantiation of the plain form takes an op, by its numbers (lanes: batch x Ho x Wo x C4, one per 16 bytes of output).
+template <class T> using dw_launch_fn = int (*)(DwArgs<T>, hipStream_t);
+template <class T>
+static dw_launch_fn<T> dw_pick_plain(int k, int stride, long long lanes) {
+    // small maps (13x13, 26x26) keep 1-row patches so the grid still fills the chip
+    const bool big = lanes >= (1ll << 21);
+    // stride 1: 4x1 patches beat 4x2, 2x1, 2x2, 8x1 and 13x1 on every 13/26/52 map of the flagship (tools/dw_probe.py):
+    // the neighbouring rows' re-reads hit L2, and the shorter patch keeps more loads in flight per CU
+    if (k == 3 && stride == 1) return launch_dw<3, 1, 4, 1, T>;
+    if (k == 3 && stride == 2) return big ? launch_dw<3, 2, 2, 2, T> : launch_dw<3, 2, 2, 1, T>;
+    if (k == 5 && stride == 1) return launch_dw<5, 1, 4, 1, T>;
+    return launch_dw<5, 2, 2, 1, T>;
+}
+
+// Which form takes an op, by its numbers (lds_form, walk_form: YOLORET_DW_LDS / YOLORET_DW_WALK as the launcher read them).  16-bit
+// 5 x 5 / 3 x 3 stride 1 on maps with at least one 64-channel chunk: the LDS forms (bit-identical maps; their SE rows are their tiles
+// or quanta - compiler.se_partials_from_depthwise sizes the buffer for whichever form the switches select).  Round 4: the walking form
+// - whole column blocks, rows walked once - for the 5 x 5 maps (tools/dwq_probe.sh: 26 x 26 x 672 @128 83 -> 66 us, SE form 106 -> 72;
+// the others -1 .. -10 %); the 3 x 3 maps are close to the HBM rate in either form and keep the tile walk (52 x 52 x 128 @128: 32 us
+// against 35).
+enum DwFamily { DW_PLAIN, DW_TILES, DW_WALK };   // dw_kernel | dwp_kernel (depthwise_lds.hip) | dwq_kernel (depthwise_walk.hip)
+static inline DwFamily dw_pick_family(int elem_bytes, int k, int stride, int c, bool lds_form, bool walk_form) {
+    if (elem_bytes != 2 || !lds_form || stride != 1 || c < 64) return DW_PLAIN;
+    if (walk_form && k == 5) return DW_WALK;
+    return k == 5 || k == 3 ? DW_TILES : DW_PLAIN;
 }
 
 template <class T>
@@ -292,25 +303,19 @@ static int launch_depthwise_t(const yr_op& op, int batch, hipStream_t s) {
         if (rc) return rc;
     }
     if (op.gate) YR_REQUIRE(op.gate_ld % 4 == 0 && op.gate_ld >= yr_round_up(in.c, V) && ((uintptr_t)op.gate % 16) == 0, "depthwise: bad SE partial-sum buffer");
-    // 16-bit 5x5 / 3x3 stride 1 on maps with at least one 64-channel chunk: the LDS-tiled form (depthwise_lds.hip, bit-identical
-    // maps; its SE rows are its tiles - compiler.se_partials_from_depthwise sizes the buffer for whichever form
-    // YOLORET_DW_LDS selects, 0 keeps this kernel for A/B runs)
-    if constexpr (sizeof(T) == 2) {
+    if constexpr (sizeof(T) == 2) {   // (0 in either switch keeps the earlier form for A/B runs)
 #ifdef YR_DW_EXPERIMENT
         const bool lds_form = !(getenv("YOLORET_DW_LDS") && atoi(getenv("YOLORET_DW_LDS")) == 0);   // re-read per launch
 #else
         static const bool lds_form = !(getenv("YOLORET_DW_LDS") && atoi(getenv("YOLORET_DW_LDS")) == 0);
 #endif
-        // (round 4: the walking form - whole column blocks, rows walked once - unless YOLORET_DW_WALK=0 keeps the tile walk for A/B runs)
         static const int walk_form = getenv("YOLORET_DW_WALK") ? atoi(getenv("YOLORET_DW_WALK")) : 1;
-        // for the 5 x 5 maps (tools/dwq_probe.sh: 26 x 26 x 672 @128 83 -> 66 us, SE form 106 -> 72; the others -1 .. -10 %); the 3 x 3
-        // maps are close to the HBM rate in either form and keep the tile walk (52 x 52 x 128 @128: 32 us against 35)
-        if (lds_form && walk_form && op.k == 5 && op.stride == 1 && in.c >= 64)
-            return yr_launch_depthwise_walk(op.dtype, op.k, in.ptr, op.wgt, op.scale, op.shift, op.out, batch, in.h, in.w, a.C4, a.ld_in, a.ld_w, a.ld_out,
-                                            a.pad_t, a.pad_l, a.act, const_cast<float*>(op.gate), op.gate_ld, op.se_reduced, s);
-        if (lds_form && (op.k == 5 || op.k == 3) && op.stride == 1 && in.c >= 64)
-            return yr_launch_depthwise_lds(op.dtype, op.k, in.ptr, op.wgt, op.scale, op.shift, op.out, batch, in.h, in.w, a.C4, a.ld_in, a.ld_w, a.ld_out,
-                                            a.pad_t, a.pad_l, a.act, const_cast<float*>(op.gate), op.gate_ld, op.se_reduced, s);
+        const DwFamily fam = dw_pick_family(sizeof(T), op.k, op.stride, in.c, lds_form, walk_form != 0);
+        if (fam != DW_PLAIN) {
+            const DwMap m = {op.dtype, in.ptr, op.wgt, op.scale, op.shift, op.out, batch, in.h, in.w, a.C4, a.ld_in, a.ld_w, a.ld_out,
+                             a.pad_t, a.pad_l, a.act, const_cast<float*>(op.gate), op.gate_ld};
+            return fam == DW_WALK ? yr_launch_depthwise_walk(m, op.k, op.se_reduced, s) : yr_launch_depthwise_lds(m, op.k, op.se_reduced, s);
+        }
     }
     if (op.gate) {   // SE form: `gate` is an OUTPUT here - float32 [B][workgroups per image][gate_ld] channel sums
         a.part = const_cast<float*>(op.gate); a.ld_part = op.gate_ld;
@@ -332,14 +337,7 @@ static int launch_depthwise_t(const yr_op& op, int batch, hipStream_t s) {
         if (f == 24) return launch_dw<5, 1, 2, 4, T>(a, s);
     }
 #endif
-    // small maps (13x13, 26x26) keep 1-row patches so the grid still fills the chip
-    const bool big = (long long)batch * a.Ho * a.Wo * a.C4 >= (1ll << 21);
-    // stride 1: 4x1 patches beat 4x2, 2x1, 2x2, 8x1 and 13x1 on every 13/26/52 map of the flagship (tools/dw_probe.py):
-    // the neighbouring rows' re-reads hit L2, and the shorter patch keeps more loads in flight per CU
-    if (op.k == 3 && op.stride == 1) return launch_dw<3, 1, 4, 1, T>(a, s);
-    if (op.k == 3 && op.stride == 2) return big ? launch_dw<3, 2, 2, 2, T>(a, s) : launch_dw<3, 2, 2, 1, T>(a, s);
-    if (op.k == 5 && op.stride == 1) return launch_dw<5, 1, 4, 1, T>(a, s);
-    return launch_dw<5, 2, 2, 1, T>(a, s);
+    return dw_pick_plain<T>(op.k, op.stride, (long long)batch * a.Ho * a.Wo * a.C4)(a, s);
 }
 
 int yr_launch_depthwise(const yr_op& op, int batch, hipStream_t s) { return YR_BY_DTYPE(op.dtype, launch_depthwise_t, op, batch, s); }

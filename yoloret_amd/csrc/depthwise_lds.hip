@@ -26,29 +26,9 @@
 //   packed FMAs instead of 4 (a dependent v_pk_fma_f32 issues only every ~13th slot, tools/peak.hip).  The order of the
 //   adds into any one output is unchanged - (ky, kx) ascending.  Stores leave through a buffer descriptor; rows or columns
 //   beyond the map and channels beyond C pass an offset beyond num_records and are dropped.
-#include "yr_common.h"
-#include <cstdlib>
-
-typedef float dwl_f2 __attribute__((ext_vector_type(2)));
-
-template <class T>
-__device__ __forceinline__ dwl_f2 dwl_widen(unsigned v) {
-    typedef T t2 __attribute__((ext_vector_type(2)));
-    return __builtin_convertvector(__builtin_bit_cast(t2, v), dwl_f2);
-}
-
-// ACT: 0 ReLU6, 1 swish (the fast form of 16-bit stores, yr_apply_act_t), 2 whatever a.act says (a switch per value)
-template <int ACT, class T>
-__device__ __forceinline__ float dwl_act(float v, int act) {
-    if constexpr (ACT == 0) return __builtin_amdgcn_fmed3f(v, 0.0f, 6.0f);
-    else if constexpr (ACT == 1) return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.44269504088896341f));
-    else return yr_apply_act_t<T>(v, act);
-}
-
-// Loads and stores go through buffer descriptors over ONE image of the map (< 1 GB): a lane whose pixel is padding, whose
-// channels are beyond C or whose column is beyond W passes an offset beyond num_records - the load returns zeros, the store
-// is dropped - so neither needs clamped coordinates, selects or a per-lane branch.
-constexpr unsigned DWL_DEAD = 0x80000000u;   // load offsets
+// Here: the tile walk, its band of rows, the tile geometry and its launch; what it shares with depthwise_walk.hip - the lane's
+// arithmetic, the dead offsets - is in dw_common.h.
+#include "dw_common.h"
 
 struct DwpArgs {
     const void* in;      // [B][H][W][ld_in] 16-bit
@@ -75,57 +55,29 @@ struct DwpArgs {
     int dbg;             // YR_DW_EXPERIMENT builds: 1 = no compute phase, 2 = no global loads
 };
 
-template <int V> struct dwp_int { static constexpr int value = V; };
-template <int N, class F>
-__device__ __forceinline__ void dwp_static_for(F&& f) {
-    if constexpr (N > 0) {
-        dwp_static_for<N - 1>(f);
-        f(dwp_int<N - 1>{});
-    }
-}
-
 // One band of R output rows: R + HALO input rows, fully unrolled and branch-free.  rows_ok (per lane): the rows of the band
 // that exist - a band of R - 1 rows, or one cut by the map's last row, computes the others on whatever the tile buffer
 // holds there (zeros beyond the map; LDS reads beyond the allocation return zeros) and stores them nowhere.
-constexpr unsigned DWP_DEAD = 0x40000000u;   // store offsets: row part + pixel part, either may be dead, the sum must not wrap
 constexpr int DWP_ROUNDS = 7;               // DMA rounds of 32 pixels per tile buffer (208 halo pixels at most)
 template <class T, int K, int ACT, bool SE, int R>
-__device__ __forceinline__ void dwp_band(const unsigned* trow, int tpitch, const dwl_f2 (&w)[K * K], dwl_f2 sc, dwl_f2 sh, int act, yr_rsrc dst,
-                                         unsigned orow, unsigned opitch, const unsigned (&ooff)[4], int rows_ok, dwl_f2& psum) {
+__device__ __forceinline__ void dwp_band(const unsigned* trow, int tpitch, const dw_f2 (&w)[K * K], dw_f2 sc, dw_f2 sh, int act, yr_rsrc dst,
+                                         unsigned orow, unsigned opitch, const unsigned (&ooff)[4], int rows_ok, dw_f2& psum) {
     constexpr int HALO = K - 1, NC = 4 + HALO;
-    dwl_f2 acc[K][4];
-    unsigned raw[NC];   // the NEXT input row: its reads are issued a step ahead, under the taps of this one
-#pragma unroll
-    for (int c = 0; c < NC; ++c) raw[c] = trow[c * 32];
-    dwp_static_for<R + HALO>([&](auto RR) {
+    dw_f2 acc[K][4];
+    unsigned raw[NC];
+    dw_row_read(raw, trow);
+    yr_static_for<R + HALO>([&](auto RR) {
         constexpr int rr = decltype(RR)::value;
         constexpr int lo = rr - R + 1 > 0 ? rr - R + 1 : 0, hi = rr < HALO ? rr : HALO;   // input row rr feeds output rows rr - lo ... rr - hi
-        dwl_f2 col[NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) col[c] = dwl_widen<T>(raw[c]);
-        if constexpr (rr + 1 < R + HALO) {
-            const unsigned* p = trow + (rr + 1) * tpitch;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) raw[c] = p[c * 32];
-        }
+        dw_f2 col[NC];
+        dw_row_next<T, (rr + 1 < R + HALO ? rr + 1 : 0)>(col, raw, trow, tpitch);
 #pragma unroll
         for (int kx = 0; kx < K; ++kx)
 #pragma unroll
-            for (int ky = lo; ky <= hi; ++ky)
-#pragma unroll
-                for (int i = 0; i < 4; ++i)   // an output row's first tap starts its sum from a literal zero
-                    acc[(rr - ky) % K][i] = __builtin_elementwise_fma(col[i + kx], w[ky * K + kx], ky == 0 && kx == 0 ? (dwl_f2){0.f, 0.f} : acc[(rr - ky) % K][i]);
+            for (int ky = lo; ky <= hi; ++ky) dw_tap4(acc, (rr - ky) % K, col, kx, w[ky * K + kx], ky == 0 && kx == 0);
         if constexpr (rr >= HALO) {
-            constexpr int o = rr - HALO, sd = o % K;
-            const unsigned ro = o < rows_ok ? orow + (unsigned)o * opitch : DWP_DEAD;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                typedef T t2 __attribute__((ext_vector_type(2)));
-                const dwl_f2 y = __builtin_elementwise_fma(acc[sd][i], sc, sh);
-                const t2 r = __builtin_convertvector((dwl_f2){dwl_act<ACT, T>(y.x, act), dwl_act<ACT, T>(y.y, act)}, t2);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, r), dst, ro + ooff[i], 0, 0);
-                if constexpr (SE) psum += ro + ooff[i] < DWP_DEAD ? __builtin_convertvector(r, dwl_f2) : (dwl_f2){0.f, 0.f};
-            }
+            constexpr int o = rr - HALO;
+            dw_finish_row<T, ACT, SE>(acc[o % K], sc, sh, act, dst, ooff, o < rows_ok ? orow + (unsigned)o * opitch : DW_SDEAD, 0u, psum);   // (the row: a vector offset)
         }
         __builtin_amdgcn_sched_barrier(0);   // (left alone the scheduler hoists the reads and conversions of all rows to the top)
     });
@@ -151,14 +103,15 @@ __global__ __launch_bounds__(256) void dwp_kernel(DwpArgs a) {
     if (a.nstrip <= 4) { strip = (sb >> 1) % a.nstrip; band = (sb >> 1) / a.nstrip * 2 + (sb & 1); }
     else { strip = sb; band = 0; }
     const bool slot_ok = strip < a.nstrip && band < a.nband;
+    // (the lane's channel pair, taps and BatchNorm pair - also in depthwise_walk.hip: sharing them changes the code of both kernels)
     const int cfirst = cc * 64 + cp * 2;
     const bool chan_ok = cfirst < a.C8 * 8;
     const int cl = chan_ok ? cfirst : 0;
-    dwl_f2 w[KK];
+    dw_f2 w[KK];
 #pragma unroll
-    for (int k = 0; k < KK; ++k) w[k] = *reinterpret_cast<const dwl_f2*>(a.w + (size_t)k * a.ld_w + cl);
-    const dwl_f2 sc = *reinterpret_cast<const dwl_f2*>(a.scale + cl);
-    const dwl_f2 sh = *reinterpret_cast<const dwl_f2*>(a.shift + cl);
+    for (int k = 0; k < KK; ++k) w[k] = *reinterpret_cast<const dw_f2*>(a.w + (size_t)k * a.ld_w + cl);
+    const dw_f2 sc = *reinterpret_cast<const dw_f2*>(a.scale + cl);
+    const dw_f2 sh = *reinterpret_cast<const dw_f2*>(a.shift + cl);
 
     // ---- DMA identity: lane = (pixel of the wave's group of 8, channel vector)
     const int cv = lane & 7;
@@ -192,10 +145,10 @@ __global__ __launch_bounds__(256) void dwp_kernel(DwpArgs a) {
                 const bool ok = (unsigned)(iy0 + rr_[u]) < (unsigned)a.H && (unsigned)(ix0 + jj_[u]) < (unsigned)a.W;
                 unsigned voff = tbase + rel_[u];
 #ifdef YR_DW_EXPERIMENT
-                if (a.dbg == 2) voff = DWL_DEAD;
+                if (a.dbg == 2) voff = DW_LDEAD;
 #endif
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(src, (__attribute__((address_space(3))) void*)(dwp_lds + buf * a.buf_words + pw * 32), 16,
-                                                         ok ? voff : DWL_DEAD, 0, 0, 0);
+                                                         ok ? voff : DW_LDEAD, 0, 0, 0);
             }
         }
     };
@@ -218,22 +171,22 @@ __global__ __launch_bounds__(256) void dwp_kernel(DwpArgs a) {
     for (; q < q1; ++q) {
         // this wave's share of tile q has landed: memory operations complete in order, so all but the 4 R stores issued after
         // its loads (waiting for vmcnt(0) would add the round trip of stores nobody waits for to every tile)
-        if (stored) __builtin_amdgcn_s_waitcnt(((4 * R) & 15) | (((4 * R) >> 4) << 14) | 0x0f70);
-        else __builtin_amdgcn_s_waitcnt(0x0f70);
+        if (stored) __builtin_amdgcn_s_waitcnt(yr_waitcnt_imm(4 * R, YR_LGKM_ANY));
+        else __builtin_amdgcn_s_waitcnt(yr_waitcnt_imm(0, YR_LGKM_ANY));
         __syncthreads();                      // everybody's share has; everybody is done with the other buffer
         if constexpr (SE) {
-            if (ptile >= 0 && tid < 32 && chan_ok) {
-                const dwl_f2* red = reinterpret_cast<const dwl_f2*>(dwp_lds + 2 * a.buf_words) + (buf ^ 1) * 256;
-                dwl_f2 sum = red[tid];
+            if (ptile >= 0 && tid < 32 && chan_ok) {   // (the flush - also behind the walk: as a lambda it changes the code of the 60 SE kernels)
+                const dw_f2* red = reinterpret_cast<const dw_f2*>(dwp_lds + 2 * a.buf_words) + (buf ^ 1) * 256;
+                dw_f2 sum = red[tid];
 #pragma unroll
                 for (int k = 1; k < 8; ++k) sum += red[k * 32 + tid];
-                *reinterpret_cast<dwl_f2*>(a.part + ((size_t)pb * (a.ntx * a.nty) + ptile) * a.ld_part + cfirst) = sum;
+                *reinterpret_cast<dw_f2*>(a.part + ((size_t)pb * (a.ntx * a.nty) + ptile) * a.ld_part + cfirst) = sum;
             }
         }
         int ntx_ = tx + 1, nty_ = ty, nb_ = b;
         if (ntx_ == a.ntx) { ntx_ = 0; ++nty_; if (nty_ == a.nty) { nty_ = 0; ++nb_; } }
         if (q + 1 < q1) fetch(ntx_, nty_, nb_, buf ^ 1);
-        dwl_f2 psum = (dwl_f2){0.f, 0.f};
+        dw_f2 psum = (dw_f2){0.f, 0.f};
         const int xo = tx * a.tw + xs, yo = ty * a.th + yb0;
         const int rows_ok = xo < a.W ? min(band_rows, a.H - yo) : 0;
         bool live = rows_ok > 0;
@@ -245,11 +198,11 @@ __global__ __launch_bounds__(256) void dwp_kernel(DwpArgs a) {
             const yr_rsrc dst = yr_make_rsrc(reinterpret_cast<T*>(a.out) + (size_t)b * a.H * a.W * a.ld_out, (unsigned)(a.H * a.W * a.ld_out) * 2u);
             unsigned ooff[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) ooff[i] = chan_ok && xo + i < a.W ? (unsigned)((xo + i) * a.ld_out + cl) * 2u : DWP_DEAD;
+            for (int i = 0; i < 4; ++i) ooff[i] = chan_ok && xo + i < a.W ? (unsigned)((xo + i) * a.ld_out + cl) * 2u : DW_SDEAD;
             dwp_band<T, K, ACT, SE, R>(tslot + buf * a.buf_words, tpitch, w, sc, sh, a.act, dst, (unsigned)yo * opitch, opitch, ooff, rows_ok, psum);
         }
         if constexpr (SE) {
-            reinterpret_cast<dwl_f2*>(dwp_lds + 2 * a.buf_words)[buf * 256 + tid] = psum;   // added up after the next barrier
+            reinterpret_cast<dw_f2*>(dwp_lds + 2 * a.buf_words)[buf * 256 + tid] = psum;   // added up after the next barrier
             ptile = ty * a.ntx + tx; pb = b;
         }
         tx = ntx_; ty = nty_; b = nb_;
@@ -258,11 +211,11 @@ __global__ __launch_bounds__(256) void dwp_kernel(DwpArgs a) {
     if constexpr (SE) {
         __syncthreads();
         if (tid < 32 && chan_ok) {
-            const dwl_f2* red = reinterpret_cast<const dwl_f2*>(dwp_lds + 2 * a.buf_words) + (buf ^ 1) * 256;
-            dwl_f2 sum = red[tid];
+            const dw_f2* red = reinterpret_cast<const dw_f2*>(dwp_lds + 2 * a.buf_words) + (buf ^ 1) * 256;
+            dw_f2 sum = red[tid];
 #pragma unroll
             for (int k = 1; k < 8; ++k) sum += red[k * 32 + tid];
-            *reinterpret_cast<dwl_f2*>(a.part + ((size_t)pb * (a.ntx * a.nty) + ptile) * a.ld_part + cfirst) = sum;
+            *reinterpret_cast<dw_f2*>(a.part + ((size_t)pb * (a.ntx * a.nty) + ptile) * a.ld_part + cfirst) = sum;
         }
     }
 }
@@ -271,13 +224,13 @@ __global__ __launch_bounds__(256) void dwp_kernel(DwpArgs a) {
 // (192 with the squeeze-excite partial sums behind them).  Tile widths with an even number of 4-column strips (a wave =
 // one band); the rows of a tile go to the bands evenly, R = the larger share.  Among the widths take the one with the least
 // lane-time per map: tiles x (per output row: the taps + BatchNorm, activation, store; per input row of a band:
-// conversions and LDS reads; per DMA round; a fixed cost per tile) - instruction counts of the kernel, not fitted.
+// conversions and LDS reads; per DMA round; a fixed cost per tile) - instruction counts of the kernel, not fitted.  A function of
+// the map's shape alone (force: YR_DWL_TW as the launcher read it, or null - one tile width only).
 constexpr int DWP_MAX_R = 6;
-static bool dwp_geometry(int H, int W, int K, bool se, DwpArgs* a, int* R) {
+static bool dwp_geometry(int H, int W, int K, bool se, const char* force, DwpArgs* a, int* R) {
     const int halo = K - 1;
     const int cap = se ? 192 : 208;
     const int row_cost = K * K * 4 + 21, in_cost = 3 * (4 + halo), round_cost = 12, tile_cost = 60;
-    const char* force = getenv("YR_DWL_TW");
     long long best = 0;
     for (int tw = 8; tw <= 32; tw += 8) {
         if (force && atoi(force) != tw) continue;
@@ -306,24 +259,16 @@ static bool dwp_geometry(int H, int W, int K, bool se, DwpArgs* a, int* R) {
 
 template <class T, int K, bool SE, int R>
 static int launch_dwp_r(const DwpArgs& a, size_t lds, hipStream_t s) {
-    const int actv = a.act == YR_ACT_RELU6 ? 0 : (a.act == YR_ACT_SWISH ? 1 : 2);
-    static char nm[3][48];   // spelled like the symbol (element type, K, activation variant, SE, R): profiles are joined on it
-    static const int nm_len = snprintf(nm[0], sizeof(nm[0]), "dwp_kernel<%s,%d,0,%d,%d>", yr_dtype_name(yr_elem<T>::dtype), K, (int)SE, R) +
-                              snprintf(nm[1], sizeof(nm[1]), "dwp_kernel<%s,%d,1,%d,%d>", yr_dtype_name(yr_elem<T>::dtype), K, (int)SE, R) +
-                              snprintf(nm[2], sizeof(nm[2]), "dwp_kernel<%s,%d,2,%d,%d>", yr_dtype_name(yr_elem<T>::dtype), K, (int)SE, R);
-    (void)nm_len;
-    yr_note_kernel(nm[actv]);
-    if (a.act == YR_ACT_RELU6) hipLaunchKernelGGL((dwp_kernel<T, K, 0, SE, R>), dim3(a.nblocks), dim3(256), lds, s, a);
-    else if (a.act == YR_ACT_SWISH) hipLaunchKernelGGL((dwp_kernel<T, K, 1, SE, R>), dim3(a.nblocks), dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((dwp_kernel<T, K, 2, SE, R>), dim3(a.nblocks), dim3(256), lds, s, a);
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+    // (the name: spelled like the symbol - element type, K, activation variant, SE, R -, profiles are joined on it)
+#define DWP_GO(ACT) YR_LAUNCH((dwp_kernel<T, K, ACT, SE, R>), dim3(a.nblocks), dim3(256), lds, 0, s, ("dwp_kernel<%s,%d,%d,%d,%d>", yr_dtype_name(yr_elem<T>::dtype), K, ACT, (int)SE, R), a)
+    return DW_BY_ACT(a.act, DWP_GO);
+#undef DWP_GO
 }
 
 template <class T, int K, bool SE>
 static int launch_dwp_t(DwpArgs a, int expect_rows, hipStream_t s) {
     int R = 0;
-    YR_REQUIRE(dwp_geometry(a.H, a.W, K, SE, &a, &R), "depthwise (LDS form): no tile fits");
+    YR_REQUIRE(dwp_geometry(a.H, a.W, K, SE, getenv("YR_DWL_TW"), &a, &R), "depthwise (LDS form): no tile fits");
     if (SE) YR_REQUIRE(a.ntx * a.nty == expect_rows, "depthwise (LDS form): the SE partial-sum buffer must hold %d rows per image (has %d)", a.ntx * a.nty, expect_rows);
     YR_REQUIRE((long long)a.H * a.W * (a.ld_in > a.ld_out ? a.ld_in : a.ld_out) * 2 < (1ll << 30), "depthwise (LDS form): one image of the map must be below 1 GB");
     a.ncc = (a.C8 + 7) / 8;
@@ -354,23 +299,13 @@ static int launch_dwp_t(DwpArgs a, int expect_rows, hipStream_t s) {
 }
 
 template <class T>
-static int launch_dwp_k(const DwpArgs& a, int k, int part_rows, hipStream_t s) {
+static int launch_dwp_k(const DwMap& m, int k, int part_rows, hipStream_t s) {
+    const DwpArgs a = dw_args_of<DwpArgs>(m);
     if (k == 5) return a.part ? launch_dwp_t<T, 5, true>(a, part_rows, s) : launch_dwp_t<T, 5, false>(a, 0, s);
     return a.part ? launch_dwp_t<T, 3, true>(a, part_rows, s) : launch_dwp_t<T, 3, false>(a, 0, s);
 }
 
-int yr_launch_depthwise_lds(int dtype, int k, const void* in, const float* w, const float* scale, const float* shift, void* out, int B, int H, int W,
-                            int C8, int ld_in, int ld_w, int ld_out, int pad_t, int pad_l, int act, float* part, int ld_part, int part_rows,
-                            hipStream_t s) {
+int yr_launch_depthwise_lds(const DwMap& m, int k, int part_rows, hipStream_t s) {
     if (k != 3 && k != 5) { yr_set_error("depthwise (LDS form): 3 x 3 and 5 x 5 only"); return YR_ERR_ARG; }
-    DwpArgs a;
-    a.in = in; a.w = w; a.scale = scale; a.shift = shift; a.out = out;
-    a.B = B; a.H = H; a.W = W; a.C8 = C8;
-    a.ld_in = ld_in; a.ld_w = ld_w; a.ld_out = ld_out;
-    a.pad_t = pad_t; a.pad_l = pad_l; a.act = act;
-    a.part = part; a.ld_part = ld_part;
-    if (dtype == YR_BF16) return launch_dwp_k<yr_bf16>(a, k, part_rows, s);
-    if (dtype == YR_F16) return launch_dwp_k<yr_f16>(a, k, part_rows, s);
-    yr_set_error("depthwise (LDS form): 16-bit maps only");
-    return YR_ERR_ARG;
+    return DW_BY_16(m.dtype, "LDS", launch_dwp_k, m, k, part_rows, s);
 }

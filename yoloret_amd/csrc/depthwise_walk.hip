@@ -21,27 +21,9 @@
 // of whole quanta so that the workgroups fill the chip (a segment re-reads and re-widens K - 1 halo rows but recomputes no tap).
 // The squeeze-excite form writes one row of channel sums per (column block, quantum) - independent of the segmentation, so the
 // sums (and everything behind them) do not depend on the batch size.
-#include "yr_common.h"
-#include <cstdlib>
-
-typedef float dwq_f2 __attribute__((ext_vector_type(2)));
-
-template <class T>
-__device__ __forceinline__ dwq_f2 dwq_widen(unsigned v) {
-    typedef T t2 __attribute__((ext_vector_type(2)));
-    return __builtin_convertvector(__builtin_bit_cast(t2, v), dwq_f2);
-}
-
-// ACT: 0 ReLU6, 1 swish (the fast form of 16-bit stores, yr_apply_act_t), 2 whatever a.act says (a switch per value)
-template <int ACT, class T>
-__device__ __forceinline__ float dwq_act(float v, int act) {
-    if constexpr (ACT == 0) return __builtin_amdgcn_fmed3f(v, 0.0f, 6.0f);
-    else if constexpr (ACT == 1) return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.44269504088896341f));
-    else return yr_apply_act_t<T>(v, act);
-}
-
-constexpr unsigned DWQ_LDEAD = 0x80000000u;   // load offsets beyond any descriptor: the DMA writes zeros
-constexpr unsigned DWQ_SDEAD = 0x40000000u;   // store offsets: row part (< 2^30) + pixel part (dead or < 2^30) never wraps
+// Here: the walk down a segment, its group of K rows, the quanta, the geometry and its launch; what it shares with depthwise_lds.hip -
+// the lane's arithmetic, the dead offsets - is in dw_common.h.
+#include "dw_common.h"
 
 struct DwqArgs {
     const void* in;      // [B][H][W][ld_in] 16-bit
@@ -66,71 +48,39 @@ struct DwqArgs {
     int ld_part;
 };
 
-template <int V> struct dwq_int { static constexpr int value = V; };
-template <int N, class F>
-__device__ __forceinline__ void dwq_static_for(F&& f) {
-    if constexpr (N > 0) {
-        dwq_static_for<N - 1>(f);
-        f(dwq_int<N - 1>{});
-    }
-}
-
 // One group of K input rows (t0 = the first one's index within the segment, a multiple of K).  Input row t feeds the output
 // rows t - ky (ky = 0 .. HALO) of the segment, whose partial sums sit in acc[(t - ky) % K]; after its taps output row
 // t - HALO is complete.  GUARD: rows of the first group (t < HALO: the output rows above the segment do not exist), of the
 // last ones (t >= n: those below) and rows beyond the segment's last input row take only the taps that exist.
 template <class T, int K, int ACT, bool SE, bool GUARD>
-__device__ __forceinline__ void dwq_group(const unsigned* lrow, int rpitch, dwq_f2 (&acc)[K][4], const dwq_f2 (&w)[K * K], dwq_f2 sc, dwq_f2 sh, int act,
-                                          yr_rsrc dst, unsigned& orow, unsigned opitch, const unsigned (&ooff)[4], int t0, int n, dwq_f2& psum, dwq_f2& psum2) {
+__device__ __forceinline__ void dwq_group(const unsigned* lrow, int rpitch, dw_f2 (&acc)[K][4], const dw_f2 (&w)[K * K], dw_f2 sc, dw_f2 sh, int act,
+                                          yr_rsrc dst, unsigned& orow, unsigned opitch, const unsigned (&ooff)[4], int t0, int n, dw_f2& psum, dw_f2& psum2) {
     constexpr int HALO = K - 1, NC = 4 + HALO;
-    unsigned raw[NC];   // the NEXT input row: its reads are issued a step ahead, under the taps of this one
-#pragma unroll
-    for (int c = 0; c < NC; ++c) raw[c] = lrow[c * 32];
-    dwq_static_for<K>([&](auto UU) {
+    unsigned raw[NC];
+    dw_row_read(raw, lrow);
+    yr_static_for<K>([&](auto UU) {
         constexpr int u = decltype(UU)::value;
         const int t = t0 + u;
-        dwq_f2 col[NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) col[c] = dwq_widen<T>(raw[c]);
-        if constexpr (u + 1 < K) {
-            const unsigned* p = lrow + (u + 1) * rpitch;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) raw[c] = p[c * 32];
-        }
+        dw_f2 col[NC];
+        dw_row_next<T, (u + 1 < K ? u + 1 : 0)>(col, raw, lrow, rpitch);
         if constexpr (!GUARD) {
 #pragma unroll
             for (int kx = 0; kx < K; ++kx)
 #pragma unroll
-                for (int ky = 0; ky <= HALO; ++ky)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)   // an output row's first tap starts its sum from a literal zero
-                        acc[(u - ky + K) % K][i] = __builtin_elementwise_fma(col[i + kx], w[ky * K + kx], ky == 0 && kx == 0 ? (dwq_f2){0.f, 0.f} : acc[(u - ky + K) % K][i]);
+                for (int ky = 0; ky <= HALO; ++ky) dw_tap4(acc, (u - ky + K) % K, col, kx, w[ky * K + kx], ky == 0 && kx == 0);
         } else {
             const int lo = t - n + 1, hi = t < HALO ? t : HALO;   // (wave-uniform)
 #pragma unroll
             for (int ky = 0; ky <= HALO; ++ky)
                 if (ky >= lo && ky <= hi) {
 #pragma unroll
-                    for (int kx = 0; kx < K; ++kx)
-#pragma unroll
-                        for (int i = 0; i < 4; ++i)
-                            acc[(u - ky + K) % K][i] = __builtin_elementwise_fma(col[i + kx], w[ky * K + kx], ky == 0 && kx == 0 ? (dwq_f2){0.f, 0.f} : acc[(u - ky + K) % K][i]);
+                    for (int kx = 0; kx < K; ++kx) dw_tap4(acc, (u - ky + K) % K, col, kx, w[ky * K + kx], ky == 0 && kx == 0);
                 }
         }
         const bool done = GUARD ? (t >= HALO && t < n + HALO) : true;   // output row t - HALO of the segment is complete
         if (done) {
-            constexpr int sd = (u + 1) % K;   // (u - HALO) mod K
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                typedef T t2 __attribute__((ext_vector_type(2)));
-                const dwq_f2 y = __builtin_elementwise_fma(acc[sd][i], sc, sh);
-                const t2 r = __builtin_convertvector((dwq_f2){dwq_act<ACT, T>(y.x, act), dwq_act<ACT, T>(y.y, act)}, t2);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, r), dst, ooff[i], orow, 0);   // (the row: a scalar offset)
-                if constexpr (SE) {   // (the squeeze-excite sums: what was stored; a quantum of rows ends behind row K - 2 of a group)
-                    const dwq_f2 v = ooff[i] < DWQ_SDEAD ? __builtin_convertvector(r, dwq_f2) : (dwq_f2){0.f, 0.f};
-                    if constexpr (u == K - 1) psum2 += v; else psum += v;
-                }
-            }
+            // acc[(u - HALO) mod K]; the row: a scalar offset; the squeeze-excite sums: a quantum of rows ends behind row K - 2 of a group
+            dw_finish_row<T, ACT, SE>(acc[(u + 1) % K], sc, sh, act, dst, ooff, 0u, orow, u == K - 1 ? psum2 : psum);
             orow += opitch;
         }
         __builtin_amdgcn_sched_barrier(0);   // (left alone the scheduler hoists the reads and conversions of all rows to the top)
@@ -165,14 +115,15 @@ __global__ __launch_bounds__(256, K == 5 ? (ACT == 2 ? 2 : 3) : 4) void dwq_kern
     const int st = sl - isl * a.spb;
     const bool slot_ok = isl < a.ni;
     if (!slot_ok) isl = 0;
+    // (the lane's channel pair, taps and BatchNorm pair - also in depthwise_lds.hip: sharing them changes the code of both kernels)
     const int cfirst = cc * 64 + cp * 2;
     const bool chan_ok = cfirst < a.C8 * 8;
     const int cl = chan_ok ? cfirst : 0;
-    dwq_f2 w[KK];
+    dw_f2 w[KK];
 #pragma unroll
-    for (int k = 0; k < KK; ++k) w[k] = *reinterpret_cast<const dwq_f2*>(a.w + (size_t)k * a.ld_w + cl);
-    const dwq_f2 sc = *reinterpret_cast<const dwq_f2*>(a.scale + cl);
-    const dwq_f2 sh = *reinterpret_cast<const dwq_f2*>(a.shift + cl);
+    for (int k = 0; k < KK; ++k) w[k] = *reinterpret_cast<const dw_f2*>(a.w + (size_t)k * a.ld_w + cl);
+    const dw_f2 sc = *reinterpret_cast<const dw_f2*>(a.scale + cl);
+    const dw_f2 sh = *reinterpret_cast<const dw_f2*>(a.shift + cl);
 
     // ---- DMA identity: lane = (pixel of the slot's group of 8, channel vector); a slot = (row of the group x image, 8 pixels)
     const int cv = lane & 7, px = lane >> 3;
@@ -213,7 +164,7 @@ __global__ __launch_bounds__(256, K == 5 ? (ACT == 2 ? 2 : 3) : 4) void dwq_kern
             if (t0 + s_r[j] < n + HALO) {   // (wave-uniform; rows beyond the segment's last input row are never used)
                 const bool ok = (unsigned)(iy0 + s_r[j]) < (unsigned)a.H && ((colmask >> j) & 1u);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(src, (__attribute__((address_space(3))) void*)(lbuf + s_lds[j]), 16,
-                                                         ok ? gbase + s_off[j] + lane_part : DWQ_LDEAD, 0, 0, 0);
+                                                         ok ? gbase + s_off[j] + lane_part : DW_LDEAD, 0, 0, 0);
             }
         }
     };
@@ -226,24 +177,24 @@ __global__ __launch_bounds__(256, K == 5 ? (ACT == 2 ? 2 : 3) : 4) void dwq_kern
         const int xo = xb0 + st * 4;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-            ooff[i] = slot_ok && chan_ok && xo + i < a.W ? (unsigned)isl * imgbytes_out + (unsigned)((xo + i) * a.ld_out + cl) * 2u : DWQ_SDEAD;
+            ooff[i] = slot_ok && chan_ok && xo + i < a.W ? (unsigned)isl * imgbytes_out + (unsigned)((xo + i) * a.ld_out + cl) * 2u : DW_SDEAD;
     }
     unsigned orow = (unsigned)o0 * opitch;
     const unsigned* lslot = dwq_lds + isl * rowwords + st * 4 * 32 + cp;
     const int rpitch = a.ni * rowwords;
     unsigned* red = dwq_lds + 2 * a.gwords;
     const int part_row0 = blk * a.nq + q0;
-    dwq_f2 acc[K][4];
-    dwq_f2 psum = (dwq_f2){0.f, 0.f}, psum2 = (dwq_f2){0.f, 0.f};
+    dw_f2 acc[K][4];
+    dw_f2 psum = (dw_f2){0.f, 0.f}, psum2 = (dw_f2){0.f, 0.f};
     auto flush = [&](int qi, int par) {   // one row of `part`: the slots' sums of quantum qi, added up in a fixed order
-        dwq_f2* rd = reinterpret_cast<dwq_f2*>(red) + par * 256;
+        dw_f2* rd = reinterpret_cast<dw_f2*>(red) + par * 256;
         rd[tid] = psum;
         __syncthreads();
         if (tid < a.ni * 32 && chan_ok && img0 + (tid >> 5) < a.B) {
-            const dwq_f2* q = rd + (tid >> 5) * a.spb * 32 + (tid & 31);
-            dwq_f2 sum = q[0];
+            const dw_f2* q = rd + (tid >> 5) * a.spb * 32 + (tid & 31);
+            dw_f2 sum = q[0];
             for (int k = 1; k < a.spb; ++k) sum += q[k * 32];
-            *reinterpret_cast<dwq_f2*>(a.part + ((size_t)(img0 + (tid >> 5)) * (a.nblk * a.nq) + part_row0 + qi) * a.ld_part + cfirst) = sum;
+            *reinterpret_cast<dw_f2*>(a.part + ((size_t)(img0 + (tid >> 5)) * (a.nblk * a.nq) + part_row0 + qi) * a.ld_part + cfirst) = sum;
         }
     };
     const int ng = (n + HALO + K - 1) / K;
@@ -253,9 +204,9 @@ __global__ __launch_bounds__(256, K == 5 ? (ACT == 2 ? 2 : 3) : 4) void dwq_kern
     // operations complete in order; group 0 stores one row, every later group K rows)
     auto step = [&](int g, auto GG) {
         constexpr bool guard = decltype(GG)::value != 0;
-        if (g == 0) __builtin_amdgcn_s_waitcnt(0x0f70);
-        else if (g == 1) __builtin_amdgcn_s_waitcnt(4 | 0x0f70);
-        else __builtin_amdgcn_s_waitcnt(((4 * K) & 15) | (((4 * K) >> 4) << 14) | 0x0f70);
+        if (g == 0) __builtin_amdgcn_s_waitcnt(yr_waitcnt_imm(0, YR_LGKM_ANY));
+        else if (g == 1) __builtin_amdgcn_s_waitcnt(yr_waitcnt_imm(4, YR_LGKM_ANY));
+        else __builtin_amdgcn_s_waitcnt(yr_waitcnt_imm(4 * K, YR_LGKM_ANY));
         __syncthreads();                      // everybody's share has; everybody is done with the other buffer
         if (g + 1 < ng) issue(g + 1, buf ^ 1);
         const int t0 = g * K;
@@ -268,15 +219,15 @@ __global__ __launch_bounds__(256, K == 5 ? (ACT == 2 ? 2 : 3) : 4) void dwq_kern
             } else {
                 psum += psum2;
             }
-            psum2 = (dwq_f2){0.f, 0.f};
+            psum2 = (dw_f2){0.f, 0.f};
         }
         buf ^= 1;
     };
     // the first group and those that reach the segment's last K - 1 output rows run the guarded copy
     int g = 0;
-    step(g++, dwq_int<1>{});
-    for (; g * K + K <= n; ++g) step(g, dwq_int<0>{});
-    for (; g < ng; ++g) step(g, dwq_int<1>{});
+    step(g++, yr_int<1>{});
+    for (; g * K + K <= n; ++g) step(g, yr_int<0>{});
+    for (; g < ng; ++g) step(g, yr_int<1>{});
     if constexpr (SE) {
         if (qi * a.Q < n) flush(qi, qi & 1);   // the image's last quantum when it is a short one
     }
@@ -284,7 +235,8 @@ __global__ __launch_bounds__(256, K == 5 ? (ACT == 2 ? 2 : 3) : 4) void dwq_kern
 
 // Geometry.  Column blocks of at most 8 strips (4 waves), two images per workgroup where that keeps more waves resident; row quanta by the
 // map's height alone (compiler.dwl_geometry mirrors nblk x nq: the rows of the squeeze-excite sums); the segmentation of a launch
-// by instruction counts: generations of workgroups x (rows of a segment x the cost of a row + what a segment costs).
+// by instruction counts: generations of workgroups x (rows of a segment x the cost of a row + what a segment costs).  Functions of
+// the op's numbers alone - a's B H W C8 in, its geometry out (force: YR_DWQ_QPS as the launcher read it, 0: the cost model's).
 static void dwq_quanta(int H, int K, int* Q, int* nq) {   // quanta of a multiple of K rows: they end behind row K - 2 of a group
     int q = H / 10;
     if (q < 1) q = 1;
@@ -293,7 +245,7 @@ static void dwq_quanta(int H, int K, int* Q, int* nq) {   // quanta of a multipl
     *nq = (H + *Q - 1) / *Q;
 }
 
-static bool dwq_geometry(int K, bool se, DwqArgs* a, size_t* lds) {
+static bool dwq_geometry(int K, bool se, int force, DwqArgs* a, size_t* lds) {
     const int halo = K - 1;
     const int strips = (a->W + 3) / 4;
     const int wave_cap = K == 5 ? 12 : 16;   // resident waves per CU at the kernel's register count (3 | 4 per SIMD)
@@ -318,7 +270,6 @@ static bool dwq_geometry(int K, bool se, DwqArgs* a, size_t* lds) {
     dwq_quanta(a->H, K, &a->Q, &a->nq);
     a->ncc = (a->C8 + 7) / 8;
     a->nig = (a->B + a->ni - 1) / a->ni;
-    static const int force = getenv("YR_DWQ_QPS") ? atoi(getenv("YR_DWQ_QPS")) : 0;
     const long long slots = 256ll * per_cu, units = (long long)a->ncc * a->nig * a->nblk;
     // time of a launch ~ (what a segment costs) x max(1, segments per resident slot): rows x the instructions of a row + the halo
     // rows' reads and conversions + the fixed part (taps, descriptors, the first group's round trip: about 3.5 rows' worth).
@@ -341,48 +292,32 @@ static bool dwq_geometry(int K, bool se, DwqArgs* a, size_t* lds) {
     return best != 0;
 }
 
+static int dwq_force_qps() { static const int force = getenv("YR_DWQ_QPS") ? atoi(getenv("YR_DWQ_QPS")) : 0; return force; }   // (read once per process)
+
 template <class T, int K, bool SE>
 static int launch_dwq_t(DwqArgs a, int expect_rows, hipStream_t s) {
     size_t lds = 0;
-    YR_REQUIRE(dwq_geometry(K, SE, &a, &lds), "depthwise (walking form): the map's rows do not fit LDS");
+    YR_REQUIRE(dwq_geometry(K, SE, dwq_force_qps(), &a, &lds), "depthwise (walking form): the map's rows do not fit LDS");
     if (SE) YR_REQUIRE(a.nblk * a.nq == expect_rows, "depthwise (walking form): the SE partial-sum buffer must hold %d rows per image (has %d)", a.nblk * a.nq, expect_rows);
     YR_REQUIRE((long long)a.ni * a.H * a.W * (a.ld_in > a.ld_out ? a.ld_in : a.ld_out) * 2 < (1ll << 30), "depthwise (walking form): the images of a workgroup must be below 1 GB");
     const long long nb = (long long)a.ncc * a.nig * a.nblk * a.nseg;
     YR_REQUIRE(nb < (1ll << 31), "depthwise: grid too large");
     a.nblocks = (unsigned)nb;
-    const int actv = a.act == YR_ACT_RELU6 ? 0 : (a.act == YR_ACT_SWISH ? 1 : 2);
-    static char nm[3][48];   // spelled like the symbol (element type, K, activation variant, SE): profiles are joined on it
-    static const int nm_len = snprintf(nm[0], sizeof(nm[0]), "dwq_kernel<%s,%d,0,%d>", yr_dtype_name(yr_elem<T>::dtype), K, (int)SE) +
-                              snprintf(nm[1], sizeof(nm[1]), "dwq_kernel<%s,%d,1,%d>", yr_dtype_name(yr_elem<T>::dtype), K, (int)SE) +
-                              snprintf(nm[2], sizeof(nm[2]), "dwq_kernel<%s,%d,2,%d>", yr_dtype_name(yr_elem<T>::dtype), K, (int)SE);
-    (void)nm_len;
-    yr_note_kernel(nm[actv]);
     const dim3 block(a.nw * 64);   // (at most 256)
-    if (a.act == YR_ACT_RELU6) hipLaunchKernelGGL((dwq_kernel<T, K, 0, SE>), dim3(a.nblocks), block, lds, s, a);
-    else if (a.act == YR_ACT_SWISH) hipLaunchKernelGGL((dwq_kernel<T, K, 1, SE>), dim3(a.nblocks), block, lds, s, a);
-    else hipLaunchKernelGGL((dwq_kernel<T, K, 2, SE>), dim3(a.nblocks), block, lds, s, a);
-    YR_LAUNCH_CHECK();
-    return YR_OK;
+    // (the name: spelled like the symbol - element type, K, activation variant, SE -, profiles are joined on it)
+#define DWQ_GO(ACT) YR_LAUNCH((dwq_kernel<T, K, ACT, SE>), dim3(a.nblocks), block, lds, 0, s, ("dwq_kernel<%s,%d,%d,%d>", yr_dtype_name(yr_elem<T>::dtype), K, ACT, (int)SE), a)
+    return DW_BY_ACT(a.act, DWQ_GO);
+#undef DWQ_GO
 }
 
 template <class T>
-static int launch_dwq_k(const DwqArgs& a, int k, int part_rows, hipStream_t s) {
-    (void)k;   // (5: the 3 x 3 instances were measured against the tile walk - 52 x 52 x 128 @128: 35 us against 32, both at the HBM rate - and are not built)
+static int launch_dwq_k(const DwMap& m, int part_rows, hipStream_t s) {
+    // (K = 5: the 3 x 3 instances were measured against the tile walk - 52 x 52 x 128 @128: 35 us against 32, both at the HBM rate - and are not built)
+    const DwqArgs a = dw_args_of<DwqArgs>(m);
     return a.part ? launch_dwq_t<T, 5, true>(a, part_rows, s) : launch_dwq_t<T, 5, false>(a, 0, s);
 }
 
-int yr_launch_depthwise_walk(int dtype, int k, const void* in, const float* w, const float* scale, const float* shift, void* out, int B, int H, int W,
-                             int C8, int ld_in, int ld_w, int ld_out, int pad_t, int pad_l, int act, float* part, int ld_part, int part_rows,
-                             hipStream_t s) {
+int yr_launch_depthwise_walk(const DwMap& m, int k, int part_rows, hipStream_t s) {
     if (k != 5) { yr_set_error("depthwise (walking form): 5 x 5 only"); return YR_ERR_ARG; }
-    DwqArgs a;
-    a.in = in; a.w = w; a.scale = scale; a.shift = shift; a.out = out;
-    a.B = B; a.H = H; a.W = W; a.C8 = C8;
-    a.ld_in = ld_in; a.ld_w = ld_w; a.ld_out = ld_out;
-    a.pad_t = pad_t; a.pad_l = pad_l; a.act = act;
-    a.part = part; a.ld_part = ld_part;
-    if (dtype == YR_BF16) return launch_dwq_k<yr_bf16>(a, k, part_rows, s);
-    if (dtype == YR_F16) return launch_dwq_k<yr_f16>(a, k, part_rows, s);
-    yr_set_error("depthwise (walking form): 16-bit maps only");
-    return YR_ERR_ARG;
+    return DW_BY_16(m.dtype, "walking", launch_dwq_k, m, part_rows, s);
 }

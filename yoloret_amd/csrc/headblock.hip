@@ -76,7 +76,7 @@ extern "C" int yr_head_regions(int h, int w, int32_t* nsy, int32_t* nsx) {
 }
 
 __device__ __forceinline__ float head_swish(float v) {   // hardware exp2 / rcp: about 1 ulp each (the op's bar is 5e-5)
-    return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.44269504088896341f));
+    return yr_swish_fast(v);
 }
 
 struct HeadRegion { int b, n0, iy, ix, y0, y1, x0, x1, ylo, xlo, RW, RP; };
@@ -143,7 +143,7 @@ __device__ __forceinline__ void head_finish(const HeadArgs& h, const HeadRegion&
                 for (int r = 0; r < 4; ++r) v[r] = __builtin_fmaf(v[r], sc[r], sh[r]);
                 if (conv_relu6) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = __builtin_amdgcn_fmed3f(v[r], 0.f, 6.f);
+                    for (int r = 0; r < 4; ++r) v[r] = yr_relu6_fast(v[r]);
                 } else {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] = yr_apply_act(v[r], a.act);
@@ -217,7 +217,7 @@ __device__ __forceinline__ void head_finish(const HeadArgs& h, const HeadRegion&
                         for (int i = 0; i < 4; ++i) v[i] = head_swish(v[i]);
                     } else if (dw_relu6) {
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) v[i] = __builtin_amdgcn_fmed3f(v[i], 0.f, 6.f);
+                        for (int i = 0; i < 4; ++i) v[i] = yr_relu6_fast(v[i]);
                     } else {
 #pragma unroll
                         for (int i = 0; i < 4; ++i) v[i] = yr_apply_act(v[i], h.dw_act);
@@ -371,7 +371,7 @@ __global__ __launch_bounds__(256, 2) void head2_kernel(HeadArgs h) {
         // one loop body issues chunk ck + 1 and multiplies chunk ck (ck = -1: the prologue's issue of chunk 0) - written out in the
         // loop, not as a lambda called from two places: the closure kept the offset arrays in scratch memory
         for (int ck = -1; ck < nk; ++ck) {
-            if (ck >= 0) __builtin_amdgcn_s_waitcnt(0x0f70);    // vmcnt(0): this wave's share of chunk ck has landed
+            if (ck >= 0) __builtin_amdgcn_s_waitcnt(yr_waitcnt_imm(0, YR_LGKM_ANY));    // vmcnt(0): this wave's share of chunk ck has landed
             __syncthreads();                                    // ... everybody's; everybody is done with the other stage
             if (ck + 1 < nk) {
                 const int ci = ck + 1, stage = ci & 1;

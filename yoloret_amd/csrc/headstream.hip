@@ -42,8 +42,6 @@ typedef __attribute__((address_space(3))) void* hs_lds_ptr;
 #define HS_T(i)
 #endif
 
-__device__ __forceinline__ float hs_swish(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.44269504088896341f)); }
-
 template <int NK, int ROWS, int NW, bool PRE>
 __global__ __launch_bounds__(64 * NW) void hstream_kernel(HsArgs a) {
     constexpr int CHB = 2 * NK * 2048;           // bytes of one pair's weight planes
@@ -291,11 +289,11 @@ __global__ __launch_bounds__(64 * NW) void hstream_kernel(HsArgs a) {
                 // Swish of half a tile row (two values), the store behind the second half
                 constexpr int x = sl - NV, i = x / 4, j = (x / 2) % 2, hf = x % 2;
                 if (a.dw_act == YR_ACT_SWISH) {   // uniform
-                    d[i][j][2 * hf] = hs_swish(d[i][j][2 * hf]);
-                    d[i][j][2 * hf + 1] = hs_swish(d[i][j][2 * hf + 1]);
+                    d[i][j][2 * hf] = yr_swish_fast(d[i][j][2 * hf]);
+                    d[i][j][2 * hf + 1] = yr_swish_fast(d[i][j][2 * hf + 1]);
                 } else if (a.dw_act == YR_ACT_RELU6) {
-                    d[i][j][2 * hf] = __builtin_amdgcn_fmed3f(d[i][j][2 * hf], 0.f, 6.f);
-                    d[i][j][2 * hf + 1] = __builtin_amdgcn_fmed3f(d[i][j][2 * hf + 1], 0.f, 6.f);
+                    d[i][j][2 * hf] = yr_relu6_fast(d[i][j][2 * hf]);
+                    d[i][j][2 * hf + 1] = yr_relu6_fast(d[i][j][2 * hf + 1]);
                 }
                 if constexpr (hf == 1)
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, d[i][j]), osrc, opix[i] == YR_DEAD ? YR_DEAD : opix[i] + 64u * (2 * q + j), 0, 0);
@@ -319,7 +317,7 @@ __global__ __launch_bounds__(64 * NW) void hstream_kernel(HsArgs a) {
 
     // ONE barrier per tile pair: behind barrier q every wave has parked its rows of pair q and the planes of pair q + 1 have landed.
     v4f ec[ROWS][2], en[ROWS][2];
-    __builtin_amdgcn_s_waitcnt(0x0f70);
+    __builtin_amdgcn_s_waitcnt(yr_waitcnt_imm(0, YR_LGKM_ANY));
     __syncthreads();
     HS_T(10)
     {   // the first pair's conv: plain order (once)
@@ -353,8 +351,8 @@ __global__ __launch_bounds__(64 * NW) void hstream_kernel(HsArgs a) {
     constexpr std::true_type Y{};
     constexpr std::false_type N{};
     for (int q = Q0; q + 1 < NQ; ++q) {
-        if (q == Q0) __builtin_amdgcn_s_waitcnt(0x0070);               // vmcnt(0) lgkmcnt(0)
-        else __builtin_amdgcn_s_waitcnt(NST | 0x0070);                // vmcnt(NST) lgkmcnt(0)
+        if (q == Q0) __builtin_amdgcn_s_waitcnt(yr_waitcnt_imm(0, 0));               // vmcnt(0) lgkmcnt(0)
+        else __builtin_amdgcn_s_waitcnt(yr_waitcnt_imm(NST, 0));                // vmcnt(NST) lgkmcnt(0)
         __builtin_amdgcn_s_barrier();
         HS_T(1)
         conv_init(q + 1, en);                    // (its addend loads go out BEFORE the next planes: they are waited for first)
@@ -367,13 +365,13 @@ __global__ __launch_bounds__(64 * NW) void hstream_kernel(HsArgs a) {
         for (int i = 0; i < ROWS; ++i) { ec[i][0] = en[i][0]; ec[i][1] = en[i][1]; }
         HS_T(5)
     }
-    __builtin_amdgcn_s_waitcnt(0x0070);          // vmcnt(0) lgkmcnt(0)
+    __builtin_amdgcn_s_waitcnt(yr_waitcnt_imm(0, 0));          // vmcnt(0) lgkmcnt(0)
     __builtin_amdgcn_s_barrier();
     HS_T(6)
     step(N, NQ - 1, lds_raw, ec, en);
 #ifdef HS_TIMING
     HS_T(7)
-    __builtin_amdgcn_s_waitcnt(0x0f70);
+    __builtin_amdgcn_s_waitcnt(yr_waitcnt_imm(0, YR_LGKM_ANY));
     {
         unsigned tv = 0;
 #pragma unroll

@@ -43,8 +43,6 @@ struct HwArgs {
     SeTail se;
 };
 
-__device__ __forceinline__ float hw_swish(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.44269504088896341f)); }
-
 template <int NKE, int NT, bool PRE, bool GATED>
 #ifndef HW_OCC
 #define HW_OCC 2          // waves per SIMD of the one-chunk kernels (the whole row in registers)
@@ -193,7 +191,7 @@ __global__ __launch_bounds__(256, NKE >= 2 && !(PRE && NKE == 4) ? HW_OCC_SHARED
     };
     auto handover = [&]() __attribute__((always_inline)) {
         asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_waitcnt(0xc07f);       // lgkmcnt(0): this wave's planes are written, its reads of the other buffer are done
+        __builtin_amdgcn_s_waitcnt(yr_waitcnt_imm(YR_VM_ANY, 0));       // lgkmcnt(0): this wave's planes are written, its reads of the other buffer are done
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
     };
@@ -266,10 +264,10 @@ __global__ __launch_bounds__(256, NKE >= 2 && !(PRE && NKE == 4) ? HW_OCC_SHARED
                 mbr_dw_row(d, ec[j], tb[24], tb[28], tb[32]);
                 if (a.dw_act == YR_ACT_SWISH) {   // uniform
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) d[i] = hw_swish(d[i]);
+                    for (int i = 0; i < 4; ++i) d[i] = yr_swish_fast(d[i]);
                 } else if (a.dw_act == YR_ACT_RELU6) {
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) d[i] = __builtin_amdgcn_fmed3f(d[i], 0.f, 6.f);
+                    for (int i = 0; i < 4; ++i) d[i] = yr_relu6_fast(d[i]);
                 }
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, d), osrc, ooff[j] == YR_DEAD ? YR_DEAD : opix + ooff[j], 0, 0);
                 if (ooff[j] != YR_DEAD) psum[j] += d;

@@ -166,10 +166,10 @@ __global__ __launch_bounds__(256, 2) void hwalkh_kernel(HwhArgs a) {
                 mbr_dw_row(d, ec[j], tb[24], tb[28], tb[32]);
                 if (a.dw_act == YR_ACT_SWISH) {   // uniform
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) d[i] = d[i] * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(d[i] * -1.44269504088896341f));
+                    for (int i = 0; i < 4; ++i) d[i] = yr_swish_fast(d[i]);
                 } else if (a.dw_act == YR_ACT_RELU6) {
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) d[i] = __builtin_amdgcn_fmed3f(d[i], 0.f, 6.f);
+                    for (int i = 0; i < 4; ++i) d[i] = yr_relu6_fast(d[i]);
                 }
                 const t4 q = __builtin_convertvector(d, t4);         // the one rounding to the 16-bit type
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, q), osrc, ooff[j] == YR_DEAD ? YR_DEAD : opix + ooff[j], 0, 0);

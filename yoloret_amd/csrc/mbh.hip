@@ -76,8 +76,8 @@ __device__ __forceinline__ mbh_f4 mbh_mfma(mbh_u4 w, mbh_u4 x, mbh_f4 acc) {
 // apply it to 6x the block's input twice).
 template <int ACT>
 __device__ __forceinline__ float mbh_act(float v, int act) {
-    if constexpr (ACT == 0) return __builtin_amdgcn_fmed3f(v, 0.0f, 6.0f);   // clamp in one instruction (== min(max(v,0),6) for finite v)
-    else if constexpr (ACT == 1) return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.44269504088896341f));
+    if constexpr (ACT == 0) return yr_relu6_fast(v);   // clamp in one instruction (== min(max(v,0),6) for finite v)
+    else if constexpr (ACT == 1) return yr_swish_fast(v);
     else return yr_apply_act(v, act);
 }
 

@@ -236,7 +236,7 @@ __global__ __launch_bounds__(64 * NW) void mbk_kernel(MbkArgs a) {
 #pragma unroll
             for (int i = 0; i < NE; ++i)
 #pragma unroll
-                for (int s = 0; s < 4; ++s) d[i][j][s] = __builtin_amdgcn_fmed3f(d[i][j][s], 0.f, 6.f);
+                for (int s = 0; s < 4; ++s) d[i][j][s] = yr_relu6_fast(d[i][j][s]);
         }
         v4u bh[NE], bm[NE];
 #pragma unroll
@@ -343,7 +343,7 @@ __global__ __launch_bounds__(64 * NW) void mbk_kernel(MbkArgs a) {
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
-                for (int s = 0; s < 4; ++s) d[i][j][s] = __builtin_amdgcn_fmed3f(d[i][j][s], 0.f, 6.f);
+                for (int s = 0; s < 4; ++s) d[i][j][s] = yr_relu6_fast(d[i][j][s]);
             const float v[8] = {d[i][0][0], d[i][0][1], d[i][0][2], d[i][0][3], d[i][1][0], d[i][1][1], d[i][1][2], d[i][1][3]};
             mbs_split8(v, bh[i], bm[i]);
         }
@@ -378,13 +378,13 @@ __global__ __launch_bounds__(64 * NW) void mbk_kernel(MbkArgs a) {
     // stage + projection of pair q and the expand conv of pair q + 1 - independent instruction streams (VALU | MFMA) - run in the same
     // stretch of code; chunk q + 2 goes into the buffer chunk q - 1 was read from (three chunk buffers, two sets of parked rows).
     v4f ec[ROWS][2];
-    __builtin_amdgcn_s_waitcnt(0x0f70);         // vmcnt(0): chunks 0 and 1 (this wave's pieces) and the pixel rows
+    __builtin_amdgcn_s_waitcnt(yr_waitcnt_imm(0, YR_LGKM_ANY));         // vmcnt(0): chunks 0 and 1 (this wave's pieces) and the pixel rows
     __syncthreads();
     expand(lds_raw, ec);
     park_rows(0, ec);
     MBK_T(0)
     for (int q = 0; q + 1 < NQ; ++q) {
-        __builtin_amdgcn_s_waitcnt(0x0f70);
+        __builtin_amdgcn_s_waitcnt(yr_waitcnt_imm(0, YR_LGKM_ANY));
         if (EXP != 4) __syncthreads();
         MBK_T(1)
         if (EXP != 5 && !ILV) issue_chunk(q + 2);              // (the interleaved body issues it inside its slices; beyond the last chunk: the last one again, into a buffer nobody reads any more)
@@ -443,7 +443,7 @@ __global__ __launch_bounds__(64 * NW) void mbk_kernel(MbkArgs a) {
     }
 #ifdef MBK_TIMING
     MBK_T(7)
-    __builtin_amdgcn_s_waitcnt(0x0f70);
+    __builtin_amdgcn_s_waitcnt(yr_waitcnt_imm(0, YR_LGKM_ANY));
     if (lane < 8) reinterpret_cast<unsigned*>(a.out)[(size_t)(gridDim.x / (a.strips * a.segs)) * a.Ho * a.Wo * a.ld_out + ((size_t)blockIdx.x * NW + w) * 8 + lane] = (unsigned)tacc[lane];
 #endif
 }

@@ -47,8 +47,8 @@ __device__ __forceinline__ mbn_f4 mbn_mfma(mbn_u4 a, mbn_u4 b, mbn_f4 c) {
 
 template <int ACT>
 __device__ __forceinline__ float mbn_act(float v) {
-    if constexpr (ACT == 0) return __builtin_amdgcn_fmed3f(v, 0.0f, 6.0f);
-    else return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.44269504088896341f));   // swish, as in mbh.hip
+    if constexpr (ACT == 0) return yr_relu6_fast(v);
+    else return yr_swish_fast(v);   // swish, as in mbh.hip
 }
 
 // NE = CexpP / 16 (even, <= 12), NCO = round_up(Cout, 16) / 16 (1 | 2).  More than 96 expanded channels go in PASSES of 96

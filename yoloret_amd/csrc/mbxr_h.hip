@@ -71,7 +71,7 @@ __device__ __forceinline__ void xr_row5(v4f& acc, const v4f e, const v4f w0, con
 template <int ACT>
 __device__ __forceinline__ float xr_act(float v, float hi) {   // hi: 6 (relu6) / 1 (swish) inside the image, 0 outside
     if constexpr (ACT == 0) return __builtin_amdgcn_fmed3f(v, 0.0f, hi);
-    else return hi * (v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.44269504088896341f)));
+    else return hi * yr_swish_fast(v);
 }
 
 // The same on the 4 channels of a lane at once, the multiplies and adds as PACKED float32 instructions (v_pk_mul_f32 / v_pk_add_f32 /

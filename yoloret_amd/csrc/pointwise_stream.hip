@@ -176,7 +176,7 @@ __global__ __launch_bounds__(64 * pwt_waves(NK, ROWS, MODE)) void pwt_kernel(PwA
     else no_fetch();
     PWT_T(0)
     if (bn_i < 16 * run) { ss[bn_i] = a.scale ? bn_sl : 1.f; ss[16 * run + bn_i] = a.shift ? bn_hl : 0.f; }
-    __builtin_amdgcn_s_waitcnt(0x0070);     // vmcnt(0) lgkmcnt(0): this wave's pieces of the planes have landed
+    __builtin_amdgcn_s_waitcnt(yr_waitcnt_imm(0, 0));     // vmcnt(0) lgkmcnt(0): this wave's pieces of the planes have landed
     __syncthreads();
     PWT_T(1)
 
@@ -249,7 +249,7 @@ __global__ __launch_bounds__(64 * pwt_waves(NK, ROWS, MODE)) void pwt_kernel(PwA
                 for (int r = 0; r < 4; ++r) v[r] = __builtin_fmaf(v[r], sc[r], sh[r]);
                 if (clamp_t) {      // (uniform) ReLU6
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = __builtin_amdgcn_fmed3f(v[r], 0.f, 6.f);
+                    for (int r = 0; r < 4; ++r) v[r] = yr_relu6_fast(v[r]);
                 }
                 if (pool_t) {     // (uniform) MaxPooling2D(2) across the 4 adjacent lanes of a window
 #pragma unroll
@@ -284,7 +284,7 @@ __global__ __launch_bounds__(64 * pwt_waves(NK, ROWS, MODE)) void pwt_kernel(PwA
 #endif
     }
 #ifdef PWT_TIMING
-    __builtin_amdgcn_s_waitcnt(0x0070);
+    __builtin_amdgcn_s_waitcnt(yr_waitcnt_imm(0, 0));
     PWT_T(6)
     if (lane < 8 && blockIdx.x < 256) {
         unsigned tv = 0;

@@ -57,7 +57,7 @@ __device__ __forceinline__ sbh_f4 sbh_mfma(sbh_u4 a, sbh_u4 b, sbh_f4 c) {
 
 template <bool RELU6, class T>
 __device__ __forceinline__ float sbh_act(float v, int act) {
-    if constexpr (RELU6) return __builtin_amdgcn_fmed3f(v, 0.0f, 6.0f);
+    if constexpr (RELU6) return yr_relu6_fast(v);
     else return yr_apply_act_t<T>(v, act);
 }
 

@@ -76,12 +76,6 @@ static inline yr_kname yr_kname_fmt(const char* fmt, ...) {
 int yr_launch_stem(const yr_op& op, int batch, hipStream_t s);
 int yr_launch_pointwise(const yr_op& op, int batch, hipStream_t s);
 int yr_launch_depthwise(const yr_op& op, int batch, hipStream_t s);
-int yr_launch_depthwise_lds(int dtype, int k, const void* in, const float* w, const float* scale, const float* shift, void* out, int B, int H, int W,
-                             int C8, int ld_in, int ld_w, int ld_out, int pad_t, int pad_l, int act, float* part, int ld_part, int part_rows,
-                             hipStream_t s);
-int yr_launch_depthwise_walk(int dtype, int k, const void* in, const float* w, const float* scale, const float* shift, void* out, int B, int H, int W,
-                              int C8, int ld_in, int ld_w, int ld_out, int pad_t, int pad_l, int act, float* part, int ld_part, int part_rows,
-                              hipStream_t s);
 int yr_launch_se_mean(const yr_op& op, int batch, hipStream_t s);
 int yr_launch_se_fc(const yr_op& op, int batch, hipStream_t s);
 int yr_launch_wsum(const yr_op& op, int batch, hipStream_t s);
@@ -146,6 +140,10 @@ __device__ __forceinline__ float yr_apply_act(float v, int act) {
 __device__ __forceinline__ float4 yr_apply_act4(float4 v, int act) {
     return make_float4(yr_apply_act(v.x, act), yr_apply_act(v.y, act), yr_apply_act(v.z, act), yr_apply_act(v.w, act));
 }
+// The one-instruction clamp (== min(max(v, 0), 6) for finite v) and the swish on the hardware exp2 and reciprocal (about 1 ulp of
+// float32 each): the forms of the 16-bit kernels and of every kernel that knows its activation at compile time.
+__device__ __forceinline__ float yr_relu6_fast(float v) { return __builtin_amdgcn_fmed3f(v, 0.0f, 6.0f); }
+__device__ __forceinline__ float yr_swish_fast(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.44269504088896341f)); }
 // Activation of a value about to be STORED as T.  16-bit T: the store keeps 8 or 11 significant bits, so swish takes the
 // hardware exp2 and reciprocal (about 1 ulp of float32 each, 5 instructions) instead of the pinned expf and the IEEE
 // division above (28 instructions - as much as the whole 3x3x3 stem convolution per output element).  float32 T: the
@@ -153,7 +151,7 @@ __device__ __forceinline__ float4 yr_apply_act4(float4 v, int act) {
 template <class T>
 __device__ __forceinline__ float yr_apply_act_t(float v, int act) {
     if constexpr (sizeof(T) == 2) {
-        if (act == YR_ACT_SWISH) return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.44269504088896341f));
+        if (act == YR_ACT_SWISH) return yr_swish_fast(v);
     }
     return yr_apply_act(v, act);
 }
@@ -164,6 +162,23 @@ __device__ __forceinline__ float4 yr_apply_act4_t(float4 v, int act) {
 __device__ __forceinline__ float4 yr_max4(float4 a, float4 b) {
     return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w));
 }
+
+// A compile-time loop: f(yr_int<0>{}) ... f(yr_int<N - 1>{}), the index a constant expression inside f.
+template <int V> struct yr_int { static constexpr int value = V; };
+template <int N, class F>
+__device__ __forceinline__ void yr_static_for(F&& f) {
+    if constexpr (N > 0) {
+        yr_static_for<N - 1>(f);
+        f(yr_int<N - 1>{});
+    }
+}
+
+// The immediate of s_waitcnt (gfx9 layout: vmcnt in bits 3:0 and 15:14, expcnt in bits 6:4, lgkmcnt in bits 11:8): wait until at
+// most `vm` vector-memory and `lgkm` LDS / scalar-memory operations are outstanding; a counter at its maximum is not waited for
+// (expcnt never is).
+constexpr int YR_VM_ANY = 63, YR_LGKM_ANY = 15;
+constexpr int yr_waitcnt_imm(int vm, int lgkm) { return (vm & 15) | ((vm >> 4) << 14) | (7 << 4) | ((lgkm & 15) << 8); }
+static_assert(yr_waitcnt_imm(0, YR_LGKM_ANY) == 0x0f70 && yr_waitcnt_imm(0, 0) == 0x0070 && yr_waitcnt_imm(YR_VM_ANY, 0) == 0xc07f, "s_waitcnt layout");
 
 // ---- element types.  float32, or the 16-bit STORAGE types of a reduced-precision plan: kernels widen to float32 on
 // load (exact) and round to nearest-even on store (v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32); arithmetic stays float32
