@@ -972,6 +972,42 @@ size_t yr_linear_wide_wgrad_workspace_bytes(long long pixels, int cin, int cout)
 int    yr_linear_wide_wgrad(const float* x, int x_ld, const float* dy, int dy_ld, long long pixels, int cin, int cout,
                             void* workspace /*device*/, size_t workspace_bytes, float* dwt /*[cout][kp]*/, void* stream);
 
+/* ---- the network entry as a training operator: the dense 3 x 3 convolution of 1..4 -> 1..64 channels every backbone starts with
+ * (code/yolo3/model.py:180,193: MobileNetV2's Conv1; code/yolo3/efficientnet.py: stem_conv; code/train.py:150-216 trains it with every
+ * other layer, tape.gradient at yolo3/train.py:39).  Added under ABI 9 (additive: no struct or existing entry changed).
+ * csrc/stemgrad.hip has the kernels' forms, tests/stemgrad_ref.py is the definition.  The conventions of the depthwise training
+ * entries hold: float32 maps [B][H][W][ld] with 4-byte alignment, stride in {1, 2}, explicit pad_top, pad_left in 0..2 and the
+ * output size (OH, OW), which must be floor((H + pad_top + pad_bottom - 3) / stride) + 1 for some pad_bottom in 0..2 (columns
+ * alike); no float atomics, nothing read before the call wrote it, every named output element written and nothing else (pad channels
+ * [cin, x_ld) and [cout, y_ld) are neither read nor written), the same call gives the same bytes.  YR_ERR_ARG with a message, nothing
+ * launched or written, for a null or misaligned pointer, cin outside 1..4, cout outside 1..64, a stride or pad outside the contract,
+ * a leading dimension below the channels, an output size the geometry does not give, B, H, W, OH or OW above 65535, a short or
+ * misaligned workspace.  The weight w is the Keras kernel [3, 3, cin, cout] as it lies in memory: row r = (ky * 3 + kx) * cin + ci,
+ * cout dense floats a row.
+ * THE ORDER: one fmaf per term and nothing else, every chain from +0, taps row-major and channels innermost.
+ *   forward  y[b][oy][ox][co]: for ky, for kx, for ci: acc = fmaf(x[b][oy s - pad_top + ky][ox s - pad_left + kx][ci], w[r][co], acc)
+ *   dgrad    dx[b][iy][ix][ci]: for ky, for kx with iy + pad_top - ky = oy s and ix + pad_left - kx = ox s, for co:
+ *            acc = fmaf(dy[b][oy][ox][co], w[r][co], acc).  Every dx[..][0..cin) is written: +0 where no window reaches.
+ *   A tap outside the map, or whose output pixel does not exist, is SKIPPED - no operation, not an fmaf with a zero: a chain that
+ *   is -0 stays -0.
+ *   wgrad    dw[r][co] = sum_{b,oy,ox} dy[b][oy][ox][co] * x[b][oy s - pad_top + ky][ox s - pad_left + kx][ci], two launches: stage 1
+ *            cuts the B * OH output rows into chunks of yr_conv3x3_wgrad_chunk(B, OH, OW, cin, cout) rows - the least number that
+ *            gives a chunk 256 pixels and leaves at most 2048 chunks: a function of its arguments only - and writes one
+ *            [9 cin][cout] slab per chunk.  Within a chunk, pixels numbered i = 0, 1, .. in (row, column) order, NS = 4 (cout <= 28),
+ *            2 (cout <= 56) or 1 partial sums s take the pixels i = s, s + NS, .. in order, acc = fmaf(dy, x, acc), skipped taps as
+ *            above, and are added as ((s0 + s1) + s2) + s3.  Stage 2 adds the slabs in index order, the first term slab 0 itself,
+ *            and writes every dw element.  The workspace (16-byte aligned) holds the slabs; its contents before the call do not
+ *            matter.  The two size entries return 0 for sizes the call refuses. */
+int    yr_conv3x3_forward(const float* x, int x_ld, const float* w /*[9*cin][cout]*/, int B, int H, int W, int cin, int cout, int stride,
+                          int pad_top, int pad_left, int OH, int OW, float* y, int y_ld, void* stream);
+int    yr_conv3x3_dgrad(const float* dy, int dy_ld, const float* w /*[9*cin][cout]*/, int B, int H, int W, int cin, int cout, int stride,
+                        int pad_top, int pad_left, int OH, int OW, float* dx, int dx_ld, void* stream);
+int    yr_conv3x3_wgrad_chunk(int B, int OH, int OW, int cin, int cout);
+size_t yr_conv3x3_wgrad_workspace_bytes(int B, int OH, int OW, int cin, int cout);
+int    yr_conv3x3_wgrad(const float* x, int x_ld, const float* dy, int dy_ld, int B, int H, int W, int cin, int cout, int stride,
+                        int pad_top, int pad_left, int OH, int OW, void* workspace /*device*/, size_t workspace_bytes,
+                        float* dw /*[9*cin][cout]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,8 @@ convolutions, depthwise convolutions and frozen BatchNorm + activation on top of
     linear1x1(x, wt)                        x [..., cin], wt [cout, round_up(cin, 4)] (pad columns 0) -> [..., cout]; cin, cout <= 256
     conv1x1(x, wt)                          the same at any width up to 1024 (csrc/linearwide.hip); linear1x1 itself where both are <= 256
     depthwise(x, w, stride=1, padding='same')   x [B, H, W, C], w [k * k, C] (the Keras kernel [k, k, C, 1] reshaped), k in {3, 5}
+    conv3x3(x, w, stride=1, padding='same')     the network entry (csrc/stemgrad.hip): x [B, H, W, cin], w [9 * cin, cout] (the Keras kernel
+                                            [3, 3, cin, cout] reshaped), cin in 1..4, cout in 1..64; differentiable in the image too
     frozen_bn_act(z, scale, shift, act)     act in {None, 'relu6', 'swish'}; scale and shift are frozen: they never get a gradient
     batchnorm_act(z, gamma, beta, moving_mean, moving_var, momentum, eps, act)   BatchNorm in training mode (csrc/bntrain.hip): batch
                                             statistics, gradients for z, gamma and beta, the moving statistics updated in place
@@ -19,6 +21,9 @@ convolutions, depthwise convolutions and frozen BatchNorm + activation on top of
                                             these; wide=True: its 1x1 convolutions through conv1x1
     detector_neck(b1, b2, b3, b4, params, training=True), neck_parameters(model, device), neck_weights(params)   everything yolov3_body
                                             runs behind the backbone (model.py:226-340), its parameters, and their way back into the model
+    mobilenetv2_stem / mobilenetv2_block / mobilenetv2_backbone(images, params, training=True), mobilenetv2_parameters(model, device),
+    backbone_weights(params)                the MobileNetV2 backbone (code/yolo3/model.py:180-190) of these operators, trained like everything else
+    detector(images, params, training=True), detector_parameters(model, device), detector_weights(params)   the backbone plus the neck: images -> logits
 
 Written the way ``_YoloLossFunction`` of yolo3/model.py is: forward and backward are calls of the C entries, only what backward needs
 is saved, a gradient is computed only for an input that requires one (the others are None and their kernel is not launched).  float32
@@ -100,6 +105,27 @@ class _Depthwise(torch.autograd.Function):
             b, oh, ow, c = dy.shape
             dw = rt.depthwise_wgrad(x, dy, k, ctx.stride, ctx.padding,
                                     workspace=_workspace(x.device, rt.depthwise_wgrad_workspace_bytes(b, oh, ow, c, k)))
+        return dx, dw, None, None
+
+
+class _Conv3x3(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, stride, padding):
+        ctx.save_for_backward(x, w)
+        ctx.stride, ctx.padding = stride, padding
+        return rt.conv3x3_forward(x, w, stride, padding)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy = _f32(dy)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = rt.conv3x3_dgrad(dy, w, x.shape[1:3], ctx.stride, ctx.padding)
+        if ctx.needs_input_grad[1]:
+            b, oh, ow, cout = dy.shape
+            dw = rt.conv3x3_wgrad(x, dy, ctx.stride, ctx.padding,
+                                  workspace=_workspace(x.device, rt.conv3x3_wgrad_workspace_bytes(b, oh, ow, x.shape[3], cout)))
         return dx, dw, None, None
 
 
@@ -247,6 +273,14 @@ def depthwise(x, w, stride=1, padding='same'):
     """A k x k depthwise convolution, differentiable in x and w.  padding: 'same' (the Keras rule) or (top, left, bottom, right)."""
     padding = padding if isinstance(padding, str) else tuple(int(v) for v in padding)
     return _Depthwise.apply(x.contiguous(), w.contiguous(), int(stride), padding)
+
+
+def conv3x3(x, w, stride=1, padding='same'):
+    """The dense 3 x 3 convolution every backbone starts with (MobileNetV2's Conv1, EfficientNet's stem_conv; csrc/stemgrad.hip), differentiable
+    in x - the image: what an adversarial loss needs - and in w.  x [B, H, W, cin], w [9 * cin, cout] (the Keras kernel [3, 3, cin, cout]
+    reshaped), cin in 1..4, cout in 1..64.  padding: 'same' (the Keras rule) or (top, left, bottom, right)."""
+    padding = padding if isinstance(padding, str) else tuple(int(v) for v in padding)
+    return _Conv3x3.apply(x.contiguous(), w.contiguous(), int(stride), padding)
 
 
 def frozen_bn_act(z, scale, shift, act=None):
@@ -548,4 +582,146 @@ def neck_weights(params):
             out[key + '/kernel'] = a.reshape(1, 1, a.shape[0], a.shape[1]).copy()
         else:                                                     # a bias, alpha, or a BatchNorm's vector: the name is the Keras name
             out[key] = a.copy()
+    return out
+
+
+# ----------------------------------------------------------------------------- the MobileNetV2 backbone and the whole detector
+MBV2_BN_MOMENTUM, MBV2_BN_EPS = 0.9, 1e-3      # code/yolo3/model.py:180,193 through override.py:207-227 (momentum 0.9); the Keras epsilon of MobileNetV2
+MBV2_STRIDES = (1, 2, 1, 2, 1, 1, 2, 1, 1, 1, 1, 1, 1, 2, 1, 1)      # blocks 0..15 of keras.applications.MobileNetV2 (oracle/model.py:59-88)
+MBV2_TAPS = (15, 12, 5, 2)                      # block_15_add, block_12_add, block_5_add, block_2_add (model.py:186-190); the last is max-pooled by 4
+
+
+def _mbv2_prefix(block):
+    return 'expanded_conv_' if block == 0 else 'block_%d_' % block
+
+
+def mobilenetv2_parameters(model, device):
+    """The parameters of ``model``'s MobileNetV2 backbone up to block 15 as float32 tensors on ``device``, in the layouts the operators
+    take, keyed by the Keras layer name -> {name: tensor}:
+        'Conv1'                                   Keras [3, 3, 3, F] -> [27, F] (``conv3x3``)
+        '<p>expand', '<p>project'                 Keras [1, 1, cin, cout] -> wt [cout, round_up(cin, 4)], pad columns 0 (``conv1x1``); <p> is
+                                                  'expanded_conv_' (block 0, which has no expand convolution) or 'block_<n>_'
+        '<p>depthwise'                            Keras [3, 3, C, 1] -> [9, C]
+        '<bn>/gamma', '<bn>/beta', '<bn>/moving_mean', '<bn>/moving_variance' for <bn> in 'bn_Conv1', '<p>expand_BN', '<p>depthwise_BN', '<p>project_BN'
+        'cin'                                     {Keras name of every 1x1 convolution: its input channels} (integers, for ``backbone_weights``)
+    ``requires_grad`` is set on every kernel, gamma and beta - the reference trains every layer (code/train.py:150-216) -; the moving
+    statistics take no gradient: ``mobilenetv2_backbone(training=True)`` updates them in place."""
+    host = model.get_weights()
+    if host is None:
+        raise ValueError('mobilenetv2_parameters: the model has no weights (set_weights / load_weights)')
+    if 'Conv1/kernel' not in host:
+        raise ValueError('mobilenetv2_parameters: the model has no Conv1/kernel: not a MobileNetV2 backbone (the EfficientNet backbones are not built: '
+                         'their training forward draws a drop-connect mask)')
+
+    def dev(a, grad=True):
+        return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(device).requires_grad_(grad)
+
+    def bn(name):
+        for leaf, grad in _BN_LEAVES:
+            out['%s/%s' % (name, leaf)] = dev(np.asarray(host['%s/%s' % (name, leaf)], np.float32).reshape(-1), grad)
+    k = np.asarray(host['Conv1/kernel'], np.float32)
+    if k.ndim != 4 or k.shape[:2] != (3, 3) or not 1 <= k.shape[2] <= 4 or not 1 <= k.shape[3] <= 64:
+        raise ValueError('mobilenetv2_parameters: Conv1/kernel has shape %s, expected [3, 3, 1..4, 1..64]' % (k.shape,))
+    out = {'Conv1': dev(k.reshape(9 * k.shape[2], k.shape[3])), 'cin': {}}
+    bn('bn_Conv1')
+    for block in range(16):
+        p = _mbv2_prefix(block)
+        for conv in ('expand', 'project'):
+            if conv == 'expand' and p + 'expand/kernel' not in host:      # block 0
+                continue
+            out[p + conv] = dev(_pack_wt(host[p + conv + '/kernel']))
+            out['cin'][p + conv] = int(np.shape(host[p + conv + '/kernel'])[-2])
+            bn(p + conv + '_BN')
+        dw = np.asarray(host[p + 'depthwise/depthwise_kernel'], np.float32)
+        out[p + 'depthwise'] = dev(dw.reshape(dw.shape[0] * dw.shape[1], -1))
+        bn(p + 'depthwise_BN')
+    return out
+
+
+def _mbv2_bn_act(z, params, bn, act, training):
+    stats = [params['%s/%s' % (bn, leaf)] for leaf, _ in _BN_LEAVES]
+    if training:
+        return batchnorm_act(z, *stats, momentum=MBV2_BN_MOMENTUM, eps=MBV2_BN_EPS, act=act)
+    return frozen_bn_act(z, *fold_batchnorm(*stats, eps=MBV2_BN_EPS), act=act)
+
+
+def mobilenetv2_stem(images, params, training=True):
+    """MobileNetV2's entry on images [B, H, W, 3]: Conv1 (3 x 3, stride 2, 'same'; ``conv3x3``) -> bn_Conv1 -> ReLU6 -> [B, H / 2, W / 2, F].
+    params: ``mobilenetv2_parameters``' dictionary.  training: the BatchNorm runs on the statistics of the batch and updates its moving
+    statistics in place (``batchnorm_act``, momentum 0.9, eps 1e-3); otherwise it is folded (``fold_batchnorm`` + ``frozen_bn_act``)."""
+    return _mbv2_bn_act(conv3x3(images, params['Conv1'], 2, 'same'), params, 'bn_Conv1', 'relu6', training)
+
+
+def mobilenetv2_block(x, params, block, training=True):
+    """MobileNetV2's inverted-residual block ``block`` (0..15; oracle/model.py:59-88) on x [B, H, W, cin]: [1x1 expand -> BN -> ReLU6] ->
+    3 x 3 depthwise, 'same', stride ``MBV2_STRIDES[block]`` -> BN -> ReLU6 -> 1x1 project -> BN [-> + x where the stride is 1 and the
+    widths agree].  Block 0 ('expanded_conv_') has no expand convolution; the widths and the expansion are those of the parameters'
+    shapes.  The 1x1 convolutions are ``conv1x1`` (up to 1024 channels on either side).  training: as ``mobilenetv2_stem``."""
+    if not 0 <= int(block) <= 15:
+        raise ValueError('mobilenetv2_block: block must be 0..15, not %r' % (block,))
+    p, stride = _mbv2_prefix(int(block)), MBV2_STRIDES[int(block)]
+    t = x
+    if p + 'expand' in params:
+        t = _mbv2_bn_act(conv1x1(t, params[p + 'expand']), params, p + 'expand_BN', 'relu6', training)
+    t = _mbv2_bn_act(depthwise(t, params[p + 'depthwise'], stride, 'same'), params, p + 'depthwise_BN', 'relu6', training)
+    t = _mbv2_bn_act(conv1x1(t, params[p + 'project']), params, p + 'project_BN', None, training)
+    if stride == 1 and t.shape[-1] == x.shape[-1]:
+        t = t + x
+    return t
+
+
+def mobilenetv2_backbone(images, params, training=True):
+    """images [B, H, W, 3] -> (b1, b2, b3, b4), the taps as ``detector_neck`` takes them: block_15_add [B, H / 32, W / 32, .],
+    block_12_add [B, H / 16, W / 16, .], block_5_add [B, H / 8, W / 8, .] and maxpool(block_2_add, 4) [B, H / 16, W / 16, .]
+    (model.py:186-190).  Differentiable in the images and in every parameter that requires a gradient."""
+    x = mobilenetv2_stem(images, params, training)
+    taps = {}
+    for block in range(16):
+        x = mobilenetv2_block(x, params, block, training)
+        if block in MBV2_TAPS:
+            taps[block] = x
+    return taps[15], taps[12], taps[5], maxpool(taps[2], 4)
+
+
+def _host_arrays(flat):
+    """[(key, tensor)] -> {key: float32 ndarray}: one copy to the host, of all tensors flattened into one"""
+    host = torch.cat([t.detach().reshape(-1).to(torch.float32) for _, t in flat]).cpu().numpy()
+    arrays, at = {}, 0
+    for key, t in flat:
+        arrays[key] = host[at:at + t.numel()].reshape(tuple(t.shape))
+        at += t.numel()
+    return arrays
+
+
+def backbone_weights(params):
+    """The inverse of ``mobilenetv2_parameters`` -> {Keras layer name/leaf: float32 ndarray in the layout ``model.get_weights()`` holds it in},
+    in ``neck_weights``' manner.  One copy to the host: it SYNCHRONISES with the device."""
+    out = {}
+    for key, a in _host_arrays([(k, v) for k, v in params.items() if isinstance(v, torch.Tensor)]).items():
+        if key in params['cin']:                                  # a 1x1 kernel
+            out[key + '/kernel'] = _unpack_wt(a, params['cin'][key])
+        elif key == 'Conv1':                                      # [9 * cin, cout] -> [3, 3, cin, cout]
+            out[key + '/kernel'] = a.reshape(3, 3, a.shape[0] // 9, a.shape[1]).copy()
+        elif key.endswith('depthwise'):                           # [9, C] -> [3, 3, C], as the model holds it
+            out[key + '/depthwise_kernel'] = a.reshape(3, 3, a.shape[1]).copy()
+        else:                                                     # a BatchNorm's vector: the name is the Keras name
+            out[key] = a.copy()
+    return out
+
+
+def detector_parameters(model, device):
+    """-> {'backbone': ``mobilenetv2_parameters(model, device)``, 'neck': ``neck_parameters(model, device)``}: every tensor of ``yolov3_body``."""
+    return {'backbone': mobilenetv2_parameters(model, device), 'neck': neck_parameters(model, device)}
+
+
+def detector(images, params, training=True, num_anchors=3):
+    """``yolov3_body`` on images [B, H, W, 3], differentiable end to end: ``mobilenetv2_backbone`` -> ``detector_neck`` -> [y1, y2, y3], the
+    logits [B, G, G, num_anchors, .] of strides 32, 16 and 8.  params: ``detector_parameters``' dictionary."""
+    return detector_neck(*mobilenetv2_backbone(images, params['backbone'], training), params['neck'], training, num_anchors)
+
+
+def detector_weights(params):
+    """The inverse of ``detector_parameters``: ``backbone_weights`` and ``neck_weights`` in one dictionary for ``model.set_weights``."""
+    out = backbone_weights(params['backbone'])
+    out.update(neck_weights(params['neck']))
     return out

@@ -141,7 +141,8 @@ EXPORTS = ['yr_jpeg_workspace_bytes', 'yr_jpeg_roundtrip_batch', 'yr_augment_geo
            'yr_maxpool_forward', 'yr_maxpool_backward', 'yr_upsample2_forward', 'yr_upsample2_backward',
            'yr_wsum_chunk', 'yr_wsum_workspace_bytes', 'yr_wsum_forward', 'yr_wsum_backward',
            'yr_se_chunk', 'yr_se_workspace_bytes', 'yr_se_forward', 'yr_se_backward',
-           'yr_linear_wide_forward', 'yr_linear_wide_dgrad', 'yr_linear_wide_wgrad_chunk', 'yr_linear_wide_wgrad_workspace_bytes', 'yr_linear_wide_wgrad']
+           'yr_linear_wide_forward', 'yr_linear_wide_dgrad', 'yr_linear_wide_wgrad_chunk', 'yr_linear_wide_wgrad_workspace_bytes', 'yr_linear_wide_wgrad',
+           'yr_conv3x3_forward', 'yr_conv3x3_dgrad', 'yr_conv3x3_wgrad_chunk', 'yr_conv3x3_wgrad_workspace_bytes', 'yr_conv3x3_wgrad']
 
 _lib = None
 
@@ -247,6 +248,13 @@ def lib():
         L.yr_depthwise_wgrad_workspace_bytes.restype = ctypes.c_size_t
         L.yr_depthwise_wgrad_workspace_bytes.argtypes = [ctypes.c_int] * 5
         L.yr_depthwise_wgrad.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_int] * 10 + \
+            [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+        for entry in (L.yr_conv3x3_forward, L.yr_conv3x3_dgrad):
+            entry.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p] + [ctypes.c_int] * 10 + [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        L.yr_conv3x3_wgrad_chunk.argtypes = [ctypes.c_int] * 5
+        L.yr_conv3x3_wgrad_workspace_bytes.restype = ctypes.c_size_t
+        L.yr_conv3x3_wgrad_workspace_bytes.argtypes = [ctypes.c_int] * 5
+        L.yr_conv3x3_wgrad.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_int] * 10 + \
             [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
         L.yr_bn_act_forward.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
@@ -791,6 +799,76 @@ def depthwise_wgrad(x, dy, k, stride=1, padding='same', out=None, workspace=None
     with torch.cuda.device(dev):
         check(lib().yr_depthwise_wgrad(_ptr(x), c, _ptr(dy), c, b, h, wd, c, int(k), int(stride), pt, pl, oh, ow, _ptr(ws), ws.numel(), _ptr(out),
                                        stream_ptr(dev)))
+    return out
+
+
+# ----------------------------------------------------------------------------- the network entry as a training operator (csrc/stemgrad.hip)
+def _conv3x3_w(w, name, cin=None):
+    """w [9 * cin, cout] (the Keras kernel [3, 3, cin, cout] reshaped), cin in 1..4, cout in 1..64 -> (cin, cout)"""
+    _require_cuda_f32(w, name)
+    if w.dim() != 2 or w.shape[0] % 9 or not 1 <= w.shape[0] // 9 <= 4 or not 1 <= w.shape[1] <= 64 or (cin is not None and w.shape[0] != 9 * cin):
+        raise ValueError('%s has shape %s, expected [9 * cin, cout] with cin in 1..4%s and cout in 1..64'
+                         % (name, tuple(w.shape), '' if cin is None else ' (here %d)' % cin))
+    return w.shape[0] // 9, w.shape[1]
+
+
+def conv3x3_forward(x, w, stride=1, padding='same', out=None):
+    """A dense 3 x 3 convolution on a plain map (yr_conv3x3_forward): x [B, H, W, cin] float32, w [9 * cin, cout] (the Keras kernel
+    [3, 3, cin, cout] reshaped), cin in 1..4, cout in 1..64 -> y [B, OH, OW, cout]; stride and padding as ``depthwise_geometry`` reads
+    them.  Every output is one chain of fmaf, taps row-major and channels innermost, padded taps skipped.  One launch."""
+    b, h, wd, cin = _dw_map(x, 'x')
+    _, cout = _conv3x3_w(w, 'w', cin)
+    if w.device != x.device:
+        raise ValueError('conv3x3_forward: w on %s, x on %s' % (w.device, x.device))
+    pt, pl, oh, ow = depthwise_geometry(h, wd, 3, stride, padding)
+    out = _out_like(out, (b, oh, ow, cout), x.device, 'conv3x3_forward')
+    with torch.cuda.device(x.device):
+        check(lib().yr_conv3x3_forward(_ptr(x), cin, _ptr(w), b, h, wd, cin, cout, int(stride), pt, pl, oh, ow, _ptr(out), cout, stream_ptr(x.device)))
+    return out
+
+
+def conv3x3_dgrad(dy, w, input_hw, stride=1, padding='same', out=None):
+    """The input gradient of ``conv3x3_forward`` (yr_conv3x3_dgrad): dy [B, OH, OW, cout], w [9 * cin, cout], input_hw = (H, W) of the
+    forward's input -> dx [B, H, W, cin], every element written once (+0 where no window reaches).  One launch."""
+    b, oh, ow, cout = _dw_map(dy, 'dy')
+    cin, wc = _conv3x3_w(w, 'w')
+    if wc != cout or w.device != dy.device:
+        raise ValueError('conv3x3_dgrad: w %s on %s for dy %s on %s' % (tuple(w.shape), w.device, tuple(dy.shape), dy.device))
+    h, wd = int(input_hw[0]), int(input_hw[1])
+    pt, pl, eh, ew = depthwise_geometry(h, wd, 3, stride, padding)
+    if (eh, ew) != (oh, ow):
+        raise ValueError('conv3x3_dgrad: dy is %d x %d, the forward of a %d x %d map gives %d x %d' % (oh, ow, h, wd, eh, ew))
+    out = _out_like(out, (b, h, wd, cin), dy.device, 'conv3x3_dgrad')
+    with torch.cuda.device(dy.device):
+        check(lib().yr_conv3x3_dgrad(_ptr(dy), cout, _ptr(w), b, h, wd, cin, cout, int(stride), pt, pl, oh, ow, _ptr(out), cin, stream_ptr(dy.device)))
+    return out
+
+
+def conv3x3_wgrad_chunk(b, oh, ow, cin, cout):
+    """Output rows (of the b * oh) per workgroup of the gradient's first stage: a function of these numbers only (0: refused sizes)."""
+    return int(lib().yr_conv3x3_wgrad_chunk(int(b), int(oh), int(ow), int(cin), int(cout)))
+
+
+def conv3x3_wgrad_workspace_bytes(b, oh, ow, cin, cout):
+    return int(lib().yr_conv3x3_wgrad_workspace_bytes(int(b), int(oh), int(ow), int(cin), int(cout)))
+
+
+def conv3x3_wgrad(x, dy, stride=1, padding='same', out=None, workspace=None):
+    """The weight gradient of ``conv3x3_forward`` (yr_conv3x3_wgrad): x [B, H, W, cin], dy [B, OH, OW, cout] -> dw [9 * cin, cout]; two
+    stages, no atomics, the same call gives the same bytes.  workspace: a uint8 tensor of at least
+    conv3x3_wgrad_workspace_bytes(B, OH, OW, cin, cout) bytes (its contents do not matter); default: a fresh one.  Two launches."""
+    b, h, wd, cin = _dw_map(x, 'x')
+    pt, pl, oh, ow = depthwise_geometry(h, wd, 3, stride, padding)
+    _require_cuda_f32(dy, 'dy')
+    if dy.dim() != 4 or tuple(dy.shape[:3]) != (b, oh, ow) or dy.device != x.device or not 1 <= cin <= 4 or not 1 <= dy.shape[3] <= 64:
+        raise ValueError('conv3x3_wgrad: x %s and dy %s on %s, expected x [B, H, W, 1..4] and dy %s + (1..64,) on %s'
+                         % (tuple(x.shape), tuple(dy.shape), dy.device, (b, oh, ow), x.device))
+    cout, dev = dy.shape[3], x.device
+    out = _out_like(out, (9 * cin, cout), dev, 'conv3x3_wgrad')
+    ws = _workspace_arg(workspace, conv3x3_wgrad_workspace_bytes(b, oh, ow, cin, cout), dev, 'conv3x3_wgrad')
+    with torch.cuda.device(dev):
+        check(lib().yr_conv3x3_wgrad(_ptr(x), cin, _ptr(dy), cout, b, h, wd, cin, cout, int(stride), pt, pl, oh, ow, _ptr(ws), ws.numel(), _ptr(out),
+                                     stream_ptr(dev)))
     return out
 
 

@@ -12,8 +12,12 @@ feature model in inference mode (what a frozen Keras layer does), the trained la
 update are the kernels of csrc/headtrain.hip, the loss and its gradient at the logits those of csrc/loss.hip.  ``yolo3.data.AugmentedDataset``
 yields the augmented ``images`` and ``y_true`` on the device.
 
-Not built: the gradient with respect to the layer's input and anything behind it (no parameter of the body has a gradient),
-BatchNorm in training mode, ``use_ema``, ``use_adv`` and the gradient reduction over several devices."""
+Training of every layer: ``DetectorTrainer`` is the same ``_train_step`` and ``fit`` for the reference's stage 2 (code/train.py:150-216, all
+layers trainable) on a MobileNetV2 backbone: ``autograd.detector`` differentiates the whole network on the device.
+
+Not built in ``OutputLayerTrainer``: the gradient with respect to the layer's input and anything behind it (no parameter of the body has
+a gradient) and BatchNorm in training mode - ``DetectorTrainer`` has both.  Not built in either: ``use_ema``, ``use_adv`` and the gradient
+reduction over several devices."""
 import math
 
 import numpy as np
@@ -184,6 +188,147 @@ class OutputLayerTrainer:
                 n += 1
             if n == 0:
                 raise ValueError('OutputLayerTrainer.fit: the training data set is empty')
+            mean = total / torch.full((), float(n), dtype=total.dtype, device=total.device)
+            train_losses.append(np.float32(mean.item()))
+            if val_dataset is not None:
+                self.commit()
+                val_losses.append(np.float32(validation_loss(self.model, val_dataset, self.anchors, self.num_scales, self.ignore_thresh)[0]))
+        self.commit()
+        return train_losses, val_losses
+
+
+class DetectorTrainer:
+    """Trains EVERY layer of ``model`` with Keras Adam: the reference's ``_train_step`` (:18-46) as its stage 2 runs it (code/train.py:150-216
+    sets ``trainable = True`` on all layers, and stage 1 as shipped freezes none): ``autograd.detector(training=True)`` - the MobileNetV2
+    backbone, the RFCR module, the links and the six head blocks, every BatchNorm on the statistics of the batch - -> the sum of
+    ``YoloLoss`` over the scales -> the gradients of every kernel, bias, alpha, gamma and beta -> one Adam update.
+
+    ``model``: ``yolov3_body``'s float32 ``Model`` of a MobileNetV2 backbone with its weights set.  All trained tensors are views of ONE
+    flat device buffer ``w`` (``params`` holds the views in ``autograd.detector_parameters``' layout), and so are their gradients in ``g``
+    and the moments ``m``, ``v``: backward accumulates into the views of ``g`` and one ``adam_step`` launch updates everything; a step
+    synchronises with the host nowhere.  The moving statistics live beside them and are updated in place by the forward.  The state is
+    created on the device of the first batch.  ``commit()`` writes everything back into ``model``.
+
+    Not built: the EfficientNet backbones (their training forward draws a drop-connect mask), 16-bit plans, ``use_ema``, ``use_adv`` and
+    the gradient reduction over several devices."""
+
+    def __init__(self, model, anchors, num_classes, num_scales, learning_rate=1e-3, beta_1=.9, beta_2=.999, epsilon=1e-8, ignore_thresh=.5):
+        self.model = model
+        self.anchors = np.asarray(anchors, np.float32).reshape(-1, 2)
+        self.num_classes, self.num_scales = int(num_classes), int(num_scales)
+        self.learning_rate = self.lr = float(learning_rate)
+        self.beta_1, self.beta_2, self.epsilon, self.ignore_thresh = float(beta_1), float(beta_2), float(epsilon), ignore_thresh
+        yolov3_features(model)          # (raises for a 16-bit plan or outputs that are not bias-free 1x1 convs)
+        weights = model.get_weights()
+        if weights is None:
+            raise ValueError('DetectorTrainer: the model has no weights (set_weights / load_weights)')
+        if 'Conv1/kernel' not in weights:
+            raise ValueError('DetectorTrainer: the model has no Conv1/kernel: only the MobileNetV2 backbones are built (an EfficientNet backbone '
+                             'draws a drop-connect mask in its training forward, which is missing)')
+        if self.num_scales != 3 or len(model.outputs) < 3:
+            raise ValueError('DetectorTrainer: %d scales; yolov3_body\'s three are built' % self.num_scales)
+        self.num_anchors = [o.node.attrs['num_anchors'] for o in model.outputs[:3]]
+        if len(set(self.num_anchors)) != 1:
+            raise ValueError('DetectorTrainer: the scales have %s anchors; one number for all is built' % (self.num_anchors,))
+        for c, a in zip(output_convs(model)[:3], self.num_anchors):
+            if c.output.shape[2] != a * (5 + self.num_classes):
+                raise ValueError('DetectorTrainer: %s has %d filters, %d anchors x (5 + %d classes) expected' % (c.name, c.output.shape[2], a, self.num_classes))
+        self.step = 0           # Adam's t: optimizer.iterations
+        self.device = None
+
+    # ------------------------------------------------------------------ state
+    @staticmethod
+    def _slots(params):
+        """[(dictionary, key)] of every tensor of ``detector_parameters``' nest, in a fixed order"""
+        out = []
+        for d in [params['backbone'], params['neck']['rfcr']] + [v for k, v in params['neck'].items() if k not in ('rfcr', 'cin')]:
+            out.extend((d, k) for k, v in d.items() if isinstance(v, torch.Tensor))
+        return out
+
+    def _ensure(self, device):
+        if self.device is not None:
+            if device != self.device:
+                raise ValueError('DetectorTrainer: the state lives on %s, this batch on %s' % (self.device, device))
+            return
+        from .. import autograd
+        self.params = autograd.detector_parameters(self.model, device)
+        trained = [(d, k) for d, k in self._slots(self.params) if d[k].requires_grad]
+        sizes = [(d[k].numel() + 3) // 4 * 4 for d, k in trained]          # every tensor starts on 16 bytes; the fill is 0 and stays 0 (its gradient is)
+        self.w = torch.zeros((sum(sizes),), dtype=torch.float32, device=device)
+        self.m, self.v, self.g = torch.zeros_like(self.w), torch.zeros_like(self.w), torch.zeros_like(self.w)
+        at = 0
+        for (d, k), size in zip(trained, sizes):          # every trained tensor becomes a view of w whose gradient is the same view of g
+            n, shape = d[k].numel(), tuple(d[k].shape)
+            self.w[at:at + n].copy_(d[k].detach().reshape(-1))
+            view = self.w[at:at + n].view(shape).requires_grad_(True)
+            view.grad = self.g[at:at + n].view(shape)
+            d[k] = view
+            at += size
+        self.trained = trained
+        self.device = device
+
+    # ------------------------------------------------------------------ one step
+    def logits(self, images, training=False):
+        """``autograd.detector`` on the trainer's own parameters -> [B,G,G,A,5+C] per scale.  training=False folds the BatchNorms (it copies
+        their vectors to the host: it synchronises) and changes nothing."""
+        from .. import autograd
+        self._ensure(images.device)
+        if training:
+            return autograd.detector(images, self.params, True, self.num_anchors[0])
+        with torch.no_grad():
+            return autograd.detector(images, self.params, False, self.num_anchors[0])
+
+    def _apply(self, ys, dys):
+        self.g.zero_()          # (backward ADDS into the views of g)
+        torch.autograd.backward(ys, [dy.reshape(y.shape) for y, dy in zip(ys, dys)])
+        self.step += 1
+        rt.adam_step(self.w, self.m, self.v, self.g, rt.adam_alpha(self.lr, self.step, self.beta_1, self.beta_2), self.beta_1, self.beta_2, self.epsilon)
+
+    def train_step(self, images, y_true):
+        """``_train_step`` (:18-46) with every layer trained: the training-mode forward -> the loss and its gradient at the logits -> backward
+        through the neck and the backbone -> one Adam update -> the total loss BEFORE the update, a 0-d float32 device tensor.  Launches
+        only: no host synchronisation.  ``y_true``: the label tensors of the scales (``preprocess_true_boxes``' rows) on the images' device."""
+        y_true = [y_true] if isinstance(y_true, torch.Tensor) else list(y_true)
+        ys = self.logits(images, training=True)
+        total, self.last_terms, dys = yolo_loss_and_grad([y.detach() for y in ys], y_true, self.anchors, self.num_scales, self.ignore_thresh)
+        self._apply(ys, dys)
+        return total
+
+    def train_step_from_boxes(self, images, true_boxes):
+        """``train_step`` with the labels encoded on the device from ground-truth boxes [B,T,5] (``yolo_loss_and_grad_from_boxes``)."""
+        ys = self.logits(images, training=True)
+        total, self.last_terms, dys = yolo_loss_and_grad_from_boxes([y.detach() for y in ys], true_boxes, self.anchors, self.num_classes, self.num_scales,
+                                                                     self.ignore_thresh)
+        self._apply(ys, dys)
+        return total
+
+    # ------------------------------------------------------------------ the loop
+    def commit(self):
+        """Writes every trained tensor and every moving statistic back into ``model`` (``set_weights`` of ``autograd.detector_weights``), so
+        ``model(images)``, ``YoloModel``, ``MAPCallback`` and ``save_weights`` see the trained network.  One copy per half to the host (synchronises)."""
+        if self.device is None:
+            return
+        from .. import autograd
+        weights = self.model.get_weights()
+        weights.update(autograd.detector_weights(self.params))
+        self.model.set_weights(weights)
+
+    def fit(self, epochs, train_dataset, val_dataset=None, use_ema=False, use_adv=False):
+        """``fit`` (:81-128) under the cosine schedule (code/train.py:95-97), as ``OutputLayerTrainer.fit``: datasets are iterables of
+        (images, y_true) on one device -> (train_losses, val_losses), lists of np.float32 (val_losses empty without a val_dataset);
+        ``val_loss`` is ``validation_loss`` of the committed model."""
+        if use_ema or use_adv:
+            raise NotImplementedError('DetectorTrainer.fit: use_ema and use_adv are not built')
+        train_losses, val_losses = [], []
+        for epoch in range(epochs):
+            self.lr = cosine_decay(self.learning_rate, epoch, epochs)
+            total, n = None, 0
+            for images, y_true in train_dataset:
+                loss = self.train_step(images, y_true)
+                total = loss if total is None else total + loss
+                n += 1
+            if n == 0:
+                raise ValueError('DetectorTrainer.fit: the training data set is empty')
             mean = total / torch.full((), float(n), dtype=total.dtype, device=total.device)
             train_losses.append(np.float32(mean.item()))
             if val_dataset is not None:
