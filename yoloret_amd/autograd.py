@@ -48,42 +48,36 @@ def _f32(g):
     return g.to(torch.float32).contiguous()
 
 
-class _Linear1x1(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, wt):
-        ctx.save_for_backward(x, wt)
-        return rt.linear_forward(x, wt)
+class _Linear(torch.autograd.Function):
+    """The body of ``_Linear1x1`` and ``_LinearWide``.  A subclass names its four functions of ``runtime``: the forward, the input
+    gradient, the weight gradient and its workspace size.  They are looked up there at every call."""
+    entries = None
 
-    @staticmethod
-    def backward(ctx, dy):
+    @classmethod
+    def forward(cls, ctx, x, wt):
+        ctx.save_for_backward(x, wt)
+        return getattr(rt, cls.entries[0])(x, wt)
+
+    @classmethod
+    def backward(cls, ctx, dy):
+        _, dgrad, wgrad, workspace_bytes = (getattr(rt, name) for name in cls.entries)
         x, wt = ctx.saved_tensors
         dy = _f32(dy)
         dx = dwt = None
         if ctx.needs_input_grad[0]:
-            dx = rt.linear_dgrad(dy, wt, x.shape[-1])
+            dx = dgrad(dy, wt, x.shape[-1])
         if ctx.needs_input_grad[1]:
             pixels, cin, cout = x.numel() // x.shape[-1], x.shape[-1], wt.shape[0]
-            dwt = rt.linear_wgrad(x, dy, workspace=_workspace(x.device, rt.linear_wgrad_workspace_bytes(pixels, cin, cout)))
+            dwt = wgrad(x, dy, workspace=_workspace(x.device, workspace_bytes(pixels, cin, cout)))
         return dx, dwt
 
 
-class _LinearWide(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, wt):
-        ctx.save_for_backward(x, wt)
-        return rt.linear_wide_forward(x, wt)
+class _Linear1x1(_Linear):
+    entries = ('linear_forward', 'linear_dgrad', 'linear_wgrad', 'linear_wgrad_workspace_bytes')
 
-    @staticmethod
-    def backward(ctx, dy):
-        x, wt = ctx.saved_tensors
-        dy = _f32(dy)
-        dx = dwt = None
-        if ctx.needs_input_grad[0]:
-            dx = rt.linear_wide_dgrad(dy, wt, x.shape[-1])
-        if ctx.needs_input_grad[1]:
-            pixels, cin, cout = x.numel() // x.shape[-1], x.shape[-1], wt.shape[0]
-            dwt = rt.linear_wide_wgrad(x, dy, workspace=_workspace(x.device, rt.linear_wide_wgrad_workspace_bytes(pixels, cin, cout)))
-        return dx, dwt
+
+class _LinearWide(_Linear):
+    entries = ('linear_wide_forward', 'linear_wide_dgrad', 'linear_wide_wgrad', 'linear_wide_wgrad_workspace_bytes')
 
 
 class _Depthwise(torch.autograd.Function):
@@ -349,6 +343,81 @@ def squeeze_excite(x, w1, b1, w2, b2):
     return _SqueezeExcite.apply(x.contiguous(), w1.contiguous(), b1.contiguous(), w2.contiguous(), b2.contiguous())
 
 
+# ----------------------------------------------------------------------------- parameters: the layouts, each way, and BatchNorm in a module
+_BN_LEAVES = (('gamma', True), ('beta', True), ('moving_mean', False), ('moving_variance', False))      # (leaf, trained)
+
+
+def _param(a, device, grad=True):
+    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(device).requires_grad_(grad)
+
+
+def _pack_wt(kernel):
+    """Keras [1, 1, cin, cout] -> wt [cout, round_up(cin, 4)], pad columns 0"""
+    k = np.asarray(kernel, np.float32)
+    cin, cout = k.shape[-2], k.shape[-1]
+    wt = np.zeros((cout, (cin + 3) // 4 * 4), np.float32)
+    wt[:, :cin] = k.reshape(cin, cout).T
+    return wt
+
+
+def _unpack_wt(wt, cin):
+    """wt [cout, round_up(cin, 4)] (host) -> Keras [1, 1, cin, cout]"""
+    return np.ascontiguousarray(wt[:, :cin].T).reshape(1, 1, cin, wt.shape[0])
+
+
+def _pack_dw(kernel):
+    """Keras [k, k, C, 1] -> [k * k, C]"""
+    dw = np.asarray(kernel, np.float32)
+    return dw.reshape(dw.shape[0] * dw.shape[1], -1)
+
+
+def _unpack_dw(w):
+    """[k * k, C] (host) -> [k, k, C], as the model holds a depthwise kernel"""
+    k = int(round(w.shape[0] ** .5))
+    return w.reshape(k, k, w.shape[1]).copy()
+
+
+def _bn_parameters(host, name, device):
+    """The four vectors of the Keras BatchNormalization ``name`` -> {leaf: tensor}, in ``_BN_LEAVES``' order"""
+    return {leaf: _param(np.asarray(host['%s/%s' % (name, leaf)], np.float32).reshape(-1), device, grad) for leaf, grad in _BN_LEAVES}
+
+
+def _bn_act(z, stats, momentum, eps, act, training):
+    """BatchNorm + activation in a module; stats: its four tensors in ``_BN_LEAVES``' order.  training: on the statistics of the batch,
+    the moving ones updated in place (``batchnorm_act``); otherwise folded (``fold_batchnorm`` + ``frozen_bn_act``)."""
+    if training:
+        return batchnorm_act(z, *stats, momentum=momentum, eps=eps, act=act)
+    return frozen_bn_act(z, *fold_batchnorm(*stats, eps=eps), act=act)
+
+
+def _host_arrays(flat):
+    """[(key, tensor)] -> {key: float32 ndarray}: one copy to the host, of all tensors flattened into one"""
+    host = torch.cat([t.detach().reshape(-1).to(torch.float32) for _, t in flat]).cpu().numpy()
+    arrays, at = {}, 0
+    for key, t in flat:
+        arrays[key] = host[at:at + t.numel()].reshape(tuple(t.shape))
+        at += t.numel()
+    return arrays
+
+
+def _keras_weights(flat, cin):
+    """[(Keras layer name [+ '/' + leaf], tensor in the operators' layout)] -> {Keras name/leaf: float32 ndarray as ``model.get_weights()``
+    holds it}; cin: {name of every 1x1 convolution: its input channels} (the packed layout rounds them up to 4)."""
+    out = {}
+    for key, a in _host_arrays(flat).items():
+        if key in cin:                                            # a 1x1 kernel
+            out[key + '/kernel'] = _unpack_wt(a, cin[key])
+        elif key == 'Conv1':                                      # [9 * cin, cout] -> [3, 3, cin, cout]
+            out[key + '/kernel'] = a.reshape(3, 3, a.shape[0] // 9, a.shape[1]).copy()
+        elif key.endswith(('_dw', 'depthwise')):                  # a depthwise kernel of the neck or of the backbone
+            out[key + '/depthwise_kernel'] = _unpack_dw(a)
+        elif key.endswith(('_se_reduce', '_se_expand')):          # [cin, cout] -> [1, 1, cin, cout]
+            out[key + '/kernel'] = a.reshape(1, 1, a.shape[0], a.shape[1]).copy()
+        else:                                                     # a bias, alpha, or a BatchNorm's vector: the name is the Keras name
+            out[key] = a.copy()
+    return out
+
+
 RFCR_BN_MOMENTUM, RFCR_BN_EPS = 0.99, 1e-3      # tf.keras.layers.BatchNormalization() as model.py:24,29 calls it: the Keras defaults
 RFCR_CONVS = ('rfcr_b1c', 'rfcr_b2c', 'rfcr_b3c', 'rfcr_b4c')
 RFCR_BNS = ('rfcr_sep_dw_BN', 'rfcr_sep_pw_BN')
@@ -366,22 +435,12 @@ def rfcr_parameters(model, device):
     host = model.get_weights()
     if host is None:
         raise ValueError('rfcr_parameters: the model has no weights (set_weights / load_weights)')
-
-    def dev(a, grad=True):
-        return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(device).requires_grad_(grad)
-    out = {}
-    for name in RFCR_CONVS + ('rfcr_sep_pw',):
-        k = np.asarray(host[name + '/kernel'], np.float32)
-        cin, cout = k.shape[-2], k.shape[-1]
-        wt = np.zeros((cout, (cin + 3) // 4 * 4), np.float32)
-        wt[:, :cin] = k.reshape(cin, cout).T
-        out[name] = dev(wt)
-    out['rfcr_wsum/alpha'] = dev(np.asarray(host['rfcr_wsum/alpha'], np.float32).reshape(4))
-    dw = np.asarray(host['rfcr_sep_dw/depthwise_kernel'], np.float32)
-    out['rfcr_sep_dw'] = dev(dw.reshape(dw.shape[0] * dw.shape[1], -1))
+    out = {name: _param(_pack_wt(host[name + '/kernel']), device) for name in RFCR_CONVS + ('rfcr_sep_pw',)}
+    out['rfcr_wsum/alpha'] = _param(np.asarray(host['rfcr_wsum/alpha'], np.float32).reshape(4), device)
+    out['rfcr_sep_dw'] = _param(_pack_dw(host['rfcr_sep_dw/depthwise_kernel']), device)
     for bn in RFCR_BNS:
-        for p, grad in (('gamma', True), ('beta', True), ('moving_mean', False), ('moving_variance', False)):
-            out['%s/%s' % (bn, p)] = dev(np.asarray(host['%s/%s' % (bn, p)], np.float32).reshape(-1), grad)
+        for leaf, t in _bn_parameters(host, bn, device).items():
+            out['%s/%s' % (bn, leaf)] = t
     return out
 
 
@@ -396,10 +455,7 @@ def rfcr_module(b1, b2, b3, b4, params, training=True):
     bc = weighted_sum([upsample2(b1c), b2c, maxpool(b3c, 2), b4c], p['rfcr_wsum/alpha'])
 
     def bn_relu6(z, bn):
-        stats = [p['%s/%s' % (bn, k)] for k in ('gamma', 'beta', 'moving_mean', 'moving_variance')]
-        if training:
-            return batchnorm_act(z, *stats, momentum=RFCR_BN_MOMENTUM, eps=RFCR_BN_EPS, act='relu6')
-        return frozen_bn_act(z, *fold_batchnorm(*stats, eps=RFCR_BN_EPS), act='relu6')
+        return _bn_act(z, [p['%s/%s' % (bn, leaf)] for leaf, _ in _BN_LEAVES], RFCR_BN_MOMENTUM, RFCR_BN_EPS, 'relu6', training)
     bc = bn_relu6(depthwise(bc, p['rfcr_sep_dw'], 1, 'same'), RFCR_BNS[0])
     bc = bn_relu6(linear1x1(bc, p['rfcr_sep_pw']), RFCR_BNS[1])
     return concat([b1, maxpool(bc, 2)]), concat([b2, bc]), concat([b3, upsample2(bc)])
@@ -427,27 +483,19 @@ def head_block_parameters(model, name, device):
     host = model.get_weights()
     if host is None:
         raise ValueError('head_block_parameters: the model has no weights (set_weights / load_weights)')
-
-    def dev(a, grad=True):
-        return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(device).requires_grad_(grad)
     out = {'name': name}
     for conv in HEAD_CONVS:
         if conv == '_y' and name + '_y/kernel' not in host:      # a top-down block: yolov3_body discards its y (model.py:240-241)
             continue
-        k = np.asarray(host[name + conv + '/kernel'], np.float32)
-        cin, cout = k.shape[-2], k.shape[-1]
-        wt = np.zeros((cout, (cin + 3) // 4 * 4), np.float32)
-        wt[:, :cin] = k.reshape(cin, cout).T
-        out[conv] = dev(wt)
-    dw = np.asarray(host[name + '_mb_dw/depthwise_kernel'], np.float32)
-    out['_mb_dw'] = dev(dw.reshape(dw.shape[0] * dw.shape[1], -1))
+        out[conv] = _param(_pack_wt(host[name + conv + '/kernel']), device)
+    out['_mb_dw'] = _param(_pack_dw(host[name + '_mb_dw/depthwise_kernel']), device)
     for se in ('_mb_se_reduce', '_mb_se_expand'):
         k = np.asarray(host[name + se + '/kernel'], np.float32)
-        out[se] = dev(k.reshape(k.shape[-2], k.shape[-1]))
-        out[se + '/bias'] = dev(np.asarray(host[name + se + '/bias'], np.float32).reshape(-1))
+        out[se] = _param(k.reshape(k.shape[-2], k.shape[-1]), device)
+        out[se + '/bias'] = _param(np.asarray(host[name + se + '/bias'], np.float32).reshape(-1), device)
     for bn in HEAD_BNS:
-        for p, grad in (('gamma', True), ('beta', True), ('moving_mean', False), ('moving_variance', False)):
-            out['%s/%s' % (bn, p)] = dev(np.asarray(host['%s%s/%s' % (name, bn, p)], np.float32).reshape(-1), grad)
+        for leaf, t in _bn_parameters(host, name + bn, device).items():
+            out['%s/%s' % (bn, leaf)] = t
     return out
 
 
@@ -466,10 +514,7 @@ def head_block(x, params, training=True, wide=False):
     lin = conv1x1 if wide else linear1x1
 
     def bn_act(z, bn, act):
-        stats = [p['%s/%s' % (bn, k)] for k in ('gamma', 'beta', 'moving_mean', 'moving_variance')]
-        if training:
-            return batchnorm_act(z, *stats, momentum=HEAD_BN_MOMENTUM, eps=HEAD_BN_EPS, act=act)
-        return frozen_bn_act(z, *fold_batchnorm(*stats, eps=HEAD_BN_EPS), act=act)
+        return _bn_act(z, [p['%s/%s' % (bn, leaf)] for leaf, _ in _BN_LEAVES], HEAD_BN_MOMENTUM, HEAD_BN_EPS, act, training)
     t = bn_act(lin(x, p['_conv']), '_conv_BN', 'relu6')
     t = bn_act(depthwise(t, p['_mb_dw'], 1, 'same'), '_mb_dw_BN', 'swish')
     t = squeeze_excite(t, p['_mb_se_reduce'], p['_mb_se_reduce/bias'], p['_mb_se_expand'], p['_mb_se_expand/bias'])
@@ -479,16 +524,6 @@ def head_block(x, params, training=True, wide=False):
 
 LINK_CONVS = ('block_20', 'block_24', 'bu3_down', 'bu2_down')
 LINK_BN_MOMENTUM, LINK_BN_EPS = 0.9, 1e-3      # model.py:248-250: BatchNormalization(momentum=0.9), the Keras epsilon
-_BN_LEAVES = (('gamma', True), ('beta', True), ('moving_mean', False), ('moving_variance', False))
-
-
-def _pack_wt(kernel):
-    """Keras [1, 1, cin, cout] -> wt [cout, round_up(cin, 4)], pad columns 0"""
-    k = np.asarray(kernel, np.float32)
-    cin, cout = k.shape[-2], k.shape[-1]
-    wt = np.zeros((cout, (cin + 3) // 4 * 4), np.float32)
-    wt[:, :cin] = k.reshape(cin, cout).T
-    return wt
 
 
 def neck_parameters(model, device):
@@ -503,9 +538,6 @@ def neck_parameters(model, device):
     host = model.get_weights()
     if host is None:
         raise ValueError('neck_parameters: the model has no weights (set_weights / load_weights)')
-
-    def dev(a, grad=True):
-        return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(device).requires_grad_(grad)
     out = {'rfcr': rfcr_parameters(model, device)}
     for name in HEAD_BLOCKS:
         out[name] = head_block_parameters(model, name, device)
@@ -513,10 +545,9 @@ def neck_parameters(model, device):
     convs += [name + '_conv' for name in LINK_CONVS]
     out['cin'] = {c: int(np.shape(host[c + '/kernel'])[-2]) for c in convs}      # the layout rounds a row up to 4: neck_weights needs these
     for name in LINK_CONVS:
-        link = {'_conv': dev(_pack_wt(host[name + '_conv/kernel']))}
-        for leaf, grad in _BN_LEAVES:
-            link['_BN/' + leaf] = dev(np.asarray(host['%s_BN/%s' % (name, leaf)], np.float32).reshape(-1), grad)
-        out[name] = link
+        out[name] = {'_conv': _param(_pack_wt(host[name + '_conv/kernel']), device)}
+        for leaf, t in _bn_parameters(host, name + '_BN', device).items():
+            out[name]['_BN/' + leaf] = t
     return out
 
 
@@ -533,11 +564,7 @@ def detector_neck(b1, b2, b3, b4, params, training=True, num_anchors=3):
 
     def link(x, name):
         q = p[name]
-        stats = [q['_BN/' + leaf] for leaf, _ in _BN_LEAVES]
-        z = conv1x1(x, q['_conv'])
-        if training:
-            return batchnorm_act(z, *stats, momentum=LINK_BN_MOMENTUM, eps=LINK_BN_EPS, act='relu6')
-        return frozen_bn_act(z, *fold_batchnorm(*stats, eps=LINK_BN_EPS), act='relu6')
+        return _bn_act(conv1x1(x, q['_conv']), [q['_BN/' + leaf] for leaf, _ in _BN_LEAVES], LINK_BN_MOMENTUM, LINK_BN_EPS, 'relu6', training)
 
     def head(x, name):
         return head_block(x, p[name], training, wide=True)
@@ -551,38 +578,15 @@ def detector_neck(b1, b2, b3, b4, params, training=True, num_anchors=3):
     return [y.reshape(y.shape[0], y.shape[1], y.shape[2], num_anchors, y.shape[3] // num_anchors) for y in (y1, y2, y3)]
 
 
-def _unpack_wt(wt, cin):
-    """wt [cout, round_up(cin, 4)] (host) -> Keras [1, 1, cin, cout]"""
-    return np.ascontiguousarray(wt[:, :cin].T).reshape(1, 1, cin, wt.shape[0])
-
-
 def neck_weights(params):
     """The inverse of ``neck_parameters`` -> {Keras layer name/leaf: float32 ndarray in the layout ``model.get_weights()`` holds it in}, so that
     ``w = model.get_weights(); w.update(neck_weights(params)); model.set_weights(w)`` ships what was trained.  (The channels a packed
     1x1 weight's rows take are ``params['cin']``, which ``neck_parameters`` records: the layout itself rounds them up to 4.)  One copy
     to the host, of all tensors flattened into one: it SYNCHRONISES with the device."""
-    flat = []      # (Keras layer name + leaf in the operators' naming, tensor)
-    for k, v in params['rfcr'].items():
-        flat.append((k, v))
+    flat = list(params['rfcr'].items())      # (Keras layer name + leaf in the operators' naming, tensor)
     for name in HEAD_BLOCKS + LINK_CONVS:
         flat.extend((name + k, v) for k, v in params[name].items() if isinstance(v, torch.Tensor))
-    host = torch.cat([t.detach().reshape(-1).to(torch.float32) for _, t in flat]).cpu().numpy()
-    arrays, at = {}, 0
-    for key, t in flat:
-        arrays[key] = host[at:at + t.numel()].reshape(tuple(t.shape))
-        at += t.numel()
-    out = {}
-    for key, a in arrays.items():
-        if key in params['cin']:                                  # a 1x1 kernel
-            out[key + '/kernel'] = _unpack_wt(a, params['cin'][key])
-        elif key.endswith('_dw'):                                 # a depthwise kernel [k * k, C] -> [k, k, C], as the model holds it
-            k = int(round(a.shape[0] ** .5))
-            out[key + '/depthwise_kernel'] = a.reshape(k, k, a.shape[1]).copy()
-        elif key.endswith(('_se_reduce', '_se_expand')):          # [cin, cout] -> [1, 1, cin, cout]
-            out[key + '/kernel'] = a.reshape(1, 1, a.shape[0], a.shape[1]).copy()
-        else:                                                     # a bias, alpha, or a BatchNorm's vector: the name is the Keras name
-            out[key] = a.copy()
-    return out
+    return _keras_weights(flat, params['cin'])
 
 
 # ----------------------------------------------------------------------------- the MobileNetV2 backbone and the whole detector
@@ -613,36 +617,29 @@ def mobilenetv2_parameters(model, device):
         raise ValueError('mobilenetv2_parameters: the model has no Conv1/kernel: not a MobileNetV2 backbone (the EfficientNet backbones are not built: '
                          'their training forward draws a drop-connect mask)')
 
-    def dev(a, grad=True):
-        return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(device).requires_grad_(grad)
-
     def bn(name):
-        for leaf, grad in _BN_LEAVES:
-            out['%s/%s' % (name, leaf)] = dev(np.asarray(host['%s/%s' % (name, leaf)], np.float32).reshape(-1), grad)
+        for leaf, t in _bn_parameters(host, name, device).items():
+            out['%s/%s' % (name, leaf)] = t
     k = np.asarray(host['Conv1/kernel'], np.float32)
     if k.ndim != 4 or k.shape[:2] != (3, 3) or not 1 <= k.shape[2] <= 4 or not 1 <= k.shape[3] <= 64:
         raise ValueError('mobilenetv2_parameters: Conv1/kernel has shape %s, expected [3, 3, 1..4, 1..64]' % (k.shape,))
-    out = {'Conv1': dev(k.reshape(9 * k.shape[2], k.shape[3])), 'cin': {}}
+    out = {'Conv1': _param(k.reshape(9 * k.shape[2], k.shape[3]), device), 'cin': {}}
     bn('bn_Conv1')
     for block in range(16):
         p = _mbv2_prefix(block)
         for conv in ('expand', 'project'):
             if conv == 'expand' and p + 'expand/kernel' not in host:      # block 0
                 continue
-            out[p + conv] = dev(_pack_wt(host[p + conv + '/kernel']))
+            out[p + conv] = _param(_pack_wt(host[p + conv + '/kernel']), device)
             out['cin'][p + conv] = int(np.shape(host[p + conv + '/kernel'])[-2])
             bn(p + conv + '_BN')
-        dw = np.asarray(host[p + 'depthwise/depthwise_kernel'], np.float32)
-        out[p + 'depthwise'] = dev(dw.reshape(dw.shape[0] * dw.shape[1], -1))
+        out[p + 'depthwise'] = _param(_pack_dw(host[p + 'depthwise/depthwise_kernel']), device)
         bn(p + 'depthwise_BN')
     return out
 
 
 def _mbv2_bn_act(z, params, bn, act, training):
-    stats = [params['%s/%s' % (bn, leaf)] for leaf, _ in _BN_LEAVES]
-    if training:
-        return batchnorm_act(z, *stats, momentum=MBV2_BN_MOMENTUM, eps=MBV2_BN_EPS, act=act)
-    return frozen_bn_act(z, *fold_batchnorm(*stats, eps=MBV2_BN_EPS), act=act)
+    return _bn_act(z, [params['%s/%s' % (bn, leaf)] for leaf, _ in _BN_LEAVES], MBV2_BN_MOMENTUM, MBV2_BN_EPS, act, training)
 
 
 def mobilenetv2_stem(images, params, training=True):
@@ -683,30 +680,10 @@ def mobilenetv2_backbone(images, params, training=True):
     return taps[15], taps[12], taps[5], maxpool(taps[2], 4)
 
 
-def _host_arrays(flat):
-    """[(key, tensor)] -> {key: float32 ndarray}: one copy to the host, of all tensors flattened into one"""
-    host = torch.cat([t.detach().reshape(-1).to(torch.float32) for _, t in flat]).cpu().numpy()
-    arrays, at = {}, 0
-    for key, t in flat:
-        arrays[key] = host[at:at + t.numel()].reshape(tuple(t.shape))
-        at += t.numel()
-    return arrays
-
-
 def backbone_weights(params):
     """The inverse of ``mobilenetv2_parameters`` -> {Keras layer name/leaf: float32 ndarray in the layout ``model.get_weights()`` holds it in},
     in ``neck_weights``' manner.  One copy to the host: it SYNCHRONISES with the device."""
-    out = {}
-    for key, a in _host_arrays([(k, v) for k, v in params.items() if isinstance(v, torch.Tensor)]).items():
-        if key in params['cin']:                                  # a 1x1 kernel
-            out[key + '/kernel'] = _unpack_wt(a, params['cin'][key])
-        elif key == 'Conv1':                                      # [9 * cin, cout] -> [3, 3, cin, cout]
-            out[key + '/kernel'] = a.reshape(3, 3, a.shape[0] // 9, a.shape[1]).copy()
-        elif key.endswith('depthwise'):                           # [9, C] -> [3, 3, C], as the model holds it
-            out[key + '/depthwise_kernel'] = a.reshape(3, 3, a.shape[1]).copy()
-        else:                                                     # a BatchNorm's vector: the name is the Keras name
-            out[key] = a.copy()
-    return out
+    return _keras_weights([(k, v) for k, v in params.items() if isinstance(v, torch.Tensor)], params['cin'])
 
 
 def detector_parameters(model, device):

@@ -546,26 +546,62 @@ def _rows(t, name):
     return t.numel() // t.shape[-1], t.shape[-1]
 
 
-def _linear_wt(wt, name, cin=None):
+def _linear_wt(wt, name, limit, cin=None):
     _require_cuda_f32(wt, name)
-    if wt.dim() != 2 or wt.shape[1] % 4 or not 1 <= wt.shape[0] <= 256 or (cin is not None and wt.shape[1] != (cin + 3) // 4 * 4):
-        raise ValueError('%s has shape %s, expected [cout, round_up(cin, 4)] with cout <= 256' % (name, tuple(wt.shape)))
+    if wt.dim() != 2 or wt.shape[1] % 4 or not 1 <= wt.shape[0] <= limit or (cin is not None and wt.shape[1] != (cin + 3) // 4 * 4):
+        raise ValueError('%s has shape %s, expected [cout, round_up(cin, 4)] with cout <= %d' % (name, tuple(wt.shape), limit))
+
+
+# The 1x1 operators exist twice, up to 256 channels (csrc/headtrain.hip, csrc/convgrad.hip) and up to LINEAR_WIDE_MAX (csrc/linearwide.hip),
+# behind one set of checks: ``name`` is the public function's (the prefix of its messages), ``limit`` the width it takes, ``entry`` its
+# C entry (and, with '_workspace_bytes', the size of the weight gradient's workspace), looked up once the arguments have passed.
+def _linear_forward(name, limit, entry, x, wt, out):
+    pixels, cin = _rows(x, 'x')
+    if not 1 <= cin <= limit:
+        raise ValueError('%s: 1..%d channels, not %d' % (name, limit, cin))
+    _linear_wt(wt, 'wt', limit, cin)
+    if wt.device != x.device:
+        raise ValueError('%s: wt on %s, x on %s' % (name, wt.device, x.device))
+    out = _out_like(out, tuple(x.shape[:-1]) + (wt.shape[0],), x.device, name)
+    with torch.cuda.device(x.device):
+        check(getattr(lib(), entry)(_ptr(x), cin, _ptr(wt), pixels, cin, wt.shape[0], _ptr(out), wt.shape[0], stream_ptr(x.device)))
+    return out
+
+
+def _linear_dgrad(name, limit, entry, dy, wt, cin, out):
+    pixels, cout = _rows(dy, 'dy')
+    cin = int(cin)
+    if not (1 <= cin <= limit and 1 <= cout <= limit):
+        raise ValueError('%s: 1..%d channels, not %d and %d' % (name, limit, cin, cout))
+    _linear_wt(wt, 'wt', limit, cin)
+    if wt.device != dy.device or wt.shape[0] != cout:
+        raise ValueError('%s: wt %s on %s for dy %s on %s' % (name, tuple(wt.shape), wt.device, tuple(dy.shape), dy.device))
+    out = _out_like(out, tuple(dy.shape[:-1]) + (cin,), dy.device, name)
+    with torch.cuda.device(dy.device):
+        check(getattr(lib(), entry)(_ptr(dy), cout, _ptr(wt), pixels, cin, cout, _ptr(out), cin, stream_ptr(dy.device)))
+    return out
+
+
+def _linear_wgrad(name, limit, entry, x, dy, out, workspace):
+    pixels, cin = _rows(x, 'x')
+    pdy, cout = _rows(dy, 'dy')
+    if pdy != pixels or dy.device != x.device:
+        raise ValueError('%s: dy %s on %s for x %s on %s' % (name, tuple(dy.shape), dy.device, tuple(x.shape), x.device))
+    if not (1 <= cin <= limit and 1 <= cout <= limit):
+        raise ValueError('%s: 1..%d channels, not %d and %d' % (name, limit, cin, cout))
+    dev = x.device
+    out = _out_like(out, (cout, (cin + 3) // 4 * 4), dev, name)
+    ws = _workspace_arg(workspace, int(getattr(lib(), entry + '_workspace_bytes')(pixels, cin, cout)), dev, name)
+    with torch.cuda.device(dev):
+        check(getattr(lib(), entry)(_ptr(x), cin, _ptr(dy), cout, pixels, cin, cout, _ptr(ws), ws.numel(), _ptr(out), stream_ptr(dev)))
+    return out
 
 
 def linear_forward(x, wt, out=None):
     """A bias-free 1x1 convolution on dense rows (yr_linear_forward): x [..., cin] float32, wt [cout, round_up(cin, 4)] (the layout of
     YR_OP_POINTWISE, pad columns 0) -> y [..., cout] = x @ wt[:, :cin].T on the float32 matrix pipe.  out: a contiguous float32
     tensor of that shape on x's device (every element is written); default: a fresh one.  One launch."""
-    pixels, cin = _rows(x, 'x')
-    if not 1 <= cin <= 256:
-        raise ValueError('linear_forward: 1..256 channels, not %d' % cin)
-    _linear_wt(wt, 'wt', cin)
-    if wt.device != x.device:
-        raise ValueError('linear_forward: wt on %s, x on %s' % (wt.device, x.device))
-    out = _out_like(out, tuple(x.shape[:-1]) + (wt.shape[0],), x.device, 'linear_forward')
-    with torch.cuda.device(x.device):
-        check(lib().yr_linear_forward(_ptr(x), cin, _ptr(wt), pixels, cin, wt.shape[0], _ptr(out), wt.shape[0], stream_ptr(x.device)))
-    return out
+    return _linear_forward('linear_forward', 256, 'yr_linear_forward', x, wt, out)
 
 
 def linear_wgrad_chunk(pixels, cin, cout):
@@ -583,18 +619,7 @@ def linear_wgrad(x, dy, out=None, workspace=None):
     the same bytes.  out: a contiguous float32 tensor of that shape on x's device (every element is written); workspace: a uint8
     tensor of at least linear_wgrad_workspace_bytes(pixels, cin, cout) bytes there (its contents do not matter).  Defaults: fresh
     ones.  Two launches."""
-    pixels, cin = _rows(x, 'x')
-    pdy, cout = _rows(dy, 'dy')
-    if pdy != pixels or dy.device != x.device:
-        raise ValueError('linear_wgrad: dy %s on %s for x %s on %s' % (tuple(dy.shape), dy.device, tuple(x.shape), x.device))
-    if not (1 <= cin <= 256 and 1 <= cout <= 256):
-        raise ValueError('linear_wgrad: 1..256 channels, not %d and %d' % (cin, cout))
-    dev = x.device
-    out = _out_like(out, (cout, (cin + 3) // 4 * 4), dev, 'linear_wgrad')
-    ws = _workspace_arg(workspace, linear_wgrad_workspace_bytes(pixels, cin, cout), dev, 'linear_wgrad')
-    with torch.cuda.device(dev):
-        check(lib().yr_linear_wgrad(_ptr(x), cin, _ptr(dy), cout, pixels, cin, cout, _ptr(ws), ws.numel(), _ptr(out), stream_ptr(dev)))
-    return out
+    return _linear_wgrad('linear_wgrad', 256, 'yr_linear_wgrad', x, dy, out, workspace)
 
 
 def adam_alpha(learning_rate, step, beta1=.9, beta2=.999):
@@ -624,60 +649,25 @@ def linear_dgrad(dy, wt, cin, out=None):
     """The input gradient of ``linear_forward`` (yr_linear_dgrad): dy [..., cout] float32, wt [cout, round_up(cin, 4)] ->
     dx [..., cin] = dy @ wt[:, :cin] on the float32 matrix pipe.  ``cin`` names the channels taken of wt's rows.  out: a contiguous
     float32 tensor of that shape on dy's device (every element is written); default: a fresh one.  One launch."""
-    pixels, cout = _rows(dy, 'dy')
-    cin = int(cin)
-    if not (1 <= cin <= 256 and 1 <= cout <= 256):
-        raise ValueError('linear_dgrad: 1..256 channels, not %d and %d' % (cin, cout))
-    _linear_wt(wt, 'wt', cin)
-    if wt.device != dy.device or wt.shape[0] != cout:
-        raise ValueError('linear_dgrad: wt %s on %s for dy %s on %s' % (tuple(wt.shape), wt.device, tuple(dy.shape), dy.device))
-    out = _out_like(out, tuple(dy.shape[:-1]) + (cin,), dy.device, 'linear_dgrad')
-    with torch.cuda.device(dy.device):
-        check(lib().yr_linear_dgrad(_ptr(dy), cout, _ptr(wt), pixels, cin, cout, _ptr(out), cin, stream_ptr(dy.device)))
-    return out
+    return _linear_dgrad('linear_dgrad', 256, 'yr_linear_dgrad', dy, wt, cin, out)
 
 
 # ----------------------------------------------------------------------------- 1x1 operators of any width up to 1024 (csrc/linearwide.hip)
 LINEAR_WIDE_MAX = 1024
 
 
-def _linear_wide_wt(wt, name, cin=None):
-    _require_cuda_f32(wt, name)
-    if wt.dim() != 2 or wt.shape[1] % 4 or not 1 <= wt.shape[0] <= LINEAR_WIDE_MAX or (cin is not None and wt.shape[1] != (cin + 3) // 4 * 4):
-        raise ValueError('%s has shape %s, expected [cout, round_up(cin, 4)] with cout <= %d' % (name, tuple(wt.shape), LINEAR_WIDE_MAX))
-
-
 def linear_wide_forward(x, wt, out=None):
     """``linear_forward`` for 1..1024 channels on either side (yr_linear_wide_forward): x [..., cin] float32, wt [cout, round_up(cin, 4)]
     -> y [..., cout] = x @ wt[:, :cin].T on the float32 matrix pipe, the activations read once per 256 output channels.  out: a
     contiguous float32 tensor of that shape on x's device (every element is written); default: a fresh one.  One launch."""
-    pixels, cin = _rows(x, 'x')
-    if not 1 <= cin <= LINEAR_WIDE_MAX:
-        raise ValueError('linear_wide_forward: 1..%d channels, not %d' % (LINEAR_WIDE_MAX, cin))
-    _linear_wide_wt(wt, 'wt', cin)
-    if wt.device != x.device:
-        raise ValueError('linear_wide_forward: wt on %s, x on %s' % (wt.device, x.device))
-    out = _out_like(out, tuple(x.shape[:-1]) + (wt.shape[0],), x.device, 'linear_wide_forward')
-    with torch.cuda.device(x.device):
-        check(lib().yr_linear_wide_forward(_ptr(x), cin, _ptr(wt), pixels, cin, wt.shape[0], _ptr(out), wt.shape[0], stream_ptr(x.device)))
-    return out
+    return _linear_forward('linear_wide_forward', LINEAR_WIDE_MAX, 'yr_linear_wide_forward', x, wt, out)
 
 
 def linear_wide_dgrad(dy, wt, cin, out=None):
     """``linear_dgrad`` for 1..1024 channels on either side (yr_linear_wide_dgrad): dy [..., cout] float32, wt [cout, round_up(cin, 4)]
     -> dx [..., cin] = dy @ wt[:, :cin].  out: a contiguous float32 tensor of that shape on dy's device (every element is written);
     default: a fresh one.  One launch."""
-    pixels, cout = _rows(dy, 'dy')
-    cin = int(cin)
-    if not (1 <= cin <= LINEAR_WIDE_MAX and 1 <= cout <= LINEAR_WIDE_MAX):
-        raise ValueError('linear_wide_dgrad: 1..%d channels, not %d and %d' % (LINEAR_WIDE_MAX, cin, cout))
-    _linear_wide_wt(wt, 'wt', cin)
-    if wt.device != dy.device or wt.shape[0] != cout:
-        raise ValueError('linear_wide_dgrad: wt %s on %s for dy %s on %s' % (tuple(wt.shape), wt.device, tuple(dy.shape), dy.device))
-    out = _out_like(out, tuple(dy.shape[:-1]) + (cin,), dy.device, 'linear_wide_dgrad')
-    with torch.cuda.device(dy.device):
-        check(lib().yr_linear_wide_dgrad(_ptr(dy), cout, _ptr(wt), pixels, cin, cout, _ptr(out), cin, stream_ptr(dy.device)))
-    return out
+    return _linear_dgrad('linear_wide_dgrad', LINEAR_WIDE_MAX, 'yr_linear_wide_dgrad', dy, wt, cin, out)
 
 
 def linear_wide_wgrad_chunk(pixels, cin, cout):
@@ -698,18 +688,7 @@ def linear_wide_wgrad(x, dy, out=None, workspace=None):
     contiguous float32 tensor of that shape on x's device (every element is written); workspace: a uint8 tensor of at least
     linear_wide_wgrad_workspace_bytes(pixels, cin, cout) bytes there (its contents do not matter).  Defaults: fresh ones.  Two
     launches."""
-    pixels, cin = _rows(x, 'x')
-    pdy, cout = _rows(dy, 'dy')
-    if pdy != pixels or dy.device != x.device:
-        raise ValueError('linear_wide_wgrad: dy %s on %s for x %s on %s' % (tuple(dy.shape), dy.device, tuple(x.shape), x.device))
-    if not (1 <= cin <= LINEAR_WIDE_MAX and 1 <= cout <= LINEAR_WIDE_MAX):
-        raise ValueError('linear_wide_wgrad: 1..%d channels, not %d and %d' % (LINEAR_WIDE_MAX, cin, cout))
-    dev = x.device
-    out = _out_like(out, (cout, (cin + 3) // 4 * 4), dev, 'linear_wide_wgrad')
-    ws = _workspace_arg(workspace, linear_wide_wgrad_workspace_bytes(pixels, cin, cout), dev, 'linear_wide_wgrad')
-    with torch.cuda.device(dev):
-        check(lib().yr_linear_wide_wgrad(_ptr(x), cin, _ptr(dy), cout, pixels, cin, cout, _ptr(ws), ws.numel(), _ptr(out), stream_ptr(dev)))
-    return out
+    return _linear_wgrad('linear_wide_wgrad', LINEAR_WIDE_MAX, 'yr_linear_wide_wgrad', x, dy, out, workspace)
 
 
 def depthwise_geometry(h, w, k, stride=1, padding='same'):

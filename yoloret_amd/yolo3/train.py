@@ -23,6 +23,7 @@ import math
 import numpy as np
 import torch
 
+from .. import autograd
 from .. import runtime as rt
 from .model import output_convs, yolo_loss, yolo_loss_and_grad, yolo_loss_and_grad_from_boxes, yolov3_features
 
@@ -54,7 +55,70 @@ def cosine_decay(learning_rate, epoch, epochs):
     return learning_rate * 0.5 * (1.0 + math.cos(math.pi * min(epoch, epochs) / epochs))
 
 
-class OutputLayerTrainer:
+class _Trainer:
+    """What the two trainers share: the hyper-parameters, the state's device, the two forms of a step, the Adam update of the flat
+    buffers ``w``, ``m``, ``v``, ``g`` and ``fit``.  A trainer adds ``_create(device)`` (the state), ``_step(images, loss_and_grad)``
+    (forward, ``loss_and_grad(logits)`` -> (total, terms, d logits), backward, ``_adam()``) and ``commit()``."""
+
+    def __init__(self, model, anchors, num_classes, num_scales, learning_rate, beta_1, beta_2, epsilon, ignore_thresh):
+        self.model = model
+        self.anchors = np.asarray(anchors, np.float32).reshape(-1, 2)
+        self.num_classes, self.num_scales = int(num_classes), int(num_scales)
+        self.learning_rate = self.lr = float(learning_rate)
+        self.beta_1, self.beta_2, self.epsilon, self.ignore_thresh = float(beta_1), float(beta_2), float(epsilon), ignore_thresh
+        self.step = 0           # Adam's t: optimizer.iterations
+        self.device = None
+
+    def _ensure(self, device):
+        if self.device is None:
+            self._create(device)
+            self.device = device
+        elif device != self.device:
+            raise ValueError('%s: the state lives on %s, this batch on %s' % (type(self).__name__, self.device, device))
+
+    def _adam(self):
+        self.step += 1
+        rt.adam_step(self.w, self.m, self.v, self.g, rt.adam_alpha(self.lr, self.step, self.beta_1, self.beta_2), self.beta_1, self.beta_2, self.epsilon)
+
+    def train_step(self, images, y_true):
+        """``_train_step`` (:18-46): the forward -> the loss and its gradient at the logits -> the gradients of everything the trainer
+        trains -> one Adam update -> the total loss BEFORE the update, a 0-d float32 device tensor.  Launches only: no host
+        synchronisation.  ``y_true``: the label tensors of the scales (``preprocess_true_boxes``' rows) on the images' device."""
+        y_true = [y_true] if isinstance(y_true, torch.Tensor) else list(y_true)
+        return self._step(images, lambda ys: yolo_loss_and_grad(ys, y_true, self.anchors, self.num_scales, self.ignore_thresh))
+
+    def train_step_from_boxes(self, images, true_boxes):
+        """``train_step`` with the labels encoded on the device from ground-truth boxes [B,T,5] (``yolo_loss_and_grad_from_boxes``)."""
+        return self._step(images, lambda ys: yolo_loss_and_grad_from_boxes(ys, true_boxes, self.anchors, self.num_classes, self.num_scales,
+                                                                           self.ignore_thresh))
+
+    def fit(self, epochs, train_dataset, val_dataset=None, use_ema=False, use_adv=False):
+        """``fit`` (:81-128) under ``cos_lr_freeze`` (code/train.py:95-97): epoch e runs at learning_rate * 0.5 * (1 + cos(pi e / epochs));
+        the train loss of an epoch is the float32 sum of its batches' losses in order divided by their number (:68-74), formed on the
+        device and read once per epoch; ``val_loss`` is ``validation_loss`` of the committed model.  Datasets: iterables of
+        (images, y_true) on one device -> (train_losses, val_losses), lists of np.float32 (val_losses empty without a val_dataset)."""
+        if use_ema or use_adv:
+            raise NotImplementedError('%s.fit: use_ema and use_adv are not built' % type(self).__name__)
+        train_losses, val_losses = [], []
+        for epoch in range(epochs):
+            self.lr = cosine_decay(self.learning_rate, epoch, epochs)
+            total, n = None, 0
+            for images, y_true in train_dataset:
+                loss = self.train_step(images, y_true)
+                total = loss if total is None else total + loss
+                n += 1
+            if n == 0:
+                raise ValueError('%s.fit: the training data set is empty' % type(self).__name__)
+            mean = total / torch.full((), float(n), dtype=total.dtype, device=total.device)
+            train_losses.append(np.float32(mean.item()))
+            if val_dataset is not None:
+                self.commit()
+                val_losses.append(np.float32(validation_loss(self.model, val_dataset, self.anchors, self.num_scales, self.ignore_thresh)[0]))
+        self.commit()
+        return train_losses, val_losses
+
+
+class OutputLayerTrainer(_Trainer):
     """Trains the convolutions that produce ``model``'s logits with Keras Adam, the body frozen.
 
     ``model``: ``yolov3_body``'s float32 ``Model`` with its weights set.  The feature model (``yolov3_features``) is built once and
@@ -64,11 +128,7 @@ class OutputLayerTrainer:
     first batch.  ``commit()`` writes them back into ``model``."""
 
     def __init__(self, model, anchors, num_classes, num_scales, learning_rate=1e-3, beta_1=.9, beta_2=.999, epsilon=1e-8, ignore_thresh=.5):
-        self.model = model
-        self.anchors = np.asarray(anchors, np.float32).reshape(-1, 2)
-        self.num_classes, self.num_scales = int(num_classes), int(num_scales)
-        self.learning_rate = self.lr = float(learning_rate)
-        self.beta_1, self.beta_2, self.epsilon, self.ignore_thresh = float(beta_1), float(beta_2), float(epsilon), ignore_thresh
+        super().__init__(model, anchors, num_classes, num_scales, learning_rate, beta_1, beta_2, epsilon, ignore_thresh)
         self.features = yolov3_features(model)          # (raises for a 16-bit plan or outputs that are not bias-free 1x1 convs)
         weights = model.get_weights()
         if weights is None:
@@ -87,8 +147,6 @@ class OutputLayerTrainer:
             if not (1 <= cin <= 256 and 1 <= cout <= 256):
                 raise ValueError('OutputLayerTrainer: %s is %d -> %d channels; 1..256 are built' % (c.name, cin, cout))
             self.dims.append((cin, cout, (cin + 3) // 4 * 4))
-        self.step = 0           # Adam's t: optimizer.iterations
-        self.device = None
         self._workspace = None
 
     # ------------------------------------------------------------------ state
@@ -99,20 +157,9 @@ class OutputLayerTrainer:
             at += cout * kp
         return out
 
-    def _ensure(self, device):
-        if self.device is not None:
-            if device != self.device:
-                raise ValueError('OutputLayerTrainer: the state lives on %s, this batch on %s' % (self.device, device))
-            return
+    def _create(self, device):
         host = self.model.get_weights()
-        n = sum(cout * kp for _, cout, kp in self.dims)
-        flat = np.zeros((n,), np.float32)
-        at = 0
-        for name, (cin, cout, kp) in zip(self.kernel_names, self.dims):
-            wt = flat[at:at + cout * kp].reshape(cout, kp)
-            wt[:, :cin] = np.asarray(host[name], np.float32).reshape(cin, cout).T          # pad columns stay 0
-            at += cout * kp
-        self.device = device
+        flat = np.concatenate([autograd._pack_wt(host[name]).reshape(-1) for name in self.kernel_names])
         self.w = torch.from_numpy(flat).to(device)
         self.m, self.v, self.g = torch.zeros_like(self.w), torch.zeros_like(self.w), torch.zeros_like(self.w)
         self.weights, self.grads = self._views(self.w), self._views(self.g)
@@ -128,32 +175,16 @@ class OutputLayerTrainer:
             ys.append(y.view(tuple(y.shape[:3]) + (a, y.shape[3] // a)))
         return ys
 
-    def _apply(self, feats, dys):
+    def _step(self, images, loss_and_grad):
+        """features -> logits -> loss and its gradient at the logits -> the weight gradients -> one Adam update"""
+        feats = self.features(images)
+        total, self.last_terms, dys = loss_and_grad(self.logits(images, feats))
         for f, dy, g, (cin, cout, kp) in zip(feats, dys, self.grads, self.dims):
             need = rt.linear_wgrad_workspace_bytes(f.numel() // cin, cin, cout)
             if self._workspace is None or self._workspace.numel() < need:
                 self._workspace = torch.empty((need,), dtype=torch.uint8, device=self.device)        # (calls on one stream are ordered: one workspace serves all scales)
             rt.linear_wgrad(f, dy.reshape(tuple(f.shape[:3]) + (cout,)), out=g, workspace=self._workspace)
-        self.step += 1
-        rt.adam_step(self.w, self.m, self.v, self.g, rt.adam_alpha(self.lr, self.step, self.beta_1, self.beta_2), self.beta_1, self.beta_2, self.epsilon)
-
-    def train_step(self, images, y_true):
-        """``_train_step`` (:18-46) for the output convolutions: features -> logits -> loss and its gradient at the logits -> the
-        weight gradients -> one Adam update -> the total loss BEFORE the update, a 0-d float32 device tensor.  Launches only: no host
-        synchronisation.  ``y_true``: the label tensors of the scales (``preprocess_true_boxes``' rows) on the images' device."""
-        y_true = [y_true] if isinstance(y_true, torch.Tensor) else list(y_true)
-        feats = self.features(images)
-        ys = self.logits(images, feats)
-        total, self.last_terms, dys = yolo_loss_and_grad(ys, y_true, self.anchors, self.num_scales, self.ignore_thresh)
-        self._apply(feats, dys)
-        return total
-
-    def train_step_from_boxes(self, images, true_boxes):
-        """``train_step`` with the labels encoded on the device from ground-truth boxes [B,T,5] (``yolo_loss_and_grad_from_boxes``)."""
-        feats = self.features(images)
-        ys = self.logits(images, feats)
-        total, self.last_terms, dys = yolo_loss_and_grad_from_boxes(ys, true_boxes, self.anchors, self.num_classes, self.num_scales, self.ignore_thresh)
-        self._apply(feats, dys)
+        self._adam()
         return total
 
     # ------------------------------------------------------------------ the loop
@@ -166,38 +197,12 @@ class OutputLayerTrainer:
         weights = self.model.get_weights()
         at = 0
         for name, (cin, cout, kp) in zip(self.kernel_names, self.dims):
-            wt = host[at:at + cout * kp].reshape(cout, kp)
-            weights[name] = np.ascontiguousarray(wt[:, :cin].T).reshape(1, 1, cin, cout)
+            weights[name] = autograd._unpack_wt(host[at:at + cout * kp].reshape(cout, kp), cin)
             at += cout * kp
         self.model.set_weights(weights)
 
-    def fit(self, epochs, train_dataset, val_dataset=None, use_ema=False, use_adv=False):
-        """``fit`` (:81-128) under ``cos_lr_freeze`` (code/train.py:95-97): epoch e runs at learning_rate * 0.5 * (1 + cos(pi e / epochs));
-        the train loss of an epoch is the float32 sum of its batches' losses in order divided by their number (:68-74), formed on the
-        device and read once per epoch; ``val_loss`` is ``validation_loss`` of the committed model.  Datasets: iterables of
-        (images, y_true) on one device -> (train_losses, val_losses), lists of np.float32 (val_losses empty without a val_dataset)."""
-        if use_ema or use_adv:
-            raise NotImplementedError('OutputLayerTrainer.fit: use_ema and use_adv are not built')
-        train_losses, val_losses = [], []
-        for epoch in range(epochs):
-            self.lr = cosine_decay(self.learning_rate, epoch, epochs)
-            total, n = None, 0
-            for images, y_true in train_dataset:
-                loss = self.train_step(images, y_true)
-                total = loss if total is None else total + loss
-                n += 1
-            if n == 0:
-                raise ValueError('OutputLayerTrainer.fit: the training data set is empty')
-            mean = total / torch.full((), float(n), dtype=total.dtype, device=total.device)
-            train_losses.append(np.float32(mean.item()))
-            if val_dataset is not None:
-                self.commit()
-                val_losses.append(np.float32(validation_loss(self.model, val_dataset, self.anchors, self.num_scales, self.ignore_thresh)[0]))
-        self.commit()
-        return train_losses, val_losses
 
-
-class DetectorTrainer:
+class DetectorTrainer(_Trainer):
     """Trains EVERY layer of ``model`` with Keras Adam: the reference's ``_train_step`` (:18-46) as its stage 2 runs it (code/train.py:150-216
     sets ``trainable = True`` on all layers, and stage 1 as shipped freezes none): ``autograd.detector(training=True)`` - the MobileNetV2
     backbone, the RFCR module, the links and the six head blocks, every BatchNorm on the statistics of the batch - -> the sum of
@@ -213,11 +218,7 @@ class DetectorTrainer:
     the gradient reduction over several devices."""
 
     def __init__(self, model, anchors, num_classes, num_scales, learning_rate=1e-3, beta_1=.9, beta_2=.999, epsilon=1e-8, ignore_thresh=.5):
-        self.model = model
-        self.anchors = np.asarray(anchors, np.float32).reshape(-1, 2)
-        self.num_classes, self.num_scales = int(num_classes), int(num_scales)
-        self.learning_rate = self.lr = float(learning_rate)
-        self.beta_1, self.beta_2, self.epsilon, self.ignore_thresh = float(beta_1), float(beta_2), float(epsilon), ignore_thresh
+        super().__init__(model, anchors, num_classes, num_scales, learning_rate, beta_1, beta_2, epsilon, ignore_thresh)
         yolov3_features(model)          # (raises for a 16-bit plan or outputs that are not bias-free 1x1 convs)
         weights = model.get_weights()
         if weights is None:
@@ -233,8 +234,6 @@ class DetectorTrainer:
         for c, a in zip(output_convs(model)[:3], self.num_anchors):
             if c.output.shape[2] != a * (5 + self.num_classes):
                 raise ValueError('DetectorTrainer: %s has %d filters, %d anchors x (5 + %d classes) expected' % (c.name, c.output.shape[2], a, self.num_classes))
-        self.step = 0           # Adam's t: optimizer.iterations
-        self.device = None
 
     # ------------------------------------------------------------------ state
     @staticmethod
@@ -245,12 +244,7 @@ class DetectorTrainer:
             out.extend((d, k) for k, v in d.items() if isinstance(v, torch.Tensor))
         return out
 
-    def _ensure(self, device):
-        if self.device is not None:
-            if device != self.device:
-                raise ValueError('DetectorTrainer: the state lives on %s, this batch on %s' % (self.device, device))
-            return
-        from .. import autograd
+    def _create(self, device):
         self.params = autograd.detector_parameters(self.model, device)
         trained = [(d, k) for d, k in self._slots(self.params) if d[k].requires_grad]
         sizes = [(d[k].numel() + 3) // 4 * 4 for d, k in trained]          # every tensor starts on 16 bytes; the fill is 0 and stays 0 (its gradient is)
@@ -265,41 +259,24 @@ class DetectorTrainer:
             d[k] = view
             at += size
         self.trained = trained
-        self.device = device
 
     # ------------------------------------------------------------------ one step
     def logits(self, images, training=False):
         """``autograd.detector`` on the trainer's own parameters -> [B,G,G,A,5+C] per scale.  training=False folds the BatchNorms (it copies
         their vectors to the host: it synchronises) and changes nothing."""
-        from .. import autograd
         self._ensure(images.device)
         if training:
             return autograd.detector(images, self.params, True, self.num_anchors[0])
         with torch.no_grad():
             return autograd.detector(images, self.params, False, self.num_anchors[0])
 
-    def _apply(self, ys, dys):
+    def _step(self, images, loss_and_grad):
+        """the training-mode forward -> the loss and its gradient at the logits -> backward through the neck and the backbone -> one Adam update"""
+        ys = self.logits(images, training=True)
+        total, self.last_terms, dys = loss_and_grad([y.detach() for y in ys])
         self.g.zero_()          # (backward ADDS into the views of g)
         torch.autograd.backward(ys, [dy.reshape(y.shape) for y, dy in zip(ys, dys)])
-        self.step += 1
-        rt.adam_step(self.w, self.m, self.v, self.g, rt.adam_alpha(self.lr, self.step, self.beta_1, self.beta_2), self.beta_1, self.beta_2, self.epsilon)
-
-    def train_step(self, images, y_true):
-        """``_train_step`` (:18-46) with every layer trained: the training-mode forward -> the loss and its gradient at the logits -> backward
-        through the neck and the backbone -> one Adam update -> the total loss BEFORE the update, a 0-d float32 device tensor.  Launches
-        only: no host synchronisation.  ``y_true``: the label tensors of the scales (``preprocess_true_boxes``' rows) on the images' device."""
-        y_true = [y_true] if isinstance(y_true, torch.Tensor) else list(y_true)
-        ys = self.logits(images, training=True)
-        total, self.last_terms, dys = yolo_loss_and_grad([y.detach() for y in ys], y_true, self.anchors, self.num_scales, self.ignore_thresh)
-        self._apply(ys, dys)
-        return total
-
-    def train_step_from_boxes(self, images, true_boxes):
-        """``train_step`` with the labels encoded on the device from ground-truth boxes [B,T,5] (``yolo_loss_and_grad_from_boxes``)."""
-        ys = self.logits(images, training=True)
-        total, self.last_terms, dys = yolo_loss_and_grad_from_boxes([y.detach() for y in ys], true_boxes, self.anchors, self.num_classes, self.num_scales,
-                                                                     self.ignore_thresh)
-        self._apply(ys, dys)
+        self._adam()
         return total
 
     # ------------------------------------------------------------------ the loop
@@ -308,31 +285,6 @@ class DetectorTrainer:
         ``model(images)``, ``YoloModel``, ``MAPCallback`` and ``save_weights`` see the trained network.  One copy per half to the host (synchronises)."""
         if self.device is None:
             return
-        from .. import autograd
         weights = self.model.get_weights()
         weights.update(autograd.detector_weights(self.params))
         self.model.set_weights(weights)
-
-    def fit(self, epochs, train_dataset, val_dataset=None, use_ema=False, use_adv=False):
-        """``fit`` (:81-128) under the cosine schedule (code/train.py:95-97), as ``OutputLayerTrainer.fit``: datasets are iterables of
-        (images, y_true) on one device -> (train_losses, val_losses), lists of np.float32 (val_losses empty without a val_dataset);
-        ``val_loss`` is ``validation_loss`` of the committed model."""
-        if use_ema or use_adv:
-            raise NotImplementedError('DetectorTrainer.fit: use_ema and use_adv are not built')
-        train_losses, val_losses = [], []
-        for epoch in range(epochs):
-            self.lr = cosine_decay(self.learning_rate, epoch, epochs)
-            total, n = None, 0
-            for images, y_true in train_dataset:
-                loss = self.train_step(images, y_true)
-                total = loss if total is None else total + loss
-                n += 1
-            if n == 0:
-                raise ValueError('DetectorTrainer.fit: the training data set is empty')
-            mean = total / torch.full((), float(n), dtype=total.dtype, device=total.device)
-            train_losses.append(np.float32(mean.item()))
-            if val_dataset is not None:
-                self.commit()
-                val_losses.append(np.float32(validation_loss(self.model, val_dataset, self.anchors, self.num_scales, self.ignore_thresh)[0]))
-        self.commit()
-        return train_losses, val_losses
